@@ -9,15 +9,20 @@ search -> PDSCH demod -> rate de-matching -> turbo -> MAC PDUs into the MAC-LTE 
 that stream.  IQ is in HBM before the timed region starts (`value`); the PCIe-inclusive rates - first H2D to last PDU, SURVEY 8(d) - are the
 `first_h2d_to_last_pdu` legs of the same line.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--step-sf 20000] [--batch 400] [--cpu-sample 1600]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--step-sf 20000] [--batch 400] [--dump-outputs DIR] [--full [--cpu-sample 1600]]
+
+A plain run sets up, warms up, times the K steps, gates them on the cached oracle stream and prints the line.  --full adds what the headline
+does not need, each outside the timed region: the live CPU oracle (cpu_baseline, and the head-of-stream check of ranks > 0), the
+first-H2D-to-last-PDU legs and the other BASELINE configurations (--no-cpu / --no-legs leave parts of it out).  --dump-outputs DIR writes the
+MAC-LTE records of the last timed step as .npy files (see dump_last_step).
 
 Parity gate: `pcap_diff` describes the TIMED stream against the CPU ORACLE.  The oracle walked the first 100 000 subframes of the stream once
 (one thread - its state is a sequential scan; 35 subframes/s) and its records were hashed per block of 200 subframes
 (tests/golden/cfg3_stream_oracle.json, made by tools/make_cfg3_golden.py, keyed by the xxh3 of the capture bytes).  The pcap writer hashes
 the records of the timed steps with the same block structure (lsn_pcap_set_digest_blocks); every block of the timed region must equal the
 oracle's block of the same stream position, record count and digest.  The same check covers the warm-up (cold-state) steps and both passes
-of every PCIe-inclusive leg.  On top, the oracle runs live on the first --cpu-sample subframes (cpu_baseline) and must reproduce the cached
-blocks on this host.
+of every PCIe-inclusive leg.  On top (--full), the oracle runs live on the first --cpu-sample subframes (cpu_baseline) and must reproduce the
+cached blocks on this host.
 
 N > 1: `--gpus N` launches N ranks itself (python -m torch.distributed.run, one process per GPU, backend nccl = RCCL) unless it already
 runs under one (RANK / WORLD_SIZE set, which is how the driver starts it).  Every rank replays its own synthetic cell (BASELINE
@@ -138,6 +143,43 @@ def auto_step_sf(nsf, steps, warmup, cached, block=200):
     return fit[0] if fit else block
 
 
+def dump_last_step(out_dir, pcap_path, blocks, origin_tti, lo, hi, block=200, pdu_budget=8 << 20):
+    """--dump-outputs: what a caller of the timed path receives from its last step - the MAC-LTE records of stream positions [lo, hi) (subframes
+    since origin_tti, the first timed subframe) out of the pcap file the timed steps wrote (timestamps zero) - as out_dir/*.npy:
+      records.npy          float32 [n, 6]: tti, rnti, direction, rnti_type, crc_ok, PDU length - every record of the step, in stream order
+      pdu_sample.npy       float32: the PDU bytes of a fixed, seeded sample of those records (at most pdu_budget bytes), concatenated in record order
+      pdu_sample_rows.npy  float64: the rows of records.npy the sample holds
+      block_digests.npy    float64 [(hi - lo) / block, 3]: the pcap writer's digest of every 200-subframe block of the step (high and low 32 bits) and its
+                           record count - covers every byte of every record"""
+    import struct
+    buf = np.fromfile(pcap_path, dtype=np.uint8)
+    mv = memoryview(buf)
+    offs, off, end = [], 24, buf.size  # 24-byte file header, then per record 16 bytes (ts, ts, length, length) + 19-byte MAC-LTE context + PDU
+    while off + 35 <= end:
+        offs.append(off)
+        off += 16 + struct.unpack_from("<I", mv, off + 8)[0]
+    o = np.array(offs, dtype=np.int64) + 16
+    ln = buf[o[:, None] - 8 + np.arange(4)].copy().view(np.uint32)[:, 0].astype(np.int64) - 19
+    fs = buf[o + 10].astype(np.int64) << 8 | buf[o + 11]
+    tti = (fs >> 4) * 10 + (fs & 15)
+    # stream position of every record: its TTI unwrapped from record to record, as the writer's block digests count them
+    want = (tti - origin_tti) % 10240
+    pos = np.cumsum(np.concatenate([[max(0, (int(want[0]) + 5120) % 10240 - 5120)], (np.diff(want) + 5120) % 10240 - 5120])) if want.size else want
+    keep = (pos >= lo) & (pos < hi)
+    o, ln = o[keep], ln[keep]
+    rec = np.stack([tti[keep], buf[o + 4].astype(np.int64) << 8 | buf[o + 5], buf[o + 1], buf[o + 2], buf[o + 13], ln], axis=1).astype(np.float32)
+    order = np.random.default_rng(0).permutation(len(o))
+    rows = np.sort(order[:int(np.searchsorted(np.cumsum(ln[order]), pdu_budget, side="right"))])
+    sample = np.concatenate([buf[o[r] + 19:o[r] + 19 + ln[r]] for r in rows]).astype(np.float32) if rows.size else np.zeros(0, np.float32)
+    bd = np.zeros(((hi - lo) // block, 3), dtype=np.float64)
+    for j, (d, c) in enumerate(blocks[lo // block:hi // block]):
+        bd[j] = (d >> 32, d & 0xFFFFFFFF, c)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in (("records", rec), ("pdu_sample", sample), ("pdu_sample_rows", rows.astype(np.float64)), ("block_digests", bd)):
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "records": int(len(o)), "pdu_sample_records": int(rows.size), "bytes": int(rec.nbytes + sample.nbytes + 8 * rows.size + bd.nbytes)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -150,18 +192,24 @@ def main():
     ap.add_argument("--nsf", type=int, default=0, help="distinct subframes of the capture (0 = the gated stream's 20 000); other values run ungated")
     ap.add_argument("--config", default="cfg3", help="scenario preset: cfg3 = 20 MHz, 150 RNTIs, TM3/TM4 up to 256QAM")
     ap.add_argument("--batch", type=int, default=400, help="subframes per pipeline chunk inside a submit (400-500 measured best on the 4 000-subframe steps: shorter fill / drain than 800, fewer launches than 200)")
-    ap.add_argument("--cpu-sample", type=int, default=1600, help="subframes the CPU oracle decodes live from cold state (rank 0): cpu_baseline + reproduction of the cached oracle blocks")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the live oracle leg (cpu_baseline)")
+    ap.add_argument("--cpu-sample", type=int, default=1600, help="--full: subframes the CPU oracle decodes live from cold state (rank 0): cpu_baseline + reproduction of the cached oracle blocks")
+    ap.add_argument("--full", action="store_true", help="after the headline, also run the live CPU oracle (cpu_baseline, head of the stream of ranks > 0), the first-H2D-to-last-PDU "
+                    "legs and the other BASELINE configurations; without it a run does only what the headline needs")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the live oracle leg (cpu_baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write the MAC-LTE records of the last timed step to DIR/*.npy (rank 0; the timed steps then also write "
+                    "their records to a pcap file on tmpfs, as the host_pinned_pcap_to_file leg does)")
     ap.add_argument("--shard", choices=("cells", "capture"), default="cells",
                     help="N > 1: 'cells' = one synthetic cell per rank (weak scaling, the default and what BASELINE configs[4] asks for); 'capture' = ONE capture "
                          "whose chunks go round-robin to the N GPUs (lsn_phy_create_multi on rank 0; the other ranks only hold their GPU) - strong scaling, "
                          "bounded by the sequential FALCON search on one host thread")
     ap.add_argument("--workload", default="", help="a downlink leg of tools/bench_legs.py (e.g. cfg3_at_16_dB_snr) as the TIMED stream instead of the headline capture - its capture, "
                     "its cached oracle stream, the same gate: how the second operating point is profiled (tools/gpu_profile.sh) with its own roofline figures; never the driver's line")
-    ap.add_argument("--no-legs", action="store_true", help="skip the PCIe-inclusive legs (host buffers, capture file, worker pool) and the other configs")
+    ap.add_argument("--no-legs", action="store_true", help="--full without the PCIe-inclusive legs (host buffers, capture file, worker pool) and the other configs")
     ap.add_argument("--leg-batch", type=int, default=0, help="pipeline chunk of the first-H2D-to-last-PDU legs (0 = --batch)")
     ap.add_argument("--gen-threads", type=int, default=0, help="threads of the synthetic transmitter (0 = the CPUs this process may use, at most 32)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the timed steps and their gate only
+        args.no_cpu = args.no_legs = True
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -322,7 +370,12 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
         return
-    pcap = la.PcapWriter(None)  # native MAC-LTE writer, the reference's pcap-emit surface; the stream is digested per block, not kept
+    dump_pcap = None
+    if args.dump_outputs and rank == 0:  # the records of the timed steps go to a file as well (the last step's are dumped after the run)
+        import tempfile
+        fd, dump_pcap = tempfile.mkstemp(prefix="lsn_bench_dump_", suffix=".pcap", dir="/dev/shm" if os.access("/dev/shm", os.W_OK) else None)
+        os.close(fd)
+    pcap = la.PcapWriter(dump_pcap, wall_clock=False)  # native MAC-LTE writer, the reference's pcap-emit surface; the stream is digested per block, not kept
     pcap.set_store(False)
     pcap.set_digest_blocks(BLOCK, tti0)
     phy = la.Phy(nof_rx_antennas=sc["nof_rx"], max_batch=batch, device=local, pcapwriter=pcap, devices=devices, harq_mode=(wl_leg or {}).get("harq_mode", 0))
@@ -344,6 +397,7 @@ def main():
     warm_records = pcap.nof_records()
     pcap.reset()
     pcap.set_digest_blocks(BLOCK, (tti0 + args.warmup * S) % 10240)  # blocks of the timed region count from its first subframe
+    pcap.set_store(dump_pcap is not None)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -387,6 +441,13 @@ def main():
         dist_echo.update({"backend": dist.get_backend() + (" (RCCL)" if dist.get_backend() == "nccl" else ""), "world_size": dist.get_world_size(),
                           "devices_pci": ["%04x:%02x:%02x" % (b >> 16, (b >> 8) & 0xFF, b & 0xFF) for b in buses], "distinct_devices": len(set(buses))})
     phy.close()
+    dumped = None
+    if dump_pcap is not None:
+        pcap.close()  # flushes the file
+        try:
+            dumped = dump_last_step(args.dump_outputs, dump_pcap, timed_blocks, (tti0 + args.warmup * S) % 10240, (args.steps - 1) * S, args.steps * S, BLOCK)
+        finally:
+            os.remove(dump_pcap)
 
     def live_oracle_blocks(n):
         """the CPU oracle, live, over the first n subframes of THIS rank's capture from cold state -> (blocks [(digest, records)], seconds, records)"""
@@ -787,7 +848,7 @@ def main():
                          # stretch each other, so `frac` falls when the engine keeps more of them resident although the throughput rises
                          "mean_launches_in_flight": round(float(kms[kt]) / (dt * 1e3), 2),
                          "rocprof": rocprof, "dominant_by_time": la.KERNELS[dom], "valu": valu, "gpu_saturation": saturation, "profile": _profile_state()},
-            "first_h2d_to_last_pdu": legs, "cold_state": cold, "cpu_baseline": cpu,
+            "first_h2d_to_last_pdu": legs, "cold_state": cold, "cpu_baseline": cpu, "full": args.full, "dumped_outputs": dumped,
             "host": {"cpu_count": os.cpu_count(), "cpu_quota_cores": host_quota, "decode_threads": int(os.environ.get("LSN_DECODE_THREADS", "12")), "cores_busy_in_timed_region": round(host_cores_busy, 2), "cores_busy_per_rank": per_rank_cores,
                      "busiest_threads": busiest},
             "detail": {"pdus_per_subframe": round(p.nof_pdus / sf_rank, 3), "algo_bytes_per_subframe": int(p.algo_bytes / sf_rank),

@@ -19,7 +19,7 @@ def test_bench_spawns_two_product_ranks():
     env.pop("RANK", None)
     env.pop("WORLD_SIZE", None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--step-sf", "800", "--nsf", "1600",
-                          "--cpu-sample", "400", "--batch", "200", "--no-legs"], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
+                          "--cpu-sample", "400", "--batch", "200", "--full", "--no-legs"], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert out.returncode == 0 and len(lines) == 1, out.stdout[-1500:] + out.stderr[-1500:]
     j = json.loads(lines[0])
