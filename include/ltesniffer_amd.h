@@ -99,6 +99,20 @@ void lsn_phy_destroy(lsn_phy_t* phy);                                     /* Phy
 int lsn_phy_create_multi(const lsn_phy_cfg_t* cfg, const int* devices, uint32_t n_devices, lsn_phy_t** out);
 uint32_t lsn_phy_nof_devices(lsn_phy_t* phy);
 int lsn_phy_set_cell(lsn_phy_t* phy, const lsn_cell_t* cell);             /* Phy::setCell, Phy.cc:111 */
+/* Sampling mode: how many samples one OFDM symbol of the IQ handed to this Phy has (sampling rate = 15 kHz x that number).
+ *   LSN_RATES_3GPP (default): the TS 36.211 sizes        6 / 15 / 25 / 50 / 75 / 100 PRB -> 128 / 256 / 512 / 1024 / 1536 / 2048
+ *   LSN_RATES_SRSRAN: srsran_symbol_sz of an srsRAN built without FORCE_STANDARD_RATE - what LTESniffer runs, records and hands to its
+ *                     workers (LTESniffer_Core.cc:222-226,358,365)                       -> 128 / 256 / 384 /  768 / 1024 / 1536
+ * Everything counted in samples follows: a subframe is 15 x symbol size samples (every process call, file blocks, offset_time_samples,
+ * lsn_worker_buffer_len = 3 subframes).  Call it in front of lsn_phy_set_cell (handles of lsn_phy_create_multi included: all engines follow).
+ * Once a cell is set the mode is fixed: asking for the other one, or for an unknown mode, is LSN_ERROR_INVALID_INPUTS (a capture at another
+ * rate is another Phy). */
+#define LSN_RATES_3GPP 0
+#define LSN_RATES_SRSRAN 1
+int lsn_phy_set_sampling(lsn_phy_t* phy, int rates);
+int lsn_phy_get_sampling(lsn_phy_t* phy);
+uint32_t lsn_symbol_sz(uint32_t nof_prb, int rates);         /* srsran_symbol_sz; 0 for a bandwidth or mode that does not exist */
+uint32_t lsn_sampling_freq_hz(uint32_t nof_prb, int rates);  /* srsran_sampling_freq_hz: 15000 x lsn_symbol_sz */
 lsn_worker_t* lsn_phy_get_avail(lsn_phy_t* phy, int blocking);            /* Phy::getAvail / getAvailImmediate, Phy.cc:79-89 */
 int lsn_phy_put_pending(lsn_phy_t* phy, lsn_worker_t* w);                 /* Phy::putPending, Phy.cc:95 */
 int lsn_phy_join_pending(lsn_phy_t* phy);                                 /* Phy::joinPending, Phy.cc:100 */
@@ -260,6 +274,9 @@ typedef struct {
 } lsn_cell_search_t;
 int lsn_cell_search(int device, const void* iq, int iq_on_device, uint64_t nof_samples, uint32_t nof_prb, const lsn_cell_search_cfg_t* cfg,
                     lsn_cell_search_t* out, float* corr_out /* optional, host: [3][75 N] accumulated PSS correlation powers */);
+/* the same on samples at the rate of sampling mode `rates` (LSN_RATES_*): N = lsn_symbol_sz(nof_prb, rates); pss_pos and sf_start count samples of that rate */
+int lsn_cell_search_rates(int device, const void* iq, int iq_on_device, uint64_t nof_samples, uint32_t nof_prb, int rates, const lsn_cell_search_cfg_t* cfg,
+                          lsn_cell_search_t* out, float* corr_out);
 
 /* ---- IQ capture file replay ----
  * Replaces the file source of the reference's file mode: srsran_ue_sync_init_file_multi(&ue_sync, nof_prb, file, offset_time,

@@ -170,6 +170,11 @@ public:
   ~Phy() { lsn_phy_destroy(h); if (common.stats_file) fclose(common.stats_file); if (common.dci_file && common.dci_file != stdout) fclose(common.dci_file); }
   Phy(const Phy&) = delete;
   Phy& operator=(const Phy&) = delete;
+  // sampling mode of the buffers the caller fills (LSN_RATES_3GPP default; LSN_RATES_SRSRAN: SRSRAN_SF_LEN_PRB of the reference's srsRAN); in front of setCell
+  bool setSampling(int rates) { return lsn_phy_set_sampling(h, rates) == LSN_SUCCESS; }
+  int getSampling() const { return lsn_phy_get_sampling(h); }
+  static uint32_t symbolSz(uint32_t nof_prb, int rates) { return lsn_symbol_sz(nof_prb, rates); }
+  static uint32_t samplingFreqHz(uint32_t nof_prb, int rates) { return lsn_sampling_freq_hz(nof_prb, rates); }
   bool setCell(const lsn_cell_t& cell) { return lsn_phy_set_cell(h, &cell) == LSN_SUCCESS; }               // Phy.cc:111
   // the caller's srsran_cell_t (LTESniffer_Core.cc:292): its enums count like lsn_cell_t's fields (SRSRAN_CP_NORM 0 / EXT 1, SRSRAN_PHICH_NORM 0, SRSRAN_PHICH_R_1_6 0 ... R_2 3)
   template <class SrsranCell> bool setCell(const SrsranCell& c)
@@ -251,6 +256,12 @@ inline int cellSearch(const cf_t* iq, uint64_t nof_samples, uint32_t nof_prb, ls
 {
   lsn_cell_search_cfg_t c{nof_periods, force_N_id_2, threshold};
   return lsn_cell_search(device, iq, 0, nof_samples, nof_prb, &c, &out, nullptr);
+}
+inline int cellSearchRates(const cf_t* iq, uint64_t nof_samples, uint32_t nof_prb, int rates, lsn_cell_search_t& out, int force_N_id_2 = -1,
+                           uint32_t nof_periods = 2, float threshold = 20.0f, int device = 0)
+{
+  lsn_cell_search_cfg_t c{nof_periods, force_N_id_2, threshold};
+  return lsn_cell_search_rates(device, iq, 0, nof_samples, nof_prb, rates, &c, &out, nullptr);
 }
 
 }  // namespace lsn_amd

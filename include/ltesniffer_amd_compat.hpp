@@ -87,6 +87,9 @@ public:
     if (mcs_tracking && mcs_tracking->get_api_mode() >= 0)   // -z api_mode: identities go to the API capture file the writer opened (PcapWriter.cc:120-145,177-190)
       setApiMode(mcs_tracking->get_api_mode(), nullptr, nullptr, pcapwriter ? pcapwriter->apiHandle() : nullptr);
   }
+  // The reference's caller fills SRSRAN_SF_LEN_PRB(nof_prb) samples per subframe (LTESniffer_Core.cc:358,365), which are srsRAN's symbol sizes unless srsRAN was
+  // built with FORCE_STANDARD_RATE: such a caller calls setSampling(LSN_RATES_SRSRAN) in front of setCell.  The default stays LSN_RATES_3GPP.
+  using lsn_amd::Phy::setSampling;
 };
 
 using lsn_amd::SubframeWorker;

@@ -38,7 +38,20 @@ EXPORTS = ["lsn_phy_create", "lsn_phy_destroy", "lsn_phy_set_cell", "lsn_phy_get
            "lsn_phy_tap_ul", "lsn_phy_set_prach_config", "lsn_phy_prach_detect", "lsn_phy_set_prach_sink", "lsn_prach_tti_opportunity", "lsn_phy_process_file", "lsn_phy_mib_decode", "lsn_phy_mib_decode_llr", "lsn_phy_submit_device", "lsn_phy_wait", "lsn_cell_search",
            "lsn_phy_set_shortcut_discovery", "lsn_phy_get_shortcut_discovery", "lsn_phy_set_histogram_threshold", "lsn_phy_print_stats",
            "lsn_phy_set_mcs_update_interval", "lsn_phy_update_mcs_database", "lsn_phy_nof_tracked_rnti", "lsn_worker_buffers_offset", "lsn_pcap_digest", "lsn_pcap_set_store", "lsn_pcap_set_digest_blocks", "lsn_pcap_block_digests", "lsn_phy_create_multi", "lsn_phy_nof_devices",
-           "lsn_phy_set_cfo_correction", "lsn_phy_get_cfo_correction", "lsn_phy_set_candidate_pruning", "lsn_phy_set_stage_c_taps", "lsn_phy_prepare_file", "lsn_phy_get_meta_formats", "lsn_phy_nof_workers", "lsn_phy_worker"]
+           "lsn_phy_set_cfo_correction", "lsn_phy_get_cfo_correction", "lsn_phy_set_candidate_pruning", "lsn_phy_set_stage_c_taps", "lsn_phy_prepare_file", "lsn_phy_get_meta_formats", "lsn_phy_nof_workers", "lsn_phy_worker",
+           "lsn_phy_set_sampling", "lsn_phy_get_sampling", "lsn_symbol_sz", "lsn_sampling_freq_hz", "lsn_cell_search_rates"]
+
+RATES_3GPP, RATES_SRSRAN = 0, 1   # LSN_RATES_*: sampling mode of a Phy / of a cell search
+
+
+def symbol_sz(nof_prb, rates=RATES_3GPP):
+    """samples per OFDM symbol of a capture of this bandwidth in this sampling mode (lsn_symbol_sz); 0: no such bandwidth / mode"""
+    return int(lib().lsn_symbol_sz(int(nof_prb), int(rates)))
+
+
+def sampling_freq_hz(nof_prb, rates=RATES_3GPP):
+    """15 kHz x symbol_sz (lsn_sampling_freq_hz); 0: no such bandwidth / mode"""
+    return int(lib().lsn_sampling_freq_hz(int(nof_prb), int(rates)))
 
 
 def turbo_nwin(K):
@@ -317,6 +330,13 @@ def lib():
         L.lsn_worker_buffers_offset.argtypes = [C.c_void_p]
         L.lsn_worker_buffers_offset.restype = C.POINTER(C.POINTER(C.c_float))
         L.lsn_cell_search.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, C.POINTER(CellSearchCfg), C.POINTER(CellSearch), C.c_void_p]
+        L.lsn_cell_search_rates.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(CellSearchCfg), C.POINTER(CellSearch), C.c_void_p]
+        L.lsn_phy_set_sampling.argtypes = [C.c_void_p, C.c_int]
+        L.lsn_phy_get_sampling.argtypes = [C.c_void_p]
+        L.lsn_symbol_sz.argtypes = [C.c_uint32, C.c_int]
+        L.lsn_symbol_sz.restype = C.c_uint32
+        L.lsn_sampling_freq_hz.argtypes = [C.c_uint32, C.c_int]
+        L.lsn_sampling_freq_hz.restype = C.c_uint32
         _lib = L
     return _lib
 
@@ -450,6 +470,14 @@ class Phy:
             self._user_sink(d, data)
         else:
             self.pdus.append((d, data))
+
+    def set_sampling(self, rates):
+        """sampling mode of the IQ this Phy is handed: RATES_3GPP (default) or RATES_SRSRAN (384 / 768 / 1024 / 1536 samples per symbol at 25 / 50 / 75 / 100 PRB,
+        what the reference records); call it in front of setCell.  False: refused (unknown mode, or another mode than the one the cell was set with)"""
+        return lib().lsn_phy_set_sampling(self._h, int(rates)) == LSN_SUCCESS
+
+    def get_sampling(self):
+        return int(lib().lsn_phy_get_sampling(self._h))
 
     def setCell(self, nof_prb, nof_ports, cell_id, phich_resources=0, cp=0):
         """cp: srsran_cell_t.cp - 0 normal, 1 extended cyclic prefix (downlink path)"""
@@ -742,11 +770,12 @@ class Phy:
             pass
 
 
-def cell_search(iq, nof_prb, nof_periods=2, force_n_id_2=-1, threshold=20.0, device=0, with_corr=False):
+def cell_search(iq, nof_prb, nof_periods=2, force_n_id_2=-1, threshold=20.0, device=0, with_corr=False, rates=RATES_3GPP):
     """rf_search_and_decode_mib of the reference (LTESniffer_Core.cc:195-204) on a block of samples of one antenna:
-    -> (rc, CellSearch[, corr[3, 75 N]]); rc 1 found / 0 not found; iq: numpy complex64 (host) or a torch cuda tensor"""
+    -> (rc, CellSearch[, corr[3, 75 N]]); rc 1 found / 0 not found; iq: numpy complex64 (host) or a torch cuda tensor;
+    rates: sampling mode of iq (RATES_SRSRAN: pss_pos / sf_start count samples of that rate)"""
     import numpy as np
-    N = {6: 128, 15: 256, 25: 512, 50: 1024, 75: 1536, 100: 2048}.get(nof_prb, 128)
+    N = symbol_sz(nof_prb, rates) or 128
     cfg = CellSearchCfg(nof_periods, force_n_id_2, threshold)
     out = CellSearch()
     corr = np.zeros((3, 75 * N), dtype=np.float32) if with_corr else None
@@ -755,7 +784,7 @@ def cell_search(iq, nof_prb, nof_periods=2, force_n_id_2=-1, threshold=20.0, dev
     else:
         iq = np.ascontiguousarray(iq, dtype=np.complex64)
         ptr, n, on_dev = iq.ctypes.data, iq.size, 0
-    rc = _check_n(lib().lsn_cell_search(device, ptr, on_dev, n, nof_prb, C.byref(cfg), C.byref(out), corr.ctypes.data if with_corr else None), "lsn_cell_search")
+    rc = _check_n(lib().lsn_cell_search_rates(device, ptr, on_dev, n, nof_prb, int(rates), C.byref(cfg), C.byref(out), corr.ctypes.data if with_corr else None), "lsn_cell_search")
     return (rc, out, corr) if with_corr else (rc, out)
 
 

@@ -233,6 +233,18 @@ void lsn_phy_destroy(lsn_phy_t* phy)
   delete phy;
 }
 
+int lsn_phy_set_sampling(lsn_phy_t* phy, int rates)
+{
+  if (!phy) return LSN_ERROR_INVALID_INPUTS;
+  const int r = phy->engine->setSampling(rates);  // every engine of a multi handle has the first one's state: one verdict
+  if (r != LSN_SUCCESS) return r;
+  for (auto& e : phy->more) { const int re = e->setSampling(rates); if (re != LSN_SUCCESS) return re; }
+  return LSN_SUCCESS;
+}
+int lsn_phy_get_sampling(lsn_phy_t* phy) { return phy ? phy->engine->sampling() : LSN_ERROR_INVALID_INPUTS; }
+uint32_t lsn_symbol_sz(uint32_t nof_prb, int rates) { return lsn::symbol_size(nof_prb, rates); }
+uint32_t lsn_sampling_freq_hz(uint32_t nof_prb, int rates) { return 15000u * lsn::symbol_size(nof_prb, rates); }
+
 int lsn_phy_set_cell(lsn_phy_t* phy, const lsn_cell_t* cell)
 {
   if (!phy || !cell) return LSN_ERROR_INVALID_INPUTS;
@@ -584,16 +596,21 @@ void lsn_phy_set_prach_sink(lsn_phy_t* phy, lsn_prach_sink_t cb, void* user)
 }
 int lsn_prach_tti_opportunity(uint32_t config_idx, uint32_t tti) { return lsn::prach_tti_opportunity(config_idx, tti) ? 1 : 0; }
 
-int lsn_cell_search(int device, const void* iq, int iq_on_device, uint64_t nof_samples, uint32_t nof_prb, const lsn_cell_search_cfg_t* cfg,
-                    lsn_cell_search_t* out, float* corr_out)
+int lsn_cell_search_rates(int device, const void* iq, int iq_on_device, uint64_t nof_samples, uint32_t nof_prb, int rates, const lsn_cell_search_cfg_t* cfg,
+                          lsn_cell_search_t* out, float* corr_out)
 {
   if (!iq || !cfg || !out) return LSN_ERROR_INVALID_INPUTS;
   try {
-    return lsn::cell_search(device, (const cf32*)iq, iq_on_device != 0, nof_samples, nof_prb, *cfg, *out, corr_out);
+    return lsn::cell_search(device, (const cf32*)iq, iq_on_device != 0, nof_samples, nof_prb, rates, *cfg, *out, corr_out);
   } catch (const std::exception& ex) {
     fprintf(stderr, "ltesniffer_amd: cell search: %s\n", ex.what());
     return LSN_ERROR;
   }
+}
+int lsn_cell_search(int device, const void* iq, int iq_on_device, uint64_t nof_samples, uint32_t nof_prb, const lsn_cell_search_cfg_t* cfg,
+                    lsn_cell_search_t* out, float* corr_out)
+{
+  return lsn_cell_search_rates(device, iq, iq_on_device, nof_samples, nof_prb, LSN_RATES_3GPP, cfg, out, corr_out);
 }
 
 long lsn_phy_tap(lsn_phy_t* phy, int what, uint32_t sf, void* out, size_t cap)

@@ -10,6 +10,7 @@
 #pragma once
 #include "../../../include/ltesniffer_amd.h"
 #include "../kernels/lsn_dev.h"
+#include "lsn_rates.h"
 #include "lsn_search.h"
 #include <atomic>
 #include <condition_variable>
@@ -215,6 +216,15 @@ public:
   ~Engine();
   int setCell(const lsn_cell_t& cell);
   bool hasCell() const { return cell_set; }
+  // sampling mode of the IQ this engine is handed (LSN_RATES_*): read by buildTables, so it is chosen in front of setCell; a configured engine keeps its mode
+  int setSampling(int r)
+  {
+    if (r != LSN_RATES_3GPP && r != LSN_RATES_SRSRAN) return LSN_ERROR_INVALID_INPUTS;
+    if (cell_set && r != rates) return LSN_ERROR_INVALID_INPUTS;
+    rates = r;
+    return LSN_SUCCESS;
+  }
+  int sampling() const { return rates; }
   int process(const void* d_iq, uint32_t nsf, uint32_t start_tti, uint32_t update_meta_period, hipStream_t stream);
   int submit(const void* d_iq, uint32_t nsf, uint32_t start_tti, uint32_t update_meta_period, hipStream_t stream, bool force_meta_first = false);
   // `nrows` = nsf x antennas rows of one subframe each (sflen samples), `row_pitch` bytes apart in PINNED host memory (the worker pool's slab:
@@ -340,6 +350,7 @@ private:
   lsn_phy_cfg_t cfg;
   Cell cell;
   bool cell_set = false;
+  int rates = LSN_RATES_3GPP;
   uint32_t max_batch = 64;
   LsnCellDev cd{};
   std::vector<void*> dev_allocs, host_allocs;
@@ -524,8 +535,8 @@ private:
 };
 
 bool prach_tti_opportunity(uint32_t config_idx, uint32_t tti);  // lsn_prach.cc
-int cell_search(int device, const cf32* iq, bool on_device, uint64_t nsamples, uint32_t nof_prb, const lsn_cell_search_cfg_t& cfg, lsn_cell_search_t& out,
-                float* corr_out);  // lsn_sync.cc
+int cell_search(int device, const cf32* iq, bool on_device, uint64_t nsamples, uint32_t nof_prb, int rates, const lsn_cell_search_cfg_t& cfg,
+                lsn_cell_search_t& out, float* corr_out);  // lsn_sync.cc
 // table builders (lsn_tables.cc)
 void gold_sequence(uint32_t cinit, uint8_t* c, int len);
 

@@ -7,6 +7,7 @@
 // Needs no Phy (the cell is not known yet).  Product code: no CPU fallback, nothing from oracle/ is included or linked.
 #include "../../../include/ltesniffer_amd.h"
 #include "../kernels/lsn_dev.h"
+#include "lsn_rates.h"
 #include <cmath>
 #include <cstring>
 #include <stdexcept>
@@ -30,19 +31,6 @@ struct SyncFin {  // LsnSyncFin of stage_sync.hip
   float y[2][2];
   float hyp[336][2];
 };
-
-static uint32_t sync_fft_size(uint32_t nof_prb)
-{
-  switch (nof_prb) {
-    case 6: return 128;
-    case 15: return 256;
-    case 25: return 512;
-    case 50: return 1024;
-    case 75: return 1536;
-    case 100: return 2048;
-    default: return 0;
-  }
-}
 
 // 36.211 6.11.1.1: d_u(n), the length-63 Zadoff-Chu sequence of root 25 / 29 / 34 without its middle element
 static void pss_sequence(uint32_t n_id_2, cf32* d)
@@ -110,11 +98,11 @@ struct DevBuf {
 };
 }  // namespace
 
-int cell_search(int device, const cf32* iq, bool on_device, uint64_t nsamples, uint32_t nof_prb, const lsn_cell_search_cfg_t& cfg, lsn_cell_search_t& out,
-                float* corr_out)
+int cell_search(int device, const cf32* iq, bool on_device, uint64_t nsamples, uint32_t nof_prb, int rates, const lsn_cell_search_cfg_t& cfg,
+                lsn_cell_search_t& out, float* corr_out)
 {
   std::memset(&out, 0, sizeof out);
-  const uint32_t N = sync_fft_size(nof_prb);
+  const uint32_t N = symbol_size(nof_prb, rates);  // 0 for an unknown bandwidth or sampling mode: refused below
   const uint32_t P = cfg.nof_periods ? cfg.nof_periods : 1;
   if (!iq || !N || P > 16 || cfg.force_n_id_2 > 2 || cfg.force_n_id_2 < -1) return LSN_ERROR_INVALID_INPUTS;
   const uint32_t W5 = 75 * N;

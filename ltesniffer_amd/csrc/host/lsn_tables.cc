@@ -26,9 +26,21 @@ void gold_sequence(uint32_t cinit, uint8_t* c, int len)
   }
 }
 
-static int fft_size_for(uint32_t nprb)
+// samples per OFDM symbol (the sampling rate is 15 kHz times this): TS 36.211 sizes, or the smaller ones srsRAN runs at unless it is built with
+// FORCE_STANDARD_RATE (srsran_symbol_sz).  0: no such bandwidth / mode
+uint32_t symbol_size(uint32_t nprb, int rates)
 {
-  switch (nprb) { case 6: return 128; case 15: return 256; case 25: return 512; case 50: return 1024; case 75: return 1536; case 100: return 2048; default: return -1; }
+  if (rates != LSN_RATES_3GPP && rates != LSN_RATES_SRSRAN) return 0;
+  const bool srs = rates == LSN_RATES_SRSRAN;
+  switch (nprb) {
+    case 6: return 128;
+    case 15: return 256;
+    case 25: return srs ? 384 : 512;
+    case 50: return srs ? 768 : 1024;
+    case 75: return srs ? 1024 : 1536;
+    case 100: return srs ? 1536 : 2048;
+    default: return 0;
+  }
 }
 
 template <typename T>
@@ -203,10 +215,11 @@ void Engine::allocChunk(Chunk& ch)
 void Engine::buildTables()
 {
   const uint32_t nprb = cell.nof_prb, P = cell.nof_ports, id = cell.id;
-  const int N = fft_size_for(nprb);
+  const int N = (int)symbol_size(nprb, rates);
+  if (N <= 0) throw std::runtime_error("no symbol size for this bandwidth and sampling mode");
   cd = LsnCellDev{};
   cd.nof_prb = nprb; cd.nof_ports = P; cd.id = id; cd.nof_rx = dlRx(); cd.iq_nant = cfg.nof_rx_antennas;
-  const int Nsub = N == 1536 ? 512 : N;  // 15 MHz: three interleaved 512-point transforms + a radix-3 combination
+  const int Nsub = N % 3 == 0 ? N / 3 : N;  // 384, 768, 1536: three interleaved power-of-two transforms + a radix-3 combination
   cd.N = (uint32_t)N; cd.nsub = (uint32_t)Nsub; cd.lgN = 0; while ((1 << cd.lgN) < Nsub) cd.lgN++;
   cd.nre = 12 * nprb; cd.nref = 2 * nprb; cd.sflen = 15u * (uint32_t)N;
   cd.cp = cell.cp; cd.nsym = cell.nsym(); cd.nslot = cell.nslot();

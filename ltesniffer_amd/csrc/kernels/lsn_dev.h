@@ -54,12 +54,12 @@ struct LsnChest {
 struct LsnCellDev {
   uint32_t nof_prb, nof_ports, id, nof_rx, N, lgN, nre, nref, sflen;
   uint32_t iq_nant;         // antennas interleaved in the IQ buffer ([sf][antenna][sflen]); nof_rx of them carry the downlink
-  uint32_t nsub;            // power-of-two transform length: N, or 512 when N = 1536 = 3 x 512 (15 MHz); lgN = log2(nsub)
+  uint32_t nsub;            // power-of-two transform length: N, or N / 3 when N = 3 x 2^k (1536 at 3GPP rates; 384, 768, 1536 at srsRAN rates); lgN = log2(nsub)
   uint32_t cp, nsym, nslot; // cyclic prefix (0 normal, 1 extended), symbols per subframe (14 / 12) and per slot (7 / 6).  Grids keep 14 rows per antenna;
                             // an extended-CP subframe fills rows 0 .. 11, rows 12, 13 stay zero (cleared once in setCell)
   uint32_t reg_w6;          // bit l set: the REGs of control symbol l span 6 REs (CRS in the symbol): symbol 0, symbol 1 of a four-port cell, symbol 3 with the extended CP
   const cf32* twiddle;      // [nsub/2] exp(-2 pi i k/nsub)
-  const cf32* twiddle3;     // N = 1536 only: [1536] exp(-2 pi i k/1536) of the radix-3 combination, else null
+  const cf32* twiddle3;     // N = 3 nsub only: [N] exp(-2 pi i k/N) of the radix-3 combination, else null
   const cf32* nco_coarse;   // [4096]
   const cf32* nco_fine;     // [1024]
   const cf32* crs;          // [10][ports][4][nref]; ports 2, 3: rows 0, 1 = symbols 1, 8

@@ -79,8 +79,8 @@ __global__ __launch_bounds__(256) void k_ofdm(LsnCellDev c, const cf32* __restri
   const int nre = (int)c.nre;
   cf32* out = grid + (((size_t)sf * c.nof_rx + rx) * 14 + l) * nre;
   if (c.twiddle3) {
-    // 15 MHz, N = 1536 = 3 x 512: x_r[m] = x[3 m + r] -> three 512-point transforms side by side in LDS, then
-    // X[k] = (F_0[k % 512] + F_1[k % 512] T[k]) + F_2[k % 512] T[2 k mod N] for the 900 carriers that are kept
+    // N = 3 M with M = 128 / 256 / 512 (384, 768, 1536): x_r[m] = x[3 m + r] -> three M-point transforms side by side in LDS, then
+    // X[k] = (F_0[k % M] + F_1[k % M] T[k]) + F_2[k % M] T[2 k mod N] for the carriers that are kept
     const int M = (int)c.nsub;
     for (int n = tid; n < M / 2; n += 256) w[n] = c.twiddle[n];
     for (int n = tid; n < N; n += 256) {
@@ -94,8 +94,11 @@ __global__ __launch_bounds__(256) void k_ofdm(LsnCellDev c, const cf32* __restri
       a[r * M + (int)(__brev((unsigned)m) >> (32 - lgN))] = x;
     }
     __syncthreads();
-    for (int s = 0; s < lgN; s += 3) {  // lgN = 9: three radix-8 passes per block
-      for (int r = 0; r < 3; r++) fft_pass<3>(a + r * M, w, s, M, lgN, tid);
+    for (int s = 0; s < lgN;) {  // the pass split of the power-of-two path below: lgN = 9 is three radix-8 passes per block, 8 = 8, 8, 4 and 7 = 8, 8, 2
+      const int left = lgN - s;
+      if (left >= 3) { for (int r = 0; r < 3; r++) fft_pass<3>(a + r * M, w, s, M, lgN, tid); s += 3; }
+      else if (left == 2) { for (int r = 0; r < 3; r++) fft_pass<2>(a + r * M, w, s, M, lgN, tid); s += 2; }
+      else { for (int r = 0; r < 3; r++) fft_pass<1>(a + r * M, w, s, M, lgN, tid); s += 1; }
       __syncthreads();
     }
     const cf32* __restrict__ T = c.twiddle3;

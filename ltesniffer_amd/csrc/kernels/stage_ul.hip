@@ -57,7 +57,7 @@ __global__ __launch_bounds__(256) void k_ul_fft(LsnCellDev c, const cf32* __rest
   const cf32* in = iq + ((size_t)sf * nant + ant) * c.sflen + pos;
   const int nre = (int)c.nre;
   cf32* out = grid + ((size_t)sf * 14 + l) * nre;
-  if (c.twiddle3) {  // 15 MHz, N = 1536 = 3 x 512 (see k_ofdm)
+  if (c.twiddle3) {  // N = 3 x nsub: 384, 768, 1536 (see k_ofdm)
     const int M = (int)c.nsub;
     for (int n = tid; n < M / 2; n += 256) w[n] = c.twiddle[n];
     for (int n = tid; n < N; n += 256) {
@@ -65,8 +65,11 @@ __global__ __launch_bounds__(256) void k_ul_fft(LsnCellDev c, const cf32* __rest
       a[r * M + (int)(__brev((unsigned)m) >> (32 - lgN))] = cmul(in[n], c.ul_shift[n]);
     }
     __syncthreads();
-    for (int s = 0; s < lgN; s += 3) {
-      for (int r = 0; r < 3; r++) ul_fft_pass<3>(a + r * M, w, s, M, lgN, tid);
+    for (int s = 0; s < lgN;) {
+      const int left = lgN - s;
+      if (left >= 3) { for (int r = 0; r < 3; r++) ul_fft_pass<3>(a + r * M, w, s, M, lgN, tid); s += 3; }
+      else if (left == 2) { for (int r = 0; r < 3; r++) ul_fft_pass<2>(a + r * M, w, s, M, lgN, tid); s += 2; }
+      else { for (int r = 0; r < 3; r++) ul_fft_pass<1>(a + r * M, w, s, M, lgN, tid); s += 1; }
       __syncthreads();
     }
     const cf32* __restrict__ T = c.twiddle3;
