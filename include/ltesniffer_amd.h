@@ -312,6 +312,57 @@ int lsn_phy_process_file(lsn_phy_t* phy, const char* path, const lsn_file_cfg_t*
  * nof_antennas = lsn_file_cfg_t.nof_antennas of the replay. */
 int lsn_phy_prepare_file(lsn_phy_t* phy, uint32_t nof_antennas);
 
+/* ---- recordings made at any sample rate: polyphase resampler on the GPU ----
+ * Output sample m sits at input position P0 + m * D, D = round(rate_in / rate_out * 2^64), a 64.64 fixed-point number formed in 128-bit
+ * integers: a sample is a function of (input, configuration, m) and of nothing else - not of block sizes or call boundaries.  The rates are
+ * doubles, so a recording whose clock is off by a KNOWN amount replays correctly when the true rate is given (open loop: nothing tracks).
+ * Filter: Kaiser-windowed sinc, cut-off min(rate_in, rate_out) / 2, 80 dB design attenuation, pass band |f| <= passband_hz, stop band from
+ * min(rate_in, rate_out) - passband_hz; the number of taps follows from the width between the two.  Refused (LSN_ERROR_INVALID_INPUTS): rate_in >
+ * 4 rate_out, a pass band the lower rate cannot carry with at most 192 taps (min(rate_in, rate_out) below about 2.06 passband_hz when up-sampling),
+ * a struct_size the library does not know, rates that are zero, negative or not finite.
+ *
+ * lsn_resample: needs no Phy.  in: [sample][antenna] in sample_format, in[0] = sample in_base of the recording; out: [antenna][n_out] cf32,
+ * out[0] = output sample out_first.  Output sample 0 sits at first_sample + first_frac.  Samples in front of sample 0 of the recording read as
+ * zeros; every other sample the outputs read must lie inside in (lsn_resample_span tells which), otherwise LSN_ERROR_INVALID_INPUTS.  A caller
+ * that resamples a long recording in pieces keeps first_sample / first_frac, moves in_base and out_first, and gets the samples of one call bit for bit. */
+typedef struct {
+  uint32_t struct_size;      /* sizeof(lsn_resample_cfg_t): the library refuses a size it does not know */
+  uint32_t nof_antennas;     /* interleaved in the input */
+  uint32_t sample_format;    /* LSN_FILE_* */
+  float    sample_scale;     /* as lsn_file_cfg_t */
+  double   rate_in_hz, rate_out_hz;
+  uint64_t first_sample;     /* input position of output sample 0: integer part ... */
+  double   first_frac;       /* ... and fraction, 0 <= f < 1 */
+  uint64_t in_base;          /* index, in the recording, of in[0] */
+  uint64_t out_first;        /* index m of out[0] */
+  double   passband_hz;      /* |f| that must come through unharmed: 15 kHz * (6 nof_prb + 1) for an LTE cell; 0 = 0.44 min(rate_in, rate_out) */
+} lsn_resample_cfg_t;
+typedef struct {
+  int64_t in_lo, in_hi;      /* outputs out_first .. out_first + n_out - 1 read the input samples in_lo <= n < in_hi (in_lo < 0: zeros) */
+  uint64_t max_out;          /* number of outputs from out_first on whose samples all lie in front of in_end */
+  uint32_t taps, reserved;   /* T: products per output */
+} lsn_resample_span_t;
+int lsn_resample(int device, const void* in, int in_on_device, uint64_t n_in, const lsn_resample_cfg_t* cfg, float* out /* [antenna][n_out] cf32 */,
+                 int out_on_device, uint64_t n_out);
+int lsn_resample_span(const lsn_resample_cfg_t* cfg, uint64_t n_out, uint64_t in_end /* samples in the recording */, lsn_resample_span_t* out);
+
+/* lsn_phy_process_file on a recording made at sample_rate_hz: the reader fetches, for every block of output subframes, the input samples the block
+ * reads, and the resampler takes the place of the format conversion (same formats, same -o rotation on the output samples).  Output rate:
+ * lsn_sampling_freq_hz(nof_prb, sampling mode of the Phy); pass band 15 kHz * (6 nof_prb + 1).  The start of subframe 0 is input position
+ * cfg->offset_time_samples + offset_time_frac; lsn_cell_search on a resampled head gives sf_start in OUTPUT samples: multiply by sample_rate_hz /
+ * output rate.  Only subframes whose whole input lies inside the file are produced.  The block buffers are those of lsn_phy_prepare_file: when
+ * sample_rate_hz is above the output rate a block carries fewer subframes so that its input fits (LSN_FILE_BLOCK too small for one subframe's
+ * input: LSN_ERROR_INVALID_INPUTS).  sample_rate_hz equal to the output rate with a zero fraction is lsn_phy_process_file.  A rate outside the
+ * accepted range (above), a wrong struct_size: LSN_ERROR_INVALID_INPUTS, nothing is decoded. */
+typedef struct {
+  uint32_t struct_size;
+  uint32_t reserved;
+  double   sample_rate_hz;     /* rate of the file; the output rate is lsn_sampling_freq_hz(nof_prb, the Phy's sampling mode) */
+  double   offset_time_frac;   /* added to cfg->offset_time_samples (both in INPUT samples); >= 0 */
+} lsn_file_rate_t;
+int lsn_phy_process_file_rate(lsn_phy_t* phy, const char* path, const lsn_file_cfg_t* cfg, const lsn_file_rate_t* rate, uint32_t start_tti, uint64_t max_subframes,
+                              uint32_t update_meta_period, uint64_t* subframes_done);
+
 /* ---- security-API sink (the step behind the path: PDSCH_Decoder::run_api_dl_mode, DL_Sniffer_PDSCH.cc:804-879) ----
  * api_mode as ArgManager's -a (ArgManager.cc:63,218): -1 off (default), 0 identity mapping, 2 IMSI catching, 3 all.  For every CRC-ok
  * downlink block the writer thread reports, in record order: paging records (modes 2, 3; decode_imsi_tmsi_paging :84-127: IMSI as 15

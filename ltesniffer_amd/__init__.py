@@ -39,7 +39,8 @@ EXPORTS = ["lsn_phy_create", "lsn_phy_destroy", "lsn_phy_set_cell", "lsn_phy_get
            "lsn_phy_set_shortcut_discovery", "lsn_phy_get_shortcut_discovery", "lsn_phy_set_histogram_threshold", "lsn_phy_print_stats",
            "lsn_phy_set_mcs_update_interval", "lsn_phy_update_mcs_database", "lsn_phy_nof_tracked_rnti", "lsn_worker_buffers_offset", "lsn_pcap_digest", "lsn_pcap_set_store", "lsn_pcap_set_digest_blocks", "lsn_pcap_block_digests", "lsn_phy_create_multi", "lsn_phy_nof_devices",
            "lsn_phy_set_cfo_correction", "lsn_phy_get_cfo_correction", "lsn_phy_set_candidate_pruning", "lsn_phy_set_stage_c_taps", "lsn_phy_prepare_file", "lsn_phy_get_meta_formats", "lsn_phy_nof_workers", "lsn_phy_worker",
-           "lsn_phy_set_sampling", "lsn_phy_get_sampling", "lsn_symbol_sz", "lsn_sampling_freq_hz", "lsn_cell_search_rates"]
+           "lsn_phy_set_sampling", "lsn_phy_get_sampling", "lsn_symbol_sz", "lsn_sampling_freq_hz", "lsn_cell_search_rates",
+           "lsn_resample", "lsn_resample_span", "lsn_phy_process_file_rate"]
 
 RATES_3GPP, RATES_SRSRAN = 0, 1   # LSN_RATES_*: sampling mode of a Phy / of a cell search
 
@@ -99,6 +100,20 @@ class FileCfg(C.Structure):
 
 
 FILE_CF32, FILE_SC16, FILE_SC8 = 0, 1, 2
+
+
+class FileRate(C.Structure):   # lsn_file_rate_t
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("sample_rate_hz", C.c_double), ("offset_time_frac", C.c_double)]
+
+
+class ResampleCfg(C.Structure):   # lsn_resample_cfg_t
+    _fields_ = [("struct_size", C.c_uint32), ("nof_antennas", C.c_uint32), ("sample_format", C.c_uint32), ("sample_scale", C.c_float),
+                ("rate_in_hz", C.c_double), ("rate_out_hz", C.c_double), ("first_sample", C.c_uint64), ("first_frac", C.c_double),
+                ("in_base", C.c_uint64), ("out_first", C.c_uint64), ("passband_hz", C.c_double)]
+
+
+class ResampleSpan(C.Structure):   # lsn_resample_span_t
+    _fields_ = [("in_lo", C.c_int64), ("in_hi", C.c_int64), ("max_out", C.c_uint64), ("taps", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class ApiEvent(C.Structure):
@@ -314,6 +329,9 @@ def lib():
         L.lsn_phy_mib_decode_llr.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(Mib), C.c_void_p]
         L.lsn_phy_process_file.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(FileCfg), C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]
         L.lsn_phy_prepare_file.argtypes = [C.c_void_p, C.c_uint32]
+        L.lsn_phy_process_file_rate.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(FileCfg), C.POINTER(FileRate), C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]
+        L.lsn_resample.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.POINTER(ResampleCfg), C.c_void_p, C.c_int, C.c_uint64]
+        L.lsn_resample_span.argtypes = [C.POINTER(ResampleCfg), C.c_uint64, C.c_uint64, C.POINTER(ResampleSpan)]
         L.lsn_phy_set_prach_config.argtypes = [C.c_void_p, C.POINTER(PrachCfg)]
         L.lsn_phy_prach_detect.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(PrachDet), C.c_uint32]
         L.lsn_phy_set_prach_sink.argtypes = [C.c_void_p, PRACH_SINK, C.c_void_p]
@@ -570,11 +588,19 @@ class Phy:
         """reserve the file source's block buffers ahead of the first replay (lsn_phy_prepare_file)"""
         _check(lib().lsn_phy_prepare_file(self._h, self.nof_rx_antennas), "prepare_file")
 
-    def process_file(self, path, start_tti=0, offset_time=0, offset_freq=0.0, max_subframes=0, update_meta_period=0, sample_format=FILE_CF32, sample_scale=0.0):
+    def process_file(self, path, start_tti=0, offset_time=0, offset_freq=0.0, max_subframes=0, update_meta_period=0, sample_format=FILE_CF32, sample_scale=0.0,
+                     sample_rate=None, offset_time_frac=0.0):
         """file mode of the reference (-i file -O offset_time -o offset_freq): replay a cf32 capture (antennas interleaved per sample);
-        sample_format FILE_SC16 / FILE_SC8: integer I/Q pairs, one LSB = sample_scale (0: full scale +-1); returns the number of subframes processed"""
+        sample_format FILE_SC16 / FILE_SC8: integer I/Q pairs, one LSB = sample_scale (0: full scale +-1); returns the number of subframes processed.
+        sample_rate (Hz): the file was recorded at this rate and goes through the GPU resampler (lsn_phy_process_file_rate); offset_time and
+        offset_time_frac then count samples of the FILE's rate"""
         fc = FileCfg(self.nof_rx_antennas, int(offset_time), float(offset_freq), int(sample_format), float(sample_scale))
         done = C.c_uint64(0)
+        if sample_rate is not None:
+            fr = FileRate(C.sizeof(FileRate), 0, float(sample_rate), float(offset_time_frac))
+            _check(lib().lsn_phy_process_file_rate(self._h, os.fsencode(path), C.byref(fc), C.byref(fr), start_tti if start_tti == TTI_FROM_MIB else start_tti % 10240,
+                                                   max_subframes, update_meta_period, C.byref(done)), "process_file_rate")
+            return int(done.value)
         _check(lib().lsn_phy_process_file(self._h, os.fsencode(path), C.byref(fc), start_tti if start_tti == TTI_FROM_MIB else start_tti % 10240, max_subframes, update_meta_period, C.byref(done)),
                "process_file")
         return int(done.value)
@@ -786,6 +812,43 @@ def cell_search(iq, nof_prb, nof_periods=2, force_n_id_2=-1, threshold=20.0, dev
         ptr, n, on_dev = iq.ctypes.data, iq.size, 0
     rc = _check_n(lib().lsn_cell_search_rates(device, ptr, on_dev, n, nof_prb, int(rates), C.byref(cfg), C.byref(out), corr.ctypes.data if with_corr else None), "lsn_cell_search")
     return (rc, out, corr) if with_corr else (rc, out)
+
+
+def _resample_cfg(nof_antennas, rate_in, rate_out, first_sample, first_frac, in_base, out_first, passband_hz, sample_format, sample_scale):
+    return ResampleCfg(C.sizeof(ResampleCfg), int(nof_antennas), int(sample_format), float(sample_scale), float(rate_in), float(rate_out), int(first_sample),
+                       float(first_frac), int(in_base), int(out_first), float(passband_hz))
+
+
+def resample_span(n_out, in_end, rate_in, rate_out, first_sample=0, first_frac=0.0, out_first=0, passband_hz=0.0):
+    """lsn_resample_span -> dict(in_lo, in_hi, max_out, taps): the input samples [in_lo, in_hi) that outputs out_first .. out_first + n_out - 1 read, and the
+    number of outputs from out_first on that a recording of in_end samples carries"""
+    cfg = _resample_cfg(1, rate_in, rate_out, first_sample, first_frac, 0, out_first, passband_hz, FILE_CF32, 0.0)
+    sp = ResampleSpan()
+    _check(lib().lsn_resample_span(C.byref(cfg), int(n_out), int(in_end), C.byref(sp)), "lsn_resample_span")
+    return dict(in_lo=int(sp.in_lo), in_hi=int(sp.in_hi), max_out=int(sp.max_out), taps=int(sp.taps))
+
+
+def resample(iq, rate_in, rate_out, n_out=None, first_sample=0, first_frac=0.0, in_base=0, out_first=0, passband_hz=0.0, sample_format=FILE_CF32,
+             sample_scale=0.0, device=0):
+    """lsn_resample (GPU polyphase resampler, needs no Phy).  iq: [sample][antenna] (or [sample]: one antenna) numpy complex64, or int16 / int8 with a last
+    axis of 2 (I, Q) for FILE_SC16 / FILE_SC8; iq[0] is sample in_base of the recording.  Output sample m sits at input position first_sample + first_frac +
+    m rate_in / rate_out; the call returns outputs out_first .. out_first + n_out - 1 as complex64 [antenna][n_out] (n_out None: as many as iq carries).
+    passband_hz: 15 kHz * (6 nof_prb + 1) for an LTE cell."""
+    import numpy as np
+    iq = np.ascontiguousarray(iq)
+    pairs = sample_format != FILE_CF32
+    if iq.ndim == (2 if pairs else 1):
+        iq = iq.reshape(iq.shape[0], 1, *iq.shape[1:])
+    iq = np.ascontiguousarray(iq, dtype=(np.complex64, np.int16, np.int8)[sample_format])
+    n_in, nant = iq.shape[0], iq.shape[1]
+    cfg = _resample_cfg(nant, rate_in, rate_out, first_sample, first_frac, in_base, out_first, passband_hz, sample_format, sample_scale)
+    if n_out is None:
+        sp = ResampleSpan()
+        _check(lib().lsn_resample_span(C.byref(cfg), 0, int(in_base) + n_in, C.byref(sp)), "lsn_resample_span")
+        n_out = int(sp.max_out)
+    out = np.zeros((nant, n_out), dtype=np.complex64)
+    _check(lib().lsn_resample(device, iq.ctypes.data, 0, n_in, C.byref(cfg), out.ctypes.data, 0, n_out), "lsn_resample")
+    return out
 
 
 def mac_lte_record(ctx, pdu):

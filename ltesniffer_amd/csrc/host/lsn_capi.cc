@@ -533,6 +533,13 @@ int lsn_phy_process_file(lsn_phy_t* phy, const char* path, const lsn_file_cfg_t*
   if (!phy || !path || !cfg) return LSN_ERROR_INVALID_INPUTS;
   return phy->engine->processFile(path, *cfg, start_tti, max_subframes, update_meta_period, subframes_done);
 }
+int lsn_phy_process_file_rate(lsn_phy_t* phy, const char* path, const lsn_file_cfg_t* cfg, const lsn_file_rate_t* rate, uint32_t start_tti, uint64_t max_subframes,
+                              uint32_t update_meta_period, uint64_t* subframes_done)
+{
+  if (subframes_done) *subframes_done = 0;
+  if (!phy || !path || !cfg || !rate) return LSN_ERROR_INVALID_INPUTS;
+  return phy->engine->processFileRate(path, *cfg, *rate, start_tti, max_subframes, update_meta_period, subframes_done);
+}
 int lsn_phy_prepare_file(lsn_phy_t* phy, uint32_t nof_antennas)
 {
   if (!phy) return LSN_ERROR_INVALID_INPUTS;

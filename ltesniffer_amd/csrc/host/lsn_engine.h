@@ -240,6 +240,8 @@ public:
   int mibDecode(const void* iq, bool on_device, lsn_mib_t* out, float* llr_raw480);
   int processFile(const char* path, const lsn_file_cfg_t& fc, uint32_t start_tti, uint64_t max_subframes, uint32_t update_meta_period,
                   uint64_t* subframes_done);
+  int processFileRate(const char* path, const lsn_file_cfg_t& fc, const lsn_file_rate_t& fr, uint32_t start_tti, uint64_t max_subframes, uint32_t update_meta_period,
+                      uint64_t* subframes_done);   // lsn_phy_process_file_rate: the same through the polyphase resampler (lsn_resample.h)
   int reserveFileBuffers(uint32_t nof_antennas);   // lsn_phy_prepare_file: pinned read blocks + device blocks of the file source, ahead of the first replay
   int processHost(const void* iq, uint32_t nsf, uint32_t start_tti, uint32_t update_meta_period, uint32_t sample_format = 0 /* LSN_FILE_* */, float sample_scale = 0.0f);
   void setSink(lsn_pdu_sink_t cb, void* user) { sink = cb; sink_user = user; }
@@ -486,6 +488,9 @@ private:
   int buildUlTables(const lsn_ul_cfg_t& u);             // DMRS base sequences, n_PN, u(ns) / v(ns), hopping offset: the device side of setUlConfig
   void syncUlConfig();                                    // commit turn: pick up a configuration another engine (or the caller) has set since
   // device / pinned blocks of the file source, kept between lsn_phy_process_file calls (allocating them costs more than replaying a short capture)
+  // the one replay loop behind processFile (rs == nullptr) and processFileRate (rs: the resampler's plan, lsn_resample.h)
+  int processFileImpl(const char* path, const lsn_file_cfg_t& fc, const struct ResamplePlan* rs, uint32_t start_tti, uint64_t max_subframes, uint32_t update_meta_period,
+                      uint64_t* subframes_done);
   struct FileBuf { cf32* h_raw = nullptr; cf32* d_raw = nullptr; cf32* d_iq = nullptr; size_t bytes = 0; };
   FileBuf file_buf[8];
   std::atomic<uint32_t>& ul_cfg_epoch = sh->ul_cfg_epoch;  // bumped by every (re)configuration: chunks whose DCI 0 grants were converted earlier are converted again at commit

@@ -10,6 +10,7 @@
 // and crosses PCIe straight from the page cache; on the boxes measured the lock / unlock per block costs more than the copy it saves.
 // Product code: no CPU fallback, nothing from oracle/ is included or linked.
 #include "lsn_engine.h"
+#include "lsn_resample.h"
 #include <chrono>
 #include <deque>
 #include <cmath>
@@ -76,6 +77,31 @@ int Engine::reserveFileBuffers(uint32_t nof_antennas)
 int Engine::processFile(const char* path, const lsn_file_cfg_t& fc, uint32_t start_tti, uint64_t max_subframes, uint32_t update_meta_period,
                         uint64_t* subframes_done)
 {
+  return processFileImpl(path, fc, nullptr, start_tti, max_subframes, update_meta_period, subframes_done);
+}
+
+// lsn_phy_process_file_rate: a recording made at fr.sample_rate_hz.  The plan (step, start, taps, bank: lsn_resample.cc) is made here, in front of
+// everything else, so that a rate the filter does not meet is refused before a byte is read.
+int Engine::processFileRate(const char* path, const lsn_file_cfg_t& fc, const lsn_file_rate_t& fr, uint32_t start_tti, uint64_t max_subframes,
+                            uint32_t update_meta_period, uint64_t* subframes_done)
+{
+  if (subframes_done) *subframes_done = 0;
+  if (!cell_set) return LSN_ERROR;
+  if (fr.struct_size != sizeof(lsn_file_rate_t) || fc.offset_time_samples < 0 || !(fr.offset_time_frac >= 0.0 && fr.offset_time_frac < 4.0e18)) return LSN_ERROR_INVALID_INPUTS;
+  const double rate_out = 15000.0 * (double)cd.N, whole = std::floor(fr.offset_time_frac);
+  if (fr.sample_rate_hz == rate_out && fr.offset_time_frac == 0.0) return processFileImpl(path, fc, nullptr, start_tti, max_subframes, update_meta_period, subframes_done);
+  const uint64_t first = (uint64_t)fc.offset_time_samples + (uint64_t)whole;
+  ResamplePlan plan;
+  const int r = plan.init(fr.sample_rate_hz, rate_out, 15000.0 * (6.0 * (double)cd.nof_prb + 1.0), first, fr.offset_time_frac - whole);
+  if (r != LSN_SUCCESS) return r;
+  return processFileImpl(path, fc, &plan, start_tti, max_subframes, update_meta_period, subframes_done);
+}
+
+// rs: the resampler's plan (processFileRate), or null: the file is at the engine's rate.  With a plan, block k of OUTPUT subframes is fed from the input
+// samples it reads (ResamplePlan::inputSpan - neighbouring blocks overlap by the filter length), and k_resample takes the place of k_file_unpack.
+int Engine::processFileImpl(const char* path, const lsn_file_cfg_t& fc, const ResamplePlan* rs, uint32_t start_tti, uint64_t max_subframes, uint32_t update_meta_period,
+                            uint64_t* subframes_done)
+{
   if (subframes_done) *subframes_done = 0;
   if (!cell_set) return LSN_ERROR;
   if (!path || fc.nof_antennas != cd.iq_nant || fc.offset_time_samples < 0 || fc.sample_format > LSN_FILE_SC8) return LSN_ERROR_INVALID_INPUTS;
@@ -93,7 +119,28 @@ int Engine::processFile(const char* path, const lsn_file_cfg_t& fc, uint32_t sta
   int NSLOT;          // blocks in flight (round 2 held eight until their chunks were written - and paid 8 x 393 MB of pinned allocation on the first call)
   file_geometry(blk, nrd, NSLOT);
   const uint64_t file_off0 = (uint64_t)fc.offset_time_samples * nant * smp_bytes;
-  const uint64_t sf_in_file = (uint64_t)sb.st_size > file_off0 ? ((uint64_t)sb.st_size - file_off0) / sf_bytes : 0;  // complete subframes only
+  uint64_t sf_in_file = (uint64_t)sb.st_size > file_off0 ? ((uint64_t)sb.st_size - file_off0) / sf_bytes : 0;  // complete subframes only
+  const size_t spb = (size_t)nant * smp_bytes;  // bytes of one sample of all antennas
+  if (rs) {
+    sf_in_file = rs->outputsInside((uint64_t)sb.st_size / spb) / sflen;  // output subframes whose whole input span lies inside the file
+    // the block buffers are sized for blk subframes of cf32 at the OUTPUT rate: a block carries as many subframes as have their input fit
+    const u128 cap = (u128)blk * sflen * sizeof(cf32) / smp_bytes;
+    const u128 fit = cap > rs->taps + 2 ? ((cap - rs->taps - 2) << 64) / ((u128)sflen * rs->step) : 0;
+    if (fit == 0) { close(fd); return LSN_ERROR_INVALID_INPUTS; }
+    if (fit < blk) blk = (uint32_t)fit;
+  }
+  // input of the output subframes [pos, pos + n): first sample (zeros in front of the file are the kernel's), number of samples
+  auto rs_span = [&](uint64_t pos, uint64_t n, int64_t& lo, uint64_t& len) {
+    int64_t hi;
+    rs->inputSpan(pos * sflen, n * sflen, lo, hi);
+    lo = std::max<int64_t>(lo, 0);
+    len = hi > lo ? (uint64_t)(hi - lo) : 0;
+  };
+  auto rs_launch = [&](const void* raw, int64_t lo, uint64_t len, uint64_t pos, uint32_t n, const float* bank, const cf32* rot, cf32* out, hipStream_t s) {
+    const u128 base = rs->position(pos * sflen);
+    lsn_launch_resample(raw, fmt, smp_scale, lo, len, (uint64_t)(base >> 64), (uint64_t)base, (uint32_t)(rs->step >> 64), (uint64_t)rs->step, rs->taps, rs->span, bank, rot,
+                        sflen, 0, nant, out, (uint64_t)n * sflen, s);
+  };
   constexpr int NSLOT_MAX = 8;
   const bool fdebug = getenv("LSN_FILE_DEBUG") != nullptr;
   auto tnow = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -111,6 +158,7 @@ int Engine::processFile(const char* path, const lsn_file_cfg_t& fc, uint32_t sta
     use_mmap = false;
   }
   cf32* d_rot = nullptr;
+  float* d_bank = nullptr;  // the resampler's bank (a few hundred kB, as short-lived as d_rot)
   hipStream_t st = nullptr;
   std::mutex fm;
   std::condition_variable fcv;
@@ -138,15 +186,24 @@ int Engine::processFile(const char* path, const lsn_file_cfg_t& fc, uint32_t sta
       HIP_CHECK(hipMalloc((void**)&d_rot, sflen * sizeof(cf32)));
       HIP_CHECK(hipMemcpy(d_rot, rot.data(), sflen * sizeof(cf32), hipMemcpyHostToDevice));
     }
+    if (rs) {
+      HIP_CHECK(hipMalloc((void**)&d_bank, rs->bank.size() * sizeof(float)));
+      HIP_CHECK(hipMemcpy(d_bank, rs->bank.data(), rs->bank.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
     uint64_t first_sf = 0;  // subframes of the file in front of the replay (DECODE_MIB state of the reference)
     if (start_tti == LSN_TTI_FROM_MIB) {
       bool found = false;
       for (uint64_t i = 0; i < sf_in_file && i < 10 * 64; i += 10) {  // the file starts at subframe 0 of a radio frame (file mode has no sync)
-        std::vector<uint8_t> one(sf_bytes);
-        if (pread(fd, one.data(), sf_bytes, (off_t)(file_off0 + i * sf_bytes)) != (ssize_t)sf_bytes) break;
-        HIP_CHECK(hipMemcpyAsync(slot[0].d_raw, one.data(), sf_bytes, hipMemcpyHostToDevice, st));
+        int64_t lo = 0;
+        uint64_t len = sflen;
+        if (rs) rs_span(i, 1, lo, len);
+        const size_t bytes = rs ? (size_t)len * spb : sf_bytes;
+        std::vector<uint8_t> one(bytes);
+        if (pread(fd, one.data(), bytes, (off_t)(rs ? (uint64_t)lo * spb : file_off0 + i * sf_bytes)) != (ssize_t)bytes) break;
+        HIP_CHECK(hipMemcpyAsync(slot[0].d_raw, one.data(), bytes, hipMemcpyHostToDevice, st));
         HIP_CHECK(hipStreamSynchronize(st));
-        lsn_launch_file_unpack(slot[0].d_raw, fmt, smp_scale, d_rot, sflen, nant, slot[0].d_iq, 1, st);
+        if (rs) rs_launch(slot[0].d_raw, lo, len, i, 1, d_bank, d_rot, slot[0].d_iq, st);
+        else lsn_launch_file_unpack(slot[0].d_raw, fmt, smp_scale, d_rot, sflen, nant, slot[0].d_iq, 1, st);
         HIP_CHECK(hipStreamSynchronize(st));
         lsn_mib_t mib;
         const int r = mibDecode(slot[0].d_iq, true, &mib, nullptr);
@@ -172,11 +229,15 @@ int Engine::processFile(const char* path, const lsn_file_cfg_t& fc, uint32_t sta
           const double tb0 = tnow();
           if (s.reg) { (void)hipHostUnregister(s.reg); s.reg = nullptr; }  // the block this slot carried last has been committed
           if (got) {
-            const size_t total = got * sf_bytes, part = (total / nrd + 4095) & ~(size_t)4095;
+            int64_t in_lo = 0;   // resampler: the block's input samples [in_lo, in_lo + in_len)
+            uint64_t in_len = 0;
+            if (rs) rs_span(pos, got, in_lo, in_len);
+            const size_t total = rs ? (size_t)in_len * spb : got * sf_bytes, part = (total / nrd + 4095) & ~(size_t)4095;
+            const uint64_t boff = rs ? (uint64_t)in_lo * spb : file_off0 + pos * sf_bytes;  // first byte of the block in the file
             const uint8_t* src = nullptr;
             if (use_mmap) {
               // fault the pages of the block in (page-cache hits: a page-table walk per page; otherwise this is the read-ahead), then lock them
-              const uint8_t* b = map + file_off0 + pos * sf_bytes;
+              const uint8_t* b = map + boff;
               uint8_t* lo = (uint8_t*)((uintptr_t)b & ~(uintptr_t)(page - 1));
               const size_t len = (size_t)(b + total - lo);
               (void)madvise(lo, len, MADV_WILLNEED);
@@ -207,7 +268,7 @@ int Engine::processFile(const char* path, const lsn_file_cfg_t& fc, uint32_t sta
                 rd.emplace_back([&, r, b0, b1] {
                   size_t o = b0;
                   while (o < b1) {
-                    const ssize_t k = pread(fd, (char*)s.h_raw + o, b1 - o, (off_t)(file_off0 + pos * sf_bytes + o));
+                    const ssize_t k = pread(fd, (char*)s.h_raw + o, b1 - o, (off_t)(boff + o));
                     if (k <= 0) { bad[r] = 1; return; }
                     o += (size_t)k;
                   }
@@ -220,8 +281,9 @@ int Engine::processFile(const char* path, const lsn_file_cfg_t& fc, uint32_t sta
             }
             // the copy and the de-interleave are only QUEUED here (stream st); the submit below is ordered behind them on the device, so
             // the reader goes straight on to the next block while this one crosses PCIe
-            HIP_CHECK(hipMemcpyAsync(s.d_raw, src, got * sf_bytes, hipMemcpyHostToDevice, st));
-            lsn_launch_file_unpack(s.d_raw, fmt, smp_scale, d_rot, sflen, nant, s.d_iq, (uint32_t)got, st);
+            HIP_CHECK(hipMemcpyAsync(s.d_raw, src, total, hipMemcpyHostToDevice, st));
+            if (rs) rs_launch(s.d_raw, in_lo, in_len, pos, (uint32_t)got, d_bank, d_rot, s.d_iq, st);
+            else lsn_launch_file_unpack(s.d_raw, fmt, smp_scale, d_rot, sflen, nant, s.d_iq, (uint32_t)got, st);
             pos += got;
           }
           left -= got;
@@ -283,6 +345,7 @@ int Engine::processFile(const char* path, const lsn_file_cfg_t& fc, uint32_t sta
     if (s.reg) (void)hipHostUnregister(s.reg);
   }
   if (d_rot) (void)hipFree(d_rot);
+  if (d_bank) (void)hipFree(d_bank);
   if (st) (void)hipStreamDestroy(st);
   if (map) munmap(map, (size_t)sb.st_size);
   close(fd);

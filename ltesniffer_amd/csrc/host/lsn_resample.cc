@@ -1,0 +1,176 @@
+// lsn_resample.cc - host side of the polyphase resampler: the plan of a rate pair (step and start in 64.64 fixed point, formed in 128-bit
+// integers; number of taps; the bank of 512 phases) and lsn_resample, the stand-alone entry point (needs no Phy, like lsn_cell_search).
+// The filter is DESIGN.md section 3.1b, restated there as a formula; tests/resample_model.py is written from that formula, not from this file.
+// Product code: no CPU fallback (the samples are computed by k_resample only), nothing from oracle/ is included or linked.
+#include "../../../include/ltesniffer_amd.h"
+#include "../kernels/lsn_dev.h"
+#include "lsn_resample.h"
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <stdexcept>
+#include <string>
+
+#define HIP_CHECK(x)                                                                                       \
+  do {                                                                                                     \
+    hipError_t _e = (x);                                                                                   \
+    if (_e != hipSuccess) throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(_e) + " at " #x); \
+  } while (0)
+
+namespace lsn {
+
+static constexpr double kAtten = 80.0;                          // design attenuation A of the Kaiser window, dB
+static constexpr double kBeta = 0.1102 * (kAtten - 8.7);        // Kaiser's beta for A > 50
+static constexpr uint32_t kPhases = 512, kMaxTaps = 192, kRun = 512;  // kRun = LSN_RS_RUN of the kernel
+
+static double bessel_i0(double x)
+{
+  double s = 1.0, t = 1.0;
+  const double q = x * x / 4.0;
+  for (int k = 1; k < 200; k++) {
+    t *= q / ((double)k * (double)k);
+    s += t;
+    if (t < 1e-20 * s) break;
+  }
+  return s;
+}
+
+int ResamplePlan::init(double rate_in, double rate_out, double passband_hz, uint64_t first_sample, double first_frac)
+{
+  if (!(rate_in > 0.0 && rate_in < 1e12) || !(rate_out > 0.0 && rate_out < 1e12)) return LSN_ERROR_INVALID_INPUTS;
+  if (!(first_frac >= 0.0 && first_frac < 1.0) || first_sample >= (1ull << 62)) return LSN_ERROR_INVALID_INPUTS;
+  const double ratio = rate_in / rate_out;
+  if (!(ratio <= 4.0 && ratio >= 1.0 / 65536.0)) return LSN_ERROR_INVALID_INPUTS;
+  const double lo_rate = std::min(rate_in, rate_out), rho = std::max(1.0, ratio);
+  if (passband_hz == 0.0) passband_hz = 0.44 * lo_rate;
+  if (!(passband_hz > 0.0)) return LSN_ERROR_INVALID_INPUTS;
+  const double width = (lo_rate - 2.0 * passband_hz) / rate_in;   // transition band [B, min(rate) - B], in cycles per input sample
+  if (!(width > 0.0)) return LSN_ERROR_INVALID_INPUTS;
+  const double want = (kAtten - 7.95) / (14.36 * width) + 1.0;    // Kaiser's estimate of the filter length
+  if (!(want <= (double)kMaxTaps)) return LSN_ERROR_INVALID_INPUTS;
+  taps = std::max(4u, 2u * (uint32_t)std::ceil(want / 2.0));
+  // D = round(rate_in / rate_out * 2^64), exactly: the two doubles are integers ma 2^(ea - 53), mb 2^(eb - 53)
+  int ea = 0, eb = 0;
+  const uint64_t ma = (uint64_t)std::ldexp(std::frexp(rate_in, &ea), 53), mb = (uint64_t)std::ldexp(std::frexp(rate_out, &eb), 53);
+  const int sh = 65 + ea - eb;   // 47 .. 68 for the accepted ratios: ma << sh stays below 2^121
+  if (sh < 0 || sh > 70) return LSN_ERROR_INVALID_INPUTS;
+  step = (((u128)ma << sh) + (u128)mb) / ((u128)mb << 1);
+  if (step == 0) return LSN_ERROR_INVALID_INPUTS;
+  start = ((u128)first_sample << 64) + (u128)(uint64_t)std::ldexp(first_frac, 64);
+  span = (uint32_t)(((u128)kRun * step) >> 64) + taps + 2;
+  // bank: H[p][j] = h(j - T/2 + 1 - p / 512), h(t) = sinc(t / rho) / rho * I0(beta sqrt(1 - (2 t / T)^2)) / I0(beta)
+  const double i0b = bessel_i0(kBeta), half = 0.5 * (double)taps;
+  auto h = [&](double t) {
+    const double u = t / half;
+    if (u < -1.0 || u > 1.0) return 0.0;
+    const double w = bessel_i0(kBeta * std::sqrt(std::max(0.0, 1.0 - u * u))) / i0b, a = M_PI * t / rho;
+    return (a == 0.0 ? 1.0 : std::sin(a) / a) / rho * w;
+  };
+  bank.assign((size_t)kPhases * taps * 2, 0.0f);
+  for (uint32_t p = 0; p < kPhases; p++)
+    for (uint32_t j = 0; j < taps; j++) {
+      const double t0 = (double)j - half + 1.0 - (double)p / kPhases, t1 = (double)j - half + 1.0 - (double)(p + 1) / kPhases;
+      const double h0 = h(t0), h1 = h(t1);
+      bank[((size_t)p * taps + j) * 2] = (float)h0;
+      bank[((size_t)p * taps + j) * 2 + 1] = (float)(h1 - h0);
+    }
+  return LSN_SUCCESS;
+}
+
+void ResamplePlan::inputSpan(uint64_t m0, uint64_t n, int64_t& lo, int64_t& hi) const
+{
+  const int64_t half = (int64_t)taps / 2;
+  lo = (int64_t)(uint64_t)(position(m0) >> 64) - half + 1;
+  hi = (int64_t)(uint64_t)(position(m0 + (n ? n - 1 : 0)) >> 64) + half + 1;
+}
+
+uint64_t ResamplePlan::outputsInside(uint64_t in_end) const
+{
+  const uint64_t half = taps / 2;
+  if (in_end <= half || in_end >= (1ull << 62)) return 0;
+  const u128 lim = (u128)(in_end - half) << 64;   // positions below lim read no sample at or behind in_end
+  if (start >= lim) return 0;
+  const u128 n = (lim - 1 - start) / step + 1;
+  return n > (u128)(1ull << 62) ? (1ull << 62) : (uint64_t)n;
+}
+
+}  // namespace lsn
+
+static int resample_plan(const lsn_resample_cfg_t* cfg, lsn::ResamplePlan& plan)
+{
+  if (!cfg || cfg->struct_size != sizeof(lsn_resample_cfg_t)) return LSN_ERROR_INVALID_INPUTS;
+  if (cfg->nof_antennas < 1 || cfg->nof_antennas > 8 || cfg->sample_format > LSN_FILE_SC8) return LSN_ERROR_INVALID_INPUTS;
+  if (cfg->sample_format != LSN_FILE_CF32 && !(cfg->sample_scale >= 0.0f && cfg->sample_scale < INFINITY)) return LSN_ERROR_INVALID_INPUTS;
+  return plan.init(cfg->rate_in_hz, cfg->rate_out_hz, cfg->passband_hz, cfg->first_sample, cfg->first_frac);
+}
+
+extern "C" {
+
+int lsn_resample_span(const lsn_resample_cfg_t* cfg, uint64_t n_out, uint64_t in_end, lsn_resample_span_t* out)
+{
+  lsn::ResamplePlan plan;
+  const int r = resample_plan(cfg, plan);
+  if (r != LSN_SUCCESS || !out) return r != LSN_SUCCESS ? r : LSN_ERROR_INVALID_INPUTS;
+  if (cfg->out_first >= (1ull << 40) || n_out >= (1ull << 40)) return LSN_ERROR_INVALID_INPUTS;
+  memset(out, 0, sizeof(*out));
+  out->taps = plan.taps;
+  plan.inputSpan(cfg->out_first, n_out, out->in_lo, out->in_hi);
+  const uint64_t inside = plan.outputsInside(in_end);
+  out->max_out = inside > cfg->out_first ? inside - cfg->out_first : 0;
+  return LSN_SUCCESS;
+}
+
+int lsn_resample(int device, const void* in, int in_on_device, uint64_t n_in, const lsn_resample_cfg_t* cfg, float* out, int out_on_device, uint64_t n_out)
+{
+  lsn::ResamplePlan plan;
+  const int r = resample_plan(cfg, plan);
+  if (r != LSN_SUCCESS) return r;
+  if (!n_out) return LSN_SUCCESS;
+  if (!in || !out || n_out >= (1ull << 32) || cfg->out_first >= (1ull << 40) || cfg->in_base >= (1ull << 62) || n_in >= (1ull << 62)) return LSN_ERROR_INVALID_INPUTS;
+  int64_t lo, hi;
+  plan.inputSpan(cfg->out_first, n_out, lo, hi);
+  if (hi >= (int64_t)1 << 62) return LSN_ERROR_INVALID_INPUTS;
+  const int64_t need_lo = std::max<int64_t>(lo, 0);   // in front of the recording: zeros
+  if (need_lo < (int64_t)cfg->in_base || hi > (int64_t)(cfg->in_base + n_in)) return LSN_ERROR_INVALID_INPUTS;   // the input does not hold what these outputs read
+  const uint32_t nant = cfg->nof_antennas, fmt = cfg->sample_format;
+  const size_t smp = (fmt == LSN_FILE_SC16 ? 4 : fmt == LSN_FILE_SC8 ? 2 : sizeof(cf32)) * (size_t)nant;
+  const float scale = fmt == LSN_FILE_CF32 ? 1.0f : cfg->sample_scale != 0.0f ? cfg->sample_scale : fmt == LSN_FILE_SC16 ? 1.0f / 32768.0f : 1.0f / 128.0f;
+  const uint64_t len = hi > need_lo ? (uint64_t)(hi - need_lo) : 0;
+  const uint8_t* src = (const uint8_t*)in + ((uint64_t)need_lo - cfg->in_base) * smp;
+  void *d_in = nullptr, *d_bank = nullptr, *d_out = nullptr;
+  hipStream_t st = nullptr;
+  int rc = LSN_SUCCESS;
+  try {
+    HIP_CHECK(hipSetDevice(device));
+    HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    HIP_CHECK(hipMalloc(&d_bank, plan.bank.size() * sizeof(float)));
+    HIP_CHECK(hipMemcpyAsync(d_bank, plan.bank.data(), plan.bank.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    const void* raw = src;
+    if (!in_on_device && len) {
+      HIP_CHECK(hipMalloc(&d_in, len * smp));
+      HIP_CHECK(hipMemcpyAsync(d_in, src, len * smp, hipMemcpyHostToDevice, st));
+      raw = d_in;
+    }
+    cf32* dst = (cf32*)out;
+    const size_t out_bytes = (size_t)n_out * nant * sizeof(cf32);
+    if (!out_on_device) {
+      HIP_CHECK(hipMalloc(&d_out, out_bytes));
+      dst = (cf32*)d_out;
+    }
+    const lsn::u128 base = plan.position(cfg->out_first);
+    lsn_launch_resample(raw, fmt, scale, need_lo, len, (uint64_t)(base >> 64), (uint64_t)base, (uint32_t)(plan.step >> 64), (uint64_t)plan.step, plan.taps, plan.span,
+                        (const float*)d_bank, nullptr, (uint32_t)n_out, 0, nant, dst, n_out, st);
+    if (!out_on_device) HIP_CHECK(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+  } catch (const std::exception& ex) {
+    fprintf(stderr, "ltesniffer_amd: resample: %s\n", ex.what());
+    rc = LSN_ERROR;
+  }
+  if (st) (void)hipStreamDestroy(st);
+  if (d_in) (void)hipFree(d_in);
+  if (d_bank) (void)hipFree(d_bank);
+  if (d_out) (void)hipFree(d_out);
+  return rc;
+}
+
+}  // extern "C"

@@ -1,0 +1,34 @@
+// lsn_resample.h - host side of the polyphase resampler (kernels/resample.hip): the plan of one rate pair - step, start, taps, bank - and the
+// 64.64 position arithmetic in 128-bit integers.  Definition: DESIGN.md section 3.1b.
+#pragma once
+#include <cstdint>
+#include <vector>
+#include <hip/hip_runtime.h>
+
+struct cf32;
+
+namespace lsn {
+
+typedef unsigned __int128 u128;
+
+struct ResamplePlan {
+  u128 step = 0;       // D = round(rate_in / rate_out * 2^64)
+  u128 start = 0;      // P0: position of output sample 0
+  uint32_t taps = 0;   // T (even)
+  uint32_t span = 0;   // input samples one run of the kernel stages
+  std::vector<float> bank;  // [512][T][2]: H[p][j] and H[p + 1][j] - H[p][j], float32 (row 511 reaches phase 512 through its difference)
+
+  // LSN_SUCCESS, or LSN_ERROR_INVALID_INPUTS when the pair is outside what the filter meets (accepted range)
+  int init(double rate_in, double rate_out, double passband_hz, uint64_t first_sample, double first_frac);
+  u128 position(uint64_t m) const { return start + (u128)m * step; }
+  // input samples [lo, hi) that outputs m0 .. m0 + n - 1 read (lo may be negative: zeros in front of the recording)
+  void inputSpan(uint64_t m0, uint64_t n, int64_t& lo, int64_t& hi) const;
+  // number of outputs m = 0, 1, ... whose taps all lie in front of input sample in_end
+  uint64_t outputsInside(uint64_t in_end) const;
+};
+
+}  // namespace lsn
+
+void lsn_launch_resample(const void* raw, uint32_t fmt, float scale, int64_t buf_base, uint64_t buf_len, uint64_t base_hi, uint64_t base_lo, uint32_t d_hi,
+                         uint64_t d_lo, uint32_t taps, uint32_t span, const float* bank, const cf32* rot, uint32_t sflen, uint32_t sf_off, uint32_t nant, cf32* out,
+                         uint64_t n_out, hipStream_t s);

@@ -1,0 +1,114 @@
+// resample.hip - polyphase Kaiser-windowed-sinc resampler of the file source and of lsn_resample (gfx950).  The filter, the bank and the
+// position arithmetic are defined in DESIGN.md section 3.1b; the host side (plan, bank, spans) is host/lsn_resample.cc.
+//
+// Output sample m of a replay sits at input position P0 + m * D, a 64.64 fixed-point number (integer part = input sample index, 64 bits of
+// fraction).  The launch is handed the position of ITS first output (base = P0 + m0 * D, formed on the host in 128-bit integers) and D; a
+// lane forms i * D with a 64 x 64 -> 128 multiply and adds.  Integer arithmetic throughout: an output is a function of the input, the
+// configuration and m alone - not of the block, the run or the launch it was computed in.
+//
+// One workgroup produces LSN_RS_RUN consecutive outputs of one antenna.  It stages the input span of the run (floor(RUN * D) + T + 1
+// samples, converted to float while loading, zeros in front of input sample 0 and outside the buffer) in LDS as [sample] float2, then every
+// lane runs the T taps of its outputs: coefficient j = H[p][j] + f * dH[p][j] (p = top 9 bits of the fraction, f = the next 24 bits), one
+// 16-byte load of the bank row gives two taps, one ds_read_b64 per sample.  Up-sampling and equal rates: neighbouring lanes read the
+// same or neighbouring float2 (broadcast / conflict free); down-sampling by r strides the lanes by r float2 = a 2- to 4-way conflict.
+#include "lsn_dev.h"
+
+#define LSN_RS_RUN 512u      // outputs per workgroup (256 lanes x 2)
+
+struct LsnResampleArgs {
+  const void* raw;       // input, [sample][antenna], element 0 = input sample buf_base of the recording
+  int64_t buf_base;      // >= 0
+  uint64_t buf_len;      // samples (per antenna) in raw
+  uint64_t base_hi, base_lo;  // position of the launch's output 0
+  uint64_t d_lo;         // D: fraction ...
+  uint32_t d_hi;         // ... and integer part (0 .. 4)
+  uint32_t taps;         // T, even
+  uint32_t span;         // samples staged per run (the LDS request is span * 8 bytes)
+  uint32_t nant;
+  uint32_t sflen;        // outputs per antenna row: launch output i goes to out[((i / sflen) * nant + a) * sflen + i % sflen]
+  uint32_t sf_off;       // phase of launch output 0 inside its row (0 for the file source: launches start on a subframe)
+  uint64_t n_out;        // outputs of the launch, per antenna
+  float scale;
+  const float2* bank;    // [512][T] (H, dH)
+  const cf32* rot;       // optional [sflen]
+  cf32* out;
+};
+
+template <int FMT>
+__global__ __launch_bounds__(256) void k_resample(const LsnResampleArgs A)
+{
+  extern __shared__ float2 rs_x[];
+  const uint32_t a = blockIdx.y, half = A.taps / 2;
+  const uint64_t i0 = (uint64_t)blockIdx.x * LSN_RS_RUN;
+  // position of the run's first output: base + i0 * D
+  uint64_t lo = i0 * A.d_lo, hi = __umul64hi(i0, A.d_lo) + i0 * (uint64_t)A.d_hi;
+  lo += A.base_lo;
+  hi += A.base_hi + (lo < A.base_lo ? 1u : 0u);
+  const int64_t n_lo = (int64_t)hi - (int64_t)half + 1;  // input sample staged at rs_x[0]
+  for (uint32_t s = threadIdx.x; s < A.span; s += 256) {
+    const int64_t n = n_lo + (int64_t)s, k = n - A.buf_base;
+    float2 x = make_float2(0.0f, 0.0f);
+    if (n >= 0 && k >= 0 && (uint64_t)k < A.buf_len) {
+      const size_t src = (size_t)k * A.nant + a;
+      if (FMT == 1) {
+        const short2 q = ((const short2*)A.raw)[src];
+        x.x = (float)q.x * A.scale; x.y = (float)q.y * A.scale;
+      } else if (FMT == 2) {
+        const char2 q = ((const char2*)A.raw)[src];
+        x.x = (float)q.x * A.scale; x.y = (float)q.y * A.scale;
+      } else {
+        x = ((const float2*)A.raw)[src];
+      }
+    }
+    rs_x[s] = x;
+  }
+  __syncthreads();
+  for (uint32_t r = 0; r < LSN_RS_RUN / 256; r++) {
+    const uint64_t i = i0 + r * 256 + threadIdx.x;
+    if (i >= A.n_out) break;
+    uint64_t plo = i * A.d_lo, phi = __umul64hi(i, A.d_lo) + i * (uint64_t)A.d_hi;
+    plo += A.base_lo;
+    phi += A.base_hi + (plo < A.base_lo ? 1u : 0u);
+    const uint32_t s0 = (uint32_t)((int64_t)phi - (int64_t)half + 1 - n_lo);   // first of the T staged samples of this output
+    const uint32_t p = (uint32_t)(plo >> 55);                                  // 9 bits of phase
+    const float f = (float)(uint32_t)((plo >> 31) & 0xFFFFFFu) * 0x1p-24f;      // 24 bits inside the phase, exact
+    if (s0 + A.taps > A.span) continue;                                        // cannot happen (the host sizes span); keeps the LDS reads inside
+    const float4* row = (const float4*)(A.bank + (size_t)p * A.taps);
+    const float2* x = rs_x + s0;
+    float yr = 0.0f, yi = 0.0f;
+    for (uint32_t j = 0; j < half; j++) {
+      const float4 c = row[j];
+      const float c0 = __builtin_fmaf(f, c.y, c.x), c1 = __builtin_fmaf(f, c.w, c.z);
+      const float2 x0 = x[2 * j], x1 = x[2 * j + 1];
+      yr = __builtin_fmaf(c0, x0.x, yr); yi = __builtin_fmaf(c0, x0.y, yi);
+      yr = __builtin_fmaf(c1, x1.x, yr); yi = __builtin_fmaf(c1, x1.y, yi);
+    }
+    const uint32_t q = (uint32_t)i + A.sf_off, sf = q / A.sflen, n = q - sf * A.sflen;   // the launcher keeps n_out + sf_off below 2^32
+    cf32 y; y.r = yr; y.i = yi;
+    if (A.rot) {
+      const cf32 w = A.rot[n];
+      cf32 z; z.r = y.r * w.r - y.i * w.i; z.i = y.r * w.i + y.i * w.r;
+      y = z;
+    }
+    A.out[((size_t)sf * A.nant + a) * A.sflen + n] = y;
+  }
+}
+
+// n_out outputs per antenna from output position (base_hi, base_lo); span = samples a run of LSN_RS_RUN outputs needs (host: lsn_resample.cc)
+void lsn_launch_resample(const void* raw, uint32_t fmt, float scale, int64_t buf_base, uint64_t buf_len, uint64_t base_hi, uint64_t base_lo, uint32_t d_hi,
+                         uint64_t d_lo, uint32_t taps, uint32_t span, const float* bank, const cf32* rot, uint32_t sflen, uint32_t sf_off, uint32_t nant, cf32* out,
+                         uint64_t n_out, hipStream_t s)
+{
+  if (!n_out) return;
+  if (taps < 2 || (taps & 1) || span < taps || (size_t)span * sizeof(float2) > 64 * 1024 || buf_base < 0 || !sflen) throw std::runtime_error("k_resample: bad geometry");
+  const uint64_t runs = (n_out + LSN_RS_RUN - 1) / LSN_RS_RUN;
+  if (runs > 0x7FFFFFFFull || n_out + sf_off > 0xFFFFFFFFull) throw std::runtime_error("k_resample: launch too long");
+  LsnResampleArgs A;
+  A.raw = raw; A.buf_base = buf_base; A.buf_len = buf_len; A.base_hi = base_hi; A.base_lo = base_lo; A.d_lo = d_lo; A.d_hi = d_hi; A.taps = taps; A.span = span;
+  A.nant = nant; A.sflen = sflen; A.sf_off = sf_off; A.n_out = n_out; A.scale = scale; A.bank = (const float2*)bank; A.rot = rot; A.out = out;
+  const dim3 g((uint32_t)runs, nant);
+  const size_t lds = (size_t)span * sizeof(float2);
+  if (fmt == 1) LSN_LAUNCH(k_resample<1>, g, dim3(256), lds, s, A);
+  else if (fmt == 2) LSN_LAUNCH(k_resample<2>, g, dim3(256), lds, s, A);
+  else LSN_LAUNCH(k_resample<0>, g, dim3(256), lds, s, A);
+}
