@@ -595,27 +595,6 @@ int Engine::newJob(Chunk& ch, uint32_t sf, const DlEntry& e, int table, float p_
   return (int)ch.jobs.size() - 1;
 }
 
-template <typename T>
-static void grow_dev(T*& p, size_t& cap, size_t need, hipStream_t st)
-{
-  if (need <= cap) return;
-  if (getenv("LSN_HOST_DEBUG")) fprintf(stderr, "grow_dev: %zu -> %zu elements of %zu B\n", cap, need + need / 2 + 1024, sizeof(T));
-  HIP_CHECK(hipStreamSynchronize(st));
-  if (p) HIP_CHECK(hipFree(p));
-  cap = need + need / 2 + 1024;
-  HIP_CHECK(hipMalloc((void**)&p, cap * sizeof(T)));
-}
-template <typename T>
-static void grow_host(T*& p, size_t& cap, size_t need, hipStream_t st)
-{
-  if (need <= cap) return;
-  if (getenv("LSN_HOST_DEBUG")) fprintf(stderr, "grow_host: %zu -> %zu elements of %zu B\n", cap, need + need / 2 + 1024, sizeof(T));
-  HIP_CHECK(hipStreamSynchronize(st));
-  if (p) HIP_CHECK(hipHostFree(p));
-  cap = need + need / 2 + 1024;
-  HIP_CHECK(hipHostMalloc((void**)&p, cap * sizeof(T), hipHostMallocCoherent | hipHostMallocMapped));
-}
-
 void Engine::runJobs(Chunk& ch, JobRunner& r, std::vector<int>& ids)
 {
   std::vector<int> todo;
@@ -672,31 +651,11 @@ void Engine::runJobs(Chunk& ch, JobRunner& r, std::vector<int>& ids)
       CbSegm s;
       const int Qm = tb.mod, G = tb.nof_bits, NL = g.tx_scheme == TXSCHEME_DIVERSITY ? 2 : 1;
       if (!cbsegm(tb.tbs, s) || Qm <= 0 || G <= 0) continue;
-      const int Gp = G / (NL * Qm), gamma = Gp % s.C;
       j.payload_off[i] = (uint32_t)pay_n;
       TbRef ref{jid, i, (uint32_t)r.h_cbs.size(), (uint32_t)s.C};
-      int rp = 0;
-      uint32_t wp = 0;
-      for (int q = 0; q < s.C; q++) {
-        LsnCbDev cb{};
-        const int K = q < s.Cm ? s.Km : s.Kp, F = q == 0 ? s.F : 0;
-        int E = (q <= s.C - gamma - 1) ? NL * Qm * (Gp / s.C) : NL * Qm * ((Gp + s.C - 1) / s.C);
-        if (rp + E > G) E = G - rp;
-        cb.e_off = d.llr_off[tb.cw_idx & 1] + (uint32_t)rp; cb.E = (uint32_t)E; cb.K = (uint32_t)K; cb.F = (uint32_t)F; cb.rv = (uint32_t)tb.rv;
-        cb.crc_b = s.C > 1 ? 1u : 0u;
-        cb.out_bytes = (uint32_t)(K - F - (s.C > 1 ? 24 : 0)) / 8;
-        cb.out_off = (uint32_t)(pay_n - pay0) + wp;
-        cb.il_off = turbo_il_offset(K);
-        cb.nwin = turbo_nwin(K);
-        cb.max_iter = (uint32_t)cfg.max_turbo_iterations;
-        // code blocks 1 .. C-1 are launched behind block 0 and skipped when it failed (the TB CRC verdict needs every block)
-        cb.dep = (q > 0 && cb_skip) ? (uint32_t)(r.h_cbs.size() - (size_t)q) : LSN_CB_NODEP;
-        wp += cb.out_bytes;
-        rp += E;
-        r.h_cbs.push_back(cb);
-      }
+      // code blocks 1 .. C-1 are launched behind block 0 and skipped when it failed (the TB CRC verdict needs every block)
+      pay_n += tb_code_blocks(s, G, Qm, NL, tb.rv, (uint32_t)cfg.max_turbo_iterations, d.llr_off[tb.cw_idx & 1], (uint32_t)(pay_n - pay0), cb_skip, r.h_cbs);
       j.cb_count[i] = (uint32_t)s.C;
-      pay_n += (wp + 15) & ~15u;
       tbrefs.push_back(ref);
       pf.nof_tb_decodes++;
       if (tbs_from_derived_rows(tb.tbs, g.nof_prb)) pf.nof_tb_on_derived_tbs++;
@@ -862,25 +821,17 @@ void Engine::runJobs(Chunk& ch, JobRunner& r, std::vector<int>& ids)
     // remainders), parity word non-zero
     for (auto& t : tbrefs) {
       DecodeJob& j = ch.jobs[t.job];
-      bool all_ok = true;
-      uint32_t rem = 0;
-      uint64_t bits_after = 0;
-      uint32_t shift = 1;   // x^bits_after mod g, carried along: one or two multiplications per block instead of a modular power
+      TbVerdict v;
       for (int q = (int)t.cb_count - 1; q >= 0; q--) {
         const LsnCbRes& cr = r.h_cbres_pinned[t.cb_first + q];
-        all_ok = all_ok && cr.ok != 0;
+        v.add(cr.ok != 0, cr.rem_a, r.h_cbs[t.cb_first + q].out_bytes);
         j.iters += cr.iters;
         pf.nof_turbo_iterations += cr.iters; pf.nof_turbo_iterations_run += cr.iters_run;
         pf.turbo_cyc_rm += cr.cyc_rm; pf.turbo_cyc_map += cr.cyc_map; pf.turbo_cyc_out += cr.cyc_out;
-        rem ^= bits_after ? crc24a_mulmod(cr.rem_a, shift) : (cr.rem_a & 0xFFFFFFu);
-        const uint32_t nb = r.h_cbs[t.cb_first + q].out_bytes;
-        bits_after += 8ull * nb;
-        if (q > 0) shift = crc24a_mulmod(shift, crc24a_xpow_bytes(nb));
       }
       const int tbs = j.grant.tb[t.tb].tbs;
       const uint8_t* pl = ch.h_payload.data() + j.payload_off[t.tb];
-      const uint32_t par = ((uint32_t)pl[tbs / 8] << 16) | ((uint32_t)pl[tbs / 8 + 1] << 8) | pl[tbs / 8 + 2];
-      j.crc[t.tb] = all_ok && rem == 0 && par != 0 && bits_after == (uint64_t)tbs + 24;
+      j.crc[t.tb] = v.pass(pl, tbs);
       if (cfg.harq_mode) {  // per-block verdicts of this transmission, next to the kept soft data (harqStore / harqCombinedDecode)
         if (ch.keep_res.size() < ch.keep_cbs.size()) ch.keep_res.resize(ch.keep_cbs.size());
         for (uint32_t q = 0; q < t.cb_count && j.keep_count[t.tb] == t.cb_count; q++) ch.keep_res[j.keep_first[t.tb] + q] = r.h_cbres_pinned[t.cb_first + q];
@@ -1480,22 +1431,11 @@ void Engine::harqRunBatch(Chunk& ch, JobRunner& r, const std::vector<HarqReq>& r
   grow_dev(r.d_payload, r.payload_cap, (size_t)out + 16, st);
   grow_host(r.h_payload_pinned, r.h_payload_cap, (size_t)out + 16, st);
   // launch order: two-wavefront class first, each class by descending size (the longest first); results stay addressable through res_idx
-  std::vector<uint32_t> order(nd);
-  for (uint32_t i = 0; i < nd; i++) order[i] = i;
-  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-    const bool ca = turbo_nwin((int)cbs[a].K) > 64 || cbs[a].K > LSN_TURBO_ONE_WAVE_KMAX, cb2 = turbo_nwin((int)cbs[b].K) > 64 || cbs[b].K > LSN_TURBO_ONE_WAVE_KMAX;
-    if (ca != cb2) return ca;
-    return cbs[a].K > cbs[b].K;
-  });
-  uint32_t n128 = 0, kmax128 = 0, kmax64 = 0;
-  for (uint32_t i = 0; i < nd; i++) {
-    const LsnCbDev& c = cbs[order[i]];
-    r.h_cbs_pinned[i] = c;
-    if (lsn_turbo_two_wave_class((int)c.K)) { n128++; kmax128 = std::max(kmax128, c.K); } else kmax64 = std::max(kmax64, c.K);
-  }
+  const TurboOrder to = turbo_classic_order(cbs);
+  for (uint32_t i = 0; i < nd; i++) r.h_cbs_pinned[i] = cbs[to.order[i]];
   lsn_launch_upload(r.d_cbs, r.h_cbs_pinned, nd * sizeof(LsnCbDev), st);
   lsn_launch_harq_combine(r.d_cbs, nd, ch.d_keep, d_harq_pool, d_harq_scratch, false, st);
-  lsn_launch_turbo(cd, r.d_cbs, d_harq_scratch, r.d_payload, r.d_cbres, n128, kmax128, nd - n128, kmax64, st, nullptr);
+  lsn_launch_turbo(cd, r.d_cbs, d_harq_scratch, r.d_payload, r.d_cbres, to.n128, to.kmax128, nd - to.n128, to.kmax64, st);
   {
     LsnCopySegs dn;   // verdicts + payload bytes down in one launch
     dn.add(r.h_cbres_pinned, r.d_cbres, nd * sizeof(LsnCbRes));
@@ -1618,14 +1558,9 @@ void Engine::harqScout(Chunk& ch, std::vector<HarqReq>& out, bool first_pass)
             }
           }
           if (have) {  // the verdict as far as the scout can tell (every block passed, CRC24A over the blocks; the parity-word and length tests are the walk's)
-            bool all_ok = true;
-            uint32_t rem = 0, shift = 1;
-            for (int b = (int)n - 1; b >= 0; b--) {
-              all_ok = all_ok && v.ok[b];
-              rem ^= b == (int)n - 1 ? (v.rem_a[b] & 0xFFFFFFu) : crc24a_mulmod(v.rem_a[b], shift);
-              if (b > 0) shift = crc24a_mulmod(shift, crc24a_xpow_bytes(ch.keep_cbs[ch.jobs[j].keep_first[tb] + b].out_bytes));
-            }
-            crc = all_ok && rem == 0;
+            TbVerdict tv;
+            for (int b = (int)n - 1; b >= 0; b--) tv.add(v.ok[b] != 0, v.rem_a[b], ch.keep_cbs[ch.jobs[j].keep_first[tb] + b].out_bytes);
+            crc = tv.all_ok && tv.rem == 0;
           }
         }
       }
@@ -1685,17 +1620,9 @@ bool Engine::harqCombinedDecode(Chunk& ch, JobRunner& r, int job, int tb, size_t
     harq_touched.push_back(slot);
   }
   // transport-block verdict, as in runJobs: every block passed (now or in an earlier transmission), CRC24A over the assembled blocks
-  bool all_ok = true;
-  uint32_t rem = 0, total = 0, shift = 1;   // shift = x^bits_after mod g, carried along (as in runJobs)
-  uint64_t bits_after = 0;
-  for (int b = (int)n - 1; b >= 0; b--) {
-    const bool okb = hk.ok[b] || (dn && dn->ok[b] != 0);
-    all_ok = all_ok && okb;
-    rem ^= bits_after ? crc24a_mulmod(hk.rem_a[b], shift) : (hk.rem_a[b] & 0xFFFFFFu);
-    const uint32_t nb = ch.keep_cbs[j.keep_first[tb] + b].out_bytes;
-    bits_after += 8ull * nb;
-    if (b > 0) shift = crc24a_mulmod(shift, crc24a_xpow_bytes(nb));
-  }
+  TbVerdict v;
+  uint32_t total = 0;
+  for (int b = (int)n - 1; b >= 0; b--) v.add(hk.ok[b] || (dn && dn->ok[b] != 0), hk.rem_a[b], ch.keep_cbs[j.keep_first[tb] + b].out_bytes);
   for (uint32_t b = 0; b < n; b++) total += (uint32_t)hk.bytes[b].size();
   const int tbs = j.grant.tb[tb].tbs;
   payload_off = (uint32_t)ch.h_payload.size();
@@ -1706,10 +1633,8 @@ bool Engine::harqCombinedDecode(Chunk& ch, JobRunner& r, int job, int tb, size_t
   }
   for (uint32_t b = 0; b < n; b++)
     if (!hk.ok[b] && dn && dn->ok[b]) hk.ok[b] = 1;
-  const uint8_t* pl = ch.h_payload.data() + payload_off;
-  if ((uint64_t)total * 8ull < (uint64_t)tbs + 24ull) return false;
-  const uint32_t par = ((uint32_t)pl[tbs / 8] << 16) | ((uint32_t)pl[tbs / 8 + 1] << 8) | pl[tbs / 8 + 2];
-  return all_ok && rem == 0 && par != 0 && bits_after == (uint64_t)tbs + 24;
+  if ((uint64_t)total * 8ull < (uint64_t)tbs + 24ull) return false;   // (the bytes on record are fewer than the block: no parity word to read)
+  return v.pass(ch.h_payload.data() + payload_off, tbs);
 }
 
 // decode threads: each takes the next chunk of the queue, plans and runs its PDSCH decodes on its own streams and hands the chunk

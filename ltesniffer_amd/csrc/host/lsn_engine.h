@@ -13,6 +13,8 @@
 #include "lsn_rates.h"
 #include "lsn_search.h"
 #include <atomic>
+#include <cstdio>
+#include <cstdlib>
 #include <condition_variable>
 #include <deque>
 #include <map>
@@ -23,6 +25,33 @@
 #include <vector>
 
 namespace lsn {
+
+// Lazy growth of the job runners' arenas (device memory / pinned, mapped host mirrors): waits for the one stream that uses the buffer, then replaces it by
+// one of need + 50 % + 1024 elements; the contents are not kept
+inline void hip_check(hipError_t e, const char* what)
+{
+  if (e != hipSuccess) throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e) + " at " + what);
+}
+template <typename T>
+void grow_dev(T*& p, size_t& cap, size_t need, hipStream_t st)
+{
+  if (need <= cap) return;
+  if (getenv("LSN_HOST_DEBUG")) fprintf(stderr, "grow_dev: %zu -> %zu elements of %zu B\n", cap, need + need / 2 + 1024, sizeof(T));
+  hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
+  if (p) hip_check(hipFree(p), "hipFree");
+  cap = need + need / 2 + 1024;
+  hip_check(hipMalloc((void**)&p, cap * sizeof(T)), "hipMalloc");
+}
+template <typename T>
+void grow_host(T*& p, size_t& cap, size_t need, hipStream_t st)
+{
+  if (need <= cap) return;
+  if (getenv("LSN_HOST_DEBUG")) fprintf(stderr, "grow_host: %zu -> %zu elements of %zu B\n", cap, need + need / 2 + 1024, sizeof(T));
+  hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
+  if (p) hip_check(hipHostFree(p), "hipHostFree");
+  cap = need + need / 2 + 1024;
+  hip_check(hipHostMalloc((void**)&p, cap * sizeof(T), hipHostMallocCoherent | hipHostMallocMapped), "hipHostMalloc");
+}
 
 struct DecodeJob {
   uint32_t sf = 0; PdschGrant grant; uint16_t rnti = 0;

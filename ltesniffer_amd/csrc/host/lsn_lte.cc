@@ -610,6 +610,47 @@ bool cbsegm(int tbs, CbSegm& s)
   s.F = s.Cp * s.Kp + s.Cm * s.Km - Bp;
   return true;
 }
+uint32_t tb_code_blocks(const CbSegm& s, int G, int Qm, int NL, int rv, uint32_t max_iter, uint32_t e_off, uint32_t out_off, bool dep_first, std::vector<LsnCbDev>& cbs)
+{
+  const int Gp = G / (NL * Qm), gamma = Gp % s.C;
+  const uint32_t first = (uint32_t)cbs.size();
+  int rp = 0;
+  uint32_t wp = 0;
+  for (int q = 0; q < s.C; q++) {
+    LsnCbDev cb{};
+    const int K = q < s.Cm ? s.Km : s.Kp, F = q == 0 ? s.F : 0;
+    int E = (q <= s.C - gamma - 1) ? NL * Qm * (Gp / s.C) : NL * Qm * ((Gp + s.C - 1) / s.C);
+    if (rp + E > G) E = G - rp;
+    cb.e_off = e_off + (uint32_t)rp; cb.E = (uint32_t)E; cb.K = (uint32_t)K; cb.F = (uint32_t)F; cb.rv = (uint32_t)rv;
+    cb.crc_b = s.C > 1 ? 1u : 0u;
+    cb.out_bytes = (uint32_t)(K - F - (s.C > 1 ? 24 : 0)) / 8;
+    cb.out_off = out_off + wp;
+    cb.il_off = turbo_il_offset(K);
+    cb.nwin = turbo_nwin(K);
+    cb.max_iter = max_iter;
+    cb.dep = (q > 0 && dep_first) ? first : LSN_CB_NODEP;
+    wp += cb.out_bytes;
+    rp += E;
+    cbs.push_back(cb);
+  }
+  return (wp + 15) & ~15u;
+}
+TurboOrder turbo_classic_order(const std::vector<LsnCbDev>& cbs)
+{
+  TurboOrder o;
+  o.order.resize(cbs.size());
+  for (uint32_t i = 0; i < cbs.size(); i++) o.order[i] = i;
+  std::sort(o.order.begin(), o.order.end(), [&](uint32_t x, uint32_t y) {
+    const uint32_t kx = cbs[x].K, ky = cbs[y].K;
+    const bool bx = lsn_turbo_two_wave_class((int)kx), by = lsn_turbo_two_wave_class((int)ky);
+    if (bx != by) return bx;
+    if (kx != ky) return kx > ky;
+    return x < y;
+  });
+  for (const LsnCbDev& c : cbs)
+    if (lsn_turbo_two_wave_class((int)c.K)) { o.n128++; o.kmax128 = std::max(o.kmax128, c.K); } else o.kmax64 = std::max(o.kmax64, c.K);
+  return o;
+}
 uint32_t turbo_il_offset(int K)
 {
   // called once per code block by the decode threads: a table indexed by K / 8, built on first use (thread-safe static initialisation)

@@ -11,6 +11,7 @@
 #include <memory>
 #include <string>
 #include <vector>
+#include "lsn_types.h"
 
 namespace lsn {
 
@@ -100,6 +101,15 @@ bool cbsegm(int tbs, CbSegm& s);
 bool qpp_params(int K, uint32_t& f1, uint32_t& f2);
 uint32_t turbo_nwin(int K);      // lsn_turbo_nwin(K) from a table (the number of trellis windows of a code block of K bits)
 uint32_t turbo_il_offset(int K);  // word offset of block size K in the interleaver address tables (sizes in table order, lsn_turbo_il_words(K) words each); K = 0: total
+// Code-block descriptors of one transport block (36.212 5.1.2 segmentation s, 5.1.4.1.2 split of its G rate-matched bits: Qm bits per symbol, NL = 2 with
+// transmit diversity, else 1), appended to cbs.  Block q reads its E soft values from LLR offset e_off + (the E of the blocks before it) and writes its payload
+// bytes behind out_off, the blocks back to back.  dep_first: blocks 1 .. C-1 may be skipped once block 0 of this transport block has failed (LsnCbDev::dep =
+// its index in cbs); otherwise every block is always decoded.  Returns the payload bytes of the transport block, padded to a multiple of 16.
+uint32_t tb_code_blocks(const CbSegm& s, int G, int Qm, int NL, int rv, uint32_t max_iter, uint32_t e_off, uint32_t out_off, bool dep_first, std::vector<LsnCbDev>& cbs);
+// Launch order of the classic decoder form (lsn_launch_turbo: uplink, HARQ re-decodes): the two-wavefront class first, each class by descending K (the longest
+// first), equal sizes by ascending index.  n128 = blocks of the two-wavefront class, kmax* = the largest K of each class.
+struct TurboOrder { std::vector<uint32_t> order; uint32_t n128 = 0, kmax128 = 0, kmax64 = 0; };
+TurboOrder turbo_classic_order(const std::vector<LsnCbDev>& cbs);
 
 // ---- Histogram / RNTIManager ----
 class Histogram {
@@ -308,5 +318,30 @@ uint32_t crc24a_xpow(uint64_t n);                 // x^n mod g_CRC24A
 uint32_t crc24a_xpow_bytes(uint32_t nbytes);      // x^(8 nbytes) mod g_CRC24A, memoised per code-block payload size
 uint32_t crc24a_mulmod(uint32_t a, uint32_t b);   // a*b mod g_CRC24A
 uint32_t crc_bits(uint32_t poly, int order, const uint8_t* bits, int n);
+// Transport-block verdict from the per-block results (LsnCbRes), fed from the LAST code block to the first: every block passed, and the CRC24A over
+// data || parity of the whole block is zero - the XOR of rem_a[q] x^(bits behind block q) mod g, where rem_a is the block's own output bytes mod g
+// (k_turbo reduces after every bit: rem_a < 2^24, and crc24a_mulmod(a, 1) == a, so the last block needs no case of its own).
+struct TbVerdict {
+  bool all_ok = true;
+  uint32_t rem = 0;          // remainder of the blocks fed so far
+  uint64_t bits_after = 0;   // their payload bits
+  void add(bool ok, uint32_t rem_a, uint32_t out_bytes)
+  {
+    all_ok = all_ok && ok;
+    rem ^= crc24a_mulmod(rem_a, shift);
+    bits_after += 8ull * out_bytes;
+    shift = crc24a_mulmod(shift, crc24a_xpow_bytes(out_bytes));
+  }
+  // the final test on the assembled payload (tbs / 8 data bytes, then the 3 parity bytes): length tbs + 24 and a parity word that is not zero
+  // (an all-zero block has remainder 0 too)
+  bool pass(const uint8_t* payload, int tbs) const
+  {
+    if (!(all_ok && rem == 0 && bits_after == (uint64_t)tbs + 24)) return false;
+    const uint8_t* p = payload + tbs / 8;
+    return (((uint32_t)p[0] << 16) | ((uint32_t)p[1] << 8) | p[2]) != 0;
+  }
+private:
+  uint32_t shift = 1;        // x^bits_after mod g, carried along: two multiplications per block instead of a modular power
+};
 
 }  // namespace lsn

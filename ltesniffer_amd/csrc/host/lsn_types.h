@@ -31,3 +31,24 @@ struct LsnPruneCfg {
   uint32_t ever[9][4], forb[9][4];
 };
 #define LSN_PRUNE_SNAP_WORDS 2052
+
+// one turbo code block
+struct LsnCbDev {
+  uint32_t e_off;     // int16 element offset of this code block's rate-matched LLRs
+  uint32_t E;
+  uint32_t K, F, rv;
+  uint32_t crc_b;     // 1: CRC24B (C>1), 0: CRC24A
+  uint32_t out_off;   // byte offset in the payload arena
+  uint32_t out_bytes; // (K - F - 24*crc_b)/8
+  uint32_t il_off;    // word offset of this block size's table in LsnCellDev::turbo_il (turbo_il_offset(K))
+  uint32_t reserved;
+  uint32_t max_iter;
+  uint32_t res_idx;   // slot of this block's LsnCbRes (launch order is sorted by size, results are not)
+  uint32_t dep;       // res_idx of the FIRST code block of the same transport block when this one may be skipped once that one has failed
+                      // (a transport block fails as soon as any of its code blocks fails); 0xFFFFFFFF: always decode
+  uint32_t spp_off;   // u32 word offset (multiple of 4) of the block's de-rate-matched soft data: K packed words + 12 termination values (k_rm -> k_turbo)
+  uint32_t nwin;      // lsn_turbo_nwin(K), from the host's table (0: the kernel works it out itself)
+};
+#define LSN_SPP_WORDS(K) (((K) + 12u + 3u) & ~3u)
+#define LSN_CB_NODEP 0xFFFFFFFFu   // LsnCbDev::dep: always decode
+struct LsnCbRes { uint32_t ok, iters, rem_a, iters_run; uint32_t cyc_rm, cyc_map, cyc_out, cyc_all; };  // cyc_*: shader cycles per phase (s_memtime)

@@ -264,28 +264,9 @@ void Engine::puschDecodeGrid(const cf32* d_grid, uint32_t nsf, uint32_t start_tt
     d.scale = 1.0f / sqrtf((float)M);
     d.q_ack = q_ack; d.q_ri = q_ri; d.q_cqi = q_cqi;
     // UL-SCH: one transport block, one layer (36.212 5.2.2.6)
-    const int Qm = (int)g.mod, Gp = G / Qm, gamma = Gp % s.C;
     TbRef ref{i, (uint32_t)r.h_cbs.size(), (uint32_t)s.C, (uint32_t)pay_n, (int)g.tbs};
-    int rp = 0;
-    uint32_t wp = 0;
-    for (int q = 0; q < s.C; q++) {
-      LsnCbDev cb{};
-      const int K = q < s.Cm ? s.Km : s.Kp, F = q == 0 ? s.F : 0;
-      int E = (q <= s.C - gamma - 1) ? Qm * (Gp / s.C) : Qm * ((Gp + s.C - 1) / s.C);
-      if (rp + E > G) E = G - rp;
-      cb.e_off = d.llr_off + (uint32_t)rp; cb.E = (uint32_t)E; cb.K = (uint32_t)K; cb.F = (uint32_t)F; cb.rv = (uint32_t)g.rv;
-      cb.crc_b = s.C > 1 ? 1u : 0u;
-      cb.out_bytes = (uint32_t)(K - F - (s.C > 1 ? 24 : 0)) / 8;
-      cb.out_off = (uint32_t)pay_n + wp;
-      cb.il_off = turbo_il_offset(K);
-      cb.nwin = turbo_nwin(K);
-      cb.max_iter = (uint32_t)cfg.max_turbo_iterations;
-      cb.dep = LSN_CB_NODEP;  // every code block is decoded: the iteration count of a grant is part of what lsn_phy_pusch_decode reports
-      wp += cb.out_bytes;
-      rp += E;
-      r.h_cbs.push_back(cb);
-    }
-    pay_n += (wp + 15) & ~15u;
+    // no skipping behind a failed block 0: every code block is decoded, the iteration count of a grant is part of what lsn_phy_pusch_decode reports
+    pay_n += tb_code_blocks(s, G, (int)g.mod, 1, g.rv, (uint32_t)cfg.max_turbo_iterations, d.llr_off, (uint32_t)pay_n, false, r.h_cbs);
     tbs.push_back(ref);
     gd.push_back(d);
     gidx.push_back((int)i);
@@ -300,59 +281,32 @@ void Engine::puschDecodeGrid(const cf32* d_grid, uint32_t nsf, uint32_t start_tt
   grow_d(r.d_cbs, r.cbs_cap, ncb);
   grow_d(r.d_cbres, r.cbres_cap, ncb);
   grow_d(r.d_payload, r.payload_cap, pay_n + 16);
-  std::vector<uint32_t> order(ncb);
-  uint32_t n128 = 0, kmax128 = 0, kmax64 = 0;
-  for (uint32_t i = 0; i < ncb; i++) { r.h_cbs[i].res_idx = i; order[i] = i; }
-  std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
-    const uint32_t kx = r.h_cbs[x].K, ky = r.h_cbs[y].K;
-    const bool bx = lsn_turbo_two_wave_class((int)kx), by = lsn_turbo_two_wave_class((int)ky);
-    if (bx != by) return bx;
-    if (kx != ky) return kx > ky;
-    return x < y;
-  });
-  std::vector<LsnCbDev> sorted(ncb);
+  for (uint32_t i = 0; i < ncb; i++) r.h_cbs[i].res_idx = i;
+  const TurboOrder to = turbo_classic_order(r.h_cbs);
+  // descriptors go through pinned mirrors and the upload kernel, not through the host -> device copy engine (its FIFO may hold IQ blocks, lsn_dev.h)
+  grow_host(ul_h_grants, ul_h_grants_cap, ng, st);
+  grow_host(r.h_cbs_pinned, r.h_cbs_cap, ncb, st);
   size_t spp_n = 0;
   uint32_t emax = 0;
   for (uint32_t i = 0; i < ncb; i++) {
-    sorted[i] = r.h_cbs[order[i]];
-    sorted[i].spp_off = (uint32_t)spp_n; spp_n += LSN_SPP_WORDS(sorted[i].K);
-    emax = std::max(emax, sorted[i].E);
-    if (lsn_turbo_two_wave_class((int)sorted[i].K)) { n128++; kmax128 = std::max(kmax128, sorted[i].K); } else kmax64 = std::max(kmax64, sorted[i].K);
+    LsnCbDev& cb = r.h_cbs_pinned[i];
+    cb = r.h_cbs[to.order[i]];
+    cb.spp_off = (uint32_t)spp_n; spp_n += LSN_SPP_WORDS(cb.K);
+    emax = std::max(emax, cb.E);
   }
   grow_d(r.d_spp, r.spp_cap, spp_n + 16);
-  // descriptors go through pinned mirrors and the upload kernel, not through the host -> device copy engine (its FIFO may hold IQ blocks, lsn_dev.h)
-  if (ng > ul_h_grants_cap) {
-    HIP_CHECK(hipStreamSynchronize(st));
-    if (ul_h_grants) HIP_CHECK(hipHostFree(ul_h_grants));
-    ul_h_grants_cap = ng + ng / 2 + 64;
-    HIP_CHECK(hipHostMalloc((void**)&ul_h_grants, ul_h_grants_cap * sizeof(LsnUlGrantDev), hipHostMallocCoherent | hipHostMallocMapped));
-  }
-  if (ncb > r.h_cbs_cap) {
-    HIP_CHECK(hipStreamSynchronize(st));
-    if (r.h_cbs_pinned) HIP_CHECK(hipHostFree(r.h_cbs_pinned));
-    r.h_cbs_cap = ncb + ncb / 2 + 1024;
-    HIP_CHECK(hipHostMalloc((void**)&r.h_cbs_pinned, r.h_cbs_cap * sizeof(LsnCbDev), hipHostMallocCoherent | hipHostMallocMapped));
-  }
   std::memcpy(ul_h_grants, gd.data(), ng * sizeof(LsnUlGrantDev));
-  std::memcpy(r.h_cbs_pinned, sorted.data(), ncb * sizeof(LsnCbDev));
   lsn_launch_upload(ul_d_grants, ul_h_grants, ng * sizeof(LsnUlGrantDev), st);
   lsn_launch_upload(r.d_cbs, r.h_cbs_pinned, ncb * sizeof(LsnCbDev), st);
   HIP_CHECK(hipMemsetAsync(r.d_llr16, 0, llr_n * sizeof(int16_t), st));
   lsn_launch_pusch_chest(cd, ul_d_grants, d_grid, ul_d_hs, ul_d_stat, ng, st);
   lsn_launch_pusch_demod(cd, ul_d_grants, d_grid, ul_d_hs, ul_d_stat, r.d_llr16, ng, st);
   lsn_launch_rm(r.d_cbs, r.d_llr16, r.d_spp, ncb, emax, st);
-  lsn_launch_turbo(cd, r.d_cbs, r.d_spp, r.d_payload, r.d_cbres, n128, kmax128, ncb - n128, kmax64, st, nullptr);
+  lsn_launch_turbo(cd, r.d_cbs, r.d_spp, r.d_payload, r.d_cbres, to.n128, to.kmax128, ncb - to.n128, to.kmax64, st);
   // results come back through pinned mirrors written by the copy kernel (lsn_dev.h), not through the copy engine
-  auto grow_pinned = [&](auto*& p, size_t& cap, size_t need) {
-    if (need <= cap) return;
-    HIP_CHECK(hipStreamSynchronize(st));
-    if (p) HIP_CHECK(hipHostFree(p));
-    cap = need + need / 2 + 1024;
-    HIP_CHECK(hipHostMalloc((void**)&p, cap * sizeof(*p), hipHostMallocCoherent | hipHostMallocMapped));
-  };
-  grow_pinned(r.h_cbres_pinned, r.h_cbres_cap, ncb);
-  grow_pinned(r.h_payload_pinned, r.h_payload_cap, pay_n + 16);
-  grow_pinned(ul_h_stat, ul_h_stat_cap, (size_t)2 * ng);
+  grow_host(r.h_cbres_pinned, r.h_cbres_cap, ncb, st);
+  grow_host(r.h_payload_pinned, r.h_payload_cap, pay_n + 16, st);
+  grow_host(ul_h_stat, ul_h_stat_cap, (size_t)2 * ng, st);
   lsn_launch_download(r.h_cbres_pinned, r.d_cbres, ncb * sizeof(LsnCbRes), st);
   lsn_launch_download(r.h_payload_pinned, r.d_payload, pay_n, st);
   lsn_launch_download(ul_h_stat, ul_d_stat, (size_t)2 * ng * sizeof(float), st);
@@ -362,20 +316,16 @@ void Engine::puschDecodeGrid(const cf32* d_grid, uint32_t nsf, uint32_t start_tt
   const float* stat = ul_h_stat;
   for (size_t t = 0; t < tbs.size(); t++) {
     const TbRef& ref = tbs[t];
-    bool all_ok = true;
-    uint32_t rem = 0, iters = 0;
-    uint64_t bits_after = 0;
+    TbVerdict v;
+    uint32_t iters = 0;
     for (int q = (int)ref.cb_count - 1; q >= 0; q--) {
       const LsnCbRes& cr = cbres[ref.cb_first + q];
-      all_ok = all_ok && cr.ok != 0;
+      v.add(cr.ok != 0, cr.rem_a, r.h_cbs[ref.cb_first + q].out_bytes);
       iters += cr.iters;
-      rem ^= crc24a_mulmod(cr.rem_a, crc24a_xpow(bits_after));
-      bits_after += 8ull * r.h_cbs[ref.cb_first + q].out_bytes;
     }
     const uint8_t* pl = pay_base + ref.pay_off;
-    const uint32_t par = ((uint32_t)pl[ref.tbs / 8] << 16) | ((uint32_t)pl[ref.tbs / 8 + 1] << 8) | pl[ref.tbs / 8 + 2];
     lsn_pusch_result_t& res = results[ref.grant];
-    res.crc_ok = all_ok && rem == 0 && par != 0 && bits_after == (uint64_t)ref.tbs + 24;
+    res.crc_ok = v.pass(pl, ref.tbs);
     res.iterations = iters;
     res.snr_db = 10.0f * log10f(stat[2 * t + 1] / stat[2 * t]);
     res.payload_off = (uint32_t)payload_out.size();

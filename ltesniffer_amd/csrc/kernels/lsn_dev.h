@@ -106,24 +106,6 @@ struct LsnGrantDev {
   float inv_amp_a, inv_amp_b;
 };
 
-// one turbo code block
-struct LsnCbDev {
-  uint32_t e_off;     // int16 element offset of this code block's rate-matched LLRs
-  uint32_t E;
-  uint32_t K, F, rv;
-  uint32_t crc_b;     // 1: CRC24B (C>1), 0: CRC24A
-  uint32_t out_off;   // byte offset in the payload arena
-  uint32_t out_bytes; // (K - F - 24*crc_b)/8
-  uint32_t il_off;    // word offset of this block size's table in LsnCellDev::turbo_il (turbo_il_offset(K))
-  uint32_t reserved;
-  uint32_t max_iter;
-  uint32_t res_idx;   // slot of this block's LsnCbRes (launch order is sorted by size, results are not)
-  uint32_t dep;       // res_idx of the FIRST code block of the same transport block when this one may be skipped once that one has failed
-                      // (a transport block fails as soon as any of its code blocks fails); 0xFFFFFFFF: always decode
-  uint32_t spp_off;   // u32 word offset (multiple of 4) of the block's de-rate-matched soft data: K packed words + 12 termination values (k_rm -> k_turbo)
-  uint32_t nwin;      // lsn_turbo_nwin(K), from the host's table (0: the kernel works it out itself)
-};
-#define LSN_SPP_WORDS(K) (((K) + 12u + 3u) & ~3u)
 // one PUSCH grant to decode
 struct LsnUlGrantDev {
   uint32_t sf;          // subframe index inside the batch
@@ -138,8 +120,6 @@ struct LsnUlGrantDev {
   float scale;          // 1 / sqrt(M)
   uint32_t q_ack, q_ri, q_cqi;  // control symbols multiplexed into the allocation (36.212 5.2.2.6): HARQ-ACK punctures, RI / CQI are skipped
 };
-
-struct LsnCbRes { uint32_t ok, iters, rem_a, iters_run; uint32_t cyc_rm, cyc_map, cyc_out, cyc_all; };  // cyc_*: shader cycles per phase (s_memtime)
 
 // Descriptor upload without the SDMA queue: a few workgroups read `bytes` (rounded up to words; both buffers are allocated with slack) from PINNED host
 // memory and store them to device memory.  hipMemcpyAsync host -> device is served by one FIFO copy engine: a 3 KB descriptor upload queued behind the
@@ -180,9 +160,8 @@ void lsn_launch_pdsch_demod(const LsnCellDev& c, const LsnGrantDev* g, const uin
                             const LsnChest* ch, int16_t* llr, hipStream_t s);
 void lsn_launch_rm(const LsnCbDev* cb, const int16_t* llr, uint32_t* spp, uint32_t ncb, uint32_t emax, hipStream_t s);
 void lsn_launch_harq_combine(const LsnCbDev* cbs, uint32_t ncb, const uint32_t* keep, uint32_t* pool, uint32_t* scratch, bool copy, hipStream_t s);
-#define LSN_CB_NODEP 0xFFFFFFFFu
 void lsn_launch_turbo(const LsnCellDev& c, const LsnCbDev* cb, const uint32_t* spp, uint8_t* payload, LsnCbRes* res, uint32_t n128, uint32_t kmax128,
-                      uint32_t n64, uint32_t kmax64, hipStream_t s, hipEvent_t between);
+                      uint32_t n64, uint32_t kmax64, hipStream_t s);
 // largest code block two of which share one decoder workgroup (one wavefront and half of the LDS slot each): 2 x (6 K + 16 + 3584) <= 40 960 = a quarter of the CU's LDS
 #define LSN_TURBO_PAIR_KMAX 2752u
 void lsn_launch_turbo_packed(const LsnCellDev& c, const LsnCbDev* cb, const uint32_t* spp, uint8_t* payload, LsnCbRes* res, uint32_t nsolo, uint32_t kmax_solo,

@@ -11,7 +11,7 @@
 // lane runs the T taps of its outputs: coefficient j = H[p][j] + f * dH[p][j] (p = top 9 bits of the fraction, f = the next 24 bits), one
 // 16-byte load of the bank row gives two taps, one ds_read_b64 per sample.  Up-sampling and equal rates: neighbouring lanes read the
 // same or neighbouring float2 (broadcast / conflict free); down-sampling by r strides the lanes by r float2 = a 2- to 4-way conflict.
-#include "lsn_dev.h"
+#include "lsn_dsp.h"
 
 #define LSN_RS_RUN 512u      // outputs per workgroup (256 lanes x 2)
 
@@ -85,11 +85,7 @@ __global__ __launch_bounds__(256) void k_resample(const LsnResampleArgs A)
     }
     const uint32_t q = (uint32_t)i + A.sf_off, sf = q / A.sflen, n = q - sf * A.sflen;   // the launcher keeps n_out + sf_off below 2^32
     cf32 y; y.r = yr; y.i = yi;
-    if (A.rot) {
-      const cf32 w = A.rot[n];
-      cf32 z; z.r = y.r * w.r - y.i * w.i; z.i = y.r * w.i + y.i * w.r;
-      y = z;
-    }
+    if (A.rot) y = cmul(y, A.rot[n]);
     A.out[((size_t)sf * A.nant + a) * A.sflen + n] = y;
   }
 }

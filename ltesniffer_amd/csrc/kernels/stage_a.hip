@@ -8,47 +8,14 @@
 // the 64 trellis states) per (subframe, location, DCI size) for the tail-biting Viterbi with __ballot decision words.
 // Float arithmetic is written one rounding per operation (compiled with -ffp-contract=off) so that results are
 // bit-identical to the CPU oracle used by the tests.
-#include "lsn_dev.h"
+#include "lsn_dsp.h"
 #include <algorithm>
 #include <type_traits>
 #include <cstdlib>
 
 #define SQRT2F 1.41421356237309504880f
 
-__device__ __forceinline__ cf32 cmul(cf32 a, cf32 b) { cf32 c; c.r = a.r * b.r - a.i * b.i; c.i = a.r * b.i + a.i * b.r; return c; }
-__device__ __forceinline__ cf32 cmulconj(cf32 a, cf32 b) { cf32 c; c.r = a.r * b.r + a.i * b.i; c.i = a.i * b.r - a.r * b.i; return c; }
-
 // ------------------------------------------------------------------------------------------------ OFDM
-template <int R>
-__device__ __forceinline__ void fft_pass(cf32* a, const cf32* w, int s, int N, int lgN, int tid)
-{
-  constexpr int G = 1 << R;
-  const int h = 1 << s;
-#pragma unroll
-  for (int u = 0; u < (8 >> R); u++) {
-    int g = tid * (8 >> R) + u;
-    if (g >= (N >> R)) break;
-    int low = g & (h - 1), high = g >> s, base = (high << (s + R)) | low;
-    cf32 e[G];
-#pragma unroll
-    for (int j = 0; j < G; j++) e[j] = a[base + j * h];
-#pragma unroll
-    for (int q = 0; q < R; q++) {
-#pragma unroll
-      for (int j = 0; j < G; j++) {
-        if (j & (1 << q)) continue;
-        int pos = low + (j & ((1 << q) - 1)) * h;
-        cf32 v = cmul(e[j + (1 << q)], w[pos << (lgN - (s + q + 1))]);
-        cf32 uu = e[j];
-        e[j].r = uu.r + v.r; e[j].i = uu.i + v.i;
-        e[j + (1 << q)].r = uu.r - v.r; e[j + (1 << q)].i = uu.i - v.i;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < G; j++) a[base + j * h] = e[j];
-  }
-}
-
 // rbp_part (optional): [sf][14][128] - the per-symbol term of SubframePower::computePower (SubframePower.cc:26-30: mean |x|^2 over the 12 REs of every PRB of
 // antenna 0), written here from the symbol the workgroup has just produced; k_rb_power then only adds the 14 terms of a PRB in symbol order (rounds 1-4: a
 // kernel that read the whole grid a second time, 0.13 MB per subframe)
@@ -65,7 +32,7 @@ __global__ __launch_bounds__(256) void k_ofdm(LsnCellDev c, const cf32* __restri
                                               cf32* __restrict__ grid, float* __restrict__ rbp_part)
 {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int N = (int)c.N, lgN = (int)c.lgN, tid = threadIdx.x;
+  const int N = (int)c.N, tid = threadIdx.x;
   cf32* a = (cf32*)smem;
   cf32* w = a + N;
   const int nsym = (int)c.nsym;  // 14, or 12 with the extended cyclic prefix (rows 12, 13 of the grid are never written)
@@ -78,67 +45,16 @@ __global__ __launch_bounds__(256) void k_ofdm(LsnCellDev c, const cf32* __restri
   const uint32_t dphi = dphi_sf ? dphi_sf[sf] : 0u;
   const int nre = (int)c.nre;
   cf32* out = grid + (((size_t)sf * c.nof_rx + rx) * 14 + l) * nre;
-  if (c.twiddle3) {
-    // N = 3 M with M = 128 / 256 / 512 (384, 768, 1536): x_r[m] = x[3 m + r] -> three M-point transforms side by side in LDS, then
-    // X[k] = (F_0[k % M] + F_1[k % M] T[k]) + F_2[k % M] T[2 k mod N] for the carriers that are kept
-    const int M = (int)c.nsub;
-    for (int n = tid; n < M / 2; n += 256) w[n] = c.twiddle[n];
-    for (int n = tid; n < N; n += 256) {
-      cf32 x = in[n];
-      if (dphi != 0u) {
-        uint32_t ph = (uint32_t)(pos + n) * dphi;
-        cf32 rot = cmul(c.nco_coarse[ph >> 20], c.nco_fine[(ph >> 10) & 1023u]);
-        x = cmul(x, rot);
-      }
-      const int m = n / 3, r = n - 3 * m;
-      a[r * M + (int)(__brev((unsigned)m) >> (32 - lgN))] = x;
-    }
-    __syncthreads();
-    for (int s = 0; s < lgN;) {  // the pass split of the power-of-two path below: lgN = 9 is three radix-8 passes per block, 8 = 8, 8, 4 and 7 = 8, 8, 2
-      const int left = lgN - s;
-      if (left >= 3) { for (int r = 0; r < 3; r++) fft_pass<3>(a + r * M, w, s, M, lgN, tid); s += 3; }
-      else if (left == 2) { for (int r = 0; r < 3; r++) fft_pass<2>(a + r * M, w, s, M, lgN, tid); s += 2; }
-      else { for (int r = 0; r < 3; r++) fft_pass<1>(a + r * M, w, s, M, lgN, tid); s += 1; }
-      __syncthreads();
-    }
-    const cf32* __restrict__ T = c.twiddle3;
-    for (int k = tid; k < nre; k += 256) {
-      const int bin = (k < nre / 2) ? (N - nre / 2 + k) : (k - nre / 2 + 1), kq = bin & (M - 1);
-      int b2 = 2 * bin;
-      b2 = b2 >= N ? b2 - N : b2;
-      const cf32 t1 = cmul(a[M + kq], T[bin]), t2 = cmul(a[2 * M + kq], T[b2]);
-      const float sr = a[kq].r + t1.r, si = a[kq].i + t1.i;
-      cf32 X;
-      X.r = sr + t2.r;
-      X.i = si + t2.i;
-      out[k] = X;
-    }
-    if (rbp_part && rx == 0) ofdm_rb_power(c, out, rbp_part, sf, l, tid);
-    return;
-  }
-  for (int n = tid; n < N / 2; n += 256) w[n] = c.twiddle[n];
-  for (int n = tid; n < N; n += 256) {
+  auto load = [&](int n) {
     cf32 x = in[n];
     if (dphi != 0u) {
       uint32_t ph = (uint32_t)(pos + n) * dphi;
       cf32 rot = cmul(c.nco_coarse[ph >> 20], c.nco_fine[(ph >> 10) & 1023u]);
       x = cmul(x, rot);
     }
-    a[__brev((unsigned)n) >> (32 - lgN)] = x;
-  }
-  __syncthreads();
-  int s = 0;
-  while (s < lgN) {
-    int r = lgN - s;
-    if (r >= 3) { fft_pass<3>(a, w, s, N, lgN, tid); s += 3; }
-    else if (r == 2) { fft_pass<2>(a, w, s, N, lgN, tid); s += 2; }
-    else { fft_pass<1>(a, w, s, N, lgN, tid); s += 1; }
-    __syncthreads();
-  }
-  for (int k = tid; k < nre; k += 256) {
-    int bin = (k < nre / 2) ? (N - nre / 2 + k) : (k - nre / 2 + 1);
-    out[k] = a[bin];
-  }
+    return x;
+  };
+  lsn_symbol_fft(c, a, w, load, out, 1, tid);  // 1: the DC carrier is not part of the downlink grid
   if (rbp_part && rx == 0) ofdm_rb_power(c, out, rbp_part, sf, l, tid);
 }
 

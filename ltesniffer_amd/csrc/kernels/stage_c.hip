@@ -6,7 +6,7 @@
 // Mapping: demod = one thread per resource element (coalesced float2 loads of grid / channel estimates, int16 LLR
 // stores); turbo = one wavefront per code block, lane = trellis window, all soft data of the block staged in LDS,
 // forward metrics check-pointed every 16 steps and recomputed so that the block fits 2 workgroups per CU.
-#include "lsn_dev.h"
+#include "lsn_dsp.h"
 #include <algorithm>
 #include "lsn_rm.h"
 #include <type_traits>
@@ -14,9 +14,6 @@
 #define SQRT1_2F 0.70710678118654752440f
 #define SQRT2F 1.41421356237309504880f
 #define LLR_Q 180.0f
-
-__device__ __forceinline__ cf32 cmulconj(cf32 a, cf32 b) { cf32 c; c.r = a.r * b.r + a.i * b.i; c.i = a.i * b.r - a.r * b.i; return c; }
-__device__ __forceinline__ float cabs2(cf32 a) { return a.r * a.r + a.i * a.i; }
 
 // ------------------------------------------------------------------------------------------------ RE bookkeeping
 // prefix[l][prb] = number of PDSCH REs of this grant in symbol l before PRB prb; prefix[14*nprb + l] = REs before symbol l.
@@ -117,25 +114,6 @@ void lsn_launch_pdsch_prep_up(const LsnCellDev& c, const LsnGrantDev* jobs_host,
 }
 
 // ------------------------------------------------------------------------------------------------ soft demodulation
-__device__ __forceinline__ void demod_llr(int Qm, float I, float Q, float* L)
-{
-  float aI = fabsf(I), aQ = fabsf(Q);
-  L[0] = -I; L[1] = -Q;
-  if (Qm == 4) {
-    const float a = 0.31622776601683794f;
-    L[2] = aI - 2.0f * a; L[3] = aQ - 2.0f * a;
-  } else if (Qm == 6) {
-    const float a = 0.15430334996209191f;
-    float tI = aI - 4.0f * a, tQ = aQ - 4.0f * a;
-    L[2] = tI; L[3] = tQ; L[4] = fabsf(tI) - 2.0f * a; L[5] = fabsf(tQ) - 2.0f * a;
-  } else if (Qm == 8) {
-    const float a = 0.07669649888473704f;
-    float tI = aI - 8.0f * a, tQ = aQ - 8.0f * a;
-    float uI = fabsf(tI) - 4.0f * a, uQ = fabsf(tQ) - 4.0f * a;
-    L[2] = tI; L[3] = tQ; L[4] = uI; L[5] = uQ; L[6] = fabsf(uI) - 2.0f * a; L[7] = fabsf(uQ) - 2.0f * a;
-  }
-}
-
 // QM is a compile-time constant so that the soft-bit array stays in registers (a run-time loop bound puts it in scratch memory).
 // Round 6 (last session): the QM positions of a resource element start at an even n0 = idx QM, so the scrambling tables are read with wide loads (x1 bytes: 2 / 4 / 8 at
 // once, x2 masks: 8 or 16 bytes per load), the soft bits leave in 4- / 8- / 16-byte stores, the scrambling bit flips the SIGN BIT of the scaled value in front of the
@@ -153,7 +131,7 @@ __device__ __forceinline__ void emit_q(const LsnCellDev& c, cf32 x, float w, flo
 {
   float L[8];
   const float wq = w * LLR_Q;
-  demod_llr(QM, x.r * inv_amp, x.i * inv_amp, L);
+  lsn_demod_llr(QM, x.r * inv_amp, x.i * inv_amp, L);
   const uint32_t n0 = idx * (uint32_t)QM;
   uint32_t x1w[2] = {0u, 0u}, m[8];
   const uint8_t* p1 = c.gold_x1 + n0;
@@ -754,10 +732,9 @@ static size_t turbo_lds_bytes_nt(uint32_t kmax, int) { return lsn_turbo_lds_byte
 // Classic form (uplink, HARQ re-decodes): cb[0 .. n128) in two-wavefront workgroups, cb[n128 .. n128 + n64) in one-wavefront workgroups; each range is
 // launched with the LDS size of its largest block (40 KiB at K = 6144 -> four code blocks per CU)
 void lsn_launch_turbo(const LsnCellDev& c, const LsnCbDev* cb, const uint32_t* spp, uint8_t* payload, LsnCbRes* res, uint32_t n128, uint32_t kmax128,
-                      uint32_t n64, uint32_t kmax64, hipStream_t s, hipEvent_t between)
+                      uint32_t n64, uint32_t kmax64, hipStream_t s)
 {
   lsn_launch_turbo_packed(c, cb, spp, payload, res, n128, kmax128, 0, 0, s);
-  if (between) (void)hipEventRecord(between, s);
   static std::atomic<uint64_t> attr64{0};
   lsn_func_max_lds((const void*)k_turbo<64>, (int)turbo_lds_bytes_nt(6144, 64), attr64, "k_turbo<64>");
   auto fix = [](uint32_t k) { return ((k < 512 ? 512u : k) + 7u) & ~7u; };  // the scratch in the check-point area needs room

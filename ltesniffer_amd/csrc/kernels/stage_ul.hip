@@ -4,49 +4,16 @@
 // srsran_chest_ul_estimate_pusch (:256) and the front half of srsran_pusch_decode (:262); the back half (rate
 // de-matching + turbo + CRC) is k_turbo of stage_c.hip.  Scope: one antenna, no hopping, no SRS, no UCI, L_prb >= 3.
 // Float arithmetic: one rounding per operation, fixed summation orders (bit-identical to the tests' CPU oracle).
-#include "lsn_dev.h"
+#include "lsn_dsp.h"
 
 #define LLR_Q 180.0f
 
-__device__ __forceinline__ cf32 cmul(cf32 a, cf32 b) { cf32 c; c.r = a.r * b.r - a.i * b.i; c.i = a.r * b.i + a.i * b.r; return c; }
-__device__ __forceinline__ cf32 cmulconj(cf32 a, cf32 b) { cf32 c; c.r = a.r * b.r + a.i * b.i; c.i = a.i * b.r - a.r * b.i; return c; }
-
 // ------------------------------------------------------------------------------------------------ SC-FDMA demodulation
-template <int R>
-__device__ __forceinline__ void ul_fft_pass(cf32* a, const cf32* w, int s, int N, int lgN, int tid)
-{
-  constexpr int G = 1 << R;
-  const int h = 1 << s;
-#pragma unroll
-  for (int u = 0; u < (8 >> R); u++) {
-    int g = tid * (8 >> R) + u;
-    if (g >= (N >> R)) break;
-    int low = g & (h - 1), high = g >> s, base = (high << (s + R)) | low;
-    cf32 e[G];
-#pragma unroll
-    for (int j = 0; j < G; j++) e[j] = a[base + j * h];
-#pragma unroll
-    for (int q = 0; q < R; q++) {
-#pragma unroll
-      for (int j = 0; j < G; j++) {
-        if (j & (1 << q)) continue;
-        int pos = low + (j & ((1 << q) - 1)) * h;
-        cf32 v = cmul(e[j + (1 << q)], w[pos << (lgN - (s + q + 1))]);
-        cf32 uu = e[j];
-        e[j].r = uu.r + v.r; e[j].i = uu.i + v.i;
-        e[j + (1 << q)].r = uu.r - v.r; e[j + (1 << q)].i = uu.i - v.i;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < G; j++) a[base + j * h] = e[j];
-  }
-}
-
 // one workgroup per (subframe, symbol): CP strip, 7.5 kHz shift, radix-8/4/2 DIT FFT in LDS, carrier extract (no DC gap)
 __global__ __launch_bounds__(256) void k_ul_fft(LsnCellDev c, const cf32* __restrict__ iq, uint32_t nant, uint32_t ant, cf32* __restrict__ grid)
 {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int N = (int)c.N, lgN = (int)c.lgN, tid = threadIdx.x;
+  const int N = (int)c.N, tid = threadIdx.x;
   cf32* a = (cf32*)smem;
   cf32* w = a + N;
   const int nsym = (int)c.nsym;  // 14, or 12 with the extended cyclic prefix (rows 12, 13 of the grid stay zero)
@@ -57,47 +24,7 @@ __global__ __launch_bounds__(256) void k_ul_fft(LsnCellDev c, const cf32* __rest
   const cf32* in = iq + ((size_t)sf * nant + ant) * c.sflen + pos;
   const int nre = (int)c.nre;
   cf32* out = grid + ((size_t)sf * 14 + l) * nre;
-  if (c.twiddle3) {  // N = 3 x nsub: 384, 768, 1536 (see k_ofdm)
-    const int M = (int)c.nsub;
-    for (int n = tid; n < M / 2; n += 256) w[n] = c.twiddle[n];
-    for (int n = tid; n < N; n += 256) {
-      const int m = n / 3, r = n - 3 * m;
-      a[r * M + (int)(__brev((unsigned)m) >> (32 - lgN))] = cmul(in[n], c.ul_shift[n]);
-    }
-    __syncthreads();
-    for (int s = 0; s < lgN;) {
-      const int left = lgN - s;
-      if (left >= 3) { for (int r = 0; r < 3; r++) ul_fft_pass<3>(a + r * M, w, s, M, lgN, tid); s += 3; }
-      else if (left == 2) { for (int r = 0; r < 3; r++) ul_fft_pass<2>(a + r * M, w, s, M, lgN, tid); s += 2; }
-      else { for (int r = 0; r < 3; r++) ul_fft_pass<1>(a + r * M, w, s, M, lgN, tid); s += 1; }
-      __syncthreads();
-    }
-    const cf32* __restrict__ T = c.twiddle3;
-    for (int k = tid; k < nre; k += 256) {
-      const int bin = (k < nre / 2) ? (N - nre / 2 + k) : (k - nre / 2), kq = bin & (M - 1);
-      int b2 = 2 * bin;
-      b2 = b2 >= N ? b2 - N : b2;
-      const cf32 t1 = cmul(a[M + kq], T[bin]), t2 = cmul(a[2 * M + kq], T[b2]);
-      const float sr = a[kq].r + t1.r, si = a[kq].i + t1.i;
-      cf32 X;
-      X.r = sr + t2.r;
-      X.i = si + t2.i;
-      out[k] = X;
-    }
-    return;
-  }
-  for (int n = tid; n < N / 2; n += 256) w[n] = c.twiddle[n];
-  for (int n = tid; n < N; n += 256) a[__brev((unsigned)n) >> (32 - lgN)] = cmul(in[n], c.ul_shift[n]);
-  __syncthreads();
-  int s = 0;
-  while (s < lgN) {
-    int r = lgN - s;
-    if (r >= 3) { ul_fft_pass<3>(a, w, s, N, lgN, tid); s += 3; }
-    else if (r == 2) { ul_fft_pass<2>(a, w, s, N, lgN, tid); s += 2; }
-    else { ul_fft_pass<1>(a, w, s, N, lgN, tid); s += 1; }
-    __syncthreads();
-  }
-  for (int k = tid; k < nre; k += 256) out[k] = a[(k < nre / 2) ? (N - nre / 2 + k) : (k - nre / 2)];
+  lsn_symbol_fft(c, a, w, [&](int n) { return cmul(in[n], c.ul_shift[n]); }, out, 0, tid);  // 0: no DC gap in the uplink grid
 }
 
 void lsn_launch_ul_fft(const LsnCellDev& c, const cf32* iq, uint32_t nant, uint32_t ant, cf32* grid, uint32_t nsf, hipStream_t s)
@@ -155,25 +82,6 @@ void lsn_launch_pusch_chest(const LsnCellDev& c, const LsnUlGrantDev* g, const c
 }
 
 // ------------------------------------------------------------------------------------------------ equalise + IDFT + demod
-__device__ __forceinline__ void ul_demod_llr(int Qm, float I, float Q, float* L)
-{
-  float aI = fabsf(I), aQ = fabsf(Q);
-  L[0] = -I; L[1] = -Q;
-  if (Qm == 4) {
-    const float a = 0.31622776601683794f;
-    L[2] = aI - 2.0f * a; L[3] = aQ - 2.0f * a;
-  } else if (Qm == 6) {
-    const float a = 0.15430334996209191f;
-    float tI = aI - 4.0f * a, tQ = aQ - 4.0f * a;
-    L[2] = tI; L[3] = tQ; L[4] = fabsf(tI) - 2.0f * a; L[5] = fabsf(tQ) - 2.0f * a;
-  } else if (Qm == 8) {
-    const float a = 0.07669649888473704f;
-    float tI = aI - 8.0f * a, tQ = aQ - 8.0f * a;
-    float uI = fabsf(tI) - 4.0f * a, uQ = fabsf(tQ) - 4.0f * a;
-    L[2] = tI; L[3] = tQ; L[4] = uI; L[5] = uQ; L[6] = fabsf(uI) - 2.0f * a; L[7] = fabsf(uQ) - 2.0f * a;
-  }
-}
-
 // one workgroup per (data symbol 0..11 - 0..9 with the extended CP -, grant): equalised carriers, a ping-pong buffer and the IDFT twiddles in LDS; transform de-precoding as
 // an autosort (Stockham) decimation-in-frequency IDFT over the radices 4 (while the remaining length divides by 4), 2, 3, 5 - one thread per
 // output of a stage, terms added in index order: the operation order of the oracle's o_idft_mixed (M = 1200: 21 complex MACs per output
@@ -246,7 +154,7 @@ __global__ __launch_bounds__(256) void k_pusch_demod(LsnCellDev c, const LsnUlGr
       dcell = (is_ri || rank < qcqi) ? -1 : rank - qcqi;
     }
     float Lb[8];
-    ul_demod_llr(Qm, ar * scale, ai * scale, Lb);
+    lsn_demod_llr(Qm, ar * scale, ai * scale, Lb);
 #pragma unroll
     for (int b = 0; b < 8; b++) {  // fixed trip count keeps Lb in registers (a run-time bound would put it in scratch memory)
       if (b >= Qm) break;

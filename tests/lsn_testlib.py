@@ -416,6 +416,11 @@ def hosttest():
         lib.lsnh_turbo_il_offset.restype = C.c_uint32
         lib.lsnh_turbo_il_offset.argtypes = [C.c_int]
         lib.lsnh_turbo_two_wave_class.argtypes = [C.c_int]
+        lib.lsnh_tbs_from_idx.argtypes = [C.c_int, C.c_uint32]
+        lib.lsnh_tb_code_blocks.argtypes = [C.c_int] * 4 + [C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
+        lib.lsnh_crc24a_mulmod.restype = C.c_uint32
+        lib.lsnh_crc24a_mulmod.argtypes = [C.c_uint32, C.c_uint32]
+        lib.lsnh_tb_verdict.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         lib.lsnh_search_new.restype = C.c_void_p
         lib.lsnh_search_new.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_double, C.c_int]
         lib.lsnh_search_free.argtypes = [C.c_void_p]

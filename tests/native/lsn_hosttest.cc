@@ -111,6 +111,37 @@ int lsnh_cbsegm(int tbs, int* out6)
   return 0;
 }
 
+int lsnh_tbs_from_idx(int i_tbs, uint32_t n_prb) { return ra_tbs_from_idx(i_tbs, n_prb); }
+
+// tb_code_blocks behind `nbefore` descriptors that are already in the list: out7[q] = {K, F, E, e_off, out_off, out_bytes, dep} of block q, *pay = the
+// padded payload bytes; returns C, -1 without a segmentation, -2 when cap is too small
+int lsnh_tb_code_blocks(int tbs, int G, int Qm, int NL, uint32_t e_off, uint32_t out_off, int dep_first, uint32_t nbefore, uint32_t* out7, uint32_t cap, uint32_t* pay)
+{
+  CbSegm s;
+  if (!cbsegm(tbs, s)) return -1;
+  std::vector<LsnCbDev> cbs(nbefore);
+  *pay = tb_code_blocks(s, G, Qm, NL, 0, 5, e_off, out_off, dep_first != 0, cbs);
+  if (cbs.size() != (size_t)nbefore + (size_t)s.C) return -3;
+  if ((uint32_t)s.C > cap) return -2;
+  for (int q = 0; q < s.C; q++) {
+    const LsnCbDev& c = cbs[nbefore + q];
+    uint32_t* o = out7 + 7 * q;
+    o[0] = c.K; o[1] = c.F; o[2] = c.E; o[3] = c.e_off; o[4] = c.out_off; o[5] = c.out_bytes; o[6] = c.dep;
+  }
+  return s.C;
+}
+
+uint32_t lsnh_crc24a_mulmod(uint32_t a, uint32_t b) { return crc24a_mulmod(a, b); }
+
+// TbVerdict over the n code blocks of one transport block (arrays in block order; fed last to first): returns pass(payload, tbs), out3 = {all_ok, rem, bits_after}
+int lsnh_tb_verdict(uint32_t n, const uint8_t* ok, const uint32_t* rem_a, const uint32_t* out_bytes, const uint8_t* payload, int tbs, uint64_t* out3)
+{
+  TbVerdict v;
+  for (int q = (int)n - 1; q >= 0; q--) v.add(ok[q] != 0, rem_a[q], out_bytes[q]);
+  out3[0] = v.all_ok ? 1 : 0; out3[1] = v.rem; out3[2] = v.bits_after;
+  return v.pass(payload, tbs) ? 1 : 0;
+}
+
 hsearch* lsnh_search_new(uint32_t nof_prb, uint32_t nof_ports, uint32_t cell_id, const uint32_t* nof_cce3, uint32_t threshold, double split, int skip)
 {
   hsearch* h = new hsearch();

@@ -173,6 +173,115 @@ def test_cbsegm_all_tbs():
             assert list(out) == [s.C, s.Cp, s.Cm, s.Kp, s.Km, s.F], tbs
 
 
+def test_tb_code_block_descriptors():
+    """tb_code_blocks (the descriptors runJobs and puschDecodeGrid hand to k_rm / k_turbo) against 36.212 5.1.4.1.2 written out here: G' = G / (N_L Q_m),
+    gamma = G' mod C, blocks 0 .. C - gamma - 1 get N_L Q_m floor(G' / C) bits and the rest the ceiling; K, F and the payload bytes from lsnh_cbsegm.  Every size of
+    the product's TBS table, Qm 2 / 4 / 6 / 8, one and two layers, G = N_L Q_m n_re with gamma = 0, gamma != 0 and fewer symbols than code blocks."""
+    h = hosttest()
+    sizes = {h.lsnh_tbs_from_idx(i, n) for i in range(0, 34) for n in range(1, 111)}
+    sizes.discard(-1)
+    sizes.discard(0)
+    assert len(sizes) > 150
+    NODEP, E0, O0, NBEFORE = 0xFFFFFFFF, 4096, 160, 7
+    out, pay, seg = (C.c_uint32 * (7 * 32))(), C.c_uint32(), (C.c_int * 6)()
+    multi = with_gamma = starved = 0
+    for tbs in sorted(sizes):
+        assert h.lsnh_cbsegm(tbs, seg) == 0
+        nC, Cp, Cm, Kp, Km, F = list(seg)
+        assert 1 <= nC <= 32 and Cp + Cm == nC
+        K = [Km if q < Cm else Kp for q in range(nC)]
+        Fq = [F if q == 0 else 0 for q in range(nC)]
+        nbytes = [(K[q] - Fq[q] - (24 if nC > 1 else 0)) // 8 for q in range(nC)]
+        assert sum(nbytes) == (tbs + 24) // 8
+        for n_re in sorted({150 * nC, 150 * nC + 1, 97 * nC + nC - 1, max(1, nC - 1)}):
+            for Qm in (2, 4, 6, 8):
+                for NL in (1, 2):
+                    G = NL * Qm * n_re
+                    Gp = G // (NL * Qm)
+                    gamma = Gp % nC
+                    E = [NL * Qm * (Gp // nC) if q <= nC - gamma - 1 else NL * Qm * -(-Gp // nC) for q in range(nC)]
+                    assert sum(E) == G
+                    multi += nC > 1
+                    with_gamma += gamma != 0
+                    starved += Gp < nC
+                    for dep_first in (0, 1):
+                        assert h.lsnh_tb_code_blocks(tbs, G, Qm, NL, E0, O0, dep_first, NBEFORE, out, 32, C.byref(pay)) == nC
+                        got = [list(out[7 * q:7 * q + 7]) for q in range(nC)]
+                        exp = [[K[q], Fq[q], E[q], E0 + sum(E[:q]), O0 + sum(nbytes[:q]), nbytes[q],
+                                NBEFORE if (dep_first and q > 0) else NODEP] for q in range(nC)]
+                        assert got == exp, (tbs, G, Qm, NL, dep_first)
+                        assert sum(g[2] for g in got) == G
+                        assert pay.value == (sum(nbytes) + 15) // 16 * 16
+    assert multi and with_gamma and starved
+
+
+def _crc24a_rem(data):
+    """the bytes as a polynomial (first bit = highest power) mod g_CRC24A, no extra shift: what k_turbo reports per code block as rem_a"""
+    reg = 0
+    for byte in data:
+        for i in range(7, -1, -1):
+            reg = (reg << 1) | ((byte >> i) & 1)
+            if reg & 0x1000000:
+                reg ^= 0x1864CFB
+    return reg
+
+
+def test_tb_verdict():
+    """TbVerdict (the transport-block verdict of runJobs, puschDecodeGrid and the two HARQ paths) on random payloads of 1 .. 13 code blocks with a CRC24A
+    attached by a Python CRC: passes on the clean payload; fails on one flipped bit, one failed block, a truncated last block and the all-zero payload; its
+    remainder is the Python CRC of the whole byte string in every case.  The two identities the carried-shift form rests on: a * 1 mod g == a for a < 2^24."""
+    h = hosttest()
+    rng = np.random.default_rng(24)
+    for a in [0, 1, 2, 0x800000, 0xFFFFFF, 0x864CFB] + [int(x) for x in rng.integers(0, 1 << 24, 200)]:
+        assert h.lsnh_crc24a_mulmod(a, 1) == a and h.lsnh_crc24a_mulmod(1, a) == a
+    out3 = (C.c_uint64 * 3)()
+
+    def verdict(blocks, ok, tbs):
+        n = len(blocks)
+        pl = np.frombuffer(b"".join(blocks) + bytes(16), dtype=np.uint8).copy()   # (the engine's payload arenas are padded too)
+        rem_a = np.array([_crc24a_rem(b) for b in blocks], dtype=np.uint32)
+        assert all(int(r) < (1 << 24) for r in rem_a)
+        nb = np.array([len(b) for b in blocks], dtype=np.uint32)
+        okv = np.array(ok, dtype=np.uint8)
+        r = h.lsnh_tb_verdict(n, okv.ctypes.data, rem_a.ctypes.data, nb.ctypes.data, pl.ctypes.data, tbs, out3)
+        assert out3[0] == (1 if all(ok) else 0)
+        assert out3[1] == _crc24a_rem(b"".join(blocks))
+        assert out3[2] == 8 * sum(len(b) for b in blocks)
+        return r
+
+    def split(data, lens):
+        o, res = 0, []
+        for n in lens:
+            res.append(data[o:o + n])
+            o += n
+        assert o == len(data)
+        return res
+
+    for trial in range(60):
+        n = trial % 13 + 1
+        lens = [int(x) for x in rng.integers(5, 769, n)]
+        lens[0] = max(5, lens[0] - int(rng.integers(0, 4)))
+        data = bytes(rng.integers(0, 256, sum(lens) - 3, dtype=np.uint8))
+        if not any(data):
+            data = b"\x01" + data[1:]
+        par = _crc24a_rem(data + bytes(3))
+        assert par != 0
+        whole = data + par.to_bytes(3, "big")
+        tbs = 8 * len(data)
+        assert _crc24a_rem(whole) == 0
+        assert verdict(split(whole, lens), [1] * n, tbs) == 1
+        bit = int(rng.integers(0, 8 * len(whole)))
+        flipped = bytearray(whole)
+        flipped[bit // 8] ^= 0x80 >> (bit % 8)
+        assert verdict(split(bytes(flipped), lens), [1] * n, tbs) == 0 and out3[1] != 0
+        bad = [1] * n
+        bad[int(rng.integers(0, n))] = 0
+        assert verdict(split(whole, lens), bad, tbs) == 0 and out3[1] == 0
+        cut = int(rng.integers(1, 4))
+        assert verdict(split(whole[:-cut], lens[:-1] + [lens[-1] - cut]), [1] * n, tbs) == 0
+        assert verdict(split(bytes(len(whole)), lens), [1] * n, tbs) == 0 and out3[1] == 0 and out3[2] == tbs + 24
+
+
 def _search_parity(scn, nsf, seed, update_meta_period=0, **over):
     """FALCON search of the product over oracle-decoded candidate tables == the oracle worker's own search."""
     h = hosttest()
