@@ -321,12 +321,20 @@ int lsn_phy_prepare_file(lsn_phy_t* phy, uint32_t nof_antennas);
  * 4 rate_out, a pass band the lower rate cannot carry with at most 192 taps (min(rate_in, rate_out) below about 2.06 passband_hz when up-sampling),
  * a struct_size the library does not know, rates that are zero, negative or not finite.
  *
+ * A cell that is not at the centre of the recording (offset-tuned capture, one carrier of a wideband capture): center_offset_hz is its carrier relative
+ * to the recording's centre.  Input sample n (its index in the RECORDING) is multiplied by exp(-2 pi j Phi(n) / 2^64) before the filter sees it, Phi(n) =
+ * n W mod 2^64, W = round(center_offset_hz / rate_in * 2^64) mod 2^64: integer phase, so pieces, block sizes and call boundaries still change no bit.  The
+ * exponential is a two-table NCO (12 + 10 phase bits, float32).  Same filter, same tap counts.  Accepted when finite and |center_offset_hz| + passband_hz <=
+ * rate_in / 2 (the cell lies inside the recording), otherwise LSN_ERROR_INVALID_INPUTS.  Open loop: nothing searches for carriers or tracks one; one cell per
+ * pass - two Phys replay two cells of one file.  0 runs the kernel without the mixer.  Unlike lsn_file_cfg_t.offset_freq_hz (a rotation of the OUTPUT samples
+ * that restarts every subframe, behind the filter) this is a translation in front of it.
+ *
  * lsn_resample: needs no Phy.  in: [sample][antenna] in sample_format, in[0] = sample in_base of the recording; out: [antenna][n_out] cf32,
  * out[0] = output sample out_first.  Output sample 0 sits at first_sample + first_frac.  Samples in front of sample 0 of the recording read as
  * zeros; every other sample the outputs read must lie inside in (lsn_resample_span tells which), otherwise LSN_ERROR_INVALID_INPUTS.  A caller
  * that resamples a long recording in pieces keeps first_sample / first_frac, moves in_base and out_first, and gets the samples of one call bit for bit. */
 typedef struct {
-  uint32_t struct_size;      /* sizeof(lsn_resample_cfg_t): the library refuses a size it does not know */
+  uint32_t struct_size;      /* sizeof(lsn_resample_cfg_t), or the size up to and including passband_hz; the library refuses every other size */
   uint32_t nof_antennas;     /* interleaved in the input */
   uint32_t sample_format;    /* LSN_FILE_* */
   float    sample_scale;     /* as lsn_file_cfg_t */
@@ -336,6 +344,7 @@ typedef struct {
   uint64_t in_base;          /* index, in the recording, of in[0] */
   uint64_t out_first;        /* index m of out[0] */
   double   passband_hz;      /* |f| that must come through unharmed: 15 kHz * (6 nof_prb + 1) for an LTE cell; 0 = 0.44 min(rate_in, rate_out) */
+  double   center_offset_hz; /* carrier of the wanted cell relative to the recording's centre (may be negative); absent in the old struct_size: 0 */
 } lsn_resample_cfg_t;
 typedef struct {
   int64_t in_lo, in_hi;      /* outputs out_first .. out_first + n_out - 1 read the input samples in_lo <= n < in_hi (in_lo < 0: zeros) */
@@ -352,13 +361,15 @@ int lsn_resample_span(const lsn_resample_cfg_t* cfg, uint64_t n_out, uint64_t in
  * cfg->offset_time_samples + offset_time_frac; lsn_cell_search on a resampled head gives sf_start in OUTPUT samples: multiply by sample_rate_hz /
  * output rate.  Only subframes whose whole input lies inside the file are produced.  The block buffers are those of lsn_phy_prepare_file: when
  * sample_rate_hz is above the output rate a block carries fewer subframes so that its input fits (LSN_FILE_BLOCK too small for one subframe's
- * input: LSN_ERROR_INVALID_INPUTS).  sample_rate_hz equal to the output rate with a zero fraction is lsn_phy_process_file.  A rate outside the
- * accepted range (above), a wrong struct_size: LSN_ERROR_INVALID_INPUTS, nothing is decoded. */
+ * input: LSN_ERROR_INVALID_INPUTS).  sample_rate_hz equal to the output rate with a zero fraction and a zero center_offset_hz is
+ * lsn_phy_process_file; with a non-zero center_offset_hz it goes through the resampler (equal rates, the mixer in front).  LSN_TTI_FROM_MIB resamples through the
+ * same plan, offset included.  A rate or an offset outside the accepted range (above), a wrong struct_size: LSN_ERROR_INVALID_INPUTS, nothing is decoded. */
 typedef struct {
-  uint32_t struct_size;
+  uint32_t struct_size;        /* sizeof(lsn_file_rate_t), or the size up to and including offset_time_frac; every other size is refused */
   uint32_t reserved;
   double   sample_rate_hz;     /* rate of the file; the output rate is lsn_sampling_freq_hz(nof_prb, the Phy's sampling mode) */
   double   offset_time_frac;   /* added to cfg->offset_time_samples (both in INPUT samples); >= 0 */
+  double   center_offset_hz;   /* carrier of the wanted cell relative to the recording's centre, as lsn_resample_cfg_t; absent in the old struct_size: 0 */
 } lsn_file_rate_t;
 int lsn_phy_process_file_rate(lsn_phy_t* phy, const char* path, const lsn_file_cfg_t* cfg, const lsn_file_rate_t* rate, uint32_t start_tti, uint64_t max_subframes,
                               uint32_t update_meta_period, uint64_t* subframes_done);

@@ -103,13 +103,14 @@ FILE_CF32, FILE_SC16, FILE_SC8 = 0, 1, 2
 
 
 class FileRate(C.Structure):   # lsn_file_rate_t
-    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("sample_rate_hz", C.c_double), ("offset_time_frac", C.c_double)]
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("sample_rate_hz", C.c_double), ("offset_time_frac", C.c_double),
+                ("center_offset_hz", C.c_double)]
 
 
 class ResampleCfg(C.Structure):   # lsn_resample_cfg_t
     _fields_ = [("struct_size", C.c_uint32), ("nof_antennas", C.c_uint32), ("sample_format", C.c_uint32), ("sample_scale", C.c_float),
                 ("rate_in_hz", C.c_double), ("rate_out_hz", C.c_double), ("first_sample", C.c_uint64), ("first_frac", C.c_double),
-                ("in_base", C.c_uint64), ("out_first", C.c_uint64), ("passband_hz", C.c_double)]
+                ("in_base", C.c_uint64), ("out_first", C.c_uint64), ("passband_hz", C.c_double), ("center_offset_hz", C.c_double)]
 
 
 class ResampleSpan(C.Structure):   # lsn_resample_span_t
@@ -589,21 +590,30 @@ class Phy:
         _check(lib().lsn_phy_prepare_file(self._h, self.nof_rx_antennas), "prepare_file")
 
     def process_file(self, path, start_tti=0, offset_time=0, offset_freq=0.0, max_subframes=0, update_meta_period=0, sample_format=FILE_CF32, sample_scale=0.0,
-                     sample_rate=None, offset_time_frac=0.0):
+                     sample_rate=None, offset_time_frac=0.0, center_offset_hz=0.0):
         """file mode of the reference (-i file -O offset_time -o offset_freq): replay a cf32 capture (antennas interleaved per sample);
         sample_format FILE_SC16 / FILE_SC8: integer I/Q pairs, one LSB = sample_scale (0: full scale +-1); returns the number of subframes processed.
         sample_rate (Hz): the file was recorded at this rate and goes through the GPU resampler (lsn_phy_process_file_rate); offset_time and
-        offset_time_frac then count samples of the FILE's rate"""
+        offset_time_frac then count samples of the FILE's rate.  center_offset_hz: see process_file_rate"""
+        if center_offset_hz != 0.0 and sample_rate is None:
+            raise ValueError("center_offset_hz needs sample_rate (the rate of the recording): the translation is part of the resampler")
         fc = FileCfg(self.nof_rx_antennas, int(offset_time), float(offset_freq), int(sample_format), float(sample_scale))
         done = C.c_uint64(0)
         if sample_rate is not None:
-            fr = FileRate(C.sizeof(FileRate), 0, float(sample_rate), float(offset_time_frac))
+            fr = FileRate(C.sizeof(FileRate), 0, float(sample_rate), float(offset_time_frac), float(center_offset_hz))
             _check(lib().lsn_phy_process_file_rate(self._h, os.fsencode(path), C.byref(fc), C.byref(fr), start_tti if start_tti == TTI_FROM_MIB else start_tti % 10240,
                                                    max_subframes, update_meta_period, C.byref(done)), "process_file_rate")
             return int(done.value)
         _check(lib().lsn_phy_process_file(self._h, os.fsencode(path), C.byref(fc), start_tti if start_tti == TTI_FROM_MIB else start_tti % 10240, max_subframes, update_meta_period, C.byref(done)),
                "process_file")
         return int(done.value)
+
+    def process_file_rate(self, path, sample_rate, center_offset_hz=0.0, **kw):
+        """lsn_phy_process_file_rate: replay a recording made at sample_rate (Hz) whose wanted cell sits center_offset_hz off the recording's centre (an
+        offset-tuned capture, or one carrier of a wideband capture; may be negative).  The input samples are translated by -center_offset_hz in front of the
+        resampler's filter, with an integer phase that is a function of the sample's index in the recording.  Accepted when |center_offset_hz| + the cell's
+        occupied half-band <= sample_rate / 2.  Two Phys replay two cells of one file.  Other arguments: process_file"""
+        return self.process_file(path, sample_rate=sample_rate, center_offset_hz=center_offset_hz, **kw)
 
     # ---- uplink ----
     def setUlConfig(self, cyclic_shift, delta_ss, hopping_offset=0, group_hopping=0, sequence_hopping=0):
@@ -814,26 +824,27 @@ def cell_search(iq, nof_prb, nof_periods=2, force_n_id_2=-1, threshold=20.0, dev
     return (rc, out, corr) if with_corr else (rc, out)
 
 
-def _resample_cfg(nof_antennas, rate_in, rate_out, first_sample, first_frac, in_base, out_first, passband_hz, sample_format, sample_scale):
+def _resample_cfg(nof_antennas, rate_in, rate_out, first_sample, first_frac, in_base, out_first, passband_hz, sample_format, sample_scale, center_offset_hz=0.0):
     return ResampleCfg(C.sizeof(ResampleCfg), int(nof_antennas), int(sample_format), float(sample_scale), float(rate_in), float(rate_out), int(first_sample),
-                       float(first_frac), int(in_base), int(out_first), float(passband_hz))
+                       float(first_frac), int(in_base), int(out_first), float(passband_hz), float(center_offset_hz))
 
 
-def resample_span(n_out, in_end, rate_in, rate_out, first_sample=0, first_frac=0.0, out_first=0, passband_hz=0.0):
+def resample_span(n_out, in_end, rate_in, rate_out, first_sample=0, first_frac=0.0, out_first=0, passband_hz=0.0, center_offset_hz=0.0):
     """lsn_resample_span -> dict(in_lo, in_hi, max_out, taps): the input samples [in_lo, in_hi) that outputs out_first .. out_first + n_out - 1 read, and the
     number of outputs from out_first on that a recording of in_end samples carries"""
-    cfg = _resample_cfg(1, rate_in, rate_out, first_sample, first_frac, 0, out_first, passband_hz, FILE_CF32, 0.0)
+    cfg = _resample_cfg(1, rate_in, rate_out, first_sample, first_frac, 0, out_first, passband_hz, FILE_CF32, 0.0, center_offset_hz)
     sp = ResampleSpan()
     _check(lib().lsn_resample_span(C.byref(cfg), int(n_out), int(in_end), C.byref(sp)), "lsn_resample_span")
     return dict(in_lo=int(sp.in_lo), in_hi=int(sp.in_hi), max_out=int(sp.max_out), taps=int(sp.taps))
 
 
 def resample(iq, rate_in, rate_out, n_out=None, first_sample=0, first_frac=0.0, in_base=0, out_first=0, passband_hz=0.0, sample_format=FILE_CF32,
-             sample_scale=0.0, device=0):
+             sample_scale=0.0, device=0, center_offset_hz=0.0):
     """lsn_resample (GPU polyphase resampler, needs no Phy).  iq: [sample][antenna] (or [sample]: one antenna) numpy complex64, or int16 / int8 with a last
     axis of 2 (I, Q) for FILE_SC16 / FILE_SC8; iq[0] is sample in_base of the recording.  Output sample m sits at input position first_sample + first_frac +
     m rate_in / rate_out; the call returns outputs out_first .. out_first + n_out - 1 as complex64 [antenna][n_out] (n_out None: as many as iq carries).
-    passband_hz: 15 kHz * (6 nof_prb + 1) for an LTE cell."""
+    passband_hz: 15 kHz * (6 nof_prb + 1) for an LTE cell.  center_offset_hz: the wanted carrier relative to the recording's centre; sample n of the
+    recording is multiplied by exp(-2 pi j center_offset_hz n / rate_in) (integer phase, two-table NCO) in front of the filter."""
     import numpy as np
     iq = np.ascontiguousarray(iq)
     pairs = sample_format != FILE_CF32
@@ -841,7 +852,7 @@ def resample(iq, rate_in, rate_out, n_out=None, first_sample=0, first_frac=0.0, 
         iq = iq.reshape(iq.shape[0], 1, *iq.shape[1:])
     iq = np.ascontiguousarray(iq, dtype=(np.complex64, np.int16, np.int8)[sample_format])
     n_in, nant = iq.shape[0], iq.shape[1]
-    cfg = _resample_cfg(nant, rate_in, rate_out, first_sample, first_frac, in_base, out_first, passband_hz, sample_format, sample_scale)
+    cfg = _resample_cfg(nant, rate_in, rate_out, first_sample, first_frac, in_base, out_first, passband_hz, sample_format, sample_scale, center_offset_hz)
     if n_out is None:
         sp = ResampleSpan()
         _check(lib().lsn_resample_span(C.byref(cfg), 0, int(in_base) + n_in, C.byref(sp)), "lsn_resample_span")

@@ -14,6 +14,7 @@
 #include <chrono>
 #include <deque>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <fcntl.h>
@@ -87,12 +88,15 @@ int Engine::processFileRate(const char* path, const lsn_file_cfg_t& fc, const ls
 {
   if (subframes_done) *subframes_done = 0;
   if (!cell_set) return LSN_ERROR;
-  if (fr.struct_size != sizeof(lsn_file_rate_t) || fc.offset_time_samples < 0 || !(fr.offset_time_frac >= 0.0 && fr.offset_time_frac < 4.0e18)) return LSN_ERROR_INVALID_INPUTS;
+  // two sizes are known: the struct up to offset_time_frac (center_offset_hz reads as 0) and the whole struct
+  if (fr.struct_size != offsetof(lsn_file_rate_t, center_offset_hz) && fr.struct_size != sizeof(lsn_file_rate_t)) return LSN_ERROR_INVALID_INPUTS;
+  const double center = fr.struct_size == sizeof(lsn_file_rate_t) ? fr.center_offset_hz : 0.0;
+  if (fc.offset_time_samples < 0 || !(fr.offset_time_frac >= 0.0 && fr.offset_time_frac < 4.0e18)) return LSN_ERROR_INVALID_INPUTS;
   const double rate_out = 15000.0 * (double)cd.N, whole = std::floor(fr.offset_time_frac);
-  if (fr.sample_rate_hz == rate_out && fr.offset_time_frac == 0.0) return processFileImpl(path, fc, nullptr, start_tti, max_subframes, update_meta_period, subframes_done);
+  if (fr.sample_rate_hz == rate_out && fr.offset_time_frac == 0.0 && center == 0.0) return processFileImpl(path, fc, nullptr, start_tti, max_subframes, update_meta_period, subframes_done);
   const uint64_t first = (uint64_t)fc.offset_time_samples + (uint64_t)whole;
   ResamplePlan plan;
-  const int r = plan.init(fr.sample_rate_hz, rate_out, 15000.0 * (6.0 * (double)cd.nof_prb + 1.0), first, fr.offset_time_frac - whole);
+  const int r = plan.init(fr.sample_rate_hz, rate_out, 15000.0 * (6.0 * (double)cd.nof_prb + 1.0), first, fr.offset_time_frac - whole, center);
   if (r != LSN_SUCCESS) return r;
   return processFileImpl(path, fc, &plan, start_tti, max_subframes, update_meta_period, subframes_done);
 }
@@ -136,9 +140,9 @@ int Engine::processFileImpl(const char* path, const lsn_file_cfg_t& fc, const Re
     lo = std::max<int64_t>(lo, 0);
     len = hi > lo ? (uint64_t)(hi - lo) : 0;
   };
-  auto rs_launch = [&](const void* raw, int64_t lo, uint64_t len, uint64_t pos, uint32_t n, const float* bank, const cf32* rot, cf32* out, hipStream_t s) {
+  auto rs_launch = [&](const void* raw, int64_t lo, uint64_t len, uint64_t pos, uint32_t n, const float* bank, const cf32* nco, const cf32* rot, cf32* out, hipStream_t s) {
     const u128 base = rs->position(pos * sflen);
-    lsn_launch_resample(raw, fmt, smp_scale, lo, len, (uint64_t)(base >> 64), (uint64_t)base, (uint32_t)(rs->step >> 64), (uint64_t)rs->step, rs->taps, rs->span, bank, rot,
+    lsn_launch_resample(raw, fmt, smp_scale, lo, len, (uint64_t)(base >> 64), (uint64_t)base, (uint32_t)(rs->step >> 64), (uint64_t)rs->step, rs->taps, rs->span, bank, rs->tune, nco, rot,
                         sflen, 0, nant, out, (uint64_t)n * sflen, s);
   };
   constexpr int NSLOT_MAX = 8;
@@ -158,7 +162,8 @@ int Engine::processFileImpl(const char* path, const lsn_file_cfg_t& fc, const Re
     use_mmap = false;
   }
   cf32* d_rot = nullptr;
-  float* d_bank = nullptr;  // the resampler's bank (a few hundred kB, as short-lived as d_rot)
+  float* d_bank = nullptr;  // the resampler's bank (a few hundred kB, as short-lived as d_rot) ...
+  const cf32* d_nco = nullptr;  // ... and, behind it in the same allocation, the mixer's tables when the plan has a tuning word
   hipStream_t st = nullptr;
   std::mutex fm;
   std::condition_variable fcv;
@@ -187,8 +192,8 @@ int Engine::processFileImpl(const char* path, const lsn_file_cfg_t& fc, const Re
       HIP_CHECK(hipMemcpy(d_rot, rot.data(), sflen * sizeof(cf32), hipMemcpyHostToDevice));
     }
     if (rs) {
-      HIP_CHECK(hipMalloc((void**)&d_bank, rs->bank.size() * sizeof(float)));
-      HIP_CHECK(hipMemcpy(d_bank, rs->bank.data(), rs->bank.size() * sizeof(float), hipMemcpyHostToDevice));
+      rs->upload(d_bank, d_nco, st);
+      HIP_CHECK(hipStreamSynchronize(st));
     }
     uint64_t first_sf = 0;  // subframes of the file in front of the replay (DECODE_MIB state of the reference)
     if (start_tti == LSN_TTI_FROM_MIB) {
@@ -202,7 +207,7 @@ int Engine::processFileImpl(const char* path, const lsn_file_cfg_t& fc, const Re
         if (pread(fd, one.data(), bytes, (off_t)(rs ? (uint64_t)lo * spb : file_off0 + i * sf_bytes)) != (ssize_t)bytes) break;
         HIP_CHECK(hipMemcpyAsync(slot[0].d_raw, one.data(), bytes, hipMemcpyHostToDevice, st));
         HIP_CHECK(hipStreamSynchronize(st));
-        if (rs) rs_launch(slot[0].d_raw, lo, len, i, 1, d_bank, d_rot, slot[0].d_iq, st);
+        if (rs) rs_launch(slot[0].d_raw, lo, len, i, 1, d_bank, d_nco, d_rot, slot[0].d_iq, st);
         else lsn_launch_file_unpack(slot[0].d_raw, fmt, smp_scale, d_rot, sflen, nant, slot[0].d_iq, 1, st);
         HIP_CHECK(hipStreamSynchronize(st));
         lsn_mib_t mib;
@@ -282,7 +287,7 @@ int Engine::processFileImpl(const char* path, const lsn_file_cfg_t& fc, const Re
             // the copy and the de-interleave are only QUEUED here (stream st); the submit below is ordered behind them on the device, so
             // the reader goes straight on to the next block while this one crosses PCIe
             HIP_CHECK(hipMemcpyAsync(s.d_raw, src, total, hipMemcpyHostToDevice, st));
-            if (rs) rs_launch(s.d_raw, in_lo, in_len, pos, (uint32_t)got, d_bank, d_rot, s.d_iq, st);
+            if (rs) rs_launch(s.d_raw, in_lo, in_len, pos, (uint32_t)got, d_bank, d_nco, d_rot, s.d_iq, st);
             else lsn_launch_file_unpack(s.d_raw, fmt, smp_scale, d_rot, sflen, nant, s.d_iq, (uint32_t)got, st);
             pos += got;
           }

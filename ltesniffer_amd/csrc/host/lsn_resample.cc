@@ -1,11 +1,12 @@
 // lsn_resample.cc - host side of the polyphase resampler: the plan of a rate pair (step and start in 64.64 fixed point, formed in 128-bit
-// integers; number of taps; the bank of 512 phases) and lsn_resample, the stand-alone entry point (needs no Phy, like lsn_cell_search).
+// integers; number of taps; the bank of 512 phases; the tuning word and tables of the mixer) and lsn_resample, the stand-alone entry point (needs no Phy, like lsn_cell_search).
 // The filter is DESIGN.md section 3.1b, restated there as a formula; tests/resample_model.py is written from that formula, not from this file.
 // Product code: no CPU fallback (the samples are computed by k_resample only), nothing from oracle/ is included or linked.
 #include "../../../include/ltesniffer_amd.h"
 #include "../kernels/lsn_dev.h"
 #include "lsn_resample.h"
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <stdexcept>
@@ -35,7 +36,7 @@ static double bessel_i0(double x)
   return s;
 }
 
-int ResamplePlan::init(double rate_in, double rate_out, double passband_hz, uint64_t first_sample, double first_frac)
+int ResamplePlan::init(double rate_in, double rate_out, double passband_hz, uint64_t first_sample, double first_frac, double center_offset_hz)
 {
   if (!(rate_in > 0.0 && rate_in < 1e12) || !(rate_out > 0.0 && rate_out < 1e12)) return LSN_ERROR_INVALID_INPUTS;
   if (!(first_frac >= 0.0 && first_frac < 1.0) || first_sample >= (1ull << 62)) return LSN_ERROR_INVALID_INPUTS;
@@ -46,6 +47,7 @@ int ResamplePlan::init(double rate_in, double rate_out, double passband_hz, uint
   if (!(passband_hz > 0.0)) return LSN_ERROR_INVALID_INPUTS;
   const double width = (lo_rate - 2.0 * passband_hz) / rate_in;   // transition band [B, min(rate) - B], in cycles per input sample
   if (!(width > 0.0)) return LSN_ERROR_INVALID_INPUTS;
+  if (!(std::fabs(center_offset_hz) + passband_hz <= 0.5 * rate_in)) return LSN_ERROR_INVALID_INPUTS;   // the cell lies inside the recording (NaN and infinity fail here)
   const double want = (kAtten - 7.95) / (14.36 * width) + 1.0;    // Kaiser's estimate of the filter length
   if (!(want <= (double)kMaxTaps)) return LSN_ERROR_INVALID_INPUTS;
   taps = std::max(4u, 2u * (uint32_t)std::ceil(want / 2.0));
@@ -57,6 +59,23 @@ int ResamplePlan::init(double rate_in, double rate_out, double passband_hz, uint
   step = (((u128)ma << sh) + (u128)mb) / ((u128)mb << 1);
   if (step == 0) return LSN_ERROR_INVALID_INPUTS;
   start = ((u128)first_sample << 64) + (u128)(uint64_t)std::ldexp(first_frac, 64);
+  // W = floor(center_offset_hz / rate_in * 2^64 + 1/2) mod 2^64, the quotient taken exactly as for D: |quotient| <= 1/2, so ec <= ea and mc << sw stays below 2^118
+  tune = 0;
+  nco.clear();
+  if (center_offset_hz != 0.0) {
+    int ec = 0;
+    const uint64_t mc = (uint64_t)std::ldexp(std::frexp(std::fabs(center_offset_hz), &ec), 53);
+    const int sw = 64 + ec - ea;
+    if (sw >= -1) {   // below that the quotient times 2^64 is under 1/2 in magnitude: W = 0
+      const __int128 num = (__int128)((u128)mc << std::max(sw, 0)) * (center_offset_hz < 0.0 ? -2 : 2), den = (__int128)((u128)ma << std::max(-sw, 0)) * 2;
+      const __int128 a = num + den / 2;   // floor(a / den) = floor(quotient 2^64 + 1/2)
+      tune = (uint64_t)(a >= 0 ? a / den : -((-a + den - 1) / den));
+    }
+  }
+  if (tune) {
+    nco.resize((4096 + 1024) * 2);
+    lsn_nco_tables((cf32*)nco.data(), (cf32*)nco.data() + 4096);
+  }
   span = (uint32_t)(((u128)kRun * step) >> 64) + taps + 2;
   // bank: H[p][j] = h(j - T/2 + 1 - p / 512), h(t) = sinc(t / rho) / rho * I0(beta sqrt(1 - (2 t / T)^2)) / I0(beta)
   const double i0b = bessel_i0(kBeta), half = 0.5 * (double)taps;
@@ -75,6 +94,17 @@ int ResamplePlan::init(double rate_in, double rate_out, double passband_hz, uint
       bank[((size_t)p * taps + j) * 2 + 1] = (float)(h1 - h0);
     }
   return LSN_SUCCESS;
+}
+
+void ResamplePlan::upload(float*& d_bank, const cf32*& d_nco, hipStream_t s) const
+{
+  HIP_CHECK(hipMalloc((void**)&d_bank, (bank.size() + nco.size()) * sizeof(float)));
+  HIP_CHECK(hipMemcpyAsync(d_bank, bank.data(), bank.size() * sizeof(float), hipMemcpyHostToDevice, s));
+  d_nco = nullptr;
+  if (!nco.empty()) {
+    HIP_CHECK(hipMemcpyAsync(d_bank + bank.size(), nco.data(), nco.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    d_nco = (const cf32*)(d_bank + bank.size());
+  }
 }
 
 void ResamplePlan::inputSpan(uint64_t m0, uint64_t n, int64_t& lo, int64_t& hi) const
@@ -98,10 +128,12 @@ uint64_t ResamplePlan::outputsInside(uint64_t in_end) const
 
 static int resample_plan(const lsn_resample_cfg_t* cfg, lsn::ResamplePlan& plan)
 {
-  if (!cfg || cfg->struct_size != sizeof(lsn_resample_cfg_t)) return LSN_ERROR_INVALID_INPUTS;
+  // two sizes are known: the struct up to passband_hz (center_offset_hz reads as 0) and the whole struct
+  if (!cfg || (cfg->struct_size != offsetof(lsn_resample_cfg_t, center_offset_hz) && cfg->struct_size != sizeof(lsn_resample_cfg_t))) return LSN_ERROR_INVALID_INPUTS;
+  const double center = cfg->struct_size == sizeof(lsn_resample_cfg_t) ? cfg->center_offset_hz : 0.0;
   if (cfg->nof_antennas < 1 || cfg->nof_antennas > 8 || cfg->sample_format > LSN_FILE_SC8) return LSN_ERROR_INVALID_INPUTS;
   if (cfg->sample_format != LSN_FILE_CF32 && !(cfg->sample_scale >= 0.0f && cfg->sample_scale < INFINITY)) return LSN_ERROR_INVALID_INPUTS;
-  return plan.init(cfg->rate_in_hz, cfg->rate_out_hz, cfg->passband_hz, cfg->first_sample, cfg->first_frac);
+  return plan.init(cfg->rate_in_hz, cfg->rate_out_hz, cfg->passband_hz, cfg->first_sample, cfg->first_frac, center);
 }
 
 extern "C" {
@@ -137,14 +169,15 @@ int lsn_resample(int device, const void* in, int in_on_device, uint64_t n_in, co
   const float scale = fmt == LSN_FILE_CF32 ? 1.0f : cfg->sample_scale != 0.0f ? cfg->sample_scale : fmt == LSN_FILE_SC16 ? 1.0f / 32768.0f : 1.0f / 128.0f;
   const uint64_t len = hi > need_lo ? (uint64_t)(hi - need_lo) : 0;
   const uint8_t* src = (const uint8_t*)in + ((uint64_t)need_lo - cfg->in_base) * smp;
-  void *d_in = nullptr, *d_bank = nullptr, *d_out = nullptr;
+  void *d_in = nullptr, *d_out = nullptr;
+  float* d_bank = nullptr;
+  const cf32* d_nco = nullptr;
   hipStream_t st = nullptr;
   int rc = LSN_SUCCESS;
   try {
     HIP_CHECK(hipSetDevice(device));
     HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    HIP_CHECK(hipMalloc(&d_bank, plan.bank.size() * sizeof(float)));
-    HIP_CHECK(hipMemcpyAsync(d_bank, plan.bank.data(), plan.bank.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    plan.upload(d_bank, d_nco, st);
     const void* raw = src;
     if (!in_on_device && len) {
       HIP_CHECK(hipMalloc(&d_in, len * smp));
@@ -159,7 +192,7 @@ int lsn_resample(int device, const void* in, int in_on_device, uint64_t n_in, co
     }
     const lsn::u128 base = plan.position(cfg->out_first);
     lsn_launch_resample(raw, fmt, scale, need_lo, len, (uint64_t)(base >> 64), (uint64_t)base, (uint32_t)(plan.step >> 64), (uint64_t)plan.step, plan.taps, plan.span,
-                        (const float*)d_bank, nullptr, (uint32_t)n_out, 0, nant, dst, n_out, st);
+                        d_bank, plan.tune, d_nco, nullptr, (uint32_t)n_out, 0, nant, dst, n_out, st);
     if (!out_on_device) HIP_CHECK(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
   } catch (const std::exception& ex) {

@@ -1,5 +1,5 @@
-// lsn_resample.h - host side of the polyphase resampler (kernels/resample.hip): the plan of one rate pair - step, start, taps, bank - and the
-// 64.64 position arithmetic in 128-bit integers.  Definition: DESIGN.md section 3.1b.
+// lsn_resample.h - host side of the polyphase resampler (kernels/resample.hip): the plan of one rate pair - step, start, taps, bank, and the
+// tuning word and NCO tables of the mixer in front of the filter - and the 64.64 position arithmetic in 128-bit integers.  Definition: DESIGN.md section 3.1b.
 #pragma once
 #include <cstdint>
 #include <vector>
@@ -17,9 +17,14 @@ struct ResamplePlan {
   uint32_t taps = 0;   // T (even)
   uint32_t span = 0;   // input samples one run of the kernel stages
   std::vector<float> bank;  // [512][T][2]: H[p][j] and H[p + 1][j] - H[p][j], float32 (row 511 reaches phase 512 through its difference)
+  uint64_t tune = 0;        // W = floor(center_offset_hz / rate_in * 2^64 + 1/2) mod 2^64: input sample n is rotated by exp(-2 pi j (n W mod 2^64) / 2^64)
+  std::vector<float> nco;   // tune != 0: the mixer's tables, [4096] coarse then [1024] fine (re, im), lsn_nco_tables; else empty
 
-  // LSN_SUCCESS, or LSN_ERROR_INVALID_INPUTS when the pair is outside what the filter meets (accepted range)
-  int init(double rate_in, double rate_out, double passband_hz, uint64_t first_sample, double first_frac);
+  // LSN_SUCCESS, or LSN_ERROR_INVALID_INPUTS when the pair is outside what the filter meets, or the cell at center_offset_hz does not lie inside
+  // the recording (accepted range)
+  int init(double rate_in, double rate_out, double passband_hz, uint64_t first_sample, double first_frac, double center_offset_hz);
+  // device copy of bank and nco in one allocation (the caller frees d_bank); d_nco = null when the plan does not mix
+  void upload(float*& d_bank, const cf32*& d_nco, hipStream_t s) const;
   u128 position(uint64_t m) const { return start + (u128)m * step; }
   // input samples [lo, hi) that outputs m0 .. m0 + n - 1 read (lo may be negative: zeros in front of the recording)
   void inputSpan(uint64_t m0, uint64_t n, int64_t& lo, int64_t& hi) const;
@@ -30,5 +35,5 @@ struct ResamplePlan {
 }  // namespace lsn
 
 void lsn_launch_resample(const void* raw, uint32_t fmt, float scale, int64_t buf_base, uint64_t buf_len, uint64_t base_hi, uint64_t base_lo, uint32_t d_hi,
-                         uint64_t d_lo, uint32_t taps, uint32_t span, const float* bank, const cf32* rot, uint32_t sflen, uint32_t sf_off, uint32_t nant, cf32* out,
-                         uint64_t n_out, hipStream_t s);
+                         uint64_t d_lo, uint32_t taps, uint32_t span, const float* bank, uint64_t w, const cf32* nco, const cf32* rot, uint32_t sflen, uint32_t sf_off,
+                         uint32_t nant, cf32* out, uint64_t n_out, hipStream_t s);

@@ -232,8 +232,7 @@ void Engine::buildTables()
     for (int k = 0; k < N; k++) { double a = 2.0 * M_PI * k / N; t3[k] = {(float)std::cos(a), (float)(-std::sin(a))}; }
     cd.twiddle3 = upload(dev_allocs, t3);
   }
-  for (int k = 0; k < 4096; k++) { double a = 2.0 * M_PI * k / 4096.0; coarse[k] = {(float)std::cos(a), (float)std::sin(a)}; }
-  for (int k = 0; k < 1024; k++) { double a = 2.0 * M_PI * k / 4194304.0; fine[k] = {(float)std::cos(a), (float)std::sin(a)}; }
+  lsn_nco_tables(coarse.data(), fine.data());
   cd.twiddle = upload(dev_allocs, tw); cd.nco_coarse = upload(dev_allocs, coarse); cd.nco_fine = upload(dev_allocs, fine);
   // CRS values for every subframe index (36.211 6.10.1.1)
   {

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <atomic>
+#include <cmath>
 #include <stdexcept>
 #include <string>
 #include "../host/lsn_types.h"
@@ -34,6 +35,14 @@ inline void lsn_func_max_lds(const void* fn, int bytes, std::atomic<uint64_t>& d
 }
 
 struct cf32 { float r, i; };
+
+// The two NCO tables (double -> float): coarse[k] = exp(2 pi j k / 4096), k < 4096, and fine[k] = exp(2 pi j k / 2^22), k < 1024.  The top 12 bits of a phase
+// index the first, the next 10 bits the second; their product is the rotation (k_ofdm's CFO correction on 32-bit phases, the resampler's mixer on 64-bit ones).
+inline void lsn_nco_tables(cf32* coarse, cf32* fine)
+{
+  for (int k = 0; k < 4096; k++) { double a = 2.0 * M_PI * k / 4096.0; coarse[k] = {(float)std::cos(a), (float)std::sin(a)}; }
+  for (int k = 0; k < 1024; k++) { double a = 2.0 * M_PI * k / 4194304.0; fine[k] = {(float)std::cos(a), (float)std::sin(a)}; }
+}
 
 #define LSN_MAX_RX 2
 #define LSN_MAX_PORTS 4

@@ -11,6 +11,10 @@
 // lane runs the T taps of its outputs: coefficient j = H[p][j] + f * dH[p][j] (p = top 9 bits of the fraction, f = the next 24 bits), one
 // 16-byte load of the bank row gives two taps, one ds_read_b64 per sample.  Up-sampling and equal rates: neighbouring lanes read the
 // same or neighbouring float2 (broadcast / conflict free); down-sampling by r strides the lanes by r float2 = a 2- to 4-way conflict.
+//
+// MIX instantiations (a cell off the recording's centre, DESIGN 3.1b "Frequency translation"): input sample n is multiplied by
+// exp(-2 pi j Phi(n) / 2^64), Phi(n) = n * W mod 2^64 with n the sample's index in the RECORDING, while it is staged - the one place every input
+// sample is touched once; the tap loop does not know.  The exponential is the two-table NCO of k_ofdm (4096 coarse x 1024 fine entries).
 #include "lsn_dsp.h"
 
 #define LSN_RS_RUN 512u      // outputs per workgroup (256 lanes x 2)
@@ -32,9 +36,11 @@ struct LsnResampleArgs {
   const float2* bank;    // [512][T] (H, dH)
   const cf32* rot;       // optional [sflen]
   cf32* out;
+  uint64_t w;            // MIX: tuning word W ...
+  const cf32* nco;       // ... and the NCO tables, [4096] coarse then [1024] fine
 };
 
-template <int FMT>
+template <int FMT, bool MIX>
 __global__ __launch_bounds__(256) void k_resample(const LsnResampleArgs A)
 {
   extern __shared__ float2 rs_x[];
@@ -58,6 +64,13 @@ __global__ __launch_bounds__(256) void k_resample(const LsnResampleArgs A)
         x.x = (float)q.x * A.scale; x.y = (float)q.y * A.scale;
       } else {
         x = ((const float2*)A.raw)[src];
+      }
+      if (MIX) {
+        const uint64_t ph = (uint64_t)n * A.w;   // low 64 bits of n W
+        const cf32 e = cmul(A.nco[ph >> 52], A.nco[4096u + (uint32_t)((ph >> 42) & 1023u)]);
+        cf32 v; v.r = x.x; v.i = x.y;
+        v = cmulconj(v, e);
+        x.x = v.r; x.y = v.i;
       }
     }
     rs_x[s] = x;
@@ -90,10 +103,11 @@ __global__ __launch_bounds__(256) void k_resample(const LsnResampleArgs A)
   }
 }
 
-// n_out outputs per antenna from output position (base_hi, base_lo); span = samples a run of LSN_RS_RUN outputs needs (host: lsn_resample.cc)
+// n_out outputs per antenna from output position (base_hi, base_lo); span = samples a run of LSN_RS_RUN outputs needs (host: lsn_resample.cc).
+// nco != null: the mixing instantiations with tuning word w; null: the plain ones, as before the mixer existed
 void lsn_launch_resample(const void* raw, uint32_t fmt, float scale, int64_t buf_base, uint64_t buf_len, uint64_t base_hi, uint64_t base_lo, uint32_t d_hi,
-                         uint64_t d_lo, uint32_t taps, uint32_t span, const float* bank, const cf32* rot, uint32_t sflen, uint32_t sf_off, uint32_t nant, cf32* out,
-                         uint64_t n_out, hipStream_t s)
+                         uint64_t d_lo, uint32_t taps, uint32_t span, const float* bank, uint64_t w, const cf32* nco, const cf32* rot, uint32_t sflen, uint32_t sf_off,
+                         uint32_t nant, cf32* out, uint64_t n_out, hipStream_t s)
 {
   if (!n_out) return;
   if (taps < 2 || (taps & 1) || span < taps || (size_t)span * sizeof(float2) > 64 * 1024 || buf_base < 0 || !sflen) throw std::runtime_error("k_resample: bad geometry");
@@ -102,9 +116,16 @@ void lsn_launch_resample(const void* raw, uint32_t fmt, float scale, int64_t buf
   LsnResampleArgs A;
   A.raw = raw; A.buf_base = buf_base; A.buf_len = buf_len; A.base_hi = base_hi; A.base_lo = base_lo; A.d_lo = d_lo; A.d_hi = d_hi; A.taps = taps; A.span = span;
   A.nant = nant; A.sflen = sflen; A.sf_off = sf_off; A.n_out = n_out; A.scale = scale; A.bank = (const float2*)bank; A.rot = rot; A.out = out;
+  A.w = w; A.nco = nco;
   const dim3 g((uint32_t)runs, nant);
   const size_t lds = (size_t)span * sizeof(float2);
-  if (fmt == 1) LSN_LAUNCH(k_resample<1>, g, dim3(256), lds, s, A);
-  else if (fmt == 2) LSN_LAUNCH(k_resample<2>, g, dim3(256), lds, s, A);
-  else LSN_LAUNCH(k_resample<0>, g, dim3(256), lds, s, A);
+  if (nco) {
+    if (fmt == 1) LSN_LAUNCH((k_resample<1, true>), g, dim3(256), lds, s, A);
+    else if (fmt == 2) LSN_LAUNCH((k_resample<2, true>), g, dim3(256), lds, s, A);
+    else LSN_LAUNCH((k_resample<0, true>), g, dim3(256), lds, s, A);
+  } else {
+    if (fmt == 1) LSN_LAUNCH((k_resample<1, false>), g, dim3(256), lds, s, A);
+    else if (fmt == 2) LSN_LAUNCH((k_resample<2, false>), g, dim3(256), lds, s, A);
+    else LSN_LAUNCH((k_resample<0, false>), g, dim3(256), lds, s, A);
+  }
 }

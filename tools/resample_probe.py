@@ -8,12 +8,15 @@ resampler round by round.  The first round is a warm-up and is left out.
 
   python tools/resample_probe.py [--rounds 6] [--out FILE]          kernel durations from `rocprofv3 --kernel-trace`: median and range per leg, bytes moved
                                                                      (input span read once + output written) per second
-  python tools/resample_probe.py --pmc [--out FILE]                 a counter run of its own (SQ busy cycles, VALU / LDS activity, LDS bank conflicts) per launch"""
+  python tools/resample_probe.py --pmc [--out FILE]                 a counter run of its own (SQ busy cycles, VALU / LDS activity, LDS bank conflicts) per launch
+  --offset HZ    center_offset_hz of the k_resample legs (|HZ| <= 3.485e6 for the 25 MS/s legs): the mixing instantiations.  Without it (0) the legs pass the
+                 struct up to passband_hz, which a library from before the mixer accepts as well: LSN_LIB_PATH=<that build> runs the same legs on it (A/B)."""
 import argparse
 import csv
 import ctypes as C
 import glob
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -26,7 +29,25 @@ RS_LEGS = [(25e6, 0, "cf32"), (25e6, 1, "sc16"), (61.44e6, 0, "cf32"), (61.44e6,
 COUNTERS = ["SQ_BUSY_CYCLES", "SQ_ACTIVE_INST_VALU", "SQ_ACTIVE_INST_LDS", "SQ_LDS_BANK_CONFLICT", "SQ_LDS_IDX_ACTIVE", "SQ_WAIT_INST_LDS", "SQ_INSTS_VALU", "SQ_INSTS_LDS"]
 
 
-def child(rounds):
+def _cfg(rate_in, fmt, offset):
+    import ltesniffer_amd as la
+    cfg = la._resample_cfg(NANT, rate_in, RATE_OUT, 0, 0.0, 0, 0, B, fmt, 1.0 / 8192)
+    if offset != 0.0:
+        cfg.center_offset_hz = offset
+    else:
+        cfg.struct_size = la.ResampleCfg.center_offset_hz.offset
+    return cfg
+
+
+def _span(rate_in, fmt, offset):
+    import ltesniffer_amd as la
+    sp = la.ResampleSpan()
+    rc = la.lib().lsn_resample_span(C.byref(_cfg(rate_in, fmt, offset)), NSF * SFLEN, 0, C.byref(sp))
+    assert rc == 0, rc
+    return dict(in_hi=int(sp.in_hi), taps=int(sp.taps))
+
+
+def child(rounds, offset):
     import numpy as np
     import torch
     import ltesniffer_amd as la
@@ -36,9 +57,9 @@ def child(rounds):
     out = torch.zeros((NANT, n_out, 2), dtype=torch.float32, device="cuda:0")
     legs = []
     for rate_in, fmt, _ in RS_LEGS:
-        n_in = la.resample_span(n_out, 0, rate_in, RATE_OUT, passband_hz=B)["in_hi"]
+        n_in = _span(rate_in, fmt, offset)["in_hi"]
         x = rng.standard_normal((n_in, NANT, 2)).astype(np.float32) if fmt == 0 else rng.integers(-8000, 8000, (n_in, NANT, 2)).astype(np.int16)
-        legs.append((torch.from_numpy(x).to("cuda:0"), n_in, la._resample_cfg(NANT, rate_in, RATE_OUT, 0, 0.0, 0, 0, B, fmt, 1.0 / 8192)))
+        legs.append((torch.from_numpy(x).to("cuda:0"), n_in, _cfg(rate_in, fmt, offset)))
     os.environ["LSN_FILE_BLOCK"] = str(NSF)
     td = tempfile.mkdtemp(prefix="rs_probe_")
     try:
@@ -68,18 +89,18 @@ def _col(row, *want):
     raise KeyError(want)
 
 
-def _run(prof_args, rounds):
+def _run(prof_args, rounds, offset):
     td = tempfile.mkdtemp(prefix="rs_prof_")
-    cmd = ["rocprofv3"] + prof_args + ["--output-format", "csv", "-d", td, "--", sys.executable, os.path.abspath(__file__), "--child", "--rounds", str(rounds)]
+    cmd = ["rocprofv3"] + prof_args + ["--output-format", "csv", "-d", td, "--", sys.executable, os.path.abspath(__file__), "--child", "--rounds", str(rounds),
+                                       "--offset", repr(offset)]
     subprocess.check_call(cmd, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     return td
 
 
 def _kind(name):
-    for k in ("k_resample<0>", "k_resample<1>", "k_file_unpack<0>", "k_file_unpack<1>"):
-        if k in name:
-            return k
-    return None
+    """k_resample<FMT> / k_file_unpack<FMT>: the first template argument (k_resample has a second one, the mixer, since center_offset_hz exists)"""
+    m = re.search(r"(k_resample|k_file_unpack)<(\d)", name)
+    return "%s<%s>" % m.groups() if m else None
 
 
 def main():
@@ -88,9 +109,10 @@ def main():
     ap.add_argument("--pmc", action="store_true")
     ap.add_argument("--child", action="store_true")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--offset", type=float, default=0.0)
     a = ap.parse_args()
     if a.child:
-        return child(a.rounds)
+        return child(a.rounds, a.offset)
     import ltesniffer_amd as la
     lines = []
 
@@ -99,9 +121,9 @@ def main():
         lines.append(s)
 
     n_out = NSF * SFLEN
-    spans = {(r, f): la.resample_span(n_out, 0, r, RATE_OUT, passband_hz=B) for r, f, _ in RS_LEGS}
+    spans = {(r, f): _span(r, f, a.offset) for r, f, _ in RS_LEGS}
     if not a.pmc:
-        td = _run(["--kernel-trace"], a.rounds)
+        td = _run(["--kernel-trace"], a.rounds, a.offset)
         seq = {}
         for p in glob.glob(os.path.join(td, "**", "*kernel_trace.csv"), recursive=True):
             for r in csv.DictReader(open(p)):
@@ -109,7 +131,8 @@ def main():
                 if k:
                     seq.setdefault(k, []).append((int(r[_col(r, "start_timestamp")]), int(r[_col(r, "end_timestamp")])))
         shutil.rmtree(td, ignore_errors=True)
-        say("resample_probe: 20 MHz, 2 antennas, %d output subframes per launch (%d outputs per antenna), %d timed rounds interleaved, warm-up round left out" % (NSF, n_out, a.rounds))
+        say("resample_probe: 20 MHz, 2 antennas, %d output subframes per launch (%d outputs per antenna), %d timed rounds interleaved, warm-up round left out, center_offset_hz %g, library %s" %
+            (NSF, n_out, a.rounds, a.offset, os.path.relpath(la.LIB_PATH, ROOT)))
 
         def report(label, durs, nbytes, extra=""):
             d = sorted(durs)
@@ -126,7 +149,7 @@ def main():
             u = [e - s for s, e in sorted(seq.get("k_file_unpack<%d>" % fmt, []))]
             report("k_file_unpack %s (baseline)" % ("cf32", "sc16")[fmt], u[1:], n_out * NANT * ((8 if fmt == 0 else 4) + 8))
     else:
-        td = _run(["--kernel-trace", "--pmc"] + COUNTERS, 2)
+        td = _run(["--kernel-trace", "--pmc"] + COUNTERS, 2, a.offset)
         acc = {}   # (kernel, counter) -> {dispatch: value summed over the rows of the dispatch}
         for p in glob.glob(os.path.join(td, "**", "*counter_collection.csv"), recursive=True):
             for r in csv.DictReader(open(p)):
