@@ -19,12 +19,6 @@
 #include <stdexcept>
 #include <string>
 
-#define HIP_CHECK(x)                                                                                       \
-  do {                                                                                                     \
-    hipError_t _e = (x);                                                                                   \
-    if (_e != hipSuccess) throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(_e) + " at " #x); \
-  } while (0)
-
 namespace lsn {
 
 // Host wait for a pipeline event.  hipEventSynchronize keeps the calling core busy for the whole wait on this runtime even
@@ -45,11 +39,6 @@ static void waitEvent(hipEvent_t ev, long nap_ns = 50000)
     timespec ts{0, nap_ns};
     nanosleep(&ts, nullptr);
   }
-}
-
-static double now_ms()
-{
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
 // pipeline event log (LSN_TRACE): thread 0 = caller/search, 1 = front, 2.. = decode threads
@@ -219,7 +208,6 @@ Engine::~Engine()
   for (auto& e : peer_ev) if (e) (void)hipEventDestroy(e);
   for (auto& e : ev_pool) if (e) (void)hipEventDestroy(e);
   if (copy_stream) (void)hipStreamDestroy(copy_stream);
-  for (auto& e : copy_done) if (e) (void)hipEventDestroy(e);
 }
 
 int Engine::setCell(const lsn_cell_t& c)
@@ -231,7 +219,7 @@ int Engine::setCell(const lsn_cell_t& c)
   cpu_set_t saved_mask;
   const bool pinned = pinThisThread(&saved_mask);  // pinned host buffers are first touched on the GPU's node
   struct Unpin { Engine* e; bool on; cpu_set_t* m; ~Unpin() { if (on) e->unpinThisThread(m); } } unpin{this, pinned, &saved_mask};
-  try {
+  const int r = guarded([&]() -> int {
     HIP_CHECK(hipSetDevice(cfg.device));
     (void)hipDeviceSynchronize();
     freeDevice(true);
@@ -248,12 +236,10 @@ int Engine::setCell(const lsn_cell_t& c)
     // wait for: without this barrier a clear still in flight could wipe what the first stage-A kernels of a fresh engine had just written (seen once
     // the process ran on 16 hardware queues: the records of the first subframes missing in 1 of 40 runs)
     HIP_CHECK(hipDeviceSynchronize());
-  } catch (const std::exception& ex) {
-    fprintf(stderr, "ltesniffer_amd: %s\n", ex.what());
-    return LSN_ERROR;
-  }
-  cell_set = true;
-  return LSN_SUCCESS;
+    return LSN_SUCCESS;
+  });
+  if (r == LSN_SUCCESS) cell_set = true;
+  return r;
 }
 
 void Engine::getStats(lsn_blind_stats_t* s) const
@@ -1999,7 +1985,7 @@ int Engine::submit(const void* d_iq, uint32_t nsf_total, uint32_t start_tti, uin
 {
   if (!cell_set) return LSN_ERROR;
   if (!d_iq && nsf_total) return LSN_ERROR_INVALID_INPUTS;
-  try {
+  return guarded([&]() -> int {
     HIP_CHECK(hipSetDevice(cfg.device));
     if (!batch_open) {  // first submit since the last wait: the counters describe one submit ... wait span
       perf = lsn_perf_t{};
@@ -2032,10 +2018,7 @@ int Engine::submit(const void* d_iq, uint32_t nsf_total, uint32_t start_tti, uin
     }
     cv_front.notify_one();
     return LSN_SUCCESS;
-  } catch (const std::exception& ex) {
-    fprintf(stderr, "ltesniffer_amd: %s\n", ex.what());
-    return LSN_ERROR;
-  }
+  });
 }
 
 int Engine::submitFrom(const void* d_iq, int src_device, uint32_t nsf, uint32_t start_tti, uint32_t update_meta_period, hipStream_t stream)
@@ -2043,33 +2026,21 @@ int Engine::submitFrom(const void* d_iq, int src_device, uint32_t nsf, uint32_t 
   static const bool force_copy = getenv("LSN_FORCE_PEER_COPY") && atoi(getenv("LSN_FORCE_PEER_COPY"));  // tests: take the staging path on one GPU too
   if (src_device == cfg.device && !force_copy) return submit(d_iq, nsf, start_tti, update_meta_period, stream);
   if (!cell_set || nsf > max_batch) return LSN_ERROR_INVALID_INPUTS;
-  try {
+  if (src_device < 0 || src_device >= 16) return LSN_ERROR_INVALID_INPUTS;
+  return guarded([&]() -> int {
     HIP_CHECK(hipSetDevice(cfg.device));
-    if (!copy_stream) {
-      createCopyStream();
-      for (auto& e : copy_done) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    const size_t sf_stride = (size_t)cfg.nof_rx_antennas * cd.sflen * sizeof(cf32);
-    const uint32_t slot = peer_slot++ % 12u;  // the staging area holds twelve chunks
-    if (peer_marks[slot]) waitIqConsumed(peer_marks[slot]);
-    uint8_t* dst = (uint8_t*)d_iq_staging + (size_t)slot * max_batch * sf_stride;
-    // the copy is ordered behind the caller's stream (the source block) and in front of this engine's stage A.  The caller's stream lives on
-    // the SOURCE device: the event that marks "block ready" must be created and recorded there (an event of this engine's device is rejected
-    // with hipErrorInvalidHandle); waiting on it from a stream of another device is allowed.
-    if (src_device < 0 || src_device >= 16) return LSN_ERROR_INVALID_INPUTS;
-    HIP_CHECK(hipSetDevice(src_device));
-    if (!peer_ev[src_device]) HIP_CHECK(hipEventCreateWithFlags(&peer_ev[src_device], hipEventDisableTiming));
-    HIP_CHECK(hipEventRecord(peer_ev[src_device], stream));
-    HIP_CHECK(hipSetDevice(cfg.device));
-    HIP_CHECK(hipStreamWaitEvent(copy_stream, peer_ev[src_device], 0));
-    HIP_CHECK(hipMemcpyPeerAsync(dst, cfg.device, d_iq, src_device, (size_t)nsf * sf_stride, copy_stream));
-    const int rc = submit(dst, nsf, start_tti, update_meta_period, copy_stream);
-    peer_marks[slot] = submitMark();
-    return rc;
-  } catch (const std::exception& ex) {
-    fprintf(stderr, "ltesniffer_amd: %s\n", ex.what());
-    return LSN_ERROR;
-  }
+    return stageAndSubmit(nsf, start_tti, update_meta_period, false, [&](uint8_t* dst, uint32_t) {
+      // the copy is ordered behind the caller's stream (the source block) and in front of this engine's stage A.  The caller's stream lives on
+      // the SOURCE device: the event that marks "block ready" must be created and recorded there (an event of this engine's device is rejected
+      // with hipErrorInvalidHandle); waiting on it from a stream of another device is allowed.
+      HIP_CHECK(hipSetDevice(src_device));
+      if (!peer_ev[src_device]) HIP_CHECK(hipEventCreateWithFlags(&peer_ev[src_device], hipEventDisableTiming));
+      HIP_CHECK(hipEventRecord(peer_ev[src_device], stream));
+      HIP_CHECK(hipSetDevice(cfg.device));
+      HIP_CHECK(hipStreamWaitEvent(copy_stream, peer_ev[src_device], 0));
+      HIP_CHECK(hipMemcpyPeerAsync(dst, cfg.device, d_iq, src_device, (size_t)nsf * cfg.nof_rx_antennas * cd.sflen * sizeof(cf32), copy_stream));
+    });
+  });
 }
 
 // The stream the IQ blocks are copied on.  Round 3 gave it the lowest priority (a class of its own, so that its "copy done" barrier packets would
@@ -2084,34 +2055,23 @@ void Engine::createCopyStream()
 int Engine::submitHostRows(const void* host_rows, size_t row_pitch, uint32_t nsf, uint32_t start_tti, bool force_meta_first, hipEvent_t copied)
 {
   if (!cell_set || !host_rows || nsf == 0 || nsf > max_batch) return LSN_ERROR_INVALID_INPUTS;
-  try {
+  return guarded([&]() -> int {
     HIP_CHECK(hipSetDevice(cfg.device));
-    if (!copy_stream) {
-      createCopyStream();
-      for (auto& e : copy_done) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    const size_t row_bytes = (size_t)cd.sflen * sizeof(cf32), sf_stride = (size_t)cfg.nof_rx_antennas * row_bytes;
-    const uint32_t slot = peer_slot++ % 12u;
-    if (peer_marks[slot]) waitIqConsumed(peer_marks[slot]);
-    uint8_t* dst = (uint8_t*)d_iq_staging + (size_t)slot * max_batch * sf_stride;
-    if (row_pitch == row_bytes)
-      HIP_CHECK(hipMemcpyAsync(dst, host_rows, (size_t)nsf * sf_stride, hipMemcpyHostToDevice, copy_stream));
-    else
-      HIP_CHECK(hipMemcpy2DAsync(dst, row_bytes, host_rows, row_pitch, row_bytes, (size_t)nsf * cfg.nof_rx_antennas, hipMemcpyHostToDevice, copy_stream));
-    if (copied) HIP_CHECK(hipEventRecord(copied, copy_stream));
-    const int rc = submit(dst, nsf, start_tti, 0u, copy_stream, force_meta_first);
-    peer_marks[slot] = submitMark();
-    return rc;
-  } catch (const std::exception& ex) {
-    fprintf(stderr, "ltesniffer_amd: %s\n", ex.what());
-    return LSN_ERROR;
-  }
+    return stageAndSubmit(nsf, start_tti, 0u, force_meta_first, [&](uint8_t* dst, uint32_t) {
+      const size_t row_bytes = (size_t)cd.sflen * sizeof(cf32), nrows = (size_t)nsf * cfg.nof_rx_antennas;
+      if (row_pitch == row_bytes)
+        HIP_CHECK(hipMemcpyAsync(dst, host_rows, nrows * row_bytes, hipMemcpyHostToDevice, copy_stream));
+      else
+        HIP_CHECK(hipMemcpy2DAsync(dst, row_bytes, host_rows, row_pitch, row_bytes, nrows, hipMemcpyHostToDevice, copy_stream));
+      if (copied) HIP_CHECK(hipEventRecord(copied, copy_stream));
+    });
+  });
 }
 
 int Engine::wait()
 {
   if (!batch_open) return LSN_SUCCESS;
-  try {
+  return guarded([&]() -> int {
     std::string err;
     {
       const double tw = now_ms();
@@ -2136,39 +2096,29 @@ int Engine::wait()
     perf.ms_total = now_ms() - t_batch;
     traceDump();
     return LSN_SUCCESS;
-  } catch (const std::exception& ex) {
-    fprintf(stderr, "ltesniffer_amd: %s\n", ex.what());
-    return LSN_ERROR;
-  }
+  });
 }
 
-// Host buffers (the worker pool's pinned staging, or any caller memory): blocks travel over PCIe into a ring of device staging buffers on a
-// copy stream of their own while the pipeline works on the blocks before them (submit() only queues).  Caller memory that is not pinned
-// yet is registered for the duration of the call so that the copies are real DMA transfers; if the registration is refused the copies
-// fall back to the runtime's bounce buffers (still overlapped with the compute of earlier blocks).
+// Host buffers (any caller memory): blocks of max_batch subframes travel over PCIe into the staging ring on the copy stream while the pipeline
+// works on the blocks before them (submit() only queues).  A block of the ring is reusable as soon as stage A of its chunk has consumed the
+// samples (not when the chunk has left the whole pipeline: with decode, commit and write behind stage A that is six or more chunk times later and
+// throttled the copies to three blocks per pipeline latency - the 27 GB/s of round 2); copies are queued ahead, so the link stays busy (large
+// copies run at the link rate, tools/ubench/h2d_bw.hip).  Caller memory that is not pinned yet is registered for the duration of the call so that
+// the copies are real DMA transfers; if the registration is refused the copies fall back to the runtime's bounce buffers (still overlapped with
+// the compute of earlier blocks).
 // sample_format LSN_FILE_SC16 / LSN_FILE_SC8 (lsn_phy_process_host_int): the caller's buffers hold integer I/Q pairs in the same [subframe][antenna][sample]
 // order; a block crosses PCIe as it is (half / a quarter of the bytes) into a raw ring and is converted into its staging block by the file source's kernel
 // (k_file_unpack with one "antenna" of nof_rx * sflen samples = a flat conversion) on the copy stream, in front of the submit.
 int Engine::processHost(const void* iq, uint32_t nsf_total, uint32_t start_tti, uint32_t update_meta_period, uint32_t fmt, float scale)
 {
   if (!cell_set) return LSN_ERROR;
-  if ((!iq && nsf_total) || fmt > LSN_FILE_SC8) return LSN_ERROR_INVALID_INPUTS;
-  if (fmt != LSN_FILE_CF32 && !(scale >= 0.0f && scale < INFINITY)) return LSN_ERROR_INVALID_INPUTS;
-  if (fmt != LSN_FILE_CF32 && scale == 0.0f) scale = fmt == LSN_FILE_SC16 ? 1.0f / 32768.0f : 1.0f / 128.0f;
+  const LsnSampleFormat sfm = lsn_sample_format(fmt, scale);
+  if ((!iq && nsf_total) || !sfm.valid) return LSN_ERROR_INVALID_INPUTS;
   bool registered = false;
   try {
     HIP_CHECK(hipSetDevice(cfg.device));
-    const size_t sf_stride = (size_t)cfg.nof_rx_antennas * cd.sflen * sizeof(cf32);
-    const size_t in_stride = fmt == LSN_FILE_SC16 ? sf_stride / 2 : fmt == LSN_FILE_SC8 ? sf_stride / 4 : sf_stride;  // bytes of one subframe in the caller's memory
-    // ring of staging blocks, one pipeline chunk each (max_batch subframes: 393 MB at 20 MHz / 2 rx / 800 subframes - large copies run at the
-    // link rate, tools/ubench/h2d_bw.hip).  A block is reusable as soon as stage A of its chunk has consumed the samples (not when the chunk has
-    // left the whole pipeline: with decode, commit and write behind stage A that is six or more chunk times later and throttled the copies to
-    // three blocks per pipeline latency - the 27 GB/s of round 2).  Copies are queued ahead on their own stream, so the link stays busy.
+    const size_t in_stride = (size_t)cfg.nof_rx_antennas * cd.sflen * sfm.bytes;  // bytes of one subframe in the caller's memory
     const uint32_t blk = max_batch;
-    if (!copy_stream) {
-      createCopyStream();
-      for (auto& e : copy_done) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
     {
       hipPointerAttribute_t attr{};
       const bool pinned = hipPointerGetAttributes(&attr, iq) == hipSuccess && attr.type == hipMemoryTypeHost;
@@ -2178,30 +2128,29 @@ int Engine::processHost(const void* iq, uint32_t nsf_total, uint32_t start_tti, 
     }
     static const bool host_debug = getenv("LSN_HOST_DEBUG") != nullptr;
     const double t_host0 = now_ms();
-    const uint32_t nring = (uint32_t)std::max<size_t>(2, staging_sf / blk);
-    if (fmt != LSN_FILE_CF32 && d_iq_raw_bytes < (size_t)nring * blk * in_stride) {
+    const size_t raw_bytes = (size_t)STAGING_SLOTS * blk * in_stride;
+    if (fmt != LSN_FILE_CF32 && d_iq_raw_bytes < raw_bytes) {
       if (d_iq_raw) { (void)hipFree(d_iq_raw); d_iq_raw = nullptr; d_iq_raw_bytes = 0; }
-      HIP_CHECK(hipMalloc(&d_iq_raw, (size_t)nring * blk * in_stride));
-      d_iq_raw_bytes = (size_t)nring * blk * in_stride;
+      HIP_CHECK(hipMalloc(&d_iq_raw, raw_bytes));
+      d_iq_raw_bytes = raw_bytes;
     }
-    std::vector<uint64_t> marks(nring, 0);
     uint32_t k = 0;
     int rc = LSN_SUCCESS;
     for (uint32_t base = 0; base < nsf_total && rc == LSN_SUCCESS; base += blk, k++) {
-      const uint32_t nsf = std::min(blk, nsf_total - base), slot = k % nring;
-      if (k >= nring) waitIqConsumed(marks[slot]);
-      uint8_t* dst = (uint8_t*)d_iq_staging + (size_t)slot * blk * sf_stride;
-      const double tc0 = now_ms();
-      if (fmt == LSN_FILE_CF32) {
-        HIP_CHECK(hipMemcpyAsync(dst, (const uint8_t*)iq + (size_t)base * sf_stride, (size_t)nsf * sf_stride, hipMemcpyHostToDevice, copy_stream));
-      } else {  // (the raw slot is free when the staging slot is: the conversion that read it ran in front of the stage A that `marks` waits for)
-        uint8_t* raw = (uint8_t*)d_iq_raw + (size_t)slot * blk * in_stride;
-        HIP_CHECK(hipMemcpyAsync(raw, (const uint8_t*)iq + (size_t)base * in_stride, (size_t)nsf * in_stride, hipMemcpyHostToDevice, copy_stream));
-        lsn_launch_file_unpack(raw, fmt, scale, nullptr, cfg.nof_rx_antennas * cd.sflen, 1, (cf32*)dst, nsf, copy_stream);
-      }
-      const double tc1 = now_ms();
-      rc = submit(dst, nsf, start_tti + base, update_meta_period, copy_stream);  // stage A of the block waits for the copy on the device
-      marks[slot] = submitMark();
+      const uint32_t nsf = std::min(blk, nsf_total - base);
+      const uint8_t* src = (const uint8_t*)iq + (size_t)base * in_stride;
+      double tc0 = 0, tc1 = 0;
+      rc = stageAndSubmit(nsf, start_tti + base, update_meta_period, false, [&](uint8_t* dst, uint32_t slot) {
+        tc0 = now_ms();
+        if (fmt == LSN_FILE_CF32) {
+          HIP_CHECK(hipMemcpyAsync(dst, src, (size_t)nsf * in_stride, hipMemcpyHostToDevice, copy_stream));
+        } else {  // (the raw slot is free when the staging slot is: the conversion that read it ran in front of the stage A that the slot's mark waits for)
+          uint8_t* raw = (uint8_t*)d_iq_raw + (size_t)slot * blk * in_stride;
+          HIP_CHECK(hipMemcpyAsync(raw, src, (size_t)nsf * in_stride, hipMemcpyHostToDevice, copy_stream));
+          lsn_launch_file_unpack(raw, fmt, sfm.scale, nullptr, cfg.nof_rx_antennas * cd.sflen, 1, (cf32*)dst, nsf, copy_stream);
+        }
+        tc1 = now_ms();
+      });
       if (host_debug) fprintf(stderr, "process_host: block %u: hipMemcpyAsync call %.3f ms, submit %.3f ms (t = %.3f ms)\n", k, tc1 - tc0, now_ms() - tc1, tc0 - t_host0);
     }
     const int w = wait();

@@ -1,15 +1,17 @@
 // lsn_engine.h - the batched, software-pipelined GPU engine behind Phy / SubframeWorker (product; no CPU fallback).
 //   stage A (GPU, stream A): OFDM -> CRS estimation -> PCFICH -> PDCCH LLRs -> CCE power -> exhaustive Viterbi candidate table
-//   stage B (CPU, caller thread): FALCON decision tree per subframe in TTI order over the candidate table
+//   stage B (CPU, search thread): FALCON decision tree per subframe in TTI order over the candidate table
 //                  (DCISearch.cc:102-528); RAR grants are decoded on demand because they feed the RNTI manager
 //                  (DL_Sniffer_PDSCH.cc:782-797)
-//   stage C (GPU, stream C): PDSCH demodulation + turbo decoding of every accepted grant
-//   commit  (CPU, commit thread): decode_dl_mode selection logic in (tti, DCI, TB) order, MCS-table learning, PDU sink
-// A call is cut into chunks of max_batch subframes; chunk i+1 runs stage A while chunk i is searched and chunk i-1 is
-// decoded/committed (three chunk slots).
+//   stage C (GPU, decode threads, one stream each): PDSCH demodulation + turbo decoding of every accepted grant
+//   commit  (CPU, commit thread): decode_dl_mode selection logic in (tti, DCI, TB) order, MCS-table learning; the writer thread feeds the PDU sink
+// A submit is cut into chunks of max_batch subframes that travel through the threads above in order, nslots of them in flight (front thread:
+// stage A of up to NSTREAM_A chunks at once).  Samples that are not on this device yet (host memory, another GPU, the worker pool's slab) get
+// there through ONE ring of staging blocks and one entry, Engine::stageAndSubmit.
 #pragma once
 #include "../../../include/ltesniffer_amd.h"
 #include "../kernels/lsn_dev.h"
+#include "lsn_hip.h"
 #include "lsn_rates.h"
 #include "lsn_search.h"
 #include <atomic>
@@ -28,10 +30,6 @@ namespace lsn {
 
 // Lazy growth of the job runners' arenas (device memory / pinned, mapped host mirrors): waits for the one stream that uses the buffer, then replaces it by
 // one of need + 50 % + 1024 elements; the contents are not kept
-inline void hip_check(hipError_t e, const char* what)
-{
-  if (e != hipSuccess) throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e) + " at " + what);
-}
 template <typename T>
 void grow_dev(T*& p, size_t& cap, size_t need, hipStream_t st)
 {
@@ -401,11 +399,26 @@ private:
   void* d_iq_staging = nullptr;
   void* d_iq_raw = nullptr;                   // processHost on integer samples: the raw blocks in front of the conversion (made on first use)
   size_t d_iq_raw_bytes = 0;
-  hipStream_t copy_stream = nullptr;          // host -> staging copies of processHost
-  hipEvent_t copy_done[3] = {};
-  uint64_t peer_marks[12] = {};               // submitFrom / submitHostRows: staging slot -> mark of the chunk that used it last
-  uint32_t peer_slot = 0;
-  size_t staging_sf = 0;
+  hipStream_t copy_stream = nullptr;          // every copy / conversion into the staging ring
+  // d_iq_staging as STAGING_SLOTS blocks of max_batch subframes, shared by submitFrom, submitHostRows and processHost (guarded by mtx)
+  static constexpr uint32_t STAGING_SLOTS = 12;
+  StagingRing iq_ring{STAGING_SLOTS};
+  // One block through the ring: takes the next slot, waits until stage A has consumed what the slot held (whichever path put it there), lets `queue_copy(dst,
+  // slot)` queue the copy or conversion into the block on copy_stream, submits the block behind it and leaves the submit's mark with the slot.
+  // At most max_batch subframes.  Throws on HIP errors.
+  template <class F>
+  int stageAndSubmit(uint32_t nsf, uint32_t start_tti, uint32_t update_meta_period, bool force_meta_first, F&& queue_copy)
+  {
+    uint64_t wait_for = 0;
+    uint32_t slot;
+    { std::unique_lock<std::mutex> lk(mtx); if (!copy_stream) createCopyStream(); slot = iq_ring.acquire(wait_for); }
+    if (wait_for) waitIqConsumed(wait_for);
+    uint8_t* dst = (uint8_t*)d_iq_staging + (size_t)slot * max_batch * cfg.nof_rx_antennas * cd.sflen * sizeof(cf32);
+    queue_copy(dst, slot);
+    const int rc = submit(dst, nsf, start_tti, update_meta_period, copy_stream, force_meta_first);  // stage A of the block waits for the copy on the device
+    { std::unique_lock<std::mutex> lk(mtx); iq_ring.retire(slot, chunks_expected); }
+    return rc;
+  }
   Chunk chunks[NSLOTS];
   JobRunner runner_c[NDEC], runner_s, runner_f, runner_k;  // decode threads / search thread (on-demand RAR decodes) / front thread (speculative RAR decodes) / commit thread (on-demand decodes)
 #ifndef LSN_NSTREAM_A
@@ -520,6 +533,7 @@ private:
   // the one replay loop behind processFile (rs == nullptr) and processFileRate (rs: the resampler's plan, lsn_resample.h)
   int processFileImpl(const char* path, const lsn_file_cfg_t& fc, const struct ResamplePlan* rs, uint32_t start_tti, uint64_t max_subframes, uint32_t update_meta_period,
                       uint64_t* subframes_done);
+  struct FileReplay;   // lsn_file.cc: what one replay opens and how it hands blocks to submit()
   struct FileBuf { cf32* h_raw = nullptr; cf32* d_raw = nullptr; cf32* d_iq = nullptr; size_t bytes = 0; };
   FileBuf file_buf[8];
   std::atomic<uint32_t>& ul_cfg_epoch = sh->ul_cfg_epoch;  // bumped by every (re)configuration: chunks whose DCI 0 grants were converted earlier are converted again at commit

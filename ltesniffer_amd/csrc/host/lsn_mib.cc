@@ -8,12 +8,6 @@
 #include <cstring>
 #include <stdexcept>
 
-#define HIP_CHECK(x)                                                                                       \
-  do {                                                                                                     \
-    hipError_t _e = (x);                                                                                   \
-    if (_e != hipSuccess) throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(_e) + " at " #x); \
-  } while (0)
-
 namespace lsn {
 
 // iq: one subframe [iq_nant][15 N] cf32; returns 1 (found), 0 (no MIB in this subframe) or a negative error
@@ -23,7 +17,7 @@ int Engine::mibDecode(const void* iq, bool on_device, lsn_mib_t* out, float* llr
   if (!iq || !out) return LSN_ERROR_INVALID_INPUTS;
   if (batch_open) return LSN_ERROR;  // borrows a chunk slot: not while submitted blocks are in flight (call lsn_phy_wait first)
   std::memset(out, 0, sizeof(*out));
-  try {
+  return guarded([&]() -> int {
     HIP_CHECK(hipSetDevice(cfg.device));
     Chunk& ch = chunks[0];  // idle between process calls
     hipStream_t st = stream_a[0];
@@ -63,10 +57,7 @@ int Engine::mibDecode(const void* iq, bool on_device, lsn_mib_t* out, float* llr
       return 1;
     }
     return 0;
-  } catch (const std::exception& ex) {
-    fprintf(stderr, "ltesniffer_amd: %s\n", ex.what());
-    return LSN_ERROR;
-  }
+  });
 }
 
 }  // namespace lsn

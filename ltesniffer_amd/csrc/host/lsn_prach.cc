@@ -11,12 +11,6 @@
 #include <cstring>
 #include <stdexcept>
 
-#define HIP_CHECK(x)                                                                                       \
-  do {                                                                                                     \
-    hipError_t _e = (x);                                                                                   \
-    if (_e != hipSuccess) throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(_e) + " at " #x); \
-  } while (0)
-
 namespace lsn {
 
 static const int NZC = 839;
@@ -48,7 +42,7 @@ int Engine::setPrachConfig(const lsn_prach_cfg_t& p)
   // one-subframe formats only (work_prach copies SF_LEN samples, UL_Sniffer_PUSCH.cc:680-686); restricted sets are not built
   if (!cell_set || p.config_idx > 15 || p.zero_corr_zone > 15 || p.root_seq_idx > 837 || p.hs_flag != 0 || p.freq_offset + 6 > cell.nof_prb)
     return LSN_ERROR_INVALID_INPUTS;
-  try {
+  return guarded([&]() -> int {
     HIP_CHECK(hipSetDevice(cfg.device));
     if (!runner_u.stream) allocRunner(runner_u);
     prach.cfg = p;
@@ -98,10 +92,7 @@ int Engine::setPrachConfig(const lsn_prach_cfg_t& p)
     sh->prach_cfg = prach.cfg; sh->prach_cfg_set = true;   // the other engines of a multi-GPU capture follow at their next commit turn (syncUlConfig)
     prach_tables_epoch = ++sh->prach_epoch;
     return LSN_SUCCESS;
-  } catch (const std::exception& ex) {
-    fprintf(stderr, "ltesniffer_amd: %s\n", ex.what());
-    return LSN_ERROR;
-  }
+  });
 }
 
 // detection on the subframes of d_iq ([sf][nant][sflen], antenna `ant`) that are PRACH occasions; stream runner_u.  Throws on HIP errors.
@@ -148,7 +139,7 @@ int Engine::prachDetect(const void* ul_iq, bool on_device, uint32_t nsf, uint32_
 {
   if (!cell_set || !prach.set) return LSN_ERROR;
   if ((!ul_iq && nsf) || (!out && cap)) return LSN_ERROR_INVALID_INPUTS;
-  try {
+  return guarded([&]() -> int {
     HIP_CHECK(hipSetDevice(cfg.device));
     const cf32* d_iq = (const cf32*)ul_iq;
     if (!on_device) {
@@ -161,10 +152,7 @@ int Engine::prachDetect(const void* ul_iq, bool on_device, uint32_t nsf, uint32_
     const uint32_t n = (uint32_t)std::min<size_t>(det.size(), cap);
     if (n) std::memcpy(out, det.data(), n * sizeof(lsn_prach_det_t));
     return (int)n;
-  } catch (const std::exception& ex) {
-    fprintf(stderr, "ltesniffer_amd: %s\n", ex.what());
-    return LSN_ERROR;
-  }
+  });
 }
 
 // parity tap: correlation power [nroots][839] of occasion `index` of the last detection call

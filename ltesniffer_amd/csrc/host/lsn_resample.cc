@@ -2,7 +2,7 @@
 // integers; number of taps; the bank of 512 phases; the tuning word and tables of the mixer) and lsn_resample, the stand-alone entry point (needs no Phy, like lsn_cell_search).
 // The filter is DESIGN.md section 3.1b, restated there as a formula; tests/resample_model.py is written from that formula, not from this file.
 // Product code: no CPU fallback (the samples are computed by k_resample only), nothing from oracle/ is included or linked.
-#include "../../../include/ltesniffer_amd.h"
+#include "lsn_hip.h"
 #include "../kernels/lsn_dev.h"
 #include "lsn_resample.h"
 #include <cmath>
@@ -11,12 +11,6 @@
 #include <cstring>
 #include <stdexcept>
 #include <string>
-
-#define HIP_CHECK(x)                                                                                       \
-  do {                                                                                                     \
-    hipError_t _e = (x);                                                                                   \
-    if (_e != hipSuccess) throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(_e) + " at " #x); \
-  } while (0)
 
 namespace lsn {
 
@@ -131,8 +125,7 @@ static int resample_plan(const lsn_resample_cfg_t* cfg, lsn::ResamplePlan& plan)
   // two sizes are known: the struct up to passband_hz (center_offset_hz reads as 0) and the whole struct
   if (!cfg || (cfg->struct_size != offsetof(lsn_resample_cfg_t, center_offset_hz) && cfg->struct_size != sizeof(lsn_resample_cfg_t))) return LSN_ERROR_INVALID_INPUTS;
   const double center = cfg->struct_size == sizeof(lsn_resample_cfg_t) ? cfg->center_offset_hz : 0.0;
-  if (cfg->nof_antennas < 1 || cfg->nof_antennas > 8 || cfg->sample_format > LSN_FILE_SC8) return LSN_ERROR_INVALID_INPUTS;
-  if (cfg->sample_format != LSN_FILE_CF32 && !(cfg->sample_scale >= 0.0f && cfg->sample_scale < INFINITY)) return LSN_ERROR_INVALID_INPUTS;
+  if (cfg->nof_antennas < 1 || cfg->nof_antennas > 8 || !lsn_sample_format(cfg->sample_format, cfg->sample_scale).valid) return LSN_ERROR_INVALID_INPUTS;
   return plan.init(cfg->rate_in_hz, cfg->rate_out_hz, cfg->passband_hz, cfg->first_sample, cfg->first_frac, center);
 }
 
@@ -165,8 +158,9 @@ int lsn_resample(int device, const void* in, int in_on_device, uint64_t n_in, co
   const int64_t need_lo = std::max<int64_t>(lo, 0);   // in front of the recording: zeros
   if (need_lo < (int64_t)cfg->in_base || hi > (int64_t)(cfg->in_base + n_in)) return LSN_ERROR_INVALID_INPUTS;   // the input does not hold what these outputs read
   const uint32_t nant = cfg->nof_antennas, fmt = cfg->sample_format;
-  const size_t smp = (fmt == LSN_FILE_SC16 ? 4 : fmt == LSN_FILE_SC8 ? 2 : sizeof(cf32)) * (size_t)nant;
-  const float scale = fmt == LSN_FILE_CF32 ? 1.0f : cfg->sample_scale != 0.0f ? cfg->sample_scale : fmt == LSN_FILE_SC16 ? 1.0f / 32768.0f : 1.0f / 128.0f;
+  const LsnSampleFormat sfm = lsn_sample_format(fmt, cfg->sample_scale);
+  const size_t smp = (size_t)sfm.bytes * nant;
+  const float scale = sfm.scale;
   const uint64_t len = hi > need_lo ? (uint64_t)(hi - need_lo) : 0;
   const uint8_t* src = (const uint8_t*)in + ((uint64_t)need_lo - cfg->in_base) * smp;
   void *d_in = nullptr, *d_out = nullptr;

@@ -5,7 +5,7 @@
 // TS 36.211 6.11, FDD, normal cyclic prefix.  Sequences and cos/sin tables are host work (double), the matched filter, the two
 // 62-carrier DFTs and the 336 SSS hypotheses are the kernels of stage_sync.hip; argmax / mean / atan2 on the host.
 // Needs no Phy (the cell is not known yet).  Product code: no CPU fallback, nothing from oracle/ is included or linked.
-#include "../../../include/ltesniffer_amd.h"
+#include "lsn_hip.h"
 #include "../kernels/lsn_dev.h"
 #include "lsn_rates.h"
 #include <cmath>
@@ -13,12 +13,6 @@
 #include <stdexcept>
 #include <string>
 #include <vector>
-
-#define HIP_CHECK(x)                                                                                       \
-  do {                                                                                                     \
-    hipError_t _e = (x);                                                                                   \
-    if (_e != hipSuccess) throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(_e) + " at " #x); \
-  } while (0)
 
 void lsn_launch_pss_corr(const cf32* x, const cf32* p, uint32_t N, uint32_t W5, uint32_t P, uint32_t nroots, float* C, hipStream_t s);
 void lsn_launch_sync_fin(const cf32* x, const cf32* p, const cf32* w, const cf32* d, const int8_t* sss, uint32_t N, uint32_t W5, uint32_t P, uint32_t bn,

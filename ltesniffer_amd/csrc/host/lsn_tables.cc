@@ -7,12 +7,6 @@
 #include <cstdio>
 #include <stdexcept>
 
-#define HIP_CHECK(x)                                                                                       \
-  do {                                                                                                     \
-    hipError_t _e = (x);                                                                                   \
-    if (_e != hipSuccess) throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(_e) + " at " #x); \
-  } while (0)
-
 namespace lsn {
 
 // c(n) = x1(n+1600) ^ x2(n+1600), TS 36.211 7.2
@@ -94,7 +88,7 @@ void Engine::freeDevice(bool keep_file_buffers)
     if (!keep_file_buffers)
       for (auto& fb : file_buf) { if (fb.h_raw) (void)hipHostFree(fb.h_raw); df(fb.d_raw); df(fb.d_iq); fb.h_raw = nullptr; fb.bytes = 0; }
   }
-  d_iq_staging = nullptr; staging_sf = 0;
+  d_iq_staging = nullptr;
   if (d_iq_raw) { (void)hipFree(d_iq_raw); d_iq_raw = nullptr; d_iq_raw_bytes = 0; }
   if (sh->harq_pool_owner == this) { d_harq_pool = nullptr; sh->harq_pool_owner = nullptr; }   // (freed with this engine's device allocations)
   if (harq_h_store) { (void)hipHostFree(harq_h_store); harq_h_store = nullptr; harq_h_store_cap = 0; }
@@ -426,8 +420,7 @@ void Engine::buildTables()
   allocRunner(runner_s);
   allocRunner(runner_f);
   allocRunner(runner_k);
-  staging_sf = (size_t)max_batch * 12;  // three staging blocks of four chunks each (processHost)
-  d_iq_staging = dalloc<cf32>(dev_allocs, staging_sf * cfg.nof_rx_antennas * cd.sflen);
+  d_iq_staging = dalloc<cf32>(dev_allocs, (size_t)STAGING_SLOTS * max_batch * cfg.nof_rx_antennas * cd.sflen);  // the staging ring (stageAndSubmit)
 }
 
 }  // namespace lsn

@@ -52,3 +52,33 @@ struct LsnCbDev {
 #define LSN_SPP_WORDS(K) (((K) + 12u + 3u) & ~3u)
 #define LSN_CB_NODEP 0xFFFFFFFFu   // LsnCbDev::dep: always decode
 struct LsnCbRes { uint32_t ok, iters, rem_a, iters_run; uint32_t cyc_rm, cyc_map, cyc_out, cyc_all; };  // cyc_*: shader cycles per phase (s_memtime)
+
+// ---- ingest (host only, HIP-free)
+// The sample-format rule of every entry that takes IQ samples (lsn_phy_process_host[_int], lsn_phy_process_file[_rate], lsn_resample[_span]):
+// (format, caller's scale) -> valid?, bytes of one complex sample, the scale the conversion multiplies with.  cf32 is taken as it is (its scale
+// field is not looked at); integer samples want a finite scale >= 0, 0 = the default of full scale -> 1.0.  LSN_FMT_* = LSN_FILE_* of the public header.
+enum : uint32_t { LSN_FMT_CF32 = 0, LSN_FMT_SC16 = 1, LSN_FMT_SC8 = 2 };
+struct LsnSampleFormat { bool valid; uint32_t bytes; float scale; };
+inline LsnSampleFormat lsn_sample_format(uint32_t fmt, float scale)
+{
+  if (fmt == LSN_FMT_CF32) return {true, 8u, 1.0f};
+  if (fmt > LSN_FMT_SC8 || !(scale >= 0.0f && scale < __builtin_inff())) return {false, 0u, 0.0f};
+  const bool sc16 = fmt == LSN_FMT_SC16;
+  return {true, sc16 ? 4u : 2u, scale != 0.0f ? scale : sc16 ? 1.0f / 32768.0f : 1.0f / 128.0f};
+}
+
+// Round-robin hand-out of the blocks of a staging area that several ingest paths share.  A slot remembers the mark its last user recorded
+// (Engine::submitMark: the chunks submitted so far); the next user of the slot, whichever path it comes from, waits for that mark before it
+// overwrites the block.  Bookkeeping only, no lock of its own: the engine calls it under its mutex and waits outside.
+struct StagingRing {
+  static constexpr uint32_t MAX_SLOTS = 16;
+  explicit StagingRing(uint32_t nslots) : n(nslots < 1 ? 1 : nslots > MAX_SLOTS ? MAX_SLOTS : nslots) {}
+  uint32_t slots() const { return n; }
+  // the next slot; wait_for: the mark to wait for in front of its reuse, 0 = never used
+  uint32_t acquire(uint64_t& wait_for) { const uint32_t s = next; next = (next + 1) % n; wait_for = marks[s]; return s; }
+  void retire(uint32_t slot, uint64_t mark) { marks[slot] = mark; }
+private:
+  const uint32_t n;
+  uint32_t next = 0;
+  uint64_t marks[MAX_SLOTS] = {};
+};

@@ -11,12 +11,6 @@
 #include <cstdio>
 #include <stdexcept>
 
-#define HIP_CHECK(x)                                                                                       \
-  do {                                                                                                     \
-    hipError_t _e = (x);                                                                                   \
-    if (_e != hipSuccess) throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(_e) + " at " #x); \
-  } while (0)
-
 namespace lsn {
 
 static int largest_prime_below(int n)
@@ -94,7 +88,7 @@ void Engine::syncUlConfig()
 int Engine::buildUlTables(const lsn_ul_cfg_t& u)
 {
   if (!cell_set || u.cyclic_shift > 7 || u.delta_ss > 29) return LSN_ERROR_INVALID_INPUTS;
-  try {
+  return guarded([&]() -> int {
     HIP_CHECK(hipSetDevice(cfg.device));
     const int N = (int)cd.N;
     (void)N;
@@ -161,20 +155,7 @@ int Engine::buildUlTables(const lsn_ul_cfg_t& u)
     search->setPuschHopOffset(u.hopping_offset);
     if (!runner_u.stream) allocRunner(runner_u);
     return LSN_SUCCESS;
-  } catch (const std::exception& ex) {
-    fprintf(stderr, "ltesniffer_amd: %s\n", ex.what());
-    return LSN_ERROR;
-  }
-}
-
-template <typename T>
-static void grow_d(T*& p, size_t& cap, size_t need)
-{
-  if (need <= cap) return;
-  HIP_CHECK(hipDeviceSynchronize());
-  if (p) HIP_CHECK(hipFree(p));
-  cap = need + need / 2 + 1024;
-  HIP_CHECK(hipMalloc((void**)&p, cap * sizeof(T)));
+  });
 }
 
 int Engine::puschDecode(const void* ul_iq, bool on_device, uint32_t nsf, uint32_t start_tti, const lsn_pusch_grant_t* grants, uint32_t ngrants,
@@ -182,26 +163,23 @@ int Engine::puschDecode(const void* ul_iq, bool on_device, uint32_t nsf, uint32_
 {
   if (!cell_set || !ul_set) return LSN_ERROR;
   if ((!ul_iq && nsf) || (!grants && ngrants) || (!results && ngrants)) return LSN_ERROR_INVALID_INPUTS;
-  try {
+  return guarded([&]() -> int {
     HIP_CHECK(hipSetDevice(cfg.device));
-    hipStream_t st = runner_u.stream;
+    hipStream_t st = runner_u.stream;   // the one stream that touches ul_d_iq and ul_d_grid (prachDetect's copy into ul_d_iq is on it as well): grow_dev waits for it alone
     const cf32* d_iq = (const cf32*)ul_iq;
     if (!on_device) {
-      grow_d(ul_d_iq, ul_iq_cap, (size_t)nsf * cd.sflen);
+      grow_dev(ul_d_iq, ul_iq_cap, (size_t)nsf * cd.sflen, st);
       HIP_CHECK(hipMemcpyAsync(ul_d_iq, ul_iq, (size_t)nsf * cd.sflen * sizeof(cf32), hipMemcpyHostToDevice, st));
       d_iq = ul_d_iq;
     }
-    grow_d(ul_d_grid, ul_grid_cap, (size_t)nsf * 14 * cd.nre);
+    grow_dev(ul_d_grid, ul_grid_cap, (size_t)nsf * 14 * cd.nre, st);
     lsn_launch_ul_fft(cd, d_iq, 1, 0, ul_d_grid, nsf, st);
     std::vector<uint8_t> pay;
     puschDecodeGrid(ul_d_grid, nsf, start_tti, grants, ngrants, results, pay);
     if (payloads && pay.size() > payload_cap) return LSN_ERROR_INVALID_INPUTS;  // results[].payload_off would point past the caller's buffer
     if (payloads) std::memcpy(payloads, pay.data(), pay.size());
     return LSN_SUCCESS;
-  } catch (const std::exception& ex) {
-    fprintf(stderr, "ltesniffer_amd: %s\n", ex.what());
-    return LSN_ERROR;
-  }
+  });
 }
 
 // srsran_chest_ul_estimate_pusch + srsran_pusch_decode for a list of grants on an uplink grid that is already on the device
@@ -274,13 +252,14 @@ void Engine::puschDecodeGrid(const cf32* d_grid, uint32_t nsf, uint32_t start_tt
   ul_last_gd = gd; ul_last_idx = gidx;
   const uint32_t ng = (uint32_t)gd.size(), ncb = (uint32_t)r.h_cbs.size();
   if (!ng) { HIP_CHECK(hipStreamSynchronize(st)); return; }
-  grow_d(ul_d_grants, ul_grants_cap, ng);
-  grow_d(ul_d_hs, ul_hs_cap, hs_n);
-  grow_d(ul_d_stat, ul_stat_cap, (size_t)2 * ng);
-  grow_d(r.d_llr16, r.llr16_cap, llr_n + 8);
-  grow_d(r.d_cbs, r.cbs_cap, ncb);
-  grow_d(r.d_cbres, r.cbres_cap, ncb);
-  grow_d(r.d_payload, r.payload_cap, pay_n + 16);
+  // (these arenas are runner_u's, written and read on its stream only - also when the UL_MODE commit calls in with a chunk's grid, which stage A finished long ago)
+  grow_dev(ul_d_grants, ul_grants_cap, ng, st);
+  grow_dev(ul_d_hs, ul_hs_cap, hs_n, st);
+  grow_dev(ul_d_stat, ul_stat_cap, (size_t)2 * ng, st);
+  grow_dev(r.d_llr16, r.llr16_cap, llr_n + 8, st);
+  grow_dev(r.d_cbs, r.cbs_cap, ncb, st);
+  grow_dev(r.d_cbres, r.cbres_cap, ncb, st);
+  grow_dev(r.d_payload, r.payload_cap, pay_n + 16, st);
   for (uint32_t i = 0; i < ncb; i++) r.h_cbs[i].res_idx = i;
   const TurboOrder to = turbo_classic_order(r.h_cbs);
   // descriptors go through pinned mirrors and the upload kernel, not through the host -> device copy engine (its FIFO may hold IQ blocks, lsn_dev.h)
@@ -294,7 +273,7 @@ void Engine::puschDecodeGrid(const cf32* d_grid, uint32_t nsf, uint32_t start_tt
     cb.spp_off = (uint32_t)spp_n; spp_n += LSN_SPP_WORDS(cb.K);
     emax = std::max(emax, cb.E);
   }
-  grow_d(r.d_spp, r.spp_cap, spp_n + 16);
+  grow_dev(r.d_spp, r.spp_cap, spp_n + 16, st);
   std::memcpy(ul_h_grants, gd.data(), ng * sizeof(LsnUlGrantDev));
   lsn_launch_upload(ul_d_grants, ul_h_grants, ng * sizeof(LsnUlGrantDev), st);
   lsn_launch_upload(r.d_cbs, r.h_cbs_pinned, ncb * sizeof(LsnCbDev), st);

@@ -504,4 +504,15 @@ int lsn_host_ul_trial(uint32_t mcs_idx, int grant_mod_bits, uint32_t L_prb_256, 
   return n;
 }
 int lsn_host_ul_grant_valid(uint32_t rnti, int is_rar, int tbs, int tbs_256, uint32_t L_prb) { return lsn::ulGrantValid((uint16_t)rnti, is_rar != 0, tbs, tbs_256, L_prb) ? 1 : 0; }
+// the ingest rules of lsn_types.h: the sample-format rule (out3 = valid, bytes per complex sample, effective scale) and the staging ring
+void lsnh_sample_format(uint32_t fmt, float scale, float* out3)
+{
+  const LsnSampleFormat f = lsn_sample_format(fmt, scale);
+  out3[0] = f.valid ? 1.0f : 0.0f; out3[1] = (float)f.bytes; out3[2] = f.scale;
+}
+void* lsnh_ring_new(uint32_t nslots) { return new StagingRing(nslots); }
+void lsnh_ring_free(void* r) { delete (StagingRing*)r; }
+uint32_t lsnh_ring_slots(void* r) { return ((StagingRing*)r)->slots(); }
+uint32_t lsnh_ring_acquire(void* r, uint64_t* wait_for) { return ((StagingRing*)r)->acquire(*wait_for); }
+void lsnh_ring_retire(void* r, uint32_t slot, uint64_t mark) { ((StagingRing*)r)->retire(slot, mark); }
 }  // extern "C"

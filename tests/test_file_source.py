@@ -196,3 +196,55 @@ def test_process_host_integer_samples_match_oracle_worker(tmp_path, fmt, pow2):
     assert L.lsn_phy_process_host_int(phy._h, q.ctypes.data, 3, 1.0, 1, 0, 0) == la.LSN_ERROR_INVALID_INPUTS
     assert L.lsn_phy_process_host_int(phy._h, q.ctypes.data, fmt, float("nan"), 1, 0, 0) == la.LSN_ERROR_INVALID_INPUTS
     phy.close()
+
+
+@pytest.mark.gpu
+def test_one_stream_through_every_ingest_path_matches_one_oracle_walk(tmp_path, monkeypatch):
+    """One Phy (max_batch = 2), one continuous stream of 150 subframes quantised once to int16 with a power-of-two LSB (every path sees bit-identical
+    values), fed in five consecutive segments of 30 subframes = 15 blocks each, so the staging ring of 12 wraps in every segment and the engine's state
+    (RNTI manager, MCS tracking, stream position, ring position) carries across: worker pool + joinPending, process_host, process_host_int,
+    process_file (blocks of 7), submit_device in pieces + wait.  The records are those of ONE oracle walk over the 150 subframes.  Meta formats are updated
+    where each path applies the flag: the worker pool at the subframes whose prepare() says so, the others where the stream position is a multiple
+    of update_meta_period."""
+    import torch
+    import ltesniffer_amd as la
+    from parity import gpu_records
+    sc = scenario("small", seed=34)
+    seg, nsf, period = 30, 150, 20
+    tti0, iq, _ = gen_subframes(sc, nsf)
+    lsb, q = write_integer_capture(str(tmp_path / "all.sc16"), iq, 1, pow2=True)
+    sub = (q[..., 0].astype(np.float32) * np.float32(lsb) + 1j * (q[..., 1].astype(np.float32) * np.float32(lsb))).astype(np.complex64)
+    ow = OracleWorker(sc["nof_prb"], sc["nof_ports"], sc["cell_id"], sc["nof_rx"])
+    for i in range(nsf):
+        ow.work(sub[i], tti0 + i, update_meta=1 if i % period == 0 else 0)
+    orecs = oracle_records(parse_pcap(ow.pcap_bytes()))
+    assert len(orecs) >= nsf // 2
+    monkeypatch.setenv("LSN_FILE_BLOCK", "7")
+    phy = la.Phy(nof_rx_antennas=sc["nof_rx"], nof_workers=8, max_batch=2, pcapwriter=la.PcapWriter(None))
+    assert phy.setCell(sc["nof_prb"], sc["nof_ports"], sc["cell_id"])
+    sflen = iq.shape[2]
+    for i in range(0, seg):                                   # 1: the worker pool
+        w = phy.getAvail()
+        bufs = w.getBuffers()
+        for rx in range(sc["nof_rx"]):
+            bufs[rx][:sflen] = sub[i, rx]
+        tti = tti0 + i
+        w.prepare(tti % 10, (tti // 10) % 1024, i % period == 0)
+        phy.putPending(w)
+    phy.joinPending()
+    phy.process_host(sub[seg:2 * seg], tti0 + seg, update_meta_period=period)                                           # 2
+    phy.process_host_int(q[2 * seg:3 * seg], tti0 + 2 * seg, update_meta_period=period, sample_scale=lsb)             # 3
+    p = str(tmp_path / "seg4.sc16")                                                                                     # 4
+    np.ascontiguousarray(np.transpose(q[3 * seg:4 * seg], (0, 2, 1, 3))).tofile(p)
+    assert phy.process_file(p, start_tti=tti0 + 3 * seg, update_meta_period=period, sample_format=la.FILE_SC16, sample_scale=lsb) == seg
+    d_iq = torch.from_numpy(np.ascontiguousarray(sub[4 * seg:]).view(np.float32)).to("cuda:0")                          # 5
+    torch.cuda.synchronize()
+    sf_floats = sc["nof_rx"] * sflen * 2
+    pos = 0
+    for n in (7, 11, 1, 11):
+        phy.submit_device(d_iq.data_ptr() + pos * sf_floats * 4, n, tti0 + 4 * seg + pos, period)
+        pos += n
+    assert pos == seg
+    phy.wait()
+    assert gpu_records(phy) == orecs
+    phy.close()

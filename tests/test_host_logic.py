@@ -349,3 +349,93 @@ def test_falcon_search_four_port_cells():
 
 def test_falcon_search_cfg3_meta_update():
     _search_parity("cfg3", 16, seed=3, update_meta_period=8, rar_period=0)
+
+
+# ---- ingest: the staging ring and the sample-format rule (lsn_types.h)
+def _ring_api():
+    h = hosttest()
+    h.lsnh_ring_new.restype = C.c_void_p
+    h.lsnh_ring_new.argtypes = [C.c_uint32]
+    h.lsnh_ring_free.argtypes = [C.c_void_p]
+    h.lsnh_ring_slots.restype = C.c_uint32
+    h.lsnh_ring_slots.argtypes = [C.c_void_p]
+    h.lsnh_ring_acquire.restype = C.c_uint32
+    h.lsnh_ring_acquire.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    h.lsnh_ring_retire.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64]
+    return h
+
+
+@pytest.mark.parametrize("nslots", [3, 12])
+def test_staging_ring_hands_every_user_the_mark_of_the_slots_last_retire(nslots):
+    """A seeded script of acquire / retire calls by several "paths" (worker pool, process_host, peer copy: the ring cannot tell them apart) with increasing
+    marks.  Slots come round-robin; a slot nobody has retired asks for no wait (0); otherwise acquire returns exactly the mark of the slot's last retire,
+    whoever recorded it - what lsn_phy_put_pending followed by lsn_phy_process_host without a join in between depends on."""
+    h = _ring_api()
+    ring = h.lsnh_ring_new(nslots)
+    try:
+        assert h.lsnh_ring_slots(ring) == nslots
+        rng = np.random.default_rng(100 + nslots)
+        last = {}                      # slot -> (mark, path) of its last retire: the model
+        held = []                      # acquired, not retired yet: (slot, path)
+        mark, count, waited_for_other = 0, 0, 0
+        for _ in range(40 * nslots):
+            if held and (len(held) >= 3 or rng.random() < 0.5):   # retire one of the blocks in flight, not always the oldest
+                slot, path = held.pop(int(rng.integers(len(held))))
+                mark += int(rng.integers(1, 5))                   # a submit of one to four chunks
+                h.lsnh_ring_retire(ring, slot, mark)
+                last[slot] = (mark, path)
+            else:
+                w = C.c_uint64(0xDEAD)
+                slot = h.lsnh_ring_acquire(ring, C.byref(w))
+                path = int(rng.integers(3))
+                assert slot == count % nslots
+                assert w.value == (last[slot][0] if slot in last else 0)
+                if slot in last and last[slot][1] != path:
+                    waited_for_other += 1
+                held.append((slot, path))
+                count += 1
+        assert count > 3 * nslots and waited_for_other > nslots   # the ring wrapped, and paths met each other's marks
+    finally:
+        h.lsnh_ring_free(ring)
+
+
+FMT_BYTES = {0: 8, 1: 4, 2: 2}                                 # LSN_FILE_CF32 / SC16 / SC8: bytes of one complex sample
+FMT_DEFAULT = {1: 1.0 / 32768.0, 2: 1.0 / 128.0}               # scale 0 = full scale -> 1.0
+FMT_SCALES = [0.0, 2.0 ** -11, 3e-5, float("nan"), float("inf"), -1.0]
+
+
+def _format_table():
+    """(format, scale) -> (valid, bytes, effective scale), written out: cf32 is taken as it is, whatever its scale field holds; integer samples want a finite
+    scale >= 0 and 0 selects the default; formats above SC8 do not exist"""
+    t = {}
+    for s in FMT_SCALES:
+        t[(0, s)] = (True, 8, 1.0)
+        for f in (1, 2):
+            ok = s in (0.0, 2.0 ** -11, 3e-5)
+            t[(f, s)] = (ok, FMT_BYTES[f], np.float32(s if s else FMT_DEFAULT[f])) if ok else (False, None, None)
+        t[(3, s)] = (False, None, None)
+    t[(0xFFFFFFFF, 0.0)] = (False, None, None)
+    return t
+
+
+def test_sample_format_rule_against_the_written_table():
+    h = hosttest()
+    h.lsnh_sample_format.argtypes = [C.c_uint32, C.c_float, C.c_void_p]
+    tab = _format_table()
+    assert len(tab) == 4 * 6 + 1
+    for (fmt, scale), (ok, nbytes, eff) in tab.items():
+        out = (C.c_float * 3)()
+        h.lsnh_sample_format(fmt, scale, out)
+        assert bool(out[0]) == ok, (fmt, scale)
+        if ok:
+            assert int(out[1]) == nbytes and np.float32(out[2]) == np.float32(eff), (fmt, scale, out[1], out[2])
+
+
+def test_sample_format_rule_through_lsn_resample_span():
+    """the same verdicts where the rule is reachable without a device: lsn_resample_span refuses (LSN_ERROR_INVALID_INPUTS, -2) exactly the rows the table calls invalid"""
+    import ltesniffer_amd as la
+    for (fmt, scale), (ok, _, _) in _format_table().items():
+        cfg = la._resample_cfg(1, 23.04e6, 30.72e6, 0, 0.0, 0, 0, 0.0, fmt, scale)
+        sp = la.ResampleSpan()
+        r = la.lib().lsn_resample_span(C.byref(cfg), 1000, 100000, C.byref(sp))
+        assert r == (0 if ok else -2), (fmt, scale, r)
