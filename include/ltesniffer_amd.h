@@ -315,7 +315,8 @@ int lsn_phy_prepare_file(lsn_phy_t* phy, uint32_t nof_antennas);
 /* ---- recordings made at any sample rate: polyphase resampler on the GPU ----
  * Output sample m sits at input position P0 + m * D, D = round(rate_in / rate_out * 2^64), a 64.64 fixed-point number formed in 128-bit
  * integers: a sample is a function of (input, configuration, m) and of nothing else - not of block sizes or call boundaries.  The rates are
- * doubles, so a recording whose clock is off by a KNOWN amount replays correctly when the true rate is given (open loop: nothing tracks).
+ * doubles, so a recording whose clock is off by a KNOWN amount replays correctly when the true rate is given (open loop: nothing tracks;
+ * lsn_clock_estimate / lsn_file_clock_estimate below MEASURE that amount ahead of the replay).
  * Filter: Kaiser-windowed sinc, cut-off min(rate_in, rate_out) / 2, 80 dB design attenuation, pass band |f| <= passband_hz, stop band from
  * min(rate_in, rate_out) - passband_hz; the number of taps follows from the width between the two.  Refused (LSN_ERROR_INVALID_INPUTS): rate_in >
  * 4 rate_out, a pass band the lower rate cannot carry with at most 192 taps (min(rate_in, rate_out) below about 2.06 passband_hz when up-sampling),
@@ -325,7 +326,8 @@ int lsn_phy_prepare_file(lsn_phy_t* phy, uint32_t nof_antennas);
  * to the recording's centre.  Input sample n (its index in the RECORDING) is multiplied by exp(-2 pi j Phi(n) / 2^64) before the filter sees it, Phi(n) =
  * n W mod 2^64, W = round(center_offset_hz / rate_in * 2^64) mod 2^64: integer phase, so pieces, block sizes and call boundaries still change no bit.  The
  * exponential is a two-table NCO (12 + 10 phase bits, float32).  Same filter, same tap counts.  Accepted when finite and |center_offset_hz| + passband_hz <=
- * rate_in / 2 (the cell lies inside the recording), otherwise LSN_ERROR_INVALID_INPUTS.  Open loop: nothing searches for carriers or tracks one; one cell per
+ * rate_in / 2 (the cell lies inside the recording), otherwise LSN_ERROR_INVALID_INPUTS.  Open loop: nothing searches for carriers or tracks one (the sample clock
+ * is measured ahead of the replay, lsn_clock_estimate); one cell per
  * pass - two Phys replay two cells of one file.  0 runs the kernel without the mixer.  Unlike lsn_file_cfg_t.offset_freq_hz (a rotation of the OUTPUT samples
  * that restarts every subframe, behind the filter) this is a translation in front of it.
  *
@@ -373,6 +375,76 @@ typedef struct {
 } lsn_file_rate_t;
 int lsn_phy_process_file_rate(lsn_phy_t* phy, const char* path, const lsn_file_cfg_t* cfg, const lsn_file_rate_t* rate, uint32_t start_tti, uint64_t max_subframes,
                               uint32_t update_meta_period, uint64_t* subframes_done);
+
+/* ---- the sample clock of a recording, measured from its PSS train ----
+ * A recording made by a radio whose clock is off by eps runs at fs (1 + eps), fs = 15 kHz * N the nominal rate: PSS occurrence q (one every 5 ms, W5 = 75 N
+ * nominal samples) starts at p_q = p_0 + q W5 (1 + eps).  lsn_clock_estimate correlates the PSS replica of the cell (rotated by cfo_hz) over a short window
+ * of lags around every occurrence (k_pss_track: the expressions of the cell search's matched filter, C(l) = |sum x[l + k] conj r[k]|^2 / sum |x[l + k]|^2),
+ * refines every peak by a parabola through its three lags and fits a line through the positions - coarse to fine: round 0 looks at the first 8 periods
+ * with windows wide enough for +-max_ppm, every later round at four times as many with windows placed by the previous fit, the last at all of them.
+ * The answer goes, as sample_rate_hz and sf_start, into lsn_phy_process_file_rate: lsn_cell_search -> lsn_clock_estimate -> lsn_phy_mib_decode / replay
+ * needs no number from the user.  ONE constant eps per recording: nothing is tracked inside the replay; max_residual shows when the drift of a recording
+ * is not a line.
+ *   windows   round 0: period q < min(Q, 8), centre pss_pos + q W5, half width 4 + ceil(q W5 max_ppm 1e-6); round r >= 1: q < Q_r = min(Q, 4 Q_(r-1)), centre
+ *             floor(p0 + q W5 (1 + eps) + 1/2) of the previous fit, half width 4 + ceil(q / (Q_(r-1) - 1)).  Q = the periods whose round-0-style window lies inside
+ *             the samples, at most max_periods (0 = 4096); Q < 4: LSN_ERROR_INVALID_INPUTS (pss_pos < 4 leaves no room for the first window: pass pss_pos + W5)
+ *   observation  l* = first maximum of C over the window; valid when l* is neither its first nor its last lag; pos = l* + 0.5 (C[l*-1] - C[l*+1]) / (C[l*-1] -
+ *             2 C[l*] + C[l*+1]) (double), peak = C[l*]
+ *   fit       valid observations with peak >= 0.25 median(peak) (the mean of the two middle ones for an even number); least squares of pos on q; those more than 1.0
+ *             sample off the line are dropped and the rest fitted once more; found when the number used is >= 4 and >= half of the observations handed in, and
+ *             the rms residual is <= 0.5 sample; eps = slope / W5 - 1, pss_pos0 = intercept.  Fewer than two left to fit: found = 0, nothing else is filled in
+ * lsn_clock_plan, lsn_clock_fit and lsn_clock_replica need no GPU. */
+typedef struct {
+  uint32_t struct_size;   /* sizeof(lsn_clock_cfg_t); every other size is refused */
+  uint32_t nof_prb;
+  int rates;              /* LSN_RATES_*: N = lsn_symbol_sz(nof_prb, rates) */
+  uint32_t n_id_2;        /* lsn_cell_search_t.n_id_2 */
+  uint64_t pss_pos;       /* an integer near p_0: lsn_cell_search_t.pss_pos (+ a multiple of 75 N) */
+  float cfo_hz;           /* lsn_cell_search_t.cfo_hz: the replica is rotated by it */
+  double max_ppm;         /* largest |eps| looked for, 1e-6; 0 < max_ppm <= 1000 (the Python binding's default is 200) */
+  uint32_t max_periods;   /* 0 = 4096, the most looked at (20 s) */
+  uint32_t sf_start;      /* lsn_cell_search_t.sf_start: only its distance to pss_pos is used (lsn_clock_t.sf_start) */
+} lsn_clock_cfg_t;
+typedef struct {
+  uint32_t period, valid;
+  int64_t centre;         /* lags centre - half_width .. centre + half_width */
+  uint32_t half_width, reserved;
+  double pos;
+  float peak;
+} lsn_clock_obs_t;
+typedef struct {
+  uint32_t found, nof_periods /* observations of the last round */, nof_used /* of those in the fit */, nof_rounds;
+  double eps;             /* the recording runs at nominal * (1 + eps) */
+  double sample_rate_hz;  /* nominal * (1 + eps): lsn_file_rate_t.sample_rate_hz of the replay */
+  double pss_pos0;        /* fitted position of occurrence 0 */
+  double rms_residual, max_residual;  /* of the observations used, samples */
+  double sf_start;        /* pss_pos0 - ((pss_pos - cfg.sf_start) mod 75 N) (1 + eps), + 75 N (1 + eps) while negative: start of a subframe 0 / 5, for
+                             lsn_file_cfg_t.offset_time_samples (whole part) and lsn_file_rate_t.offset_time_frac.  It lies a whole number k of half frames
+                             (k = round of the difference / 75 N, normally 0) behind the cell search's sf_start: its subframe index is the search's sf_idx + 5 k */
+} lsn_clock_t;
+/* the windows of round `round` (previous: the fit of round - 1, ignored for round 0) -> number written (period, centre, half_width filled, the rest zero);
+ * 0: the previous round was the last; windows == NULL: the number alone; cap too small or a previous fit that was not found: LSN_ERROR_INVALID_INPUTS */
+int lsn_clock_plan(const lsn_clock_cfg_t* cfg, uint64_t nof_samples, uint32_t round, const lsn_clock_t* previous, lsn_clock_obs_t* windows, uint32_t cap);
+/* fills found, nof_periods = n, nof_used, eps, pss_pos0 and the residuals; returns found */
+int lsn_clock_fit(const lsn_clock_obs_t* obs, uint32_t n, uint32_t W5, lsn_clock_t* out);
+/* the replica the correlator uses: the unit-energy time-domain PSS of n_id_2 times exp(2 pi j cfo_hz k / fs), formed in double, rounded to float once; out: [N] cf32 */
+int lsn_clock_replica(const lsn_clock_cfg_t* cfg, float* out);
+/* one round on the GPU: fills pos / peak / valid of the given windows, each of which must lie inside the samples (lags >= 0, lag + N <= nof_samples);
+ * corr_out optional (host): the C values window by window.  iq: one antenna, cf32 at the nominal rate, host or device memory */
+int lsn_clock_track(int device, const void* iq, int iq_on_device, uint64_t nof_samples, const lsn_clock_cfg_t* cfg, lsn_clock_obs_t* windows, uint32_t n,
+                    float* corr_out);
+/* all rounds; 1 found, 0 not found (a round's fit failed, or placed a window outside the samples), < 0 error.  obs_out optional: the observations of the last
+ * round that ran (cap >= their number, at most the Q of the plan) */
+int lsn_clock_estimate(int device, const void* iq, int iq_on_device, uint64_t nof_samples, const lsn_clock_cfg_t* cfg, lsn_clock_t* out, lsn_clock_obs_t* obs_out,
+                       uint32_t cap);
+/* the same on a recording.  Only the slices the windows read are fetched (pread) - a few MB of a recording of any length.  cf32 / sc16 / sc8 as lsn_file_cfg_t
+ * (antenna `antenna` of the interleaved file, counted from cfg->offset_time_samples; offset_freq_hz is not applied); integer samples are converted on the host by
+ * the file source's rule, sample = (float)integer * scale.  rate == NULL: the file is nominally at the rate of cfg (nof_prb, rates).  Otherwise every slice comes
+ * out of the resampler's plan at the NOMINAL sample_rate_hz / center_offset_hz / offset_time_frac (k_resample, output samples from the first lag of the slice
+ * on; lags and pss_pos count output samples, output sample 0 = file position offset_time_samples + offset_time_frac), and the answer's sample_rate_hz =
+ * rate->sample_rate_hz * (1 + eps).  sf_start of the answer counts samples of the FILE from its first one (the offset included): directly the offset of the replay. */
+int lsn_file_clock_estimate(int device, const char* path, const lsn_file_cfg_t* fcfg, const lsn_file_rate_t* rate, uint32_t antenna, const lsn_clock_cfg_t* cfg,
+                            lsn_clock_t* out);
 
 /* ---- security-API sink (the step behind the path: PDSCH_Decoder::run_api_dl_mode, DL_Sniffer_PDSCH.cc:804-879) ----
  * api_mode as ArgManager's -a (ArgManager.cc:63,218): -1 off (default), 0 identity mapping, 2 IMSI catching, 3 all.  For every CRC-ok

@@ -40,7 +40,8 @@ EXPORTS = ["lsn_phy_create", "lsn_phy_destroy", "lsn_phy_set_cell", "lsn_phy_get
            "lsn_phy_set_mcs_update_interval", "lsn_phy_update_mcs_database", "lsn_phy_nof_tracked_rnti", "lsn_worker_buffers_offset", "lsn_pcap_digest", "lsn_pcap_set_store", "lsn_pcap_set_digest_blocks", "lsn_pcap_block_digests", "lsn_phy_create_multi", "lsn_phy_nof_devices",
            "lsn_phy_set_cfo_correction", "lsn_phy_get_cfo_correction", "lsn_phy_set_candidate_pruning", "lsn_phy_set_stage_c_taps", "lsn_phy_prepare_file", "lsn_phy_get_meta_formats", "lsn_phy_nof_workers", "lsn_phy_worker",
            "lsn_phy_set_sampling", "lsn_phy_get_sampling", "lsn_symbol_sz", "lsn_sampling_freq_hz", "lsn_cell_search_rates",
-           "lsn_resample", "lsn_resample_span", "lsn_phy_process_file_rate"]
+           "lsn_resample", "lsn_resample_span", "lsn_phy_process_file_rate",
+           "lsn_clock_plan", "lsn_clock_fit", "lsn_clock_replica", "lsn_clock_track", "lsn_clock_estimate", "lsn_file_clock_estimate"]
 
 RATES_3GPP, RATES_SRSRAN = 0, 1   # LSN_RATES_*: sampling mode of a Phy / of a cell search
 
@@ -115,6 +116,21 @@ class ResampleCfg(C.Structure):   # lsn_resample_cfg_t
 
 class ResampleSpan(C.Structure):   # lsn_resample_span_t
     _fields_ = [("in_lo", C.c_int64), ("in_hi", C.c_int64), ("max_out", C.c_uint64), ("taps", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ClockCfg(C.Structure):   # lsn_clock_cfg_t
+    _fields_ = [("struct_size", C.c_uint32), ("nof_prb", C.c_uint32), ("rates", C.c_int), ("n_id_2", C.c_uint32), ("pss_pos", C.c_uint64), ("cfo_hz", C.c_float),
+                ("max_ppm", C.c_double), ("max_periods", C.c_uint32), ("sf_start", C.c_uint32)]
+
+
+class ClockObs(C.Structure):   # lsn_clock_obs_t
+    _fields_ = [("period", C.c_uint32), ("valid", C.c_uint32), ("centre", C.c_int64), ("half_width", C.c_uint32), ("reserved", C.c_uint32), ("pos", C.c_double),
+                ("peak", C.c_float)]
+
+
+class Clock(C.Structure):   # lsn_clock_t
+    _fields_ = [("found", C.c_uint32), ("nof_periods", C.c_uint32), ("nof_used", C.c_uint32), ("nof_rounds", C.c_uint32), ("eps", C.c_double),
+                ("sample_rate_hz", C.c_double), ("pss_pos0", C.c_double), ("rms_residual", C.c_double), ("max_residual", C.c_double), ("sf_start", C.c_double)]
 
 
 class ApiEvent(C.Structure):
@@ -356,6 +372,12 @@ def lib():
         L.lsn_symbol_sz.restype = C.c_uint32
         L.lsn_sampling_freq_hz.argtypes = [C.c_uint32, C.c_int]
         L.lsn_sampling_freq_hz.restype = C.c_uint32
+        L.lsn_clock_plan.argtypes = [C.POINTER(ClockCfg), C.c_uint64, C.c_uint32, C.POINTER(Clock), C.POINTER(ClockObs), C.c_uint32]
+        L.lsn_clock_fit.argtypes = [C.POINTER(ClockObs), C.c_uint32, C.c_uint32, C.POINTER(Clock)]
+        L.lsn_clock_replica.argtypes = [C.POINTER(ClockCfg), C.c_void_p]
+        L.lsn_clock_track.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.POINTER(ClockCfg), C.POINTER(ClockObs), C.c_uint32, C.c_void_p]
+        L.lsn_clock_estimate.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.POINTER(ClockCfg), C.POINTER(Clock), C.POINTER(ClockObs), C.c_uint32]
+        L.lsn_file_clock_estimate.argtypes = [C.c_int, C.c_char_p, C.POINTER(FileCfg), C.POINTER(FileRate), C.c_uint32, C.POINTER(ClockCfg), C.POINTER(Clock)]
         _lib = L
     return _lib
 
@@ -822,6 +844,48 @@ def cell_search(iq, nof_prb, nof_periods=2, force_n_id_2=-1, threshold=20.0, dev
         ptr, n, on_dev = iq.ctypes.data, iq.size, 0
     rc = _check_n(lib().lsn_cell_search_rates(device, ptr, on_dev, n, nof_prb, int(rates), C.byref(cfg), C.byref(out), corr.ctypes.data if with_corr else None), "lsn_cell_search")
     return (rc, out, corr) if with_corr else (rc, out)
+
+
+def clock_cfg(nof_prb, search, max_ppm=200.0, rates=RATES_3GPP, max_periods=0):
+    """lsn_clock_cfg_t from the answer of cell_search (or anything with n_id_2, pss_pos, sf_start, cfo_hz).  A pss_pos in the first four samples leaves no room
+    for the first window: the occurrence one period later is taken as number 0"""
+    W5 = 75 * (symbol_sz(nof_prb, rates) or 128)
+    pss_pos = int(search.pss_pos) + (W5 if int(search.pss_pos) < 4 else 0)
+    return ClockCfg(C.sizeof(ClockCfg), int(nof_prb), int(rates), int(search.n_id_2), pss_pos, float(search.cfo_hz), float(max_ppm), int(max_periods),
+                    int(search.sf_start))
+
+
+def clock_estimate(iq, nof_prb, search, max_ppm=200.0, rates=RATES_3GPP, with_obs=False, max_periods=0, device=0):
+    """lsn_clock_estimate: the sample-clock error of the samples iq (one antenna at the nominal rate; numpy complex64 or a torch cuda tensor) from the positions of
+    their PSS occurrences; search: the CellSearch of cell_search on their head.  -> Clock (found, eps, sample_rate_hz, sf_start, ...)[, the observations of
+    the last round]"""
+    import numpy as np
+    cfg = clock_cfg(nof_prb, search, max_ppm, rates, max_periods)
+    if hasattr(iq, "data_ptr"):
+        ptr, n, on_dev = iq.data_ptr(), iq.numel(), 1
+    else:
+        iq = np.ascontiguousarray(iq, dtype=np.complex64)
+        ptr, n, on_dev = iq.ctypes.data, iq.size, 0
+    out = Clock()
+    obs = (ClockObs * 4096)() if with_obs else None
+    _check_n(lib().lsn_clock_estimate(device, ptr, on_dev, n, C.byref(cfg), C.byref(out), obs, 4096 if with_obs else 0), "lsn_clock_estimate")
+    return (out, list(obs[:out.nof_periods])) if with_obs else out
+
+
+def file_clock_estimate(path, nof_prb, search, nof_antennas=1, antenna=0, sample_format=FILE_CF32, sample_scale=0.0, offset_time=0, sample_rate=None,
+                        center_offset_hz=0.0, offset_time_frac=0.0, max_ppm=200.0, rates=RATES_3GPP, max_periods=0, device=0):
+    """lsn_file_clock_estimate: the same on a recording, of which only the slices around the PSS occurrences are read.  search: cell_search on the head of the
+    file from offset_time on (resampled at the NOMINAL sample_rate when the file has a rate of its own).  -> Clock; sample_rate_hz and sf_start (samples of the
+    file from its first one) are the sample_rate and offset_time + offset_time_frac of Phy.process_file"""
+    cfg = clock_cfg(nof_prb, search, max_ppm, rates, max_periods)
+    fc = FileCfg(int(nof_antennas), int(offset_time), 0.0, int(sample_format), float(sample_scale))
+    fr = FileRate(C.sizeof(FileRate), 0, float(sample_rate), float(offset_time_frac), float(center_offset_hz)) if sample_rate is not None else None
+    if fr is None and (center_offset_hz != 0.0 or offset_time_frac != 0.0):
+        raise ValueError("center_offset_hz / offset_time_frac need sample_rate (the nominal rate of the recording): both are part of the resampler")
+    out = Clock()
+    _check_n(lib().lsn_file_clock_estimate(device, os.fsencode(path), C.byref(fc), C.byref(fr) if fr is not None else None, int(antenna), C.byref(cfg), C.byref(out)),
+             "lsn_file_clock_estimate")
+    return out
 
 
 def _resample_cfg(nof_antennas, rate_in, rate_out, first_sample, first_frac, in_base, out_first, passband_hz, sample_format, sample_scale, center_offset_hz=0.0):

@@ -38,12 +38,13 @@ static void pss_sequence(uint32_t n_id_2, cf32* d)
 }
 static inline int sync_bin(int m, int N) { return m < 31 ? N - 31 + m : m - 30; }  // carriers -31..-1, +1..+31
 
-// unit-energy time-domain replica
-static void pss_replica(uint32_t n_id_2, uint32_t N, cf32* p)
+// unit-energy time-domain replica in double, (re, im) pairs; rot_hz != 0: multiplied by exp(2 pi j rot_hz n / (15 kHz N)), the carrier offset the
+// clock estimate's correlator takes out (lsn_clock.cc) - one rounding to float at the caller either way
+void pss_replica_d(uint32_t n_id_2, uint32_t N, double rot_hz, double* p)
 {
   cf32 d[62];
   pss_sequence(n_id_2, d);
-  const double sc = 1.0 / std::sqrt(62.0 * (double)N);
+  const double sc = 1.0 / std::sqrt(62.0 * (double)N), fs = 15000.0 * (double)N;
   for (uint32_t n = 0; n < N; n++) {
     double ar = 0, ai = 0;
     for (int m = 0; m < 62; m++) {
@@ -53,8 +54,23 @@ static void pss_replica(uint32_t n_id_2, uint32_t N, cf32* p)
       ar += (double)d[m].r * c - (double)d[m].i * s;
       ai += (double)d[m].r * s + (double)d[m].i * c;
     }
-    p[n] = {(float)(ar * sc), (float)(ai * sc)};
+    ar = ar * sc;
+    ai = ai * sc;
+    if (rot_hz != 0.0) {
+      const double ph = 2.0 * M_PI * rot_hz * (double)n / fs, c = std::cos(ph), s = std::sin(ph);
+      const double br = ar * c - ai * s, bi = ar * s + ai * c;
+      ar = br;
+      ai = bi;
+    }
+    p[2 * n] = ar;
+    p[2 * n + 1] = ai;
   }
+}
+static void pss_replica(uint32_t n_id_2, uint32_t N, cf32* p)
+{
+  std::vector<double> pd(2 * (size_t)N);
+  pss_replica_d(n_id_2, N, 0.0, pd.data());
+  for (uint32_t n = 0; n < N; n++) p[n] = {(float)pd[2 * n], (float)pd[2 * n + 1]};
 }
 
 // 36.211 6.11.2.1: all 168 x 2 SSS sequences of one N_id_2, row h = 2 N_id_1 + (subframe 5)

@@ -9,6 +9,10 @@
 // k_sync_fin   one workgroup: (a) the matched filter in two halves at the winning lag for each of the P + 1 occurrences,
 //              (b) pick the strongest occurrence whose SSS symbol is inside the buffer, (c) 62-carrier DFT of its PSS and SSS
 //              symbols (twiddle table), channel from the PSS, (d) the 336 SSS hypotheses (168 N_id_1 x subframe 0 / 5).
+// k_pss_track  the same matched filter of ONE replica on short windows of lags around the PSS occurrences of a whole recording (lsn_clock.cc):
+//              a table names, per 5 ms period, where its slice of samples starts in a packed buffer and how many lags it has.  One lane per lag, 64 lags
+//              (one wavefront) per workgroup, grid (lag tiles, periods); the 64 + N samples of a tile are staged as k_pss_corr stages them, the N taps
+//              of a lag stay in one lane in index order, so C has the bits of k_pss_corr's expressions.
 // The search runs once per capture; it is latency, not throughput, that matters: 0.5 M lags x 2048 taps x 3 roots at 20 MHz.
 #include "lsn_dev.h"
 
@@ -61,6 +65,41 @@ __global__ __launch_bounds__(SYNC_TILE) void k_pss_corr(const cf32* __restrict__
       C[2 * (size_t)W5 + n] = c2;
     }
   }
+}
+
+#define TRACK_TILE 64
+
+// one period of k_pss_track: its slice holds nlag + N - 1 samples from x[off]; its nlag values go to C[c_off ...]
+struct LsnTrackSlice {
+  uint64_t off;
+  uint32_t nlag, c_off;
+};
+
+__global__ __launch_bounds__(TRACK_TILE) void k_pss_track(const cf32* __restrict__ x, const LsnTrackSlice* __restrict__ tab, const cf32* __restrict__ p /* [N] */, uint32_t N,
+                                                          float* __restrict__ C)
+{
+  __shared__ cf32 xs[TRACK_TILE + 2048];
+  const cf32* __restrict__ ps = p;  // uniform index: scalar loads
+  const LsnTrackSlice sl = tab[blockIdx.y];
+  const uint32_t t = threadIdx.x, n0 = blockIdx.x * TRACK_TILE;
+  if (n0 >= sl.nlag) return;  // the grid is as wide as the widest window (the whole workgroup leaves: no barrier is missed)
+  const uint32_t len = sl.nlag - n0 + N - 1;  // samples of the slice from this tile's first lag on: nothing behind them is read
+  const cf32* xq = x + sl.off + n0;
+  for (uint32_t i = t; i < TRACK_TILE + N; i += TRACK_TILE) {
+    cf32 v = {0.0f, 0.0f};
+    if (i < len) v = xq[i];
+    xs[i] = v;
+  }
+  __syncthreads();
+  float ar = 0.0f, ai = 0.0f, e = 0.0f;
+  for (uint32_t k = 0; k < N; k++) {
+    const cf32 v = xs[t + k];
+    const cf32 a = ps[k];
+    e = e + (v.r * v.r + v.i * v.i);
+    ar = ar + (v.r * a.r + v.i * a.i);
+    ai = ai + (v.i * a.r - v.r * a.i);
+  }
+  if (n0 + t < sl.nlag) C[sl.c_off + n0 + t] = e > 0.0f ? (ar * ar + ai * ai) / e : 0.0f;  // lanes behind the window staged and waited, and write nothing
 }
 
 struct LsnSyncFin {
@@ -149,6 +188,13 @@ __global__ __launch_bounds__(512) void k_sync_fin(const cf32* __restrict__ x, co
 void lsn_launch_pss_corr(const cf32* x, const cf32* p, uint32_t N, uint32_t W5, uint32_t P, uint32_t nroots, float* C, hipStream_t s)
 {
   LSN_LAUNCH(k_pss_corr, dim3((W5 + SYNC_TILE - 1) / SYNC_TILE), dim3(SYNC_TILE), 0, s, x, p, N, W5, P, nroots, C);
+}
+// tab: nper entries of LsnTrackSlice (device); max_lag: the widest window.  The caller has checked every slice against the buffer.
+void lsn_launch_pss_track(const cf32* x, const void* tab, uint32_t nper, uint32_t max_lag, const cf32* p, uint32_t N, float* C, hipStream_t s)
+{
+  if (!nper || !max_lag) return;
+  if (N < 1 || N > 2048 || nper > 65535) throw std::runtime_error("k_pss_track: bad geometry");
+  LSN_LAUNCH(k_pss_track, dim3((max_lag + TRACK_TILE - 1) / TRACK_TILE, nper), dim3(TRACK_TILE), 0, s, x, (const LsnTrackSlice*)tab, p, N, C);
 }
 void lsn_launch_sync_fin(const cf32* x, const cf32* p, const cf32* w, const cf32* d, const int8_t* sss, uint32_t N, uint32_t W5, uint32_t P, uint32_t bn,
                          uint32_t cp, void* out, hipStream_t s)
