@@ -30,7 +30,7 @@ namespace lsn {
 // (read when an engine is made: Engine::cb_skip; the GPU suite runs with it)
 // (Round 6: naps of 200 / 500 us in the decode threads and 60 us in the front thread were measured - same rate, same busy cores: the polling is not what the
 // decode threads' CPU time goes into, profiles/r06_host_cost.txt.)
-static void waitEvent(hipEvent_t ev, long nap_ns = 50000)
+void waitEvent(hipEvent_t ev, long nap_ns)
 {
   for (;;) {
     const hipError_t e = hipEventQuery(ev);
@@ -581,53 +581,60 @@ int Engine::newJob(Chunk& ch, uint32_t sf, const DlEntry& e, int table, float p_
   return (int)ch.jobs.size() - 1;
 }
 
-void Engine::runJobs(Chunk& ch, JobRunner& r, std::vector<int>& ids)
+// The PDSCH grant descriptor of one job: PRB masks, modulation, scrambling and power allocation.  false: srsran_pdsch_decode's preconditions do not hold, the
+// job gets no descriptor.  Per transport block that will be decoded (enabled, a size): is its size from the derived TBS rows, and its algorithmic bytes.
+bool Engine::pdschGrantDev(const DecodeJob& j, const SubframeCtx& c, LsnGrantDev& d, bool derived_tbs[2], uint64_t algo_bytes[2]) const
 {
-  std::vector<int> todo;
-  for (int j : ids)
-    if (j >= 0 && !ch.jobs[j].done && !ch.jobs[j].planned) { ch.jobs[j].planned = true; todo.push_back(j); }
-  if (todo.empty()) return;
-  hipStream_t st = r.stream;
+  const PdschGrant& g = j.grant;
+  const uint32_t nprb = cell.nof_prb;
+  d = LsnGrantDev{};
+  d.sf = j.sf; d.sf_idx = c.sf_idx; d.l0 = c.cfi + (nprb <= 10 ? 1u : 0u);
+  for (int s = 0; s < 2; s++)
+    for (uint32_t rb = g.prb_lo; rb <= g.prb_hi && rb < nprb; rb++)
+      if (g.prb_idx[s][rb]) d.prb_mask[s][rb >> 5] |= 1u << (rb & 31);   // (per slot: the kernels index it with l >= nslot)
+  d.nof_re = g.nof_re; d.tx_scheme = (uint32_t)g.tx_scheme; d.pmi = g.pmi; d.nof_layers = g.nof_layers;
+  for (int i = 0; i < 2; i++)
+    if (g.tb[i].enabled) d.qm[g.tb[i].cw_idx & 1] = (uint32_t)g.tb[i].mod;
+  // demodulation possible? (srsran_pdsch_decode preconditions)
+  bool demod_ok = (g.tb[0].enabled || g.tb[1].enabled) && g.nof_re > 0;
+  if (g.tx_scheme == TXSCHEME_SPATIALMUX || g.tx_scheme == TXSCHEME_CDD) {
+    if (cell.nof_ports != 2) demod_ok = false;  // one port: no such transmission; four ports: the reference's srsRAN precodes them for transmit diversity only
+    if (g.nof_layers != 1 && dlRx() < 2) demod_ok = false;
+  }
+  if (g.tx_scheme == TXSCHEME_DIVERSITY && cell.nof_ports < 2) demod_ok = false;
+  if (!demod_ok) return false;
+  for (int q = 0; q < 2; q++) d.cinit[q] = ((uint32_t)j.rnti << 14) | ((uint32_t)q << 13) | (c.sf_idx << 9) | cell.id;
+  // power allocation 36.213 5.2: rho_A from the job's p_a, p_b = 1 (SubframeWorker.cc:372)
+  const float rho_a = powf(10.0f, j.p_a / 20.0f);
+  const float rho_b = cell.nof_ports == 1 ? rho_a * sqrtf(0.8f) : rho_a;
+  d.inv_amp_a = 1.0f / rho_a; d.inv_amp_b = 1.0f / rho_b;
+  for (int i = 0; i < 2; i++) {
+    const GrantTb& tb = g.tb[i];
+    const bool on = tb.enabled && tb.tbs > 0;
+    derived_tbs[i] = on && tbs_from_derived_rows(tb.tbs, g.nof_prb);
+    algo_bytes[i] = on ? 2ull * (uint64_t)tb.nof_bits * 2ull + (uint64_t)tb.tbs / 8ull : 0;
+  }
+  return true;
+}
+
+void Engine::packJobs(Chunk& ch, JobRunner& r, DecodeLaunch& L)
+{
   lsn_perf_t& pf = r.perf;
   const uint32_t nprb = cell.nof_prb;
   r.h_jobs.clear(); r.h_cbs.clear(); r.h_items.clear();
-  size_t llr_n = 0, prefix_n = 0;
-  const size_t pay0 = ch.h_payload.size();
-  size_t pay_n = pay0;
-  struct TbRef { int job, tb; uint32_t cb_first, cb_count; };
-  std::vector<TbRef> tbrefs;
-  std::vector<int> jid_of_hjob;
-  for (int jid : todo) {
+  L.pay0 = L.pay_n = ch.h_payload.size();
+  for (int jid : L.todo) {
     DecodeJob& j = ch.jobs[jid];
     const PdschGrant& g = j.grant;
-    const SubframeCtx& c = ch.ctx[j.sf];
-    LsnGrantDev d{};
-    d.sf = j.sf; d.sf_idx = c.sf_idx; d.l0 = c.cfi + (nprb <= 10 ? 1u : 0u);
-    for (int s = 0; s < 2; s++)
-      for (uint32_t rb = g.prb_lo; rb <= g.prb_hi && rb < nprb; rb++)
-        if (g.prb_idx[s][rb]) d.prb_mask[s][rb >> 5] |= 1u << (rb & 31);   // (per slot: the kernels index it with l >= nslot)
-    d.nof_re = g.nof_re; d.tx_scheme = (uint32_t)g.tx_scheme; d.pmi = g.pmi; d.nof_layers = g.nof_layers;
-    for (int i = 0; i < 2; i++)
-      if (g.tb[i].enabled) d.qm[g.tb[i].cw_idx & 1] = (uint32_t)g.tb[i].mod;
-    // demodulation possible? (srsran_pdsch_decode preconditions)
-    bool demod_ok = (g.tb[0].enabled || g.tb[1].enabled) && g.nof_re > 0;
-    if (g.tx_scheme == TXSCHEME_SPATIALMUX || g.tx_scheme == TXSCHEME_CDD) {
-      if (cell.nof_ports != 2) demod_ok = false;  // one port: no such transmission; four ports: the reference's srsRAN precodes them for transmit diversity only
-      if (g.nof_layers != 1 && dlRx() < 2) demod_ok = false;
-    }
-    if (g.tx_scheme == TXSCHEME_DIVERSITY && cell.nof_ports < 2) demod_ok = false;
-    if (!demod_ok) continue;
+    LsnGrantDev d;
+    bool derived[2]; uint64_t bytes[2];
+    if (!pdschGrantDev(j, ch.ctx[j.sf], d, derived, bytes)) continue;
     for (int q = 0; q < 2; q++) {
-      d.cinit[q] = ((uint32_t)j.rnti << 14) | ((uint32_t)q << 13) | (c.sf_idx << 9) | cell.id;
-      d.llr_off[q] = (uint32_t)llr_n;
-      if (d.qm[q]) llr_n += ((size_t)g.nof_re * d.qm[q] + 7) & ~(size_t)7;
+      d.llr_off[q] = (uint32_t)L.llr_n;
+      if (d.qm[q]) L.llr_n += ((size_t)g.nof_re * d.qm[q] + 7) & ~(size_t)7;
     }
-    d.prefix_off = (uint32_t)prefix_n;
-    prefix_n += 14 * nprb + 16;
-    // power allocation 36.213 5.2: rho_A from the job's p_a, p_b = 1 (SubframeWorker.cc:372)
-    const float rho_a = powf(10.0f, j.p_a / 20.0f);
-    const float rho_b = cell.nof_ports == 1 ? rho_a * sqrtf(0.8f) : rho_a;
-    d.inv_amp_a = 1.0f / rho_a; d.inv_amp_b = 1.0f / rho_b;
+    d.prefix_off = (uint32_t)L.prefix_n;
+    L.prefix_n += 14 * nprb + 16;
     // transport blocks -> code blocks (36.212 5.1.2, 5.1.4.1.2)
     j.cb_first = (uint32_t)r.h_cbs.size();
     for (int i = 0; i < 2; i++) {
@@ -637,209 +644,187 @@ void Engine::runJobs(Chunk& ch, JobRunner& r, std::vector<int>& ids)
       CbSegm s;
       const int Qm = tb.mod, G = tb.nof_bits, NL = g.tx_scheme == TXSCHEME_DIVERSITY ? 2 : 1;
       if (!cbsegm(tb.tbs, s) || Qm <= 0 || G <= 0) continue;
-      j.payload_off[i] = (uint32_t)pay_n;
-      TbRef ref{jid, i, (uint32_t)r.h_cbs.size(), (uint32_t)s.C};
+      j.payload_off[i] = (uint32_t)L.pay_n;
+      L.tbrefs.push_back({jid, i, (uint32_t)r.h_cbs.size(), (uint32_t)s.C});
       // code blocks 1 .. C-1 are launched behind block 0 and skipped when it failed (the TB CRC verdict needs every block)
-      pay_n += tb_code_blocks(s, G, Qm, NL, tb.rv, (uint32_t)cfg.max_turbo_iterations, d.llr_off[tb.cw_idx & 1], (uint32_t)(pay_n - pay0), cb_skip, r.h_cbs);
+      L.pay_n += tb_code_blocks(s, G, Qm, NL, tb.rv, (uint32_t)cfg.max_turbo_iterations, d.llr_off[tb.cw_idx & 1], (uint32_t)(L.pay_n - L.pay0), cb_skip, r.h_cbs);
       j.cb_count[i] = (uint32_t)s.C;
-      tbrefs.push_back(ref);
       pf.nof_tb_decodes++;
-      if (tbs_from_derived_rows(tb.tbs, g.nof_prb)) pf.nof_tb_on_derived_tbs++;
+      if (derived[i]) pf.nof_tb_on_derived_tbs++;
       pf.nof_cb_decodes += (uint64_t)s.C;
-      pf.algo_bytes += 2ull * (uint64_t)tb.nof_bits * 2ull + (uint64_t)tb.tbs / 8ull;
+      pf.algo_bytes += bytes[i];
     }
     if (g.prb_lo <= g.prb_hi)
       for (uint32_t grp = g.prb_lo / 16; grp <= std::min<uint32_t>(g.prb_hi, nprb - 1) / 16; grp++) r.h_items.push_back(((uint32_t)r.h_jobs.size() << 8) | grp);
     r.h_jobs.push_back(d);
-    jid_of_hjob.push_back(jid);
+    L.jid_of_hjob.push_back(jid);
   }
-  // ONE decoder launch per phase (late round 4: + 5.7 % against one launch per wavefront class).  Round 5: the blocks of at most 64 windows - one working
-  // wavefront - share workgroups two by two (k_turbo, stage_c.hip) instead of holding a whole LDS / wavefront slot each with the second wavefront idle:
-  // half of the metric's code blocks, half of the decoder's slot time (every block alone in its workgroup, rounds 2-4: - 3 %, profiles/r05_ab_session*.txt).
-  auto pairable = [&](uint32_t K) { return K <= LSN_TURBO_PAIR_KMAX && turbo_nwin((int)K) <= 64; };
-  const uint32_t njobs = (uint32_t)r.h_jobs.size(), ncb = (uint32_t)r.h_cbs.size();
-  uint32_t kmax_solo = 0, kmax_pair = 0, emax = 0, nsolo[2] = {0, 0}, npair[2] = {0, 0};
-  size_t spp_n = 0;
-  std::vector<uint32_t> order;
-  if (njobs) {
-    grow_dev(r.d_jobs, r.jobs_cap, njobs, st);
-    grow_dev(r.d_cbs, r.cbs_cap, ncb, st);
-    grow_dev(r.d_cbres, r.cbres_cap, ncb, st);
-    grow_dev(r.d_prefix, r.prefix_cap, prefix_n, st);
-    grow_dev(r.d_llr16, r.llr16_cap, llr_n + 8, st);
-    grow_dev(r.d_payload, r.payload_cap, pay_n - pay0 + 16, st);
-    grow_host(r.h_cbres_pinned, r.h_cbres_cap, ncb, st);
-    grow_host(r.h_payload_pinned, r.h_payload_cap, pay_n - pay0 + 16, st);
-    grow_host(r.h_jobs_pinned, r.h_jobs_cap, njobs, st);
-    grow_host(r.h_cbs_pinned, r.h_cbs_cap, ncb, st);
-    const uint32_t nitems = (uint32_t)r.h_items.size();
-    grow_dev(r.d_items, r.items_cap, nitems + 1, st);
-    grow_host(r.h_items_pinned, r.h_items_cap, nitems + 1, st);
-    LsnCopySegs up;   // items, jobs and code-block descriptors go up in one launch
-    std::memcpy(r.h_items_pinned, r.h_items.data(), nitems * sizeof(uint32_t));
-    up.add(r.d_items, r.h_items_pinned, nitems * sizeof(uint32_t));
-    std::memcpy(r.h_jobs_pinned, r.h_jobs.data(), njobs * sizeof(LsnGrantDev));
-    if (ncb) {
-      // launch order: per phase the blocks that get a workgroup of their own first, then the blocks that share one; each class by descending size (longest
-      // jobs first; the two blocks of a pair are neighbours in size, so their wavefronts run for about the same time)
-      // two phases: first every block that nothing depends on having passed (block 0 of each transport block), then the dependants.  The key (phase, solo before
-      // paired, K descending, index ascending) has 2 x 6 144 values: a counting sort - the comparison sort this replaces cost 1.5 us of decode-thread CPU per
-      // subframe (round 6, thread-CPU sections)
-      order.resize(ncb);
-      {
-        static thread_local std::vector<uint32_t> cnt;
-        cnt.assign(2 * 2 * 6145 + 1, 0);
-        auto key = [&](const LsnCbDev& q) { return ((q.dep != LSN_CB_NODEP ? 1u : 0u) * 2u + (pairable(q.K) ? 1u : 0u)) * 6145u + (6144u - std::min<uint32_t>(q.K, 6144u)); };
-        for (uint32_t i = 0; i < ncb; i++) { r.h_cbs[i].res_idx = i; cnt[key(r.h_cbs[i]) + 1]++; }
-        for (size_t k = 1; k < cnt.size(); k++) cnt[k] += cnt[k - 1];
-        for (uint32_t i = 0; i < ncb; i++) order[cnt[key(r.h_cbs[i])]++] = i;   // stable: equal keys keep ascending index
-      }
-      for (uint32_t i = 0; i < ncb; i++) {
-        LsnCbDev q = r.h_cbs[order[i]];
-        q.spp_off = (uint32_t)spp_n; spp_n += LSN_SPP_WORDS(q.K);
-        emax = std::max(emax, q.E);
-        r.h_cbs_pinned[i] = q;
-        const int ph = q.dep != LSN_CB_NODEP ? 1 : 0;
-        if (pairable(q.K)) { npair[ph]++; kmax_pair = std::max(kmax_pair, q.K); } else { nsolo[ph]++; kmax_solo = std::max(kmax_solo, q.K); }
-      }
-      grow_dev(r.d_spp, r.spp_cap, spp_n + 16, st);
-      up.add(r.d_cbs, r.h_cbs_pinned, ncb * sizeof(LsnCbDev));
+  L.njobs = (uint32_t)r.h_jobs.size(); L.ncb = (uint32_t)r.h_cbs.size(); L.nitems = (uint32_t)r.h_items.size();
+}
+
+void Engine::growLaunchArenas(JobRunner& r, const DecodeLaunch& L)
+{
+  hipStream_t st = r.stream;
+  const size_t pay = L.pay_n - L.pay0 + 16;
+  grow_dev(r.d_jobs, r.jobs_cap, L.njobs, st);
+  grow_dev(r.d_cbs, r.cbs_cap, L.ncb, st);
+  grow_dev(r.d_cbres, r.cbres_cap, L.ncb, st);
+  grow_dev(r.d_prefix, r.prefix_cap, L.prefix_n, st);
+  grow_dev(r.d_llr16, r.llr16_cap, L.llr_n + 8, st);
+  grow_dev(r.d_payload, r.payload_cap, pay, st);
+  grow_host(r.h_cbres_pinned, r.h_cbres_cap, L.ncb, st);
+  grow_host(r.h_payload_pinned, r.h_payload_cap, pay, st);
+  grow_host(r.h_jobs_pinned, r.h_jobs_cap, L.njobs, st);
+  grow_host(r.h_cbs_pinned, r.h_cbs_cap, L.ncb, st);
+  grow_dev(r.d_items, r.items_cap, L.nitems + 1, st);
+  grow_host(r.h_items_pinned, r.h_items_cap, L.nitems + 1, st);
+}
+
+// ONE decoder launch per phase (late round 4: + 5.7 % against one launch per wavefront class).  Round 5: the blocks of at most 64 windows - one working
+// wavefront - share workgroups two by two (k_turbo, stage_c.hip) instead of holding a whole LDS / wavefront slot each with the second wavefront idle:
+// half of the metric's code blocks, half of the decoder's slot time (every block alone in its workgroup, rounds 2-4: - 3 %, profiles/r05_ab_session*.txt).
+void Engine::orderAndPlace(JobRunner& r, DecodeLaunch& L)
+{
+  if (!L.ncb) return;
+  L.ord = turbo_packed_order(r.h_cbs);
+  L.place = turbo_place(r.h_cbs, L.ord.order, 0, r.h_cbs_pinned);
+  grow_dev(r.d_spp, r.spp_cap, L.place.spp_n + 16, r.stream);
+}
+
+void Engine::launchDecode(Chunk& ch, JobRunner& r, const DecodeLaunch& L)
+{
+  hipStream_t st = r.stream;
+  const TurboPackedOrder& o = L.ord;
+  LsnCopySegs up;   // items, jobs and code-block descriptors go up in one launch
+  std::memcpy(r.h_items_pinned, r.h_items.data(), L.nitems * sizeof(uint32_t));
+  up.add(r.d_items, r.h_items_pinned, L.nitems * sizeof(uint32_t));
+  std::memcpy(r.h_jobs_pinned, r.h_jobs.data(), L.njobs * sizeof(LsnGrantDev));
+  if (L.ncb) up.add(r.d_cbs, r.h_cbs_pinned, L.ncb * sizeof(LsnCbDev));
+  const bool tk = L.timed;   // prep / demod / rm: timed on a sample of the launches; the decoders on every launch
+  if (tk) HIP_CHECK(hipEventRecord(r.ev[0], st));  // (no clear of the LLR arena: k_pdsch_demod writes every soft bit of every codeword it is given, zeros of unpaired SFBC REs included)
+  lsn_launch_pdsch_prep_up(cd, r.h_jobs_pinned, r.d_jobs, L.njobs, up, r.d_prefix, st);   // descriptors up + prefix tables in one launch
+  if (tk) HIP_CHECK(hipEventRecord(r.ev[1], st));
+  lsn_launch_pdsch_demod(cd, r.d_jobs, r.d_items, L.nitems, r.d_prefix, ch.d_grid, ch.d_ce, ch.d_chest, r.d_llr16, st);
+  if (tk) HIP_CHECK(hipEventRecord(r.ev[2], st));
+  if (!L.ncb) return;
+  lsn_launch_rm(r.d_cbs, r.d_llr16, r.d_spp, L.ncb, L.place.emax, st);
+  if (timing_period) HIP_CHECK(hipEventRecord(r.ev[5], st));
+  // phase 0: the independent blocks [solo | paired], phase 1: the same of the dependants (descriptor order = launch order)
+  lsn_launch_turbo_packed(cd, r.d_cbs, r.d_spp, r.d_payload, r.d_cbres, o.nsolo[0], o.kmax_solo, o.npair[0], o.kmax_pair, st);
+  const uint32_t o1 = o.nsolo[0] + o.npair[0];
+  if (L.ncb > o1) {
+    if (timing_period) HIP_CHECK(hipEventRecord(r.ev[8], st));
+    lsn_launch_turbo_packed(cd, r.d_cbs + o1, r.d_spp, r.d_payload, r.d_cbres, o.nsolo[1], o.kmax_solo, o.npair[1], o.kmax_pair, st);
+  }
+  if (timing_period) HIP_CHECK(hipEventRecord(r.ev[3], st));
+  LsnCopySegs dn;
+  dn.add(r.h_cbres_pinned, r.d_cbres, L.ncb * sizeof(LsnCbRes));
+  dn.add(r.h_payload_pinned, r.d_payload, L.pay_n - L.pay0);
+  lsn_launch_copy_multi(dn, true, st);
+}
+
+void Engine::launchPerf(JobRunner& r, const DecodeLaunch& L)
+{
+  lsn_perf_t& pf = r.perf;
+  float ms = 0;
+  const bool tk = L.timed; const float scale = (float)timing_period;
+  if (tk && hipEventElapsedTime(&ms, r.ev[0], r.ev[1]) == hipSuccess) pf.kernel_ms[LSN_K_PDSCH_PREP] += ms * scale;
+  if (tk && hipEventElapsedTime(&ms, r.ev[1], r.ev[2]) == hipSuccess) pf.kernel_ms[LSN_K_PDSCH_DEMOD] += ms * scale;
+  pf.kernel_launches[LSN_K_PDSCH_PREP]++; pf.kernel_launches[LSN_K_PDSCH_DEMOD]++;
+  if (!L.ncb) return;
+  if (tk && hipEventElapsedTime(&ms, r.ev[2], r.ev[5]) == hipSuccess) pf.kernel_ms[LSN_K_RM] += ms * scale;
+  pf.kernel_launches[LSN_K_RM]++;
+  const bool ph1 = L.ncb > L.ord.nsolo[0] + L.ord.npair[0];
+  auto acc = [&](int k, hipEvent_t a, hipEvent_t b) { if (timing_period && hipEventElapsedTime(&ms, a, b) == hipSuccess) { pf.kernel_ms[k] += ms; pf.kernel_launches[k]++; } };
+  acc(LSN_K_TURBO128, r.ev[5], ph1 ? r.ev[8] : r.ev[3]);
+  if (ph1) acc(LSN_K_TURBO128, r.ev[8], r.ev[3]);
+  for (uint32_t i = 0; i < L.ncb; i++) {
+    // algorithmic bytes of the decoder kernels: every code block reads its K + 12 packed soft words (k_rm's output) and writes its payload
+    const uint64_t b = 4ull * (r.h_cbs[i].K + 12u) + r.h_cbs[i].out_bytes;
+    pf.turbo_algo_bytes += b;
+    pf.turbo128_algo_bytes += b;   // (every downlink block runs in the two-wavefront instance)
+    const LsnCbRes& cr = r.h_cbres_pinned[i];
+    pf.nof_turbo_iterations += cr.iters; pf.nof_turbo_iterations_run += cr.iters_run;
+    pf.turbo_cyc_rm += cr.cyc_rm; pf.turbo_cyc_map += cr.cyc_map; pf.turbo_cyc_out += cr.cyc_out;
+  }
+}
+
+void Engine::tapLaunch(Chunk& ch, JobRunner& r, const DecodeLaunch& L)
+{
+  std::vector<int16_t> llr(L.llr_n);
+  std::vector<uint32_t> spp(L.place.spp_n);
+  if (L.llr_n) HIP_CHECK(hipMemcpy(llr.data(), r.d_llr16, L.llr_n * sizeof(int16_t), hipMemcpyDeviceToHost));
+  if (L.place.spp_n) HIP_CHECK(hipMemcpy(spp.data(), r.d_spp, L.place.spp_n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  std::lock_guard<std::mutex> lk(tap_mtx);
+  if (ch.tapjobs.size() < ch.jobs.size()) ch.tapjobs.resize(ch.jobs.size());
+  for (uint32_t h = 0; h < L.njobs; h++) {
+    TapJob& t = ch.tapjobs[L.jid_of_hjob[h]];
+    t = TapJob{};
+    t.have = true; t.d = r.h_jobs[h];
+    for (int q = 0; q < 2; q++)
+      if (t.d.qm[q]) t.llr[q].assign(llr.begin() + t.d.llr_off[q], llr.begin() + t.d.llr_off[q] + (size_t)t.d.nof_re * t.d.qm[q]);
+  }
+  for (auto& tr : L.tbrefs)
+    for (uint32_t q = 0; q < tr.cb_count; q++) {
+      TapCb c;
+      c.cb = r.h_cbs[tr.cb_first + q]; c.tb = (uint32_t)tr.tb; c.res = r.h_cbres_pinned[tr.cb_first + q];
+      const uint32_t at = L.place.spp_of[tr.cb_first + q];
+      c.words.assign(spp.begin() + at, spp.begin() + at + c.cb.K + 12);
+      ch.tapjobs[tr.job].cbs.push_back(std::move(c));
     }
-    const bool tk = timing_period && (r.launches++ % timing_period) == 0;   // prep / demod / rm: timed on a sample of the launches; the decoders on every launch
-    hipStream_t sl = st;
-    if (tk) HIP_CHECK(hipEventRecord(r.ev[0], sl));  // (no clear of the LLR arena: k_pdsch_demod writes every soft bit of every codeword it is given, zeros of unpaired SFBC REs included)
-    lsn_launch_pdsch_prep_up(cd, r.h_jobs_pinned, r.d_jobs, njobs, up, r.d_prefix, sl);   // descriptors up + prefix tables in one launch
-    if (tk) HIP_CHECK(hipEventRecord(r.ev[1], sl));
-    lsn_launch_pdsch_demod(cd, r.d_jobs, r.d_items, nitems, r.d_prefix, ch.d_grid, ch.d_ce, ch.d_chest, r.d_llr16, sl);
-    if (tk) HIP_CHECK(hipEventRecord(r.ev[2], sl));
-    if (ncb) {
-      lsn_launch_rm(r.d_cbs, r.d_llr16, r.d_spp, ncb, emax, sl);
-      if (timing_period) HIP_CHECK(hipEventRecord(r.ev[5], sl));
-      // phase 0: the independent blocks [solo | paired], phase 1: the same of the dependants (descriptor order = launch order)
-      lsn_launch_turbo_packed(cd, r.d_cbs, r.d_spp, r.d_payload, r.d_cbres, nsolo[0], kmax_solo, npair[0], kmax_pair, st);
-      const uint32_t o1 = nsolo[0] + npair[0];
-      if (ncb > o1) {
-        if (timing_period) HIP_CHECK(hipEventRecord(r.ev[8], st));
-        lsn_launch_turbo_packed(cd, r.d_cbs + o1, r.d_spp, r.d_payload, r.d_cbres, nsolo[1], kmax_solo, npair[1], kmax_pair, st);
-      }
-      if (timing_period) HIP_CHECK(hipEventRecord(r.ev[3], st));
-      {
-        LsnCopySegs dn;
-        dn.add(r.h_cbres_pinned, r.d_cbres, ncb * sizeof(LsnCbRes));
-        dn.add(r.h_payload_pinned, r.d_payload, pay_n - pay0);
-        lsn_launch_copy_multi(dn, true, st);
-      }
-      if (cfg.harq_mode) {  // the soft data of this launch stays with the chunk until its commit (HARQ buffers are filled / combined there)
-        if (ch.keep_n + spp_n >= ((size_t)1 << 30)) throw std::runtime_error("harq_mode: the soft data of one chunk exceeds 4 GB (2^30 words) - process smaller batches");   // (HarqKeep::loc: 30-bit word offsets)
-        if (ch.keep_n + spp_n > ch.keep_cap) {
-          const size_t cap = (ch.keep_n + spp_n) * 2 + (1u << 20);
-          uint32_t* nb = nullptr;
-          HIP_CHECK(hipMalloc((void**)&nb, cap * sizeof(uint32_t)));
-          if (ch.keep_n) HIP_CHECK(hipMemcpy(nb, ch.d_keep, ch.keep_n * sizeof(uint32_t), hipMemcpyDeviceToDevice));
-          if (ch.d_keep) HIP_CHECK(hipFree(ch.d_keep));
-          ch.d_keep = nb; ch.keep_cap = cap;
-        }
-        HIP_CHECK(hipMemcpyAsync(ch.d_keep + ch.keep_n, r.d_spp, spp_n * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-        std::vector<uint32_t> spp_of(ncb, 0);
-        for (uint32_t i = 0; i < ncb; i++) spp_of[order[i]] = r.h_cbs_pinned[i].spp_off;
-        for (auto& tr : tbrefs) {
-          DecodeJob& j = ch.jobs[tr.job];
-          j.keep_first[tr.tb] = (uint32_t)ch.keep_cbs.size(); j.keep_count[tr.tb] = tr.cb_count;
-          for (uint32_t q = 0; q < tr.cb_count; q++) {
-            LsnCbDev cb = r.h_cbs[tr.cb_first + q];
-            cb.spp_off = (uint32_t)(ch.keep_n + spp_of[tr.cb_first + q]);
-            ch.keep_cbs.push_back(cb);
-          }
-        }
-        ch.keep_n += spp_n;
+}
+
+void Engine::takeVerdicts(Chunk& ch, JobRunner& r, const DecodeLaunch& L)
+{
+  ch.h_payload.resize(L.pay_n);
+  if (L.pay_n > L.pay0) std::memcpy(ch.h_payload.data() + L.pay0, r.h_payload_pinned, L.pay_n - L.pay0);
+  // transport-block verdicts: every code block ok, CRC24A over data||parity zero (combined from the per-block remainders), parity word non-zero
+  for (auto& t : L.tbrefs) {
+    DecodeJob& j = ch.jobs[t.job];
+    const TbResult res = tb_verdict(r.h_cbres_pinned + t.cb_first, r.h_cbs.data() + t.cb_first, t.cb_count);
+    j.iters += res.iters;
+    const int tbs = j.grant.tb[t.tb].tbs;
+    const uint8_t* pl = ch.h_payload.data() + j.payload_off[t.tb];
+    j.crc[t.tb] = res.v.pass(pl, tbs);
+    if (cfg.harq_mode) harqKeepResults(ch, r, t);
+    JobRes& jr = ch.jres[t.job];
+    jr.crc[t.tb] = j.crc[t.tb] ? 1 : 0;
+    jr.payload_off[t.tb] = j.payload_off[t.tb];
+    // DL_Sniffer_PDSCH.cc:1041-1070: a decoded C-RNTI block is walked for RRCConnectionSetups - here, by the thread that ran the decode, so that the commit thread never touches the payload
+    if (j.crc[t.tb] && tbs >= 8 && cfg.sniffer_mode == 0 && rnti_name(j.rnti)[0] == 'C') {
+      UeSpecConfig sc[20];
+      const int n = MCSTracking::setups_of_pdu(pl, tbs / 8, sc, 20, true);   // every SDU: which of them count is the commit's decision (known-table branch: LCID 0 only)
+      if (n > 0) {
+        jr.setup_first[t.tb] = (uint32_t)ch.setup_cfgs.size();
+        jr.nsetup[t.tb] = (uint8_t)n;
+        ch.setup_cfgs.insert(ch.setup_cfgs.end(), sc, sc + n);
       }
     }
-    HIP_CHECK(hipEventRecord(r.ev_done, st));
+  }
+}
+
+// Stage C for a list of jobs in one launch: pack, grow, order and place, launch, (harq_mode: keep the soft data,) wait, perf, taps, verdicts
+void Engine::runJobs(Chunk& ch, JobRunner& r, std::vector<int>& ids)
+{
+  DecodeLaunch L;
+  for (int j : ids)
+    if (j >= 0 && !ch.jobs[j].done && !ch.jobs[j].planned) { ch.jobs[j].planned = true; L.todo.push_back(j); }
+  if (L.todo.empty()) return;
+  packJobs(ch, r, L);
+  if (L.njobs) {
+    growLaunchArenas(r, L);
+    orderAndPlace(r, L);
+    L.timed = timing_period && (r.launches++ % timing_period) == 0;
+    launchDecode(ch, r, L);
+    if (cfg.harq_mode && L.ncb) harqKeepSoftData(ch, r, L);
+    HIP_CHECK(hipEventRecord(r.ev_done, r.stream));
     waitEvent(r.ev_done);
-    float ms = 0;
-    const float scale = (float)timing_period;
-    if (tk && hipEventElapsedTime(&ms, r.ev[0], r.ev[1]) == hipSuccess) pf.kernel_ms[LSN_K_PDSCH_PREP] += ms * scale;
-    if (tk && hipEventElapsedTime(&ms, r.ev[1], r.ev[2]) == hipSuccess) pf.kernel_ms[LSN_K_PDSCH_DEMOD] += ms * scale;
-    pf.kernel_launches[LSN_K_PDSCH_PREP]++; pf.kernel_launches[LSN_K_PDSCH_DEMOD]++;
-    if (ncb) {
-      if (tk && hipEventElapsedTime(&ms, r.ev[2], r.ev[5]) == hipSuccess) pf.kernel_ms[LSN_K_RM] += ms * scale;
-      pf.kernel_launches[LSN_K_RM]++;
-      {
-        const bool ph1 = ncb > nsolo[0] + npair[0];
-        auto acc = [&](int k, hipEvent_t a, hipEvent_t b) { if (timing_period && hipEventElapsedTime(&ms, a, b) == hipSuccess) { pf.kernel_ms[k] += ms; pf.kernel_launches[k]++; } };
-        acc(LSN_K_TURBO128, r.ev[5], ph1 ? r.ev[8] : r.ev[3]);
-        if (ph1) acc(LSN_K_TURBO128, r.ev[8], r.ev[3]);
-      }
-      // algorithmic bytes of the decoder kernels: every code block reads its K + 12 packed soft words (k_rm's output) and writes its payload
-      for (uint32_t i = 0; i < ncb; i++) {
-        const uint64_t b = 4ull * (r.h_cbs_pinned[i].K + 12u) + r.h_cbs_pinned[i].out_bytes;
-        pf.turbo_algo_bytes += b;
-        pf.turbo128_algo_bytes += b;   // (every downlink block runs in the two-wavefront instance)
-      }
-    }
-    if (keep_stage_c.load()) {  // parity taps: the arenas are recycled by the next launch of this runner
-      std::vector<int16_t> llr(llr_n);
-      std::vector<uint32_t> spp(spp_n);
-      if (llr_n) HIP_CHECK(hipMemcpy(llr.data(), r.d_llr16, llr_n * sizeof(int16_t), hipMemcpyDeviceToHost));
-      if (spp_n) HIP_CHECK(hipMemcpy(spp.data(), r.d_spp, spp_n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-      std::vector<uint32_t> spp_of(ncb, 0);
-      for (uint32_t i = 0; i < ncb; i++) spp_of[order[i]] = r.h_cbs_pinned[i].spp_off;
-      std::lock_guard<std::mutex> lk(tap_mtx);
-      if (ch.tapjobs.size() < ch.jobs.size()) ch.tapjobs.resize(ch.jobs.size());
-      for (uint32_t h = 0; h < njobs; h++) {
-        TapJob& t = ch.tapjobs[jid_of_hjob[h]];
-        t = TapJob{};
-        t.have = true; t.d = r.h_jobs[h];
-        for (int q = 0; q < 2; q++)
-          if (t.d.qm[q]) t.llr[q].assign(llr.begin() + t.d.llr_off[q], llr.begin() + t.d.llr_off[q] + (size_t)t.d.nof_re * t.d.qm[q]);
-      }
-      for (auto& tr : tbrefs)
-        for (uint32_t q = 0; q < tr.cb_count; q++) {
-          TapCb c;
-          c.cb = r.h_cbs[tr.cb_first + q]; c.tb = (uint32_t)tr.tb; c.res = r.h_cbres_pinned[tr.cb_first + q];
-          c.words.assign(spp.begin() + spp_of[tr.cb_first + q], spp.begin() + spp_of[tr.cb_first + q] + c.cb.K + 12);
-          ch.tapjobs[tr.job].cbs.push_back(std::move(c));
-        }
-    }
-    ch.h_payload.resize(pay_n);
-    if (pay_n > pay0) std::memcpy(ch.h_payload.data() + pay0, r.h_payload_pinned, pay_n - pay0);
-    // transport-block verdicts: every code block ok, CRC24A over data||parity zero (combined from the per-block
-    // remainders), parity word non-zero
-    for (auto& t : tbrefs) {
-      DecodeJob& j = ch.jobs[t.job];
-      TbVerdict v;
-      for (int q = (int)t.cb_count - 1; q >= 0; q--) {
-        const LsnCbRes& cr = r.h_cbres_pinned[t.cb_first + q];
-        v.add(cr.ok != 0, cr.rem_a, r.h_cbs[t.cb_first + q].out_bytes);
-        j.iters += cr.iters;
-        pf.nof_turbo_iterations += cr.iters; pf.nof_turbo_iterations_run += cr.iters_run;
-        pf.turbo_cyc_rm += cr.cyc_rm; pf.turbo_cyc_map += cr.cyc_map; pf.turbo_cyc_out += cr.cyc_out;
-      }
-      const int tbs = j.grant.tb[t.tb].tbs;
-      const uint8_t* pl = ch.h_payload.data() + j.payload_off[t.tb];
-      j.crc[t.tb] = v.pass(pl, tbs);
-      if (cfg.harq_mode) {  // per-block verdicts of this transmission, next to the kept soft data (harqStore / harqCombinedDecode)
-        if (ch.keep_res.size() < ch.keep_cbs.size()) ch.keep_res.resize(ch.keep_cbs.size());
-        for (uint32_t q = 0; q < t.cb_count && j.keep_count[t.tb] == t.cb_count; q++) ch.keep_res[j.keep_first[t.tb] + q] = r.h_cbres_pinned[t.cb_first + q];
-      }
-      JobRes& jr = ch.jres[t.job];
-      jr.crc[t.tb] = j.crc[t.tb] ? 1 : 0;
-      jr.payload_off[t.tb] = j.payload_off[t.tb];
-      // DL_Sniffer_PDSCH.cc:1041-1070: a decoded C-RNTI block is walked for RRCConnectionSetups - here, by the thread that ran the decode,
-      // so that the commit thread never touches the payload
-      if (j.crc[t.tb] && tbs >= 8 && cfg.sniffer_mode == 0 && rnti_name(j.rnti)[0] == 'C') {
-        UeSpecConfig sc[20];
-        const int n = MCSTracking::setups_of_pdu(pl, tbs / 8, sc, 20, true);   // every SDU: which of them count is the commit's decision (known-table branch: LCID 0 only)
-        if (n > 0) {
-          jr.setup_first[t.tb] = (uint32_t)ch.setup_cfgs.size();
-          jr.nsetup[t.tb] = (uint8_t)n;
-          ch.setup_cfgs.insert(ch.setup_cfgs.end(), sc, sc + n);
-        }
-      }
-    }
+    launchPerf(r, L);
+    if (keep_stage_c.load()) tapLaunch(ch, r, L);
+    takeVerdicts(ch, r, L);
   }
-  for (int jid : todo) { ch.jobs[jid].done = true; ch.jres[jid].done = 1; }
-  pf.nof_decode_jobs += todo.size();
+  for (int jid : L.todo) { ch.jobs[jid].done = true; ch.jres[jid].done = 1; }
+  r.perf.nof_decode_jobs += L.todo.size();
 }
 
 void Engine::ensureJob(Chunk& ch, JobRunner& r, int j)
@@ -1109,26 +1094,7 @@ void Engine::ageTrackingDatabase()
 void Engine::commitChunk(Chunk& ch, JobRunner& r)
 {
   std::vector<McsTable> tables;
-  if (cfg.harq_mode) {
-    // the retransmissions of this chunk, combined and decoded in a few batches ahead of the walk (harqScout): pass p serves the p-th retransmission in a row
-    // of the same buffer.  The scratch area is empty here (harqFlush of the previous turn): it may be given a new size
-    harq_scratch_n = 0;
-    const size_t want = std::min<size_t>(ch.keep_n + 4096, (size_t)(1u << 30) - 1);
-    if (want > harq_scratch_cap) grow_dev(d_harq_scratch, harq_scratch_cap, want, r.stream);
-    std::vector<HarqReq> reqs;
-    for (int pass = 0; pass < 8; pass++) {
-      const double t0 = now_ms();
-      harqScout(ch, reqs, pass == 0);
-      r.perf.ms_harq[0] += now_ms() - t0;
-      if (reqs.empty()) break;
-      size_t need = 0;
-      for (const HarqReq& q : reqs)
-        for (uint32_t b = 0; b < q.n; b++)
-          if (!q.ok[b]) need += LSN_SPP_WORDS(ch.keep_cbs[ch.jobs[q.job].keep_first[q.tb] + b].K);
-      if (harq_scratch_n + need > harq_scratch_cap) break;   // (what does not fit is decoded by the walk itself)
-      harqRunBatch(ch, r, reqs);
-    }
-  }
+  if (cfg.harq_mode) harqBatchAhead(ch, r);
   for (uint32_t sf = 0; sf < ch.nsf; sf++, commit_sf_cnt++) {
     SubframeCtx& c = ch.ctx[sf];
     // the tracking database is only WRITTEN here (commit thread); decode threads read the published prediction arrays, the API getter
@@ -1224,7 +1190,7 @@ void Engine::commitChunk(Chunk& ch, JobRunner& r)
               const HarqRet hr = harq_db.is_retransmission(d.rnti, e.dci.pid, tb, e.dci.tb[tb].ndi != 0, tbs, c.sfn, c.sf_idx, ent);
               const size_t slot = ent < 0 ? 0 : ((size_t)ent * HarqDatabase::NPID + (e.dci.pid & 7u)) * 2 + (size_t)tb;
               if (hr == HARQ_NEW_TX) {
-                if (!crc[tb]) harqStore(ch, r, j, tb, slot);   // srsran_softbuffer_rx_reset_tbs + this transmission (the buffer is only read again if the block failed)
+                if (!crc[tb]) harqStore(ch, j, tb, slot);   // srsran_softbuffer_rx_reset_tbs + this transmission (the buffer is only read again if the block failed)
               } else if (hr == HARQ_RE_TX) {
                 crc[tb] = harqCombinedDecode(ch, r, j, tb, slot, poff);
                 combined = true;
@@ -1287,340 +1253,6 @@ void Engine::commitChunk(Chunk& ch, JobRunner& r)
     r.perf.jobs_by_kind[k]++; r.perf.iters_by_kind[k] += j.iters;
     if (!j.used) { r.perf.jobs_unused_by_kind[k]++; r.perf.iters_unused_by_kind[k] += j.iters; }
   }
-}
-
-// ------------------------------------------------------------------------------------------------ HARQ soft buffers (harq_mode = 1)
-// Block q of the buffer of a (RNTI entity, process, transport block) has its home in the pool at slot * HARQ_SLOT_WORDS + q * HARQ_CB_WORDS.  Inside a commit
-// turn the content may lie elsewhere (HarqKeep::loc): a failed new transmission stays in the chunk's keep store, a combination in the turn's scratch area;
-// harqFlush brings everything home before the chunk (and with it the keep store) is recycled.  Round 6: retransmissions are combined and decoded in batches
-// ahead of the walk (lsn_engine.h: HarqReq) - rounds 4-5 paid one GPU round trip per retransmission inside the sequential turn.
-uint64_t Engine::harqMix(uint64_t a, uint64_t b, uint64_t c, uint64_t d)
-{
-  auto sm = [](uint64_t x) { x += 0x9E3779B97F4A7C15ull; x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull; x = (x ^ (x >> 27)) * 0x94D049BB133111EBull; return x ^ (x >> 31); };
-  return sm(sm(sm(sm(a) ^ b) ^ c) ^ d);
-}
-
-// The request a retransmission (job, block) makes when it meets a buffer in the state (ncb_have, ver, ok, loc) - the SAME function serves the walk and the
-// scout, so that equal states give equal keys.  A buffer without a first transmission on record for this geometry (ncb_have != n) is taken as it lies in
-// the pool, nothing passed (rounds 4-5: hk = HarqKeep{}); the pool does not change inside a turn, so (slot, n) names that content.  false: every block has
-// passed already, nothing to combine or decode.
-bool Engine::harqRequest(const Chunk& ch, int job, int tb, size_t slot, uint32_t n, uint32_t ncb_have, uint64_t ver, const uint8_t* ok, const uint32_t* loc, HarqReq& q) const
-{
-  (void)ch;
-  q = HarqReq{};
-  q.job = job; q.tb = tb; q.slot = slot; q.n = n;
-  uint64_t okmask = 0;
-  if (ncb_have != n) {
-    q.ver = harqMix(0x52455345u /* reset */, slot, n, 0);
-    for (uint32_t i = 0; i < n; i++) { q.ok[i] = 0; q.loc[i] = HARQ_LOC_POOL | (uint32_t)(slot * HARQ_SLOT_WORDS + i * HARQ_CB_WORDS); }
-  } else {
-    q.ver = ver;
-    for (uint32_t i = 0; i < n; i++) { q.ok[i] = ok[i] ? 1 : 0; q.loc[i] = loc[i]; okmask |= (uint64_t)(ok[i] ? 1 : 0) << i; }
-  }
-  q.key = harqMix(q.ver, ((uint64_t)(uint32_t)job << 1) | (uint64_t)(tb & 1), okmask, n);
-  return okmask != ((1ull << n) - 1ull);
-}
-
-void Engine::harqStore(Chunk& ch, JobRunner& r, int job, int tb, size_t slot)
-{
-  (void)r;
-  const DecodeJob& j = ch.jobs[job];
-  const uint32_t n = j.keep_count[tb];
-  if (!n || n > HARQ_MAX_CB) { harq_keep.erase(slot); return; }   // nothing stored for this transmission: what the slot held belongs to an older one and must not be combined with
-  // cb_crc / data of the soft buffer: what passed in this (failed) transmission is remembered, a retransmission decodes the other blocks only
-  HarqKeep& hk = harq_keep[slot];
-  hk.ncb = n;
-  hk.ver = harqMix(0x53544F52u /* store */, ch.gseq, (uint64_t)(uint32_t)job, (uint64_t)tb);
-  uint32_t boff = 0;
-  for (uint32_t q = 0; q < n; q++) {
-    const LsnCbDev& cb = ch.keep_cbs[j.keep_first[tb] + q];
-    const LsnCbRes cr = j.keep_first[tb] + q < ch.keep_res.size() ? ch.keep_res[j.keep_first[tb] + q] : LsnCbRes{};
-    hk.ok[q] = cr.ok ? 1 : 0; hk.rem_a[q] = cr.rem_a; hk.K[q] = cb.K;
-    const uint8_t* pb = ch.h_payload.data() + j.payload_off[tb] + boff;
-    hk.bytes[q].assign(pb, pb + cb.out_bytes);
-    boff += cb.out_bytes;
-    hk.loc[q] = HARQ_LOC_KEEP | cb.spp_off;   // this transmission, where it lies in the chunk's keep store: nothing reads it before a retransmission combines with it
-  }
-  harq_touched.push_back(slot);
-}
-
-// end of the commit turn: the blocks that do not lie at home go there in at most one launch (rounds 4 / early 5 paid an upload, a launch and a stream
-// synchronisation per failed transport block: 2.7 k subframes/s on the gated HARQ leg)
-void Engine::harqFlush(Chunk& ch, JobRunner& r)
-{
-  struct Timer { double t0, &acc; ~Timer() { acc += now_ms() - t0; } } timer{now_ms(), r.perf.ms_harq[2]};
-  std::vector<LsnCbDev> cp;
-  std::sort(harq_touched.begin(), harq_touched.end());
-  harq_touched.erase(std::unique(harq_touched.begin(), harq_touched.end()), harq_touched.end());
-  for (size_t slot : harq_touched) {
-    auto it = harq_keep.find(slot);
-    if (it == harq_keep.end()) continue;
-    HarqKeep& hk = it->second;
-    for (uint32_t q = 0; q < hk.ncb && q < HARQ_MAX_CB; q++) {
-      const uint32_t home = HARQ_LOC_POOL | (uint32_t)(slot * HARQ_SLOT_WORDS + q * HARQ_CB_WORDS);
-      if (hk.loc[q] == home) continue;
-      LsnCbDev cb{};
-      cb.K = hk.K[q]; cb.reserved = hk.loc[q]; cb.spp_off = home;
-      cp.push_back(cb);
-      hk.loc[q] = home;
-    }
-  }
-  harq_touched.clear();
-  for (auto& kv : harq_cache) if (!kv.second.used) r.perf.nof_harq_combines[3]++;
-  harq_cache.clear();
-  harq_scratch_n = 0;
-  (void)ch;
-  if (cp.empty()) return;
-  const uint32_t n = (uint32_t)cp.size();
-  grow_host(harq_h_store, harq_h_store_cap, n, r.stream);
-  grow_dev(harq_d_store, harq_d_store_cap, n, r.stream);
-  std::memcpy(harq_h_store, cp.data(), n * sizeof(LsnCbDev));
-  lsn_launch_upload(harq_d_store, harq_h_store, n * sizeof(LsnCbDev), r.stream);
-  lsn_launch_harq_combine(harq_d_store, n, ch.d_keep, d_harq_pool, d_harq_scratch, true, r.stream);
-  HIP_CHECK(hipStreamSynchronize(r.stream));   // the chunk's keep store is recycled with the chunk
-}
-
-// combine + decode a batch of requests: one descriptor upload, one combination launch, one decoder launch per wavefront class, one download, one wait
-void Engine::harqRunBatch(Chunk& ch, JobRunner& r, const std::vector<HarqReq>& reqs)
-{
-  if (reqs.empty()) return;
-  struct Timer { double t0, &acc; ~Timer() { acc += now_ms() - t0; } } timer{now_ms(), r.perf.ms_harq[1]};
-  hipStream_t st = r.stream;
-  struct Ref { uint32_t req, q, out; };
-  std::vector<LsnCbDev> cbs;
-  std::vector<Ref> refs;
-  uint32_t out = 0;
-  size_t words = harq_scratch_n;
-  for (uint32_t i = 0; i < reqs.size(); i++) {
-    const HarqReq& q = reqs[i];
-    const DecodeJob& j = ch.jobs[q.job];
-    for (uint32_t b = 0; b < q.n; b++) {
-      if (q.ok[b]) continue;   // srsRAN: if (!softbuffer->cb_crc[cb_idx]) { rate de-matching into the buffer, decoding } - a passed block is left alone
-      LsnCbDev cb = ch.keep_cbs[j.keep_first[q.tb] + b];
-      cb.e_off = cb.spp_off;                       // this transmission, in the chunk's keep store
-      cb.reserved = q.loc[b];                      // what the buffer holds, wherever it lies
-      cb.spp_off = (uint32_t)words; words += LSN_SPP_WORDS(cb.K);
-      cb.res_idx = (uint32_t)cbs.size(); cb.dep = LSN_CB_NODEP; cb.out_off = out;
-      refs.push_back({i, b, out});
-      out += cb.out_bytes;
-      cbs.push_back(cb);
-    }
-  }
-  const uint32_t nd = (uint32_t)cbs.size();
-  if (!nd) return;
-  if (words > harq_scratch_cap || words >= (1u << 30)) throw std::runtime_error("HARQ scratch area exhausted");   // (sized by the caller: harqEnsureScratch)
-  harq_scratch_n = words;
-  grow_host(r.h_cbs_pinned, r.h_cbs_cap, nd, st);
-  grow_dev(r.d_cbs, r.cbs_cap, nd, st);
-  if (nd > r.cbres_cap) grow_dev(r.d_cbres, r.cbres_cap, nd, st);
-  grow_host(r.h_cbres_pinned, r.h_cbres_cap, nd, st);
-  grow_dev(r.d_payload, r.payload_cap, (size_t)out + 16, st);
-  grow_host(r.h_payload_pinned, r.h_payload_cap, (size_t)out + 16, st);
-  // launch order: two-wavefront class first, each class by descending size (the longest first); results stay addressable through res_idx
-  const TurboOrder to = turbo_classic_order(cbs);
-  for (uint32_t i = 0; i < nd; i++) r.h_cbs_pinned[i] = cbs[to.order[i]];
-  lsn_launch_upload(r.d_cbs, r.h_cbs_pinned, nd * sizeof(LsnCbDev), st);
-  lsn_launch_harq_combine(r.d_cbs, nd, ch.d_keep, d_harq_pool, d_harq_scratch, false, st);
-  lsn_launch_turbo(cd, r.d_cbs, d_harq_scratch, r.d_payload, r.d_cbres, to.n128, to.kmax128, nd - to.n128, to.kmax64, st);
-  {
-    LsnCopySegs dn;   // verdicts + payload bytes down in one launch
-    dn.add(r.h_cbres_pinned, r.d_cbres, nd * sizeof(LsnCbRes));
-    dn.add(r.h_payload_pinned, r.d_payload, out);
-    lsn_launch_copy_multi(dn, true, st);
-  }
-  HIP_CHECK(hipEventRecord(r.ev_done, st));
-  waitEvent(r.ev_done, 3000);   // inside the sequential commit turn: short naps (the decode threads' waits are milliseconds long and nap 50 us)
-  r.perf.nof_harq_combines[0]++;
-  for (uint32_t i = 0; i < reqs.size(); i++) { HarqDone& d = harq_cache[reqs[i].key]; d = HarqDone{}; d.req = reqs[i]; }
-  for (uint32_t k = 0; k < nd; k++) {
-    const Ref& f = refs[k];
-    HarqDone& d = harq_cache[reqs[f.req].key];
-    const LsnCbRes& cr = r.h_cbres_pinned[k];   // (res_idx = k: the index before sorting)
-    d.ok[f.q] = cr.ok ? 1 : 0; d.rem_a[f.q] = cr.rem_a; d.iters[f.q] = cr.iters;
-    d.loc[f.q] = HARQ_LOC_SCRATCH | cbs[k].spp_off;
-    d.bytes[f.q].assign(r.h_payload_pinned + f.out, r.h_payload_pinned + f.out + cbs[k].out_bytes);
-  }
-}
-
-// The combined decodes the walk over this chunk will probably ask for, as far as their inputs are known now: the walk's HARQ decisions (commitChunk,
-// known-table branch) replayed on COPIES of the process database and of the touched buffers' states, with the tables, jobs and p-a values as they stand at
-// the start of the turn.  A retransmission whose result is in harq_cache continues its buffer's chain; one without becomes a request, and the chain of that
-// buffer stops for this pass (its later retransmissions need the result first).  Nothing but speed depends on how well this guesses: the walk makes its own
-// requests and takes a result only under the key of exactly its inputs.
-void Engine::harqScout(Chunk& ch, std::vector<HarqReq>& out, bool first_pass)
-{
-  out.clear();
-  struct View { uint32_t ncb = 0; uint8_t ok[16] = {}; uint32_t rem_a[16] = {}, loc[16] = {}; uint64_t ver = 0; bool pending = false; };
-  std::unordered_map<size_t, View> ov;
-  auto view = [&](size_t slot) -> View& {
-    auto it = ov.find(slot);
-    if (it != ov.end()) return it->second;
-    View v;
-    auto k = harq_keep.find(slot);
-    if (k != harq_keep.end()) {
-      v.ncb = k->second.ncb; v.ver = k->second.ver;
-      for (int q = 0; q < 16; q++) { v.ok[q] = k->second.ok[q]; v.rem_a[q] = k->second.rem_a[q]; v.loc[q] = k->second.loc[q]; }
-    }
-    return ov.emplace(slot, v).first->second;
-  };
-  // The transport blocks the walk will put to the process database, in walk order (tables, jobs and p-a values as they stand at the start of the turn: the
-  // same in every pass of this turn, so the list is made by the first pass and replayed by the others).  job < 0: the database's 10 s timer.
-  if (first_pass) {
-    harq_events.clear();
-    uint32_t cnt = commit_sf_cnt;
-    for (uint32_t sf = 0; sf < ch.nsf; sf++, cnt++) {
-      const SubframeCtx& c = ch.ctx[sf];
-      if (cnt && (cnt % 10000u) == 0) { HarqEvent ev; ev.job = -1; ev.now = cnt; harq_events.push_back(ev); }
-      if (!c.searched) continue;
-      for (uint32_t k = ch.cdci_first[sf]; k < ch.cdci_first[sf + 1]; k++) {
-        const CommitDci& d = ch.cdci[k];
-        const char* name = rnti_name(d.rnti);
-        if (name[0] != 'C') continue;
-        McsTable table = TABLE_64QAM;
-        if (cfg.mcs_tracking_mode == 1) table = (DciFormat)d.format == FORMAT1A ? TABLE_64QAM : mcs_tracking.peek(d.rnti);
-        else if (cfg.mcs_tracking_mode == 2) table = TABLE_UNKNOWN;
-        if (!(table == TABLE_64QAM || table == TABLE_256QAM)) continue;
-        const TableView tv = table_view(table, d.rnti, d.flags & 1, d.flags & 2, d.flags & 4);
-        const DlEntry& e = c.dl[d.di];
-        if (table == TABLE_64QAM && e.unpack_ok && ((e.grant64.tb[0].enabled && e.grant64.tb[0].mcs_idx > 28) || (e.grant64.tb[1].enabled && e.grant64.tb[1].mcs_idx > 28)))
-          continue;   // (a reserved MCS index takes its size from the database at commit and is decoded there)
-        const int cur_t = table == TABLE_256QAM ? 1 : 0;
-        const bool cur_has = cur_t ? tv.has256 : tv.has64;
-        const int32_t cur_tbs0 = cur_has ? (cur_t ? d.tbs0_256 : d.tbs0_64) : 0;
-        const bool two_tb = (tv.has64 && (d.flags & 8)) || (tv.has256 && (d.flags & 16));
-        if (!(cur_tbs0 > 0 && tv.dci_rnti_ok && !(dlRx() == 1 && two_tb))) continue;
-        const int j = d.job[cur_t];
-        if (!cur_has || j < 0 || !ch.jres[j].done || ch.jres[j].p_a != mcs_tracking.get_ue_config_rnti(d.rnti).p_a) continue;
-        const JobRes& jr = ch.jres[j];
-        for (int tb = 0; tb < 2; tb++) {
-          if (!jr.enabled[tb]) continue;
-          HarqEvent ev;
-          ev.job = j; ev.now = cnt; ev.sfn = c.sfn; ev.sf_idx = c.sf_idx; ev.rnti = d.rnti; ev.pid = (uint8_t)e.dci.pid; ev.tb = (uint8_t)tb;
-          ev.ndi = e.dci.tb[tb].ndi != 0; ev.rv = (uint8_t)e.dci.tb[tb].rv; ev.tbs = ch.jobs[j].grant.tb[tb].tbs; ev.crc = jr.crc[tb] != 0; ev.n = ch.jobs[j].keep_count[tb];
-          harq_events.push_back(ev);
-        }
-      }
-    }
-  }
-  HarqDatabase db = harq_db;
-  for (const HarqEvent& ev : harq_events) {
-    if (ev.job < 0) { db.update_database(ev.now); continue; }
-    const int j = ev.job, tb = ev.tb;
-    int ent = -1;
-    const HarqRet hr = db.is_retransmission(ev.rnti, ev.pid, tb, ev.ndi, ev.tbs, ev.sfn, ev.sf_idx, ent);
-    const size_t slot = ent < 0 ? 0 : ((size_t)ent * HarqDatabase::NPID + (ev.pid & 7u)) * 2 + (size_t)tb;
-    bool crc = ev.crc;
-    const uint32_t n = ev.n;
-    if (hr == HARQ_NEW_TX) {
-      if (!crc) {
-        View& v = view(slot);
-        v = View{};
-        if (n && n <= HARQ_MAX_CB) {
-          v.ncb = n; v.ver = harqMix(0x53544F52u, ch.gseq, (uint64_t)(uint32_t)j, (uint64_t)tb);
-          for (uint32_t q = 0; q < n; q++) {
-            const size_t ki = ch.jobs[j].keep_first[tb] + q;
-            const LsnCbRes cr = ki < ch.keep_res.size() ? ch.keep_res[ki] : LsnCbRes{};
-            v.ok[q] = cr.ok ? 1 : 0; v.rem_a[q] = cr.rem_a; v.loc[q] = HARQ_LOC_KEEP | ch.keep_cbs[ki].spp_off;
-          }
-        }
-      }
-    } else if (hr == HARQ_RE_TX) {
-      crc = false;
-      if (n && n <= HARQ_MAX_CB) {
-        View& v = view(slot);
-        if (!v.pending) {
-          HarqReq q;
-          const bool work = harqRequest(ch, j, tb, slot, n, v.ncb, v.ver, v.ok, v.loc, q);
-          if (v.ncb != n) { v = View{}; v.ncb = n; v.ver = q.ver; for (uint32_t b = 0; b < n; b++) v.loc[b] = q.loc[b]; }
-          bool have = true;
-          if (work) {
-            auto it = harq_cache.find(q.key);
-            if (it == harq_cache.end()) { out.push_back(q); v.pending = true; have = false; }
-            else {
-              const HarqDone& dn = it->second;
-              for (uint32_t b = 0; b < n; b++)
-                if (!v.ok[b]) { v.rem_a[b] = dn.rem_a[b]; v.loc[b] = dn.loc[b]; v.ok[b] = dn.ok[b]; }
-              v.ver = q.key;
-            }
-          }
-          if (have) {  // the verdict as far as the scout can tell (every block passed, CRC24A over the blocks; the parity-word and length tests are the walk's)
-            TbVerdict tv;
-            for (int b = (int)n - 1; b >= 0; b--) tv.add(v.ok[b] != 0, v.rem_a[b], ch.keep_cbs[ch.jobs[j].keep_first[tb] + b].out_bytes);
-            crc = tv.all_ok && tv.rem == 0;
-          }
-        }
-      }
-    } else if (hr == HARQ_DECODED) {
-      crc = false;
-    }
-    if (hr == HARQ_NEW_TX || hr == HARQ_RE_TX) db.update(ent, ev.pid, tb, ev.sfn, ev.sf_idx, crc, ev.ndi, ev.rv, ev.tbs, ev.now);
-  }
-}
-
-bool Engine::harqCombinedDecode(Chunk& ch, JobRunner& r, int job, int tb, size_t slot, uint32_t& payload_off)
-{
-  const DecodeJob& j = ch.jobs[job];
-  const uint32_t n = j.keep_count[tb];
-  if (!n || n > HARQ_MAX_CB) return false;
-  HarqKeep& hk = harq_keep[slot];
-  HarqReq q;
-  const bool work = harqRequest(ch, job, tb, slot, n, hk.ncb, hk.ver, hk.ok, hk.loc, q);
-  if (hk.ncb != n) {  // (no first transmission on record for this geometry: nothing passed before)
-    hk = HarqKeep{};
-    hk.ncb = n; hk.ver = q.ver;
-    for (uint32_t b = 0; b < n; b++) hk.loc[b] = q.loc[b];
-  }
-  for (uint32_t b = 0; b < n; b++) hk.K[b] = ch.keep_cbs[j.keep_first[tb] + b].K;
-  const HarqDone* dn = nullptr;
-  if (work) {
-    auto it = harq_cache.find(q.key);
-    if (it != harq_cache.end() && !(it->second.req.ver == q.ver && it->second.req.job == job && it->second.req.tb == tb && it->second.req.n == n && std::memcmp(it->second.req.ok, q.ok, 16) == 0)) it = harq_cache.end();  // (a hash collision)
-    if (it == harq_cache.end()) {
-      // not foreseen by the scout: decoded now, alone (a round trip inside the turn, as every retransmission was in rounds 4-5)
-      size_t need = 0;
-      for (uint32_t b = 0; b < n; b++) if (!q.ok[b]) need += LSN_SPP_WORDS(hk.K[b]);
-      if (harq_scratch_n + need > harq_scratch_cap) {  // scratch area full: everything goes home first (the unused results of the batches are lost with it)
-        harqFlush(ch, r);
-        harqRequest(ch, job, tb, slot, n, hk.ncb, hk.ver, hk.ok, hk.loc, q);
-        if (need > harq_scratch_cap) { HIP_CHECK(hipStreamSynchronize(r.stream)); grow_dev(d_harq_scratch, harq_scratch_cap, need, r.stream); }
-      }
-      std::vector<HarqReq> one{q};
-      harqRunBatch(ch, r, one);
-      r.perf.nof_harq_combines[2]++;
-      r.perf.nof_ondemand_decodes++;
-      it = harq_cache.find(q.key);
-    } else {
-      r.perf.nof_harq_combines[1]++;
-    }
-    it->second.used = true;
-    dn = &it->second;
-    for (uint32_t b = 0; b < n; b++) {
-      if (hk.ok[b]) continue;
-      r.perf.nof_turbo_iterations += dn->iters[b];
-      hk.rem_a[b] = dn->rem_a[b];
-      hk.bytes[b] = dn->bytes[b];
-      hk.loc[b] = dn->loc[b];
-      // (ok is set below, after the verdict of THIS pass has been taken)
-    }
-    hk.ver = q.key;
-    harq_touched.push_back(slot);
-  }
-  // transport-block verdict, as in runJobs: every block passed (now or in an earlier transmission), CRC24A over the assembled blocks
-  TbVerdict v;
-  uint32_t total = 0;
-  for (int b = (int)n - 1; b >= 0; b--) v.add(hk.ok[b] || (dn && dn->ok[b] != 0), hk.rem_a[b], ch.keep_cbs[j.keep_first[tb] + b].out_bytes);
-  for (uint32_t b = 0; b < n; b++) total += (uint32_t)hk.bytes[b].size();
-  const int tbs = j.grant.tb[tb].tbs;
-  payload_off = (uint32_t)ch.h_payload.size();
-  ch.h_payload.resize(ch.h_payload.size() + (((size_t)total + 15) & ~(size_t)15));
-  {
-    uint8_t* dst = ch.h_payload.data() + payload_off;
-    for (uint32_t b = 0; b < n; b++) { std::memcpy(dst, hk.bytes[b].data(), hk.bytes[b].size()); dst += hk.bytes[b].size(); }
-  }
-  for (uint32_t b = 0; b < n; b++)
-    if (!hk.ok[b] && dn && dn->ok[b]) hk.ok[b] = 1;
-  if ((uint64_t)total * 8ull < (uint64_t)tbs + 24ull) return false;   // (the bytes on record are fewer than the block: no parity word to read)
-  return v.pass(ch.h_payload.data() + payload_off, tbs);
 }
 
 // decode threads: each takes the next chunk of the queue, plans and runs its PDSCH decodes on its own streams and hands the chunk

@@ -157,6 +157,20 @@ struct JobRunner {
   lsn_perf_t perf{};
 };
 
+// What one decode launch (Engine::runJobs) carries from step to step; the descriptors themselves are the runner's (h_jobs, h_cbs, h_items).
+struct DecodeLaunch {
+  struct TbRef { int job, tb; uint32_t cb_first, cb_count; };
+  std::vector<int> todo;             // the jobs of this launch
+  std::vector<TbRef> tbrefs;         // their transport blocks: code blocks [cb_first, cb_first + cb_count) of h_cbs
+  std::vector<int> jid_of_hjob;      // the job behind each descriptor of h_jobs (a job that cannot be demodulated has none)
+  uint32_t njobs = 0, ncb = 0, nitems = 0;
+  size_t llr_n = 0, prefix_n = 0, pay0 = 0, pay_n = 0;   // arena sizes; this launch's payload bytes are Chunk::h_payload[pay0, pay_n)
+  TurboPackedOrder ord;              // launch order of the code blocks ...
+  TurboPlacement place;              // ... and where their soft data lies in d_spp
+  bool timed = false;                // prep / demod / rm carry timing events (every Engine::timing_period-th launch of a runner)
+};
+void waitEvent(hipEvent_t ev, long nap_ns = 50000);   // host wait for a pipeline event (lsn_engine.cc)
+
 // one entry of the ULSchedule databases (ULSchedule.cc:11-138): a DCI 0 / RAR grant waiting for its PUSCH subframe
 struct UlSchedGrant { uint16_t rnti = 0; PuschGrant g, g256; uint32_t n_dmrs = 0; bool hopping = false, is_rar = false; uint32_t nof_ack = 0; bool cqi_req = false; };
 
@@ -323,6 +337,15 @@ private:
   void planJobs(Chunk& ch, JobRunner& r);
   void buildCommitView(Chunk& ch);
   void runJobs(Chunk& ch, JobRunner& r, std::vector<int>& job_ids);
+  // the steps of runJobs, in order (harqKeepSoftData, below, sits between the launches and the wait; harqKeepResults inside takeVerdicts)
+  bool pdschGrantDev(const DecodeJob& j, const SubframeCtx& c, LsnGrantDev& d, bool derived_tbs[2], uint64_t algo_bytes[2]) const;  // false: srsran_pdsch_decode would refuse the grant
+  void packJobs(Chunk& ch, JobRunner& r, DecodeLaunch& L);            // jobs -> grant descriptors, code blocks, demodulator work items
+  void growLaunchArenas(JobRunner& r, const DecodeLaunch& L);
+  void orderAndPlace(JobRunner& r, DecodeLaunch& L);                  // code blocks in launch order into the pinned mirror, each with its place in d_spp
+  void launchDecode(Chunk& ch, JobRunner& r, const DecodeLaunch& L);  // upload + prep, demodulation, rate de-matching, the decoder phases, results down
+  void launchPerf(JobRunner& r, const DecodeLaunch& L);
+  void tapLaunch(Chunk& ch, JobRunner& r, const DecodeLaunch& L);     // stage-C taps: the arenas are recycled by the next launch of this runner
+  void takeVerdicts(Chunk& ch, JobRunner& r, const DecodeLaunch& L);  // payload bytes, transport-block verdicts, RRCConnectionSetups of the passed blocks
   void ensureJob(Chunk& ch, JobRunner& r, int j);
   void commitChunk(Chunk& ch, JobRunner& r);
   void commitChunkUl(Chunk& ch, JobRunner& r);
@@ -352,8 +375,11 @@ private:
   uint32_t* d_harq_scratch = nullptr; size_t harq_scratch_cap = 0, harq_scratch_n = 0;
   LsnCbDev *harq_h_store = nullptr, *harq_d_store = nullptr; size_t harq_h_store_cap = 0, harq_d_store_cap = 0;   // descriptors of the end-of-turn copies
   static uint64_t harqMix(uint64_t a, uint64_t b, uint64_t c, uint64_t d);
-  bool harqRequest(const Chunk& ch, int job, int tb, size_t slot, uint32_t n, uint32_t ncb_have, uint64_t ver, const uint8_t* ok, const uint32_t* loc, HarqReq& q) const;
-  void harqStore(Chunk& ch, JobRunner& r, int job, int tb, size_t slot);                       // a failed new transmission becomes the buffer's content (it stays in the keep store until harqFlush)
+  bool harqRequest(int job, int tb, size_t slot, uint32_t n, uint32_t ncb_have, uint64_t ver, const uint8_t* ok, const uint32_t* loc, HarqReq& q) const;
+  void harqKeepSoftData(Chunk& ch, JobRunner& r, const DecodeLaunch& L);                        // runJobs: the soft data of a launch goes to the chunk's keep store (queued behind the decoders)
+  void harqKeepResults(Chunk& ch, JobRunner& r, const DecodeLaunch::TbRef& t);                  // ... and the per-block verdicts of one of its transport blocks next to it
+  void harqBatchAhead(Chunk& ch, JobRunner& r);                                                  // start of the turn: the chunk's retransmissions in up to 8 batches (harqScout / harqRunBatch)
+  void harqStore(Chunk& ch, int job, int tb, size_t slot);                                      // a failed new transmission becomes the buffer's content (it stays in the keep store until harqFlush)
   void harqFlush(Chunk& ch, JobRunner& r);                                                       // end of the turn: every touched buffer into the pool
   struct HarqEvent { int job = -1; uint32_t now = 0, sfn = 0, sf_idx = 0, n = 0; int tbs = 0; uint16_t rnti = 0; uint8_t pid = 0, tb = 0, rv = 0; bool ndi = false, crc = false; };
   std::vector<HarqEvent> harq_events;   // harqScout: the transport blocks of the chunk in commit that go to the process database

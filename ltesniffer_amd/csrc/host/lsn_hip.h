@@ -22,6 +22,14 @@ inline double now_ms()
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
+// adds the milliseconds its scope took to acc
+struct ScopeTimer {
+  explicit ScopeTimer(double& a) : t0(now_ms()), acc(a) {}
+  ~ScopeTimer() { acc += now_ms() - t0; }
+  const double t0;
+  double& acc;
+};
+
 // entry guard of the calls that report through a return code: an exception on the way becomes one line on stderr and LSN_ERROR
 template <class F>
 int guarded(F&& f)

@@ -628,6 +628,7 @@ uint32_t tb_code_blocks(const CbSegm& s, int G, int Qm, int NL, int rv, uint32_t
     cb.il_off = turbo_il_offset(K);
     cb.nwin = turbo_nwin(K);
     cb.max_iter = max_iter;
+    cb.res_idx = (uint32_t)cbs.size();
     cb.dep = (q > 0 && dep_first) ? first : LSN_CB_NODEP;
     wp += cb.out_bytes;
     rp += E;
@@ -650,6 +651,39 @@ TurboOrder turbo_classic_order(const std::vector<LsnCbDev>& cbs)
   for (const LsnCbDev& c : cbs)
     if (lsn_turbo_two_wave_class((int)c.K)) { o.n128++; o.kmax128 = std::max(o.kmax128, c.K); } else o.kmax64 = std::max(o.kmax64, c.K);
   return o;
+}
+TurboPackedOrder turbo_packed_order(const std::vector<LsnCbDev>& cbs)
+{
+  // The key (phase, solo before paired, K descending) has 2 x 2 x 6 145 values and equal keys keep ascending index: a stable counting sort - the comparison sort
+  // this replaces cost 1.5 us of decode-thread CPU per subframe (round 6, thread-CPU sections)
+  constexpr uint32_t NK = LSN_TURBO_KMAX + 1, NKEYS = 2 * 2 * NK;
+  TurboPackedOrder o;
+  const uint32_t n = (uint32_t)cbs.size();
+  o.order.resize(n);
+  static thread_local std::vector<uint32_t> cnt;   // cnt[key + 1]: blocks of that key, then the first place of the next key
+  cnt.assign(NKEYS + 1, 0);
+  auto phase = [](const LsnCbDev& c) { return c.dep != LSN_CB_NODEP ? 1u : 0u; };
+  auto key = [&](const LsnCbDev& c) { return (phase(c) * 2u + (turbo_pairable(c.K) ? 1u : 0u)) * NK + (LSN_TURBO_KMAX - std::min(c.K, LSN_TURBO_KMAX)); };
+  for (const LsnCbDev& c : cbs) {
+    cnt[key(c) + 1]++;
+    if (turbo_pairable(c.K)) { o.npair[phase(c)]++; o.kmax_pair = std::max(o.kmax_pair, c.K); } else { o.nsolo[phase(c)]++; o.kmax_solo = std::max(o.kmax_solo, c.K); }
+  }
+  for (uint32_t k = 1; k <= NKEYS; k++) cnt[k] += cnt[k - 1];
+  for (uint32_t i = 0; i < n; i++) o.order[cnt[key(cbs[i])]++] = i;
+  return o;
+}
+TurboPlacement turbo_place(const std::vector<LsnCbDev>& cbs, const std::vector<uint32_t>& order, uint32_t spp_base, LsnCbDev* dst)
+{
+  TurboPlacement p;
+  p.spp_of.resize(cbs.size());
+  for (size_t i = 0; i < order.size(); i++) {
+    LsnCbDev q = cbs[order[i]];
+    q.spp_off = p.spp_of[order[i]] = spp_base + (uint32_t)p.spp_n;
+    p.spp_n += LSN_SPP_WORDS(q.K);
+    p.emax = std::max(p.emax, q.E);
+    dst[i] = q;
+  }
+  return p;
 }
 uint32_t turbo_il_offset(int K)
 {

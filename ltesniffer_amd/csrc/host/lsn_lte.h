@@ -104,12 +104,26 @@ uint32_t turbo_il_offset(int K);  // word offset of block size K in the interlea
 // Code-block descriptors of one transport block (36.212 5.1.2 segmentation s, 5.1.4.1.2 split of its G rate-matched bits: Qm bits per symbol, NL = 2 with
 // transmit diversity, else 1), appended to cbs.  Block q reads its E soft values from LLR offset e_off + (the E of the blocks before it) and writes its payload
 // bytes behind out_off, the blocks back to back.  dep_first: blocks 1 .. C-1 may be skipped once block 0 of this transport block has failed (LsnCbDev::dep =
-// its index in cbs); otherwise every block is always decoded.  Returns the payload bytes of the transport block, padded to a multiple of 16.
+// its index in cbs); otherwise every block is always decoded.  A block's verdict goes to the slot of its index in cbs (res_idx), whatever the launch order.
+// Returns the payload bytes of the transport block, padded to a multiple of 16.
 uint32_t tb_code_blocks(const CbSegm& s, int G, int Qm, int NL, int rv, uint32_t max_iter, uint32_t e_off, uint32_t out_off, bool dep_first, std::vector<LsnCbDev>& cbs);
 // Launch order of the classic decoder form (lsn_launch_turbo: uplink, HARQ re-decodes): the two-wavefront class first, each class by descending K (the longest
 // first), equal sizes by ascending index.  n128 = blocks of the two-wavefront class, kmax* = the largest K of each class.
 struct TurboOrder { std::vector<uint32_t> order; uint32_t n128 = 0, kmax128 = 0, kmax64 = 0; };
 TurboOrder turbo_classic_order(const std::vector<LsnCbDev>& cbs);
+// Launch order of the packed decoder form (lsn_launch_turbo_packed: the downlink), the order in which k_turbo sees its blocks.  Two phases: first every block
+// that nothing depends on having passed (dep == LSN_CB_NODEP: block 0 of each transport block), then the dependants.  Per phase the blocks that get a workgroup
+// of their own, then the ones that share one two by two (turbo_pairable: at most one working wavefront and half of an LDS slot); each class by descending K (the
+// longest first; the two blocks of a pair are neighbours in size), equal sizes by ascending index.  nsolo / npair = blocks of each class per phase, kmax_* =
+// the largest K of each class over both phases.
+constexpr uint32_t LSN_TURBO_KMAX = 6144u;   // the largest turbo code block (36.212 Table 5.1.3-3)
+inline bool turbo_pairable(uint32_t K) { return K <= LSN_TURBO_PAIR_KMAX && turbo_nwin((int)K) <= 64; }
+struct TurboPackedOrder { std::vector<uint32_t> order; uint32_t nsolo[2] = {0, 0}, npair[2] = {0, 0}, kmax_solo = 0, kmax_pair = 0; };
+TurboPackedOrder turbo_packed_order(const std::vector<LsnCbDev>& cbs);
+// The blocks in launch order with their place in the soft-data arena (k_rm -> k_turbo): dst[i] = cbs[order[i]] with spp_off = spp_base + the LSN_SPP_WORDS of
+// the blocks launched before it.  spp_n = words taken, emax = the largest E, spp_of[q] = the spp_off block q of cbs was given.
+struct TurboPlacement { size_t spp_n = 0; uint32_t emax = 0; std::vector<uint32_t> spp_of; };
+TurboPlacement turbo_place(const std::vector<LsnCbDev>& cbs, const std::vector<uint32_t>& order, uint32_t spp_base, LsnCbDev* dst);
 
 // ---- Histogram / RNTIManager ----
 class Histogram {
@@ -343,5 +357,13 @@ struct TbVerdict {
 private:
   uint32_t shift = 1;        // x^bits_after mod g, carried along: two multiplications per block instead of a modular power
 };
+// ... of the n code blocks of one transport block as one decode launch left them: res[q] and cbs[q] of block q.  iters = the blocks' iteration counts, summed
+struct TbResult { TbVerdict v; uint32_t iters = 0; };
+inline TbResult tb_verdict(const LsnCbRes* res, const LsnCbDev* cbs, uint32_t n)
+{
+  TbResult t;
+  for (int q = (int)n - 1; q >= 0; q--) { t.v.add(res[q].ok != 0, res[q].rem_a, cbs[q].out_bytes); t.iters += res[q].iters; }
+  return t;
+}
 
 }  // namespace lsn

@@ -51,6 +51,8 @@ struct LsnCbDev {
 };
 #define LSN_SPP_WORDS(K) (((K) + 12u + 3u) & ~3u)
 #define LSN_CB_NODEP 0xFFFFFFFFu   // LsnCbDev::dep: always decode
+// largest code block two of which share one decoder workgroup (one wavefront and half of the LDS slot each): 2 x (6 K + 16 + 3584) <= 40 960 = a quarter of the CU's LDS
+#define LSN_TURBO_PAIR_KMAX 2752u
 struct LsnCbRes { uint32_t ok, iters, rem_a, iters_run; uint32_t cyc_rm, cyc_map, cyc_out, cyc_all; };  // cyc_*: shader cycles per phase (s_memtime)
 
 // ---- ingest (host only, HIP-free)

@@ -260,27 +260,19 @@ void Engine::puschDecodeGrid(const cf32* d_grid, uint32_t nsf, uint32_t start_tt
   grow_dev(r.d_cbs, r.cbs_cap, ncb, st);
   grow_dev(r.d_cbres, r.cbres_cap, ncb, st);
   grow_dev(r.d_payload, r.payload_cap, pay_n + 16, st);
-  for (uint32_t i = 0; i < ncb; i++) r.h_cbs[i].res_idx = i;
   const TurboOrder to = turbo_classic_order(r.h_cbs);
   // descriptors go through pinned mirrors and the upload kernel, not through the host -> device copy engine (its FIFO may hold IQ blocks, lsn_dev.h)
   grow_host(ul_h_grants, ul_h_grants_cap, ng, st);
   grow_host(r.h_cbs_pinned, r.h_cbs_cap, ncb, st);
-  size_t spp_n = 0;
-  uint32_t emax = 0;
-  for (uint32_t i = 0; i < ncb; i++) {
-    LsnCbDev& cb = r.h_cbs_pinned[i];
-    cb = r.h_cbs[to.order[i]];
-    cb.spp_off = (uint32_t)spp_n; spp_n += LSN_SPP_WORDS(cb.K);
-    emax = std::max(emax, cb.E);
-  }
-  grow_dev(r.d_spp, r.spp_cap, spp_n + 16, st);
+  const TurboPlacement place = turbo_place(r.h_cbs, to.order, 0, r.h_cbs_pinned);
+  grow_dev(r.d_spp, r.spp_cap, place.spp_n + 16, st);
   std::memcpy(ul_h_grants, gd.data(), ng * sizeof(LsnUlGrantDev));
   lsn_launch_upload(ul_d_grants, ul_h_grants, ng * sizeof(LsnUlGrantDev), st);
   lsn_launch_upload(r.d_cbs, r.h_cbs_pinned, ncb * sizeof(LsnCbDev), st);
   HIP_CHECK(hipMemsetAsync(r.d_llr16, 0, llr_n * sizeof(int16_t), st));
   lsn_launch_pusch_chest(cd, ul_d_grants, d_grid, ul_d_hs, ul_d_stat, ng, st);
   lsn_launch_pusch_demod(cd, ul_d_grants, d_grid, ul_d_hs, ul_d_stat, r.d_llr16, ng, st);
-  lsn_launch_rm(r.d_cbs, r.d_llr16, r.d_spp, ncb, emax, st);
+  lsn_launch_rm(r.d_cbs, r.d_llr16, r.d_spp, ncb, place.emax, st);
   lsn_launch_turbo(cd, r.d_cbs, r.d_spp, r.d_payload, r.d_cbres, to.n128, to.kmax128, ncb - to.n128, to.kmax64, st);
   // results come back through pinned mirrors written by the copy kernel (lsn_dev.h), not through the copy engine
   grow_host(r.h_cbres_pinned, r.h_cbres_cap, ncb, st);
@@ -295,17 +287,11 @@ void Engine::puschDecodeGrid(const cf32* d_grid, uint32_t nsf, uint32_t start_tt
   const float* stat = ul_h_stat;
   for (size_t t = 0; t < tbs.size(); t++) {
     const TbRef& ref = tbs[t];
-    TbVerdict v;
-    uint32_t iters = 0;
-    for (int q = (int)ref.cb_count - 1; q >= 0; q--) {
-      const LsnCbRes& cr = cbres[ref.cb_first + q];
-      v.add(cr.ok != 0, cr.rem_a, r.h_cbs[ref.cb_first + q].out_bytes);
-      iters += cr.iters;
-    }
+    const TbResult tr = tb_verdict(cbres + ref.cb_first, r.h_cbs.data() + ref.cb_first, ref.cb_count);
     const uint8_t* pl = pay_base + ref.pay_off;
     lsn_pusch_result_t& res = results[ref.grant];
-    res.crc_ok = v.pass(pl, ref.tbs);
-    res.iterations = iters;
+    res.crc_ok = tr.v.pass(pl, ref.tbs);
+    res.iterations = tr.iters;
     res.snr_db = 10.0f * log10f(stat[2 * t + 1] / stat[2 * t]);
     res.payload_off = (uint32_t)payload_out.size();
     payload_out.insert(payload_out.end(), pl, pl + ref.tbs / 8);

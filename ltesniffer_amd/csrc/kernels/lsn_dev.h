@@ -171,7 +171,5 @@ void lsn_launch_rm(const LsnCbDev* cb, const int16_t* llr, uint32_t* spp, uint32
 void lsn_launch_harq_combine(const LsnCbDev* cbs, uint32_t ncb, const uint32_t* keep, uint32_t* pool, uint32_t* scratch, bool copy, hipStream_t s);
 void lsn_launch_turbo(const LsnCellDev& c, const LsnCbDev* cb, const uint32_t* spp, uint8_t* payload, LsnCbRes* res, uint32_t n128, uint32_t kmax128,
                       uint32_t n64, uint32_t kmax64, hipStream_t s);
-// largest code block two of which share one decoder workgroup (one wavefront and half of the LDS slot each): 2 x (6 K + 16 + 3584) <= 40 960 = a quarter of the CU's LDS
-#define LSN_TURBO_PAIR_KMAX 2752u
 void lsn_launch_turbo_packed(const LsnCellDev& c, const LsnCbDev* cb, const uint32_t* spp, uint8_t* payload, LsnCbRes* res, uint32_t nsolo, uint32_t kmax_solo,
                              uint32_t npair, uint32_t kmax_pair, hipStream_t s);

@@ -421,6 +421,13 @@ def hosttest():
         lib.lsnh_crc24a_mulmod.restype = C.c_uint32
         lib.lsnh_crc24a_mulmod.argtypes = [C.c_uint32, C.c_uint32]
         lib.lsnh_tb_verdict.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        lib.lsnh_tb_verdict_blocks.argtypes = [C.c_uint32] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]
+        lib.lsnh_turbo_nwin.restype = lib.lsnh_turbo_pair_kmax.restype = lib.lsnh_spp_words.restype = C.c_uint32
+        lib.lsnh_turbo_nwin.argtypes = [C.c_int]
+        lib.lsnh_spp_words.argtypes = [C.c_uint32]
+        lib.lsnh_turbo_packed_order.restype = lib.lsnh_turbo_place.restype = None
+        lib.lsnh_turbo_packed_order.argtypes = [C.c_uint32] + [C.c_void_p] * 4
+        lib.lsnh_turbo_place.argtypes = [C.c_uint32] + [C.c_void_p] * 3 + [C.c_uint32] + [C.c_void_p] * 3
         lib.lsnh_search_new.restype = C.c_void_p
         lib.lsnh_search_new.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_double, C.c_int]
         lib.lsnh_search_free.argtypes = [C.c_void_p]

@@ -142,6 +142,40 @@ int lsnh_tb_verdict(uint32_t n, const uint8_t* ok, const uint32_t* rem_a, const 
   return v.pass(payload, tbs) ? 1 : 0;
 }
 
+// ... and the same through tb_verdict (the helper of runJobs / puschDecodeGrid) on LsnCbRes / LsnCbDev arrays: out4 = {all_ok, rem, bits_after, iteration sum}
+int lsnh_tb_verdict_blocks(uint32_t n, const uint8_t* ok, const uint32_t* rem_a, const uint32_t* iters, const uint32_t* out_bytes, const uint8_t* payload, int tbs, uint64_t* out4)
+{
+  std::vector<LsnCbRes> res(n);
+  std::vector<LsnCbDev> cbs(n);
+  for (uint32_t q = 0; q < n; q++) { res[q] = LsnCbRes{}; res[q].ok = ok[q]; res[q].rem_a = rem_a[q]; res[q].iters = iters[q]; cbs[q] = LsnCbDev{}; cbs[q].out_bytes = out_bytes[q]; }
+  const TbResult t = tb_verdict(res.data(), cbs.data(), n);
+  out4[0] = t.v.all_ok ? 1 : 0; out4[1] = t.v.rem; out4[2] = t.v.bits_after; out4[3] = t.iters;
+  return t.v.pass(payload, tbs) ? 1 : 0;
+}
+
+uint32_t lsnh_turbo_nwin(int K) { return turbo_nwin(K); }
+uint32_t lsnh_turbo_pair_kmax() { return LSN_TURBO_PAIR_KMAX; }
+uint32_t lsnh_spp_words(uint32_t K) { return LSN_SPP_WORDS(K); }
+// turbo_packed_order of n blocks (K, dep): order[n], out6 = {nsolo[0], nsolo[1], npair[0], npair[1], kmax_solo, kmax_pair}
+void lsnh_turbo_packed_order(uint32_t n, const uint32_t* K, const uint32_t* dep, uint32_t* order, uint32_t* out6)
+{
+  std::vector<LsnCbDev> cbs(n);
+  for (uint32_t i = 0; i < n; i++) { cbs[i] = LsnCbDev{}; cbs[i].K = K[i]; cbs[i].dep = dep[i]; }
+  const TurboPackedOrder o = turbo_packed_order(cbs);
+  for (uint32_t i = 0; i < n && i < o.order.size(); i++) order[i] = o.order[i];
+  out6[0] = o.nsolo[0]; out6[1] = o.nsolo[1]; out6[2] = o.npair[0]; out6[3] = o.npair[1]; out6[4] = o.kmax_solo; out6[5] = o.kmax_pair;
+  if (o.order.size() != n) out6[0] = 0xFFFFFFFFu;
+}
+// turbo_place of n blocks (K, E) in the given order from spp_base: placed[i] = {K, E, spp_off, res_idx} of launch position i, spp_of[n]; out2 = {spp_n, emax}
+void lsnh_turbo_place(uint32_t n, const uint32_t* K, const uint32_t* E, const uint32_t* order, uint32_t spp_base, uint32_t* placed4, uint32_t* spp_of, uint64_t* out2)
+{
+  std::vector<LsnCbDev> cbs(n), dst(n);
+  for (uint32_t i = 0; i < n; i++) { cbs[i] = LsnCbDev{}; cbs[i].K = K[i]; cbs[i].E = E[i]; cbs[i].res_idx = i; }
+  const TurboPlacement p = turbo_place(cbs, std::vector<uint32_t>(order, order + n), spp_base, dst.data());
+  for (uint32_t i = 0; i < n; i++) { placed4[4 * i] = dst[i].K; placed4[4 * i + 1] = dst[i].E; placed4[4 * i + 2] = dst[i].spp_off; placed4[4 * i + 3] = dst[i].res_idx; spp_of[i] = p.spp_of[i]; }
+  out2[0] = p.spp_n; out2[1] = p.emax;
+}
+
 hsearch* lsnh_search_new(uint32_t nof_prb, uint32_t nof_ports, uint32_t cell_id, const uint32_t* nof_cce3, uint32_t threshold, double split, int skip)
 {
   hsearch* h = new hsearch();

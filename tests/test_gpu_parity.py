@@ -518,6 +518,22 @@ def test_a_failing_chunk_is_reported_and_does_not_wedge_the_pipeline():
     phy.close()
 
 
+_harq_tm3 = []
+
+
+def _harq_tm3_stream():
+    """40 subframes on 20 MHz with 2 code words per grant (TM3) and retransmissions 8 subframes later: big transport blocks of several code blocks each.
+    -> (scenario, first tti, samples, the oracle's records with harq_mode = 1); made once for the tests that use it"""
+    if not _harq_tm3:
+        sc = scenario("cfg3", seed=95, n_rnti=4, dl_min=2, dl_max=2, ul_min=0, ul_max=0, mix_tm3_pct=100, mix_tm4_pct=0, pct_256qam=0, mcs_min=20, mcs_max=24, snr_db=13.0,
+                      rar_period=0, paging_period=0, pct_harq=60)
+        tti0, iq, _ = gen_subframes(sc, 40)
+        ow, _, orecs = run_oracle(sc, tti0, iq, taps=False, harq_mode=1, mcs_tracking_mode=0)
+        assert ow.harq_stats()[1] > 3
+        _harq_tm3.append((sc, tti0, iq, orecs))
+    return _harq_tm3[0]
+
+
 def test_harq_soft_combining_matches_oracle():
     """harq_mode = 1 (HARQ.cc:71-190, DL_Sniffer_PDSCH.cc:943-1020): retransmissions 8 subframes after a failed transport block are
     combined with the soft buffer of their HARQ process on the GPU (k_harq_combine), blocks decoded before are not decoded again - record stream
@@ -535,14 +551,44 @@ def test_harq_soft_combining_matches_oracle():
         assert gpu_records(phy) == oracle_records(orecs), batch
         phy.close()
     # the same stream with 2 code words per grant (TM3) on 20 MHz: big transport blocks of several code blocks each
-    sc = scenario("cfg3", seed=95, n_rnti=4, dl_min=2, dl_max=2, ul_min=0, ul_max=0, mix_tm3_pct=100, mix_tm4_pct=0, pct_256qam=0, mcs_min=20, mcs_max=24, snr_db=13.0,
-                  rar_period=0, paging_period=0, pct_harq=60)
-    tti0, iq, _ = gen_subframes(sc, 40)
-    ow, _, orecs = run_oracle(sc, tti0, iq, taps=False, harq_mode=1, mcs_tracking_mode=0)
-    assert ow.harq_stats()[1] > 3
+    sc, tti0, iq, orecs = _harq_tm3_stream()
     phy = la.Phy(nof_rx_antennas=sc["nof_rx"], max_batch=40, pcapwriter=la.PcapWriter(None), harq_mode=1, mcs_tracking_mode=0)
     assert phy.setCell(sc["nof_prb"], sc["nof_ports"], sc["cell_id"])
     phy.process_host(iq, tti0, 0)
+    assert gpu_records(phy) == oracle_records(orecs) and len(orecs) > 0
+    phy.close()
+
+
+def test_harq_keep_store_and_stage_c_taps_read_one_placement():
+    """harq_mode = 1 with the stage-C taps switched on: the keep step and the tap step of a decode launch both find a block's soft data through the one inverse
+    map of the launch's placement (DecodeLaunch::place).  40 subframes at 100 PRB, retransmissions 8 subframes later, chunks of 16: retransmissions inside a chunk
+    and across two.  The launches hold transport blocks of several code blocks, blocks above LSN_TURBO_PAIR_KMAX (solo) and, in one of them, an odd number of
+    paired blocks (counted below from the taps; with the tracking database off a chunk's planned jobs go out in one launch).  Under harq_mode every code block is
+    always decoded (no first-block gating), so all of them are in phase 0.
+    Records: the oracle's with harq_mode = 1.  Stage-C by-products: what runJobs decodes under harq_mode is every grant's transmission on its OWN (combining is
+    the commit's), which is what the oracle decodes with HARQ off - its trace of the same samples is the reference, every block and iteration count (the oracle's
+    HARQ trace shows combined streams and leaves passed blocks out)."""
+    sc, tti0, iq, orecs = _harq_tm3_stream()
+    nsf, batch = 40, 16
+    run_oracle(sc, tti0, iq, taps=False, mcs_tracking_mode=0, trace=True)
+    otrace = oracle_trace()
+    phy = la.Phy(nof_rx_antennas=sc["nof_rx"], max_batch=batch, pcapwriter=la.PcapWriter(None), harq_mode=1, mcs_tracking_mode=0)
+    assert phy.setCell(sc["nof_prb"], sc["nof_ports"], sc["cell_id"])
+    phy.set_stage_c_taps(True)
+    badc, ncall, ncb, it_o, it_g, mix = [], 0, 0, 0, 0, []
+    for base in range(0, nsf, batch):
+        n = min(batch, nsf - base)
+        phy.process_host(iq[base:base + n], tti0 + base, 0)
+        b, c, k, io, ig = compare_stage_c(phy, otrace, tti0 + base, n, exact_iters=True)
+        badc += [(base,) + x for x in b]
+        ncall, ncb, it_o, it_g = ncall + c, ncb + k, it_o + io, it_g + ig
+        jobs = [j for j in phy.stage_c_jobs() if j["have"]]
+        K = [c["K"] for j in jobs for c in j["cbs"]]
+        mix.append((sum(1 for j in jobs for tb in (0, 1) if sum(1 for c in j["cbs"] if c["tb"] == tb) >= 2), sum(k > 2752 for k in K), sum(k <= 2752 for k in K)))   # (LSN_TURBO_PAIR_KMAX = 2752)
+    print("code blocks per chunk (transport blocks of >= 2, solo, paired):", mix, "compared:", ncall, ncb, it_o, it_g)
+    assert not badc, (len(badc), badc[:5])
+    assert ncall == len([o for o in otrace if not o["is_ul"]]) and ncb == sum(len(o["cbs"]) for o in otrace) > 0 and it_o == it_g
+    assert all(m[0] > 0 and m[1] > 0 for m in mix) and any(m[2] % 2 == 1 for m in mix), mix
     assert gpu_records(phy) == oracle_records(orecs) and len(orecs) > 0
     phy.close()
 

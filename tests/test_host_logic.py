@@ -247,6 +247,11 @@ def test_tb_verdict():
         assert out3[0] == (1 if all(ok) else 0)
         assert out3[1] == _crc24a_rem(b"".join(blocks))
         assert out3[2] == 8 * sum(len(b) for b in blocks)
+        # tb_verdict (the helper runJobs and puschDecodeGrid call) on the same blocks as LsnCbRes / LsnCbDev arrays: the same verdict, and the iteration sum
+        iters = rng.integers(0, 13, n).astype(np.uint32)
+        out4 = (C.c_uint64 * 4)()
+        assert h.lsnh_tb_verdict_blocks(n, okv.ctypes.data, rem_a.ctypes.data, iters.ctypes.data, nb.ctypes.data, pl.ctypes.data, tbs, out4) == r
+        assert list(out4) == list(out3) + [int(iters.sum())]
         return r
 
     def split(data, lens):
@@ -280,6 +285,93 @@ def test_tb_verdict():
         cut = int(rng.integers(1, 4))
         assert verdict(split(whole[:-cut], lens[:-1] + [lens[-1] - cut]), [1] * n, tbs) == 0
         assert verdict(split(bytes(len(whole)), lens), [1] * n, tbs) == 0 and out3[1] == 0 and out3[2] == tbs + 24
+
+
+NODEP = 0xFFFFFFFF
+LEGAL_K = list(range(40, 512, 8)) + list(range(512, 1024, 16)) + list(range(1024, 2048, 32)) + list(range(2048, 6145, 64))   # 36.212 Table 5.1.3-3
+
+
+def _packed_order_sets():
+    """(K, dep) lists for the packed launch order: the named edge cases, then random sets of 0 .. 400 blocks of the 188 legal sizes"""
+    h = hosttest()
+    kmax = h.lsnh_turbo_pair_kmax()
+    below, above = max(k for k in LEGAL_K if k <= kmax), min(k for k in LEGAL_K if k > kmax)
+    pairable = [k for k in LEGAL_K if k <= kmax and h.lsnh_turbo_nwin(k) <= 64]
+    rng = np.random.default_rng(2752)
+    sets = [([], []), ([below], [NODEP]), ([6144], [NODEP]),
+            (LEGAL_K, [NODEP] * 188),                                          # all independent
+            (LEGAL_K[::-1], [NODEP] + [0] * 187),                              # all but one dependent
+            ([40, 6144, 40, 6144, below, above, below, above] * 2, [NODEP, NODEP, 0, 1] * 4),   # equal K, the smallest and the largest, both sides of the limit
+            (pairable[:3] + [6144], [NODEP] * 4),                              # an odd number of paired blocks in phase 0 ...
+            ([above, 40] + pairable[-5:], [NODEP, NODEP] + [0] * 5)]           # ... and in phase 1
+    wide = [k for k in LEGAL_K if k <= kmax and h.lsnh_turbo_nwin(k) > 64]
+    if wide:
+        sets.append(([max(wide), below, max(wide), 40], [NODEP, NODEP, 0, 0]))
+    for trial in range(40):
+        n = int(rng.integers(0, 401))
+        pool = LEGAL_K if trial % 3 else [int(k) for k in rng.choice(LEGAL_K, 5)]      # (few sizes: many equal K)
+        K = [int(k) for k in rng.choice(pool, n)]
+        dep = [NODEP if (i == 0 or rng.random() < (0.0, 0.3, 1.0)[trial % 3]) else int(rng.integers(0, i)) for i in range(n)]
+        sets.append((K, dep))
+    return sets, wide
+
+
+def test_turbo_packed_order_against_a_stable_sort():
+    """turbo_packed_order (the order in which k_turbo sees the blocks of a downlink launch) against the key written out here and sorted by Python's stable sort:
+    phase (blocks that depend on nothing first), solo before paired, K descending, index ascending; paired = K <= LSN_TURBO_PAIR_KMAX and at most 64 trellis
+    windows.  Order, the four counts and both maxima.  The second condition of `paired` never decides: every legal K up to LSN_TURBO_PAIR_KMAX has at most 64
+    windows (asserted below), so no set can hold a block that it alone keeps solo."""
+    h = hosttest()
+    kmax = h.lsnh_turbo_pair_kmax()
+    assert len(LEGAL_K) == 188 and kmax in LEGAL_K
+    sets, wide = _packed_order_sets()
+    assert wide == []
+    odd = 0
+    for K, dep in sets:
+        n = len(K)
+        pair = [k <= kmax and h.lsnh_turbo_nwin(k) <= 64 for k in K]
+        phase = [0 if d == NODEP else 1 for d in dep]
+        want = sorted(range(n), key=lambda i: (phase[i], pair[i], -K[i]))
+        counts = [sum(1 for i in range(n) if phase[i] == ph and pair[i] == pr) for pr in (False, True) for ph in (0, 1)]
+        maxima = [max([K[i] for i in range(n) if pair[i] == pr], default=0) for pr in (False, True)]
+        odd += counts[2] % 2 + counts[3] % 2
+        Ka, da = np.array(K, dtype=np.uint32), np.array(dep, dtype=np.uint32)
+        order, out6 = np.full(n, 0xFFFFFFFF, dtype=np.uint32), np.zeros(6, dtype=np.uint32)
+        h.lsnh_turbo_packed_order(n, Ka.ctypes.data, da.ctypes.data, order.ctypes.data, out6.ctypes.data)
+        assert list(order) == want, (K, dep)
+        assert list(out6) == counts + maxima, (K, dep)
+    assert odd
+
+
+def test_turbo_place_lays_the_blocks_out_in_launch_order():
+    """turbo_place (the soft-data layout of runJobs and puschDecodeGrid): offsets are multiples of 4, ascend in launch order from the base and do not overlap
+    (K + 12 words each), spp_n = sum of LSN_SPP_WORDS(K), the inverse map inverts the order, emax is the largest E, and launch position i holds block order[i]."""
+    h = hosttest()
+    rng = np.random.default_rng(12)
+    for si, (K, dep) in enumerate(_packed_order_sets()[0]):
+        n = len(K)
+        Ka, da, E = np.array(K, dtype=np.uint32), np.array(dep, dtype=np.uint32), rng.integers(1, 40000, n).astype(np.uint32)
+        order, out6 = np.zeros(n, dtype=np.uint32), np.zeros(6, dtype=np.uint32)
+        h.lsnh_turbo_packed_order(n, Ka.ctypes.data, da.ctypes.data, order.ctypes.data, out6.ctypes.data)
+        base = 0 if si % 2 else 4 * int(rng.integers(0, 1000))
+        placed, spp_of, out2 = np.zeros((n, 4), dtype=np.uint32), np.zeros(n, dtype=np.uint32), np.zeros(2, dtype=np.uint64)
+        h.lsnh_turbo_place(n, Ka.ctypes.data, E.ctypes.data, order.ctypes.data, base, placed.ctypes.data, spp_of.ctypes.data, out2.ctypes.data)
+        words = [h.lsnh_spp_words(k) for k in K]
+        assert all(w % 4 == 0 and k + 12 <= w < k + 16 for w, k in zip(words, K))
+        assert int(out2[0]) == sum(words) and int(out2[1]) == (int(E.max()) if n else 0)
+        at = base
+        for i in range(n):
+            q = int(order[i])
+            assert list(placed[i]) == [K[q], int(E[q]), at, q] and at % 4 == 0 and int(spp_of[q]) == at
+            at += words[q]
+        assert at == base + int(out2[0])
+
+
+def test_turbo_order_and_placement_under_sanitizers():
+    """the same two functions in a program of its own built with -fsanitize=address,undefined (the counting sort indexes a table by K)"""
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "tests", "native"), "_build/test_turbo_order"], stdout=subprocess.DEVNULL)
+    out = subprocess.check_output([os.path.join(ROOT, "tests", "native", "_build", "test_turbo_order")]).decode()
+    assert out.startswith("OK")
 
 
 def _search_parity(scn, nsf, seed, update_meta_period=0, **over):
