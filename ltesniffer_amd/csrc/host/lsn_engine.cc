@@ -563,16 +563,13 @@ int Engine::newJob(Chunk& ch, uint32_t sf, const DlEntry& e, int table, float p_
   DecodeJob j;
   j.sf = sf; j.rnti = e.rnti; j.kind = (uint8_t)kind;
   j.risky = kind == 2;  // the speculative second-table attempt
-  // pdsch_cfg->p_a: DL mode looks the UE's p-a up before every decode (DL_Sniffer_PDSCH.cc:926-927); the UL-mode decoders never set
-  // it and run with the -3 dB of SubframeWorker::set_pdsch_uecfg (SubframeWorker.cc:370)
-  j.p_a = cfg.sniffer_mode == 1 ? -3.0f : p_a;
-  j.grant = table ? e.grant256 : e.grant64;
-  if (dl_sniffer_config_mimo(cell, e.format, e.dci, j.grant) != 0) return -1;
-  if (cfg.sniffer_mode == 1) {  // run_decode / run_rar_decode, DL_Sniffer_PDSCH.cc:240-247,694-701
-    const uint32_t sfn = ch.ctx[sf].sfn;
-    for (auto& tb : j.grant.tb)
-      if (tb.enabled && tb.rv < 0) tb.rv = (int)((uint32_t)ceilf(1.5f * (float)((sfn / 2) % 4)) % 4u);
-  } else if (e.dci.tb[0].rv < 0 && e.rnti == SIRNTI) j.grant.tb[0].rv = 0;  // DL_Sniffer_PDSCH.cc:891-897
+  if (!configure_decode(cell, cfg.sniffer_mode, e, table, p_a, ch.ctx[sf].sfn, j.grant, j.p_a)) return -1;
+  // A block without a redundancy version (rv -1: format 1C) never goes to the device - k_rm's start offset is computed from rv.  DL mode leaves it on the
+  // 256QAM-table grant of an SI-RNTI DCI (configure_decode) and on format 1C DCIs of user RNTIs.  The plan serves the former with the 64QAM-table job
+  // (same_decode); where the commit asks for it on demand it gets no job, and the attempt counts as failed - as the identical second decode did
+  if (cfg.sniffer_mode == 0)
+    for (const GrantTb& tb : j.grant.tb)
+      if (tb.enabled && tb.rv < 0) return -1;
   ch.jobs.push_back(j);
   JobRes jr;
   jr.p_a = j.p_a;
@@ -880,13 +877,33 @@ void Engine::hintEvent(uint16_t rnti, uint32_t pos)
   sh->hint_pos[(size_t)rnti * SharedSeq::HINT_RING + (k % SharedSeq::HINT_RING)].store(pos + 1, std::memory_order_relaxed);
 }
 
+// every enabled block with a size passed its CRC
+static bool all_sized_blocks_passed(const DecodeJob& j)
+{
+  bool all_ok = true;
+  for (int i = 0; i < 2; i++) all_ok = all_ok && (!j.grant.tb[i].enabled || !(j.grant.tb[i].tbs > 0) || j.crc[i]);
+  return all_ok;
+}
+
 // wave 1: the first decode the reference would attempt for every accepted DL DCI, predicted from the MCS-tracking
 // state as of now; wave 2: the 256QAM-table retry of "unknown table" grants whose first attempt failed on both TBs
 void Engine::planJobs(Chunk& ch, JobRunner& r)
 {
-  std::vector<int> wave;
-  struct Pending { uint32_t sf; size_t di; bool always; };
-  std::vector<Pending> retry, deferred;
+  JobPlan p;
+  planFirstWave(ch, p);
+  const uint8_t trk = (uint8_t)(2 + (&r - runner_c));
+  trace(trk, TR_W1_LAUNCHED, ch.trace_id);  // host-side planning done
+  runJobs(ch, r, p.wave);
+  trace(trk, TR_W1_DONE, ch.trace_id);
+  p.wave.clear();
+  planSecondWave(ch, r, p);
+  runJobs(ch, r, p.wave);
+  if (cfg.mcs_tracking_mode == 1) noteTeachingEvents(ch, p);
+  buildCommitView(ch);
+}
+
+void Engine::planFirstWave(Chunk& ch, JobPlan& p)
+{
   // In-chunk learning (round 4): a UE whose table the plan does not know yet gets its first HINT_EVENTS teachable grants of the chunk decoded the
   // reference's way (64QAM table, then 256QAM table) - the rest wait for those verdicts in a third wave.  Before, all grants of a new 256QAM UE in
   // the chunks in flight (about 200 per UE) ran a hopeless 64QAM-table attempt the commit never read: 19 % of all turbo iterations.
@@ -903,14 +920,10 @@ void Engine::planJobs(Chunk& ch, JobRunner& r)
       if (cfg.sniffer_mode == 1) {  // decode_ul_mode: RAR + format 1 / 1A (not SI) with the 64QAM table only
         if (!(ul_set ? ulModeDecodesDl(e) : e.rnti == SIRNTI)) continue;  // before the SIB2 configuration: decode_SIB (a prediction, commit decides)
         if (e.job[0] < 0) e.job[0] = newJob(ch, sf, e, 0);
-        if (e.job[0] >= 0) wave.push_back(e.job[0]);
+        if (e.job[0] >= 0) p.wave.push_back(e.job[0]);
         continue;
       }
-      McsTable table;
-      if (cfg.mcs_tracking_mode == 1)
-        table = (e.rnti == SIRNTI || e.rnti == PRNTI || rnti_israr(e.rnti) || e.format == FORMAT1A) ? TABLE_64QAM : predictedTable(e.rnti);
-      else
-        table = cfg.mcs_tracking_mode == 2 ? TABLE_UNKNOWN : TABLE_64QAM;
+      McsTable table = collection_table_from(cfg.mcs_tracking_mode, e.rnti, e.format, [&] { return predictedTable(e.rnti); });
       e.hinted = false;
       if (table >= TABLE_UNKNOWN && e.format > FORMAT1A && e.ok64 && e.ok256 && e.job[0] < 0 && e.job[1] < 0 && hintedTable256(e.rnti, ch.gpos0 + sf)) {
         table = TABLE_256QAM;   // the commit will have learnt it by then: no 64QAM-table attempt
@@ -927,102 +940,98 @@ void Engine::planJobs(Chunk& ch, JobRunner& r)
         size_t k = 0;
         while (k < seen.size() && seen[k].first != e.rnti) k++;
         if (k == seen.size()) seen.push_back({e.rnti, (uint8_t)0});
-        if (seen[k].second >= SharedSeq::HINT_EVENTS) { deferred.push_back({sf, di, false}); continue; }
+        if (seen[k].second >= SharedSeq::HINT_EVENTS) { p.deferred.push_back({sf, di, false}); continue; }
         seen[k].second++;
       }
       if (e.job[first] < 0) {
         e.job[first] = newJob(ch, sf, e, first, predictedPa(e.rnti));  // as of now; commit checks it
         if (e.job[first] >= 0 && table >= TABLE_UNKNOWN && e.format > FORMAT1A) ch.jobs[e.job[first]].risky = true;
       }
-      if (e.job[first] >= 0) wave.push_back(e.job[first]);
+      if (e.job[first] >= 0) p.wave.push_back(e.job[first]);
       if (e.job[first] >= 0 && e.job[1 - first] < 0 && e.ok64 && e.ok256 && same_decode(e.grant64, e.grant256)) e.job[1 - first] = e.job[first];
       // the 256QAM-table attempt: the reference makes it when both TBs failed with the 64QAM table.  A DCI of a format that can teach the
       // table (> 1A, DL_Sniffer_PDSCH.cc:1168-1171) may find its RNTI's table KNOWN by the time it is committed (the plan runs thousands of
       // subframes ahead of the commit while a new UE is being learned), and then commit wants exactly that attempt: decode it now rather
       // than as a GPU round trip of the sequential commit thread
-      if (table >= TABLE_UNKNOWN && e.ok256 && e.job[1] < 0) retry.push_back({sf, di, g_speculate_second_table && e.format > FORMAT1A});
+      if (table >= TABLE_UNKNOWN && e.ok256 && e.job[1] < 0) p.retry.push_back({sf, di, g_speculate_second_table && e.format > FORMAT1A});
     }
   }
-  const uint8_t trk = (uint8_t)(2 + (&r - runner_c));
-  trace(trk, TR_W1_LAUNCHED, ch.trace_id);  // host-side planning done
-  runJobs(ch, r, wave);
-  trace(trk, TR_W1_DONE, ch.trace_id);
-  wave.clear();
-  for (auto& p : retry) {
-    DlEntry& e = ch.ctx[p.sf].dl[p.di];
+}
+
+void Engine::planSecondWave(Chunk& ch, JobRunner& r, JobPlan& p)
+{
+  for (auto& q : p.retry) {
+    DlEntry& e = ch.ctx[q.sf].dl[q.di];
     if (e.job[0] < 0 || !ch.jobs[e.job[0]].done) continue;
-    if (!p.always && (ch.jobs[e.job[0]].crc[0] || ch.jobs[e.job[0]].crc[1])) continue;
+    if (!q.always && (ch.jobs[e.job[0]].crc[0] || ch.jobs[e.job[0]].crc[1])) continue;
     const bool spec = ch.jobs[e.job[0]].crc[0] || ch.jobs[e.job[0]].crc[1];
-    if (spec) {
-      // The speculative attempt serves a commit that finds the RNTI's table KNOWN as 256QAM.  A UE whose 64QAM-table attempt passed the CRC of
-      // EVERY enabled transport block is on the 64QAM table: nothing can have taught the commit otherwise, so the attempt (hopeless by
-      // construction: 12 iterations per block) is left out - measured in round 4: 3 326 speculative jobs per 6 400 subframes, 280 of them used,
-      // 15 % of all turbo iterations.  Kept: partial passes (one block of a two-block grant whose MCS index means the same in both tables).
-      const DecodeJob& j0 = ch.jobs[e.job[0]];
-      bool all_ok = true;
-      for (int i = 0; i < 2; i++) all_ok = all_ok && (!j0.grant.tb[i].enabled || !(j0.grant.tb[i].tbs > 0) || j0.crc[i]);
-      if (all_ok) continue;
-    }
+    // The speculative attempt serves a commit that finds the RNTI's table KNOWN as 256QAM.  A UE whose 64QAM-table attempt passed the CRC of
+    // EVERY enabled transport block is on the 64QAM table: nothing can have taught the commit otherwise, so the attempt (hopeless by
+    // construction: 12 iterations per block) is left out - measured in round 4: 3 326 speculative jobs per 6 400 subframes, 280 of them used,
+    // 15 % of all turbo iterations.  Kept: partial passes (one block of a two-block grant whose MCS index means the same in both tables).
+    if (spec && all_sized_blocks_passed(ch.jobs[e.job[0]])) continue;
     if (spec) r.perf.nof_speculative_jobs++;
-    if (e.job[1] < 0) e.job[1] = newJob(ch, p.sf, e, 1, ch.jobs[e.job[0]].p_a, spec ? 2 : 1);
-    if (e.job[1] >= 0) wave.push_back(e.job[1]);
+    if (e.job[1] < 0) e.job[1] = newJob(ch, q.sf, e, 1, ch.jobs[e.job[0]].p_a, spec ? 2 : 1);
+    if (e.job[1] >= 0) p.wave.push_back(e.job[1]);
   }
-  if (!deferred.empty()) {
-    // the grants held back above join the second wave.  Evidence = the 64QAM-table verdicts of THIS chunk's first wave in front of the grant + the ring
-    // (a third wave that waits for the 256QAM-table verdicts as well was measured: 11 % fewer turbo iterations and 6 % FEWER subframes/s - one more
-    // round of launches per chunk costs more than the hopeless attempts it saves)
-    struct Ev { uint16_t rnti; uint32_t pos; bool fail64, full64; };  // fail64: no block passed with the 64QAM table; full64: every enabled block passed
-    std::vector<Ev> ev;
-    for (auto& p : retry) {
-      const DlEntry& e = ch.ctx[p.sf].dl[p.di];
-      if (!(e.format > FORMAT1A) || e.job[0] < 0 || !ch.jobs[e.job[0]].done || same_decode(e.grant64, e.grant256)) continue;
-      const DecodeJob& j0 = ch.jobs[e.job[0]];
-      bool full64 = true;
-      for (int i = 0; i < 2; i++) full64 = full64 && (!j0.grant.tb[i].enabled || !(j0.grant.tb[i].tbs > 0) || j0.crc[i]);
-      ev.push_back({e.rnti, ch.gpos0 + p.sf, !j0.crc[0] && !j0.crc[1], full64});
+  if (!p.deferred.empty()) planDeferred(ch, r, p);
+}
+
+// the grants held back by the first wave join the second.  Evidence = the 64QAM-table verdicts of THIS chunk's first wave in front of the grant + the ring
+// (a third wave that waits for the 256QAM-table verdicts as well was measured: 11 % fewer turbo iterations and 6 % FEWER subframes/s - one more
+// round of launches per chunk costs more than the hopeless attempts it saves)
+void Engine::planDeferred(Chunk& ch, JobRunner& r, JobPlan& p)
+{
+  struct Ev { uint16_t rnti; uint32_t pos; bool fail64, full64; };  // fail64: no block passed with the 64QAM table; full64: every enabled block passed
+  std::vector<Ev> ev;
+  for (auto& q : p.retry) {
+    const DlEntry& e = ch.ctx[q.sf].dl[q.di];
+    if (!(e.format > FORMAT1A) || e.job[0] < 0 || !ch.jobs[e.job[0]].done || same_decode(e.grant64, e.grant256)) continue;
+    const DecodeJob& j0 = ch.jobs[e.job[0]];
+    ev.push_back({e.rnti, ch.gpos0 + q.sf, !j0.crc[0] && !j0.crc[1], all_sized_blocks_passed(j0)});
+  }
+  for (auto& q : p.deferred) {
+    DlEntry& e = ch.ctx[q.sf].dl[q.di];
+    const uint32_t pos = ch.gpos0 + q.sf;
+    uint32_t lo = 0;
+    const int ring = hintEvents(e.rnti, pos, &lo);
+    int nfail = 0, n64 = 0, nother = 0;
+    for (auto& x : ev)
+      if (x.rnti == e.rnti && x.pos < pos && x.pos >= lo) { nfail += x.fail64 ? 1 : 0; n64 += x.full64 ? 1 : 0; nother += (!x.fail64 && !x.full64) ? 1 : 0; }
+    const float p_a = predictedPa(e.rnti);
+    if (ring >= 0 && (ring >= SharedSeq::HINT_EVENTS || (nfail >= SharedSeq::HINT_EVENTS && n64 == 0 && nother == 0))) {
+      // the 256QAM-table attempt only: the ring says the commit knows the table, or every one of this UE's HINT_EVENTS grants in front failed with
+      // the 64QAM table (their 256QAM-table attempts run in this same wave: a UE that fails those too makes the commit ask for the attempt left
+      // out here, which counts as a miss and closes the hints)
+      e.hinted = true;
+      sh->hint_used.fetch_add(1, std::memory_order_relaxed);
+      if (e.job[1] < 0) e.job[1] = newJob(ch, q.sf, e, 1, p_a);
+      if (e.job[1] >= 0) p.wave.push_back(e.job[1]);
+      continue;
     }
-    for (auto& p : deferred) {
-      DlEntry& e = ch.ctx[p.sf].dl[p.di];
-      const uint32_t pos = ch.gpos0 + p.sf;
-      uint32_t lo = 0;
-      const int ring = hintEvents(e.rnti, pos, &lo);
-      int nfail = 0, n64 = 0, nother = 0;
-      for (auto& x : ev)
-        if (x.rnti == e.rnti && x.pos < pos && x.pos >= lo) { nfail += x.fail64 ? 1 : 0; n64 += x.full64 ? 1 : 0; nother += (!x.fail64 && !x.full64) ? 1 : 0; }
-      const float p_a = predictedPa(e.rnti);
-      if (ring >= 0 && (ring >= SharedSeq::HINT_EVENTS || (nfail >= SharedSeq::HINT_EVENTS && n64 == 0 && nother == 0))) {
-        // the 256QAM-table attempt only: the ring says the commit knows the table, or every one of this UE's HINT_EVENTS grants in front failed with
-        // the 64QAM table (their 256QAM-table attempts run in this same wave: a UE that fails those too makes the commit ask for the attempt left
-        // out here, which counts as a miss and closes the hints)
-        e.hinted = true;
-        sh->hint_used.fetch_add(1, std::memory_order_relaxed);
-        if (e.job[1] < 0) e.job[1] = newJob(ch, p.sf, e, 1, p_a);
-        if (e.job[1] >= 0) wave.push_back(e.job[1]);
-        continue;
-      }
-      // otherwise the reference's own order: its 64QAM-table attempt and, unless everything of this UE passed with that table so far, the
-      // 256QAM-table attempt with it
-      if (e.job[0] < 0) e.job[0] = newJob(ch, p.sf, e, 0, p_a);
-      if (e.job[0] >= 0) wave.push_back(e.job[0]);
-      if (!(n64 > 0 && nfail == 0 && nother == 0) && e.job[1] < 0) {
-        e.job[1] = newJob(ch, p.sf, e, 1, p_a, 2);
-        if (e.job[1] >= 0) { wave.push_back(e.job[1]); r.perf.nof_speculative_jobs++; }
-      }
+    // otherwise the reference's own order: its 64QAM-table attempt and, unless everything of this UE passed with that table so far, the
+    // 256QAM-table attempt with it
+    if (e.job[0] < 0) e.job[0] = newJob(ch, q.sf, e, 0, p_a);
+    if (e.job[0] >= 0) p.wave.push_back(e.job[0]);
+    if (!(n64 > 0 && nfail == 0 && nother == 0) && e.job[1] < 0) {
+      e.job[1] = newJob(ch, q.sf, e, 1, p_a, 2);
+      if (e.job[1] >= 0) { p.wave.push_back(e.job[1]); r.perf.nof_speculative_jobs++; }
     }
   }
-  runJobs(ch, r, wave);
-  // teaching decodes of this chunk (SharedSeq::hint_pos): 64QAM-table attempt failed on every block, 256QAM-table attempt passed with a learnable MCS index
-  if (cfg.mcs_tracking_mode == 1)
-    for (auto& p : retry) {
-      const DlEntry& e = ch.ctx[p.sf].dl[p.di];
-      if (!(e.format > FORMAT1A) || e.job[0] < 0 || e.job[1] < 0 || e.job[0] == e.job[1]) continue;
-      const DecodeJob &j0 = ch.jobs[e.job[0]], &j1 = ch.jobs[e.job[1]];
-      if (!j0.done || !j1.done || j0.crc[0] || j0.crc[1]) continue;
-      bool teach = false;
-      for (int i = 0; i < 2; i++) teach = teach || (j1.crc[i] && e.dci.tb[i].mcs_idx > 0 && e.dci.tb[i].mcs_idx < 28);
-      if (teach) hintEvent(e.rnti, ch.gpos0 + p.sf);
-    }
-  buildCommitView(ch);
+}
+
+// teaching decodes of this chunk (SharedSeq::hint_pos): 64QAM-table attempt failed on every block, 256QAM-table attempt passed with a learnable MCS index
+void Engine::noteTeachingEvents(Chunk& ch, const JobPlan& p)
+{
+  for (auto& q : p.retry) {
+    const DlEntry& e = ch.ctx[q.sf].dl[q.di];
+    if (!(e.format > FORMAT1A) || e.job[0] < 0 || e.job[1] < 0 || e.job[0] == e.job[1]) continue;
+    const DecodeJob &j0 = ch.jobs[e.job[0]], &j1 = ch.jobs[e.job[1]];
+    if (!j0.done || !j1.done || j0.crc[0] || j0.crc[1]) continue;
+    bool teach = false;
+    for (int i = 0; i < 2; i++) teach = teach || (j1.crc[i] && e.dci.tb[i].mcs_idx > 0 && e.dci.tb[i].mcs_idx < 28);
+    if (teach) hintEvent(e.rnti, ch.gpos0 + q.sf);
+  }
 }
 
 void Engine::buildCommitView(Chunk& ch)
@@ -1031,22 +1040,7 @@ void Engine::buildCommitView(Chunk& ch)
   ch.cdci_first.assign(ch.nsf + 1, 0);
   for (uint32_t sf = 0; sf < ch.nsf; sf++) {
     ch.cdci_first[sf] = (uint32_t)ch.cdci.size();
-    const SubframeCtx& c = ch.ctx[sf];
-    if (!c.searched) continue;
-    for (size_t di = 0; di < c.dl.size(); di++) {
-      const DlEntry& e = c.dl[di];
-      CommitDci d;
-      d.rnti = e.rnti; d.format = (uint8_t)e.format; d.di = (uint32_t)di;
-      d.flags = (uint8_t)((e.unpack_ok ? 1 : 0) | (e.ok64 ? 2 : 0) | (e.ok256 ? 4 : 0) | (e.grant64.nof_tb == 2 ? 8 : 0) | (e.grant256.nof_tb == 2 ? 16 : 0));
-      for (int i = 0; i < 2; i++) {
-        if (e.grant64.tb[i].enabled) d.en64 |= (uint8_t)(1u << i);
-        if (e.grant256.tb[i].enabled) d.en256 |= (uint8_t)(1u << i);
-        d.mcs_idx[i] = (uint8_t)e.dci.tb[i].mcs_idx;
-        d.job[i] = e.job[i];
-      }
-      d.tbs0_64 = e.grant64.tb[0].tbs; d.tbs0_256 = e.grant256.tb[0].tbs;
-      ch.cdci.push_back(d);
-    }
+    if (ch.ctx[sf].searched) commit_view_append(ch.ctx[sf], ch.cdci);
   }
   ch.cdci_first[ch.nsf] = (uint32_t)ch.cdci.size();
 }
@@ -1088,163 +1082,81 @@ void Engine::ageTrackingDatabase()
   nof_mcs_db_updates++;
 }
 
-// PDSCH_Decoder::decode_dl_mode (DL_Sniffer_PDSCH.cc:881-1291) over the decode results of every subframe of the chunk.
-// The loop reads the compact CommitDci / JobRes views (buildCommitView, runJobs); the wide DlEntry / DecodeJob records are only touched
-// on the slow path (a decode that has to be created here because the plan-time prediction of table or p-a was wrong).
+// What the commit walk (lsn_commit.h) asks of the engine for one subframe of a chunk.  The walk reads the compact CommitDci / JobRes views (buildCommitView,
+// runJobs); the wide DlEntry / DecodeJob records are only touched on the slow path (a decode that has to be created here because the plan-time prediction of
+// table or p-a was wrong).
+struct Engine::CommitHost {
+  Engine& en; Chunk& ch; JobRunner& r; SubframeCtx& c; uint32_t sf;
+  // the planned job, or one created and decoded on demand
+  int attempt(CommitDci& d, int t, float p_a_now)
+  {
+    if (d.job[t] >= 0 && ch.jres[d.job[t]].p_a != p_a_now) d.job[t] = -1;
+    if (d.job[t] >= 0 && ch.jres[d.job[t]].done) { r.perf.nof_decode_jobs_used++; ch.jobs[d.job[t]].used = 1; return d.job[t]; }
+    DlEntry& e = c.dl[d.di];  // slow path
+    if (e.hinted && t == 0 && d.job[0] < 0) en.sh->hint_missed.fetch_add(1, std::memory_order_relaxed);
+    const int why = (e.job[t] >= 0 && d.job[t] < 0) ? 0 : (e.job[t] < 0 ? (e.job[1 - t] >= 0 ? 1 : 2) : 3);
+    e.job[t] = d.job[t];
+    if (e.job[t] < 0) e.job[t] = en.newJob(ch, sf, e, t, p_a_now, 4);
+    if (e.job[t] >= 0 && !ch.jobs[e.job[t]].done) {
+      const double t0 = now_ms();
+      static const bool dbg = getenv("LSN_DEBUG_ONDEMAND") != nullptr;
+      if (dbg) fprintf(stderr, "ondemand: sf_cnt %u tti %u rnti %u fmt %d t %d job0 %d job1 %d pred %d mcs %u/%u crc0job %d%d\n", en.commit_sf_cnt, c.tti, d.rnti, (int)d.format, t,
+                       e.job[0], e.job[1], (int)en.pred_table[d.rnti].load(), d.mcs_idx[0], d.mcs_idx[1], e.job[1 - t] >= 0 ? (int)ch.jres[e.job[1 - t]].crc[0] : -1, e.job[1 - t] >= 0 ? (int)ch.jres[e.job[1 - t]].crc[1] : -1);
+      en.ensureJob(ch, r, e.job[t]);
+      r.perf.nof_ondemand_decodes++; r.perf.nof_ondemand_commit[why]++; r.perf.ms_ondemand_commit += now_ms() - t0;
+    }
+    d.job[t] = e.job[t];
+    if (d.job[t] >= 0) { r.perf.nof_decode_jobs_used++; ch.jobs[d.job[t]].used = 1; }
+    return d.job[t];
+  }
+  const JobRes& result(int j) const { return ch.jres[j]; }
+  int tbs(int j, int tb) const { return ch.jobs[j].grant.tb[tb].tbs; }
+  const uint8_t* payload(uint32_t off) const { return ch.h_payload.data() + off; }
+  int mimo_verdict(const CommitDci& d, int t) const
+  {
+    const DlEntry& e = c.dl[d.di];
+    PdschGrant g = t ? e.grant256 : e.grant64;
+    return -dl_sniffer_config_mimo(en.cell, e.format, e.dci, g);
+  }
+  void record(const char* name, uint32_t off, uint32_t len, uint16_t rnti, uint32_t tti, uint8_t tb) { en.emitPdu(ch, r, name, off, len, rnti, tti, tb); }
+  void rar(const uint8_t* pdu, int len) { en.unpackRar(pdu, len, false); }
+  void learn_setups(const JobRes& jr, int tb, uint16_t rnti, bool any_lcid)  // the PDU was walked ahead of time (takeVerdicts)
+  {
+    if (jr.nsetup[tb] && en.mcs_tracking.learn_setups(ch.setup_cfgs.data() + jr.setup_first[tb], jr.nsetup[tb], rnti, en.commit_sf_cnt, any_lcid))
+      en.default_p_a.store(en.mcs_tracking.default_p_a(), std::memory_order_relaxed);
+  }
+  void learn_pdu(const uint8_t* pdu, int len, uint16_t rnti) { en.learnUeConfig(pdu, len, rnti); }
+  void harq_store(int j, int tb, size_t slot) { en.harqStore(ch, j, tb, slot); }
+  bool harq_combined_decode(int j, int tb, size_t slot, uint32_t& payload_off) { return en.harqCombinedDecode(ch, r, j, tb, slot, payload_off); }
+  void harq_size_from_database(CommitDci& d)
+  {
+    DlEntry& e = c.dl[d.di];
+    if (!collection_last_tbs(true, TABLE_64QAM, e, en.harq_db)) return;
+    d.tbs0_64 = e.grant64.tb[0].tbs;
+    d.job[0] = -1; e.job[0] = -1;
+  }
+  void publish(uint16_t rnti) { en.publishPrediction(rnti); }
+};
+
+// PDSCH_Decoder::decode_dl_mode (DL_Sniffer_PDSCH.cc:881-1291) over the decode results of every subframe of the chunk: the walk itself is
+// commit_walk_subframe (lsn_commit.h); here is what belongs to the engine
 void Engine::commitChunk(Chunk& ch, JobRunner& r)
 {
   std::vector<McsTable> tables;
+  const CommitCfg ccfg{cfg.mcs_tracking_mode, cfg.harq_mode != 0, dlRx()};
   if (cfg.harq_mode) harqBatchAhead(ch, r);
   for (uint32_t sf = 0; sf < ch.nsf; sf++, commit_sf_cnt++) {
     SubframeCtx& c = ch.ctx[sf];
     // the tracking database is only WRITTEN here (commit thread); decode threads read the published prediction arrays, the API getter
     // (lsn_phy_get_ue_config) takes this lock
     std::unique_lock<std::mutex> mcs_lk(mcs_mtx);
-    const uint32_t now = commit_sf_cnt;
     commit_pos.store(commit_sf_cnt, std::memory_order_relaxed);
     if (cfg.mcs_tracking_mode && mcs_update_period && commit_sf_cnt && (commit_sf_cnt % mcs_update_period) == 0) ageTrackingDatabase();
     if (cfg.harq_mode && commit_sf_cnt && (commit_sf_cnt % 10000u) == 0) harq_db.update_database(commit_sf_cnt);  // the 10 s timer, LTESniffer_Core.cc:487-494
     if (!c.searched) continue;
     const uint32_t k0 = ch.cdci_first[sf], k1 = ch.cdci_first[sf + 1];
-    // DCICollection.cc:107-134: the table of every DCI of this subframe is fixed before any of them is decoded
-    tables.resize(k1 - k0);
-    for (uint32_t k = k0; k < k1; k++) {
-      const CommitDci& d = ch.cdci[k];
-      tables[k - k0] = collection_table(cfg.mcs_tracking_mode, d.rnti, (DciFormat)d.format, mcs_tracking, now);
-    }
-    // addCandidate looks the table up for EVERY accepted DCI, format 0 included: an uplink grant refreshes the entry's time stamp too
-    if (cfg.mcs_tracking_mode == 1)
-      for (const UlEntry& u : c.ul)
-        if (!(u.rnti == SIRNTI || u.rnti == PRNTI || rnti_israr(u.rnti))) (void)mcs_tracking.find_tracking_info_RNTI_dl(u.rnti, now);
-    for (uint32_t k = k0; k < k1; k++) {
-      CommitDci& d = ch.cdci[k];
-      const McsTable table = tables[k - k0];
-      const bool unpack_ok = d.flags & 1, ok64 = d.flags & 2, ok256 = d.flags & 4;
-      const TableView tv = table_view(table, d.rnti, unpack_ok, ok64, ok256);  // falcon_dci.c:284-310
-      const bool has64 = tv.has64, has256 = tv.has256, dci_rnti_ok = tv.dci_rnti_ok;
-      // DCICollection.cc:236-251: a reserved MCS index of a 64QAM-table grant takes its size from the HARQ database (harq_mode only).  The plan knew no size for
-      // it (0): whatever it decoded for this entry is dropped and the grant is decoded on demand with the size in
-      if (cfg.harq_mode && has64 && collection_last_tbs(true, table, c.dl[d.di], harq_db)) {
-        d.tbs0_64 = c.dl[d.di].grant64.tb[0].tbs;
-        d.job[0] = -1; c.dl[d.di].job[0] = -1;
-      }
-      const int cur_t = table == TABLE_256QAM ? 1 : 0;
-      const bool cur_has = cur_t ? has256 : has64;
-      const int32_t cur_tbs0 = cur_has ? (cur_t ? d.tbs0_256 : d.tbs0_64) : 0;
-      const uint8_t cur_en = cur_has ? (cur_t ? d.en256 : d.en64) : 0;
-      const bool two_tb = (has64 && (d.flags & 8)) || (has256 && (d.flags & 16));
-      const bool gate = (cur_tbs0 > 0 && dci_rnti_ok && !(dlRx() == 1 && two_tb)) || d.rnti == PRNTI;  // :887-889
-      if (!gate) continue;
-      const char* name = rnti_name(d.rnti);
-      // :926-927: the p-a in force when this DCI is decoded.  A job planned (or speculated) with another value - a connection setup
-      // was committed in between - is dropped and decoded again, so results do not depend on how far ahead the pipeline planned
-      const float p_a_now = mcs_tracking.get_ue_config_rnti(d.rnti).p_a;
-      auto run = [&](int t) -> int {
-        if (!(t ? has256 : has64)) return -1;
-        if (d.job[t] >= 0 && ch.jres[d.job[t]].p_a != p_a_now) d.job[t] = -1;
-        if (d.job[t] >= 0 && ch.jres[d.job[t]].done) { r.perf.nof_decode_jobs_used++; ch.jobs[d.job[t]].used = 1; return d.job[t]; }
-        DlEntry& e = c.dl[d.di];  // slow path
-        if (e.hinted && t == 0 && d.job[0] < 0) sh->hint_missed.fetch_add(1, std::memory_order_relaxed);
-        const int why = (e.job[t] >= 0 && d.job[t] < 0) ? 0 : (e.job[t] < 0 ? (e.job[1 - t] >= 0 ? 1 : 2) : 3);
-        e.job[t] = d.job[t];
-        if (e.job[t] < 0) e.job[t] = newJob(ch, sf, e, t, p_a_now, 4);
-        if (e.job[t] >= 0 && !ch.jobs[e.job[t]].done) {
-          const double t0 = now_ms();
-          static const bool dbg = getenv("LSN_DEBUG_ONDEMAND") != nullptr;
-          if (dbg) fprintf(stderr, "ondemand: sf_cnt %u tti %u rnti %u fmt %d table %d t %d job0 %d job1 %d pred %d mcs %u/%u crc0job %d%d\n", commit_sf_cnt, c.tti, d.rnti, (int)d.format, (int)table, t,
-                           e.job[0], e.job[1], (int)pred_table[d.rnti].load(), d.mcs_idx[0], d.mcs_idx[1], e.job[1 - t] >= 0 ? (int)ch.jres[e.job[1 - t]].crc[0] : -1, e.job[1 - t] >= 0 ? (int)ch.jres[e.job[1 - t]].crc[1] : -1);
-          ensureJob(ch, r, e.job[t]);
-          r.perf.nof_ondemand_decodes++; r.perf.nof_ondemand_commit[why]++; r.perf.ms_ondemand_commit += now_ms() - t0;
-        }
-        d.job[t] = e.job[t];
-        if (d.job[t] >= 0) { r.perf.nof_decode_jobs_used++; ch.jobs[d.job[t]].used = 1; }
-        return d.job[t];
-      };
-      // dl_sniffer_config_mimo's verdict 0 / -1 / -2 / -3 for the statistics: a job exists exactly when it was 0 (newJob), so the
-      // function itself only runs again for the rare rejected grant
-      auto mimo_of = [&](int t, int job) {
-        if (job >= 0) return 0;
-        const DlEntry& e = c.dl[d.di];
-        PdschGrant g = t ? e.grant256 : e.grant64;
-        return -dl_sniffer_config_mimo(cell, e.format, e.dci, g);
-      };
-      auto learn = [&](const JobRes& jr, int tb, bool any_lcid) {  // :1041-1070 / :1133-1160 with the PDU walked ahead of time (runJobs)
-        if (jr.nsetup[tb] && mcs_tracking.learn_setups(ch.setup_cfgs.data() + jr.setup_first[tb], jr.nsetup[tb], d.rnti, now, any_lcid))
-          default_p_a.store(mcs_tracking.default_p_a(), std::memory_order_relaxed);
-      };
-      bool crc[2] = {false, false};   // pdsch_res[].crc as the statistics see it at the end of the iteration
-      int mimo_ret = 0;
-      if (table == TABLE_64QAM || table == TABLE_256QAM) {  // :932-1083
-        const int j = run(cur_t);
-        mimo_ret = cur_has ? mimo_of(cur_t, j) : -1;
-        if (j >= 0) {
-          const JobRes jr = ch.jres[j];  // (by value: a combined decode below appends to the chunk's vectors)
-          for (int tb = 0; tb < 2; tb++) {
-            crc[tb] = jr.crc[tb] != 0;
-            uint32_t poff = jr.payload_off[tb];
-            bool combined = false;
-            if (cfg.harq_mode && name[0] == 'C' && jr.enabled[tb]) {  // :943-1020: new transmission / retransmission / already decoded, per transport block
-              const DlEntry& e = c.dl[d.di];
-              const int tbs = ch.jobs[j].grant.tb[tb].tbs;
-              int ent = -1;
-              const HarqRet hr = harq_db.is_retransmission(d.rnti, e.dci.pid, tb, e.dci.tb[tb].ndi != 0, tbs, c.sfn, c.sf_idx, ent);
-              const size_t slot = ent < 0 ? 0 : ((size_t)ent * HarqDatabase::NPID + (e.dci.pid & 7u)) * 2 + (size_t)tb;
-              if (hr == HARQ_NEW_TX) {
-                if (!crc[tb]) harqStore(ch, j, tb, slot);   // srsran_softbuffer_rx_reset_tbs + this transmission (the buffer is only read again if the block failed)
-              } else if (hr == HARQ_RE_TX) {
-                crc[tb] = harqCombinedDecode(ch, r, j, tb, slot, poff);
-                combined = true;
-              } else if (hr == HARQ_DECODED) {
-                crc[tb] = false;                 // decoded 8 subframes ago: not decoded again, nothing written
-              }
-              if (hr == HARQ_NEW_TX || hr == HARQ_RE_TX) harq_db.update(ent, e.dci.pid, tb, c.sfn, c.sf_idx, crc[tb], e.dci.tb[tb].ndi != 0, e.dci.tb[tb].rv, tbs, now);
-            }
-            if (crc[tb] && jr.len[tb] > 0) {
-              emitPdu(ch, r, name, poff, (uint32_t)jr.len[tb], d.rnti, c.tti, (uint8_t)tb);
-              if (name[0] == 'R') unpackRar(ch.h_payload.data() + poff, jr.len[tb], false);
-              if (name[0] == 'C') {
-                if (combined) learnUeConfig(ch.h_payload.data() + poff, jr.len[tb], d.rnti);  // (not pre-parsed: the block was decoded in this turn)
-                else learn(jr, tb, false);
-              }
-            }
-          }
-        }
-      } else {  // unknown table: 64QAM table first, the 256QAM table only if both TBs failed, :1089-1243
-        const int j = run(0);
-        mimo_ret = has64 ? mimo_of(0, j) : -1;
-        if (j >= 0) {
-          const JobRes& jr = ch.jres[j];
-          for (int tb = 0; tb < 2; tb++) {
-            crc[tb] = jr.crc[tb] != 0;
-            if (crc[tb] && jr.len[tb] > 0) {
-              emitPdu(ch, r, name, jr.payload_off[tb], (uint32_t)jr.len[tb], d.rnti, c.tti, (uint8_t)tb);
-              if (name[0] == 'R') unpackRar(ch.h_payload.data() + jr.payload_off[tb], jr.len[tb], false);
-              if (name[0] == 'C') learn(jr, tb, true);  // :1133-1160: every SDU, whatever its logical channel
-              if (d.mcs_idx[tb] > 0 && d.mcs_idx[tb] < 29 && d.format > FORMAT1A) mcs_tracking.update_RNTI_dl(d.rnti, TABLE_64QAM, now);
-            }
-          }
-        }
-        if (!crc[0] && !crc[1] && mimo_ret == 0) {
-          const int j2 = run(1);
-          mimo_ret = has256 ? mimo_of(1, j2) : -1;
-          if (j2 >= 0) {
-            const JobRes& jr = ch.jres[j2];
-            for (int tb = 0; tb < 2; tb++) {
-              if (jr.enabled[tb]) crc[tb] = jr.crc[tb] != 0;
-              if (jr.crc[tb] && jr.len[tb] > 0) {
-                emitPdu(ch, r, name, jr.payload_off[tb], (uint32_t)jr.len[tb], d.rnti, c.tti, (uint8_t)tb);
-                if (d.mcs_idx[tb] > 0 && d.mcs_idx[tb] < 28 && d.format > FORMAT1A) mcs_tracking.update_RNTI_dl(d.rnti, TABLE_256QAM, now);
-              }
-            }
-          }
-        }
-      }
-      if (name[0] == 'C' && cfg.mcs_tracking_mode) {  // :1268-1285
-        const bool tb_en[2] = {(cur_en & 1) != 0, (cur_en & 2) != 0};
-        mcs_tracking.update_statistic_dl(d.rnti, (DciFormat)d.format, table, tb_en, crc, mimo_ret, now);
-      }
-      publishPrediction(d.rnti);
-    }
+    CommitHost host{*this, ch, r, c, sf};
+    commit_walk_subframe(ccfg, mcs_tracking, harq_db, c, ch.cdci.data() + k0, k1 - k0, commit_sf_cnt, tables, host);
   }
   if (cfg.harq_mode) harqFlush(ch, r);   // the chunk's keep store is recycled with the chunk: what its buffers hold there (and in the scratch area) goes home now
   for (const DecodeJob& j : ch.jobs) {

@@ -11,6 +11,7 @@
 #pragma once
 #include "../../../include/ltesniffer_amd.h"
 #include "../kernels/lsn_dev.h"
+#include "lsn_commit.h"
 #include "lsn_hip.h"
 #include "lsn_rates.h"
 #include "lsn_search.h"
@@ -62,24 +63,6 @@ struct DecodeJob {
   bool crc[2] = {false, false};
   uint32_t iters = 0;
   uint32_t keep_first[2] = {0, 0}, keep_count[2] = {0, 0};  // harq_mode: this job's code blocks in Chunk::keep_cbs (their soft data sits in Chunk::d_keep)
-};
-
-// Compact views for the sequential commit thread (it walks them linearly instead of chasing the wide DlEntry / DecodeJob records that
-// other threads wrote): one JobRes per decode job (same index), one CommitDci per accepted downlink DCI in (subframe, acceptance) order.
-struct JobRes {
-  uint8_t done = 0, crc[2] = {0, 0}, enabled[2] = {0, 0};
-  uint8_t nsetup[2] = {0, 0};          // RRCConnectionSetups found in a CRC-ok transport block (pre-parsed by the thread that ran the decode)
-  float p_a = 0.0f;
-  uint32_t payload_off[2] = {0, 0};
-  int32_t len[2] = {0, 0};             // tbs / 8
-  uint32_t setup_first[2] = {0, 0};    // into Chunk::setup_cfgs
-};
-struct CommitDci {
-  uint16_t rnti = 0; uint8_t format = 0, flags = 0;   // flags: 1 unpack_ok, 2 ok64, 4 ok256, 8 grant64 has two TBs, 16 grant256 has two TBs
-  uint8_t en64 = 0, en256 = 0, mcs_idx[2] = {0, 0};   // en*: bit i = tb[i].enabled of that table's grant
-  int32_t tbs0_64 = 0, tbs0_256 = 0;                  // tb[0].tbs of the two grants
-  int32_t job[2] = {-1, -1};
-  uint32_t di = 0;                                    // index in SubframeCtx::dl (slow path: a decode has to be created at commit)
 };
 
 // stage-C taps (lsn_phy_set_stage_c_taps): what one decode job left behind in the launch arenas, copied out before they are recycled
@@ -335,6 +318,16 @@ private:
   void searchChunk(Chunk& ch, uint32_t update_meta_period);
   void speculateRar(Chunk& ch);
   void planJobs(Chunk& ch, JobRunner& r);
+  // the steps of planJobs, in order; they hand on one plan.  Speculation only: the commit re-derives every decision
+  struct JobPlan {
+    struct Pending { uint32_t sf; size_t di; bool always; };
+    std::vector<int> wave;                 // the jobs of the next runJobs call
+    std::vector<Pending> retry, deferred;  // unknown-table grants that may want their 256QAM-table attempt; grants held back for the first wave's verdicts
+  };
+  void planFirstWave(Chunk& ch, JobPlan& p);                  // the first decode the reference would attempt for every accepted DL DCI
+  void planSecondWave(Chunk& ch, JobRunner& r, JobPlan& p);   // 256QAM-table retries + the deferred grants (planDeferred)
+  void planDeferred(Chunk& ch, JobRunner& r, JobPlan& p);
+  void noteTeachingEvents(Chunk& ch, const JobPlan& p);       // SharedSeq::hint_pos
   void buildCommitView(Chunk& ch);
   void runJobs(Chunk& ch, JobRunner& r, std::vector<int>& job_ids);
   // the steps of runJobs, in order (harqKeepSoftData, below, sits between the launches and the wait; harqKeepResults inside takeVerdicts)
@@ -348,6 +341,7 @@ private:
   void takeVerdicts(Chunk& ch, JobRunner& r, const DecodeLaunch& L);  // payload bytes, transport-block verdicts, RRCConnectionSetups of the passed blocks
   void ensureJob(Chunk& ch, JobRunner& r, int j);
   void commitChunk(Chunk& ch, JobRunner& r);
+  struct CommitHost;   // lsn_engine.cc: what the commit walk (lsn_commit.h) asks of (engine, chunk, runner, subframe)
   void commitChunkUl(Chunk& ch, JobRunner& r);
   void prachDetectDev(const cf32* d_iq, uint32_t nant, uint32_t ant, uint32_t nsf, uint32_t start_tti, std::vector<lsn_prach_det_t>& out, uint32_t first_sf = 0);
   void puschDecodeGrid(const cf32* d_grid, uint32_t nsf, uint32_t start_tti, const lsn_pusch_grant_t* grants, uint32_t ngrants,

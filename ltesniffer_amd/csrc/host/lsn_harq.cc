@@ -225,21 +225,15 @@ void Engine::harqScout(Chunk& ch, std::vector<HarqReq>& out, bool first_pass)
         const CommitDci& d = ch.cdci[k];
         const char* name = rnti_name(d.rnti);
         if (name[0] != 'C') continue;
-        McsTable table = TABLE_64QAM;
-        if (cfg.mcs_tracking_mode == 1) table = (DciFormat)d.format == FORMAT1A ? TABLE_64QAM : mcs_tracking.peek(d.rnti);
-        else if (cfg.mcs_tracking_mode == 2) table = TABLE_UNKNOWN;
+        const McsTable table = collection_table_from(cfg.mcs_tracking_mode, d.rnti, (DciFormat)d.format, [&] { return mcs_tracking.peek(d.rnti); });
         if (!(table == TABLE_64QAM || table == TABLE_256QAM)) continue;
-        const TableView tv = table_view(table, d.rnti, d.flags & 1, d.flags & 2, d.flags & 4);
         const DlEntry& e = c.dl[d.di];
         if (table == TABLE_64QAM && e.unpack_ok && ((e.grant64.tb[0].enabled && e.grant64.tb[0].mcs_idx > 28) || (e.grant64.tb[1].enabled && e.grant64.tb[1].mcs_idx > 28)))
           continue;   // (a reserved MCS index takes its size from the database at commit and is decoded there)
-        const int cur_t = table == TABLE_256QAM ? 1 : 0;
-        const bool cur_has = cur_t ? tv.has256 : tv.has64;
-        const int32_t cur_tbs0 = cur_has ? (cur_t ? d.tbs0_256 : d.tbs0_64) : 0;
-        const bool two_tb = (tv.has64 && (d.flags & 8)) || (tv.has256 && (d.flags & 16));
-        if (!(cur_tbs0 > 0 && tv.dci_rnti_ok && !(dlRx() == 1 && two_tb))) continue;
-        const int j = d.job[cur_t];
-        if (!cur_has || j < 0 || !ch.jres[j].done || ch.jres[j].p_a != mcs_tracking.get_ue_config_rnti(d.rnti).p_a) continue;
+        const CommitGate g = commit_gate(d, table, dlRx());   // (C-RNTIs only here: the gate's paging clause does not apply)
+        if (!g.gate) continue;
+        const int j = d.job[g.cur_t];
+        if (!g.cur_has || j < 0 || !ch.jres[j].done || ch.jres[j].p_a != mcs_tracking.get_ue_config_rnti(d.rnti).p_a) continue;
         const JobRes& jr = ch.jres[j];
         for (int tb = 0; tb < 2; tb++) {
           if (!jr.enabled[tb]) continue;

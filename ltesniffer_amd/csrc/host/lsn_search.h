@@ -147,11 +147,17 @@ const char* rnti_name(uint16_t r);  // DL_Sniffer_PDSCH.cc:1398-1418
 
 // DCICollection::addCandidate, DCICollection.cc:107-134: the MCS table an accepted DCI is collected under (the tracking database is asked for every user
 // RNTI that does not come in format 1A - the look-up refreshes the entry's time stamp)
-inline McsTable collection_table(int mcs_tracking_mode, uint16_t rnti, DciFormat format, MCSTracking& mcs_tracking, uint32_t now)
+// `tracked()`: where the table of a user RNTI comes from - the database itself at commit, what is known of it ahead of the commit for a prediction
+template <class F>
+inline McsTable collection_table_from(int mcs_tracking_mode, uint16_t rnti, DciFormat format, F&& tracked)
 {
   if (mcs_tracking_mode == 1)
-    return (rnti == SIRNTI || rnti == PRNTI || rnti_israr(rnti) || format == FORMAT1A) ? TABLE_64QAM : mcs_tracking.find_tracking_info_RNTI_dl(rnti, now);
+    return (rnti == SIRNTI || rnti == PRNTI || rnti_israr(rnti) || format == FORMAT1A) ? TABLE_64QAM : tracked();
   return mcs_tracking_mode == 2 ? TABLE_UNKNOWN : TABLE_64QAM;
+}
+inline McsTable collection_table(int mcs_tracking_mode, uint16_t rnti, DciFormat format, MCSTracking& mcs_tracking, uint32_t now)
+{
+  return collection_table_from(mcs_tracking_mode, rnti, format, [&] { return mcs_tracking.find_tracking_info_RNTI_dl(rnti, now); });
 }
 // srsran_dci_msg_to_trace_timestamp, falcon_dci.c:284-310: which of the two grants of a downlink entry the reference computes under that table, and
 // whether the unpacked DCI keeps its RNTI (a failed conversion sets it to 0: "to avoid decode")

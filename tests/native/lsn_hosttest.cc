@@ -1,5 +1,6 @@
-// Test glue (NOT product): exposes the HIP-free host logic of the product (lsn_lte.cc, lsn_search.cc) through a
+// Test glue (NOT product): exposes the HIP-free host logic of the product (lsn_lte.cc, lsn_search.cc, lsn_commit.cc) through a
 // C interface so that the CPU test-suite can compare it with the oracle without a GPU.
+#include "commit_script_host.h"
 #include "../../ltesniffer_amd/csrc/host/lsn_search.h"
 #include "../../ltesniffer_amd/csrc/kernels/lsn_rm.h"
 #include <chrono>
@@ -510,6 +511,44 @@ uint32_t lsnh_collect_subframe(void* p, uint32_t sfn, uint32_t sf_idx, uint32_t 
   }
   counts2[0] = (uint32_t)c.dl.size(); counts2[1] = (uint32_t)c.ul.size();
   return (b1.nof_subframe_collisions_dw != b0.nof_subframe_collisions_dw ? 1u : 0u) | (b1.nof_subframe_collisions_up != b0.nof_subframe_collisions_up ? 2u : 0u);
+}
+
+// ---- PDSCH_Decoder::decode_dl_mode as the product does it (tests/test_ref_decode.py: the REFERENCE's DL_Sniffer_PDSCH.cc, oracle/_ref) ----
+// FalconSearch::finishSubframe, the commit view and the commit walk of lsn_commit.h - the code the engine's commit thread runs - with a host whose PDSCH decoder
+// is a script (signature of o_worker_set_script_decoder): every decode is made on demand, configured by configure_decode like Engine::newJob's.
+void* lsnh_commit_new(uint32_t nof_prb, uint32_t nof_ports, uint32_t cell_id, uint32_t cp, int mcs_tracking_mode, int harq_mode, uint32_t nof_rx)
+{
+  hcommit* h = new hcommit();
+  commit_script_init(*h, nof_prb, nof_ports, cell_id, cp, mcs_tracking_mode, harq_mode, nof_rx);
+  return h;
+}
+void lsnh_commit_free(void* p) { delete (hcommit*)p; }
+void lsnh_commit_set_script(void* p, void* fn, void* user) { ((hcommit*)p)->script = (lsnh_script_fn)fn; ((hcommit*)p)->script_user = user; }
+void lsnh_commit_set_now(void* p, uint32_t now) { ((hcommit*)p)->now = now; }
+void lsnh_commit_update_database(void* p) { hcommit* h = (hcommit*)p; h->mcs.update_database_dl(h->now); }
+// state probes (ref_decode.Oracle.state): the look-up refreshes the entry's time stamp like find_tracking_info_RNTI_dl does; out6 as lsnh_mcs_get
+int lsnh_commit_find_table(void* p, uint16_t rnti) { hcommit* h = (hcommit*)p; return (int)h->mcs.find_tracking_info_RNTI_dl(rnti, h->now); }
+int lsnh_commit_activation_reason(void* p, uint16_t rnti) { return (int)((hcommit*)p)->rm->getActivationReason(rnti); }
+uint32_t lsnh_commit_nof_tracked(void* p) { return ((hcommit*)p)->mcs.nof_RNTI_member_dl(); }
+void lsnh_commit_ue_config(void* p, uint16_t rnti, uint32_t* out6) { lsnh_mcs_get(&((hcommit*)p)->mcs, rnti, out6); }
+void lsnh_commit_harq_stats(void* p, uint32_t* out5) { for (int i = 0; i < 5; i++) out5[i] = (uint32_t)((hcommit*)p)->harq.stats[i]; }
+// one subframe of n accepted DCI (meta6 / bits as lsnh_collect_subframe) through finishSubframe, the commit view and the walk.  Returns the number of records:
+// recs5 = {kind, tti, rnti, length, offset into the payload bytes} each (cap records), their bytes back to back in bytes (byte_cap); -1 when they do not fit
+int lsnh_commit_subframe(void* p, uint32_t sfn, uint32_t sf_idx, uint32_t cfi, uint32_t n, const uint32_t* meta6, const uint8_t* bits, uint32_t* recs5, uint32_t cap, uint8_t* bytes,
+                         uint32_t byte_cap)
+{
+  hcommit* h = (hcommit*)p;
+  commit_script_subframe(*h, sfn, sf_idx, cfi, n, meta6, bits);
+  uint32_t at = 0;
+  for (size_t i = 0; i < h->recs.size(); i++) {
+    const hcommit::Rec& r = h->recs[i];
+    if (i >= cap || at + r.len > byte_cap) return -1;
+    std::memcpy(bytes + at, h->payload.data() + r.off, r.len);
+    uint32_t* o = recs5 + 5 * i;
+    o[0] = r.kind; o[1] = r.tti; o[2] = r.rnti; o[3] = r.len; o[4] = at;
+    at += r.len;
+  }
+  return (int)h->recs.size();
 }
 
 // the product's RNTIManager on its own (tests/test_ref_rnti_manager.py: operation sequences against the REFERENCE's RNTIManager.cc, oracle/_ref)

@@ -4,7 +4,7 @@ classes, oracle/ref_shim_search/decode_glue.cc).  The PDSCH decoder itself (srsR
 verdicts and payload bytes - random bytes, real RRCConnectionSetup PDUs (the reference's own captures), random-access responses - and the same function answers the
 oracle's decode calls (o_worker_set_script_decoder).  Compared per subframe: every decode call as configured (grant of the table that was tried, MIMO configuration,
 redundancy versions, p_a), every record handed to the pcap writer; at check points the tracking database, the RNTI manager's activation reasons, the UE
-configurations.  Test infrastructure only."""
+configurations.  A third side, Product, runs the same lives through the product's commit walk (csrc/host/lsn_commit.h).  Test infrastructure only."""
 import ctypes as C
 import hashlib
 import json
@@ -125,14 +125,17 @@ def _tb0_mcs(o, cell, fmt, rnti, bits):
     return d.tb[0].mcs_idx
 
 
-def script(life, reserved_first_block=False):
+def script(life, reserved_first_block=False, mcs28_share=0.0):
     """like ref_collect.script, with what the decoders need on top: RNTIs of a UE pool whose DCI come in the formats of their transmission mode, common RNTIs in
     formats 1A / 1C, and now and then an ageing pass of the tracking database.
 
     One kind of DCI is left out unless `reserved_first_block`: a user grant beyond format 1A whose FIRST block carries I_MCS >= 28 or is disabled.  Under the 256QAM table
     that block has no size of its own, and decode_dl_mode's gate (DL_Sniffer_PDSCH.cc:887) then reads tb[0].tbs of the 64QAM-table grant - which the reference did not compute
     for a 256QAM-table entry: uninitialised memory, i.e. whatever an earlier grant left in that heap block.  The oracle defines the gate on the grant that is used
-    (o_worker.c header).  tests/test_ref_decode.py has a test of its own for that case."""
+    (o_worker.c header).  tests/test_ref_decode.py has a test of its own for that case.
+
+    mcs28_share (with reserved_first_block): that share of the user grants beyond format 1A gets a first block with I_MCS 28 - the last index the 64QAM table gives a
+    size, and the bound of its learning rule (DL_Sniffer_PDSCH.cc:1168-1171)."""
     name, nprb, ports, cid, cp, mode, harq, nrx, nsf, seed, fill = life
     rng = random.Random(seed)
     o = oracle()
@@ -157,13 +160,17 @@ def script(life, reserved_first_block=False):
                 rnti = rng.choice(ues)
                 fmt = rng.choice((fmt_of[rnti], fmt_of[rnti], fmt_of[rnti], RC.FMT1A, RC.FMT0))
             n = sizes[fmt]
+            want28 = mcs28_share > 0 and fmt not in (RC.FMT0, RC.FMT1A, RC.FMT1C) and 0x000B <= rnti <= 0xFFF3 and rng.random() < mcs28_share
             while True:
                 bits = [rng.randrange(2) for _ in range(n)]
                 if fmt == RC.FMT0:
                     bits[0] = 0
                 if fmt == RC.FMT1A:
                     bits[0] = 1
-                if reserved_first_block or fmt in (RC.FMT0, RC.FMT1A, RC.FMT1C) or not (0x000B <= rnti <= 0xFFF3) or _tb0_mcs(o, cell, fmt, rnti, bits) < 28:
+                if want28:
+                    if _tb0_mcs(o, cell, fmt, rnti, bits) == 28:
+                        break
+                elif reserved_first_block or fmt in (RC.FMT0, RC.FMT1A, RC.FMT1C) or not (0x000B <= rnti <= 0xFFF3) or _tb0_mcs(o, cell, fmt, rnti, bits) < 28:
                     break
             L = rng.randrange(4)
             dcis.append((rnti, fmt, L, rng.randrange(0, 80) // (1 << L) * (1 << L), rng.randrange(0, 40), bits))
@@ -322,9 +329,82 @@ class Oracle:
         return (self.o.o_worker_nof_tracked(self.h), out)
 
 
-def run(side, life, reserved_first_block=False):
-    """-> list of per-subframe (decode calls [(call16, p_a, verdicts)], records) + check points ("state", ...)"""
-    ues, ev = script(life, reserved_first_block)
+class Product:
+    """the product's commit stage without a GPU: FalconSearch::finishSubframe, the commit view and the commit walk of csrc/host/lsn_commit.h (the code the engine's
+    commit thread runs) with a host whose decodes are the scripted decoder's (tests/native/lsn_hosttest.cc: lsnh_commit_*)"""
+    name = "product"
+
+    def __init__(self):
+        from lsn_testlib import hosttest
+        self.lib = hosttest()
+        L = self.lib
+        L.lsnh_commit_new.restype = C.c_void_p
+        L.lsnh_commit_new.argtypes = [C.c_uint32] * 4 + [C.c_int] * 2 + [C.c_uint32]
+        L.lsnh_commit_free.argtypes = [C.c_void_p]
+        L.lsnh_commit_set_script.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.lsnh_commit_set_now.argtypes = [C.c_void_p, C.c_uint32]
+        L.lsnh_commit_update_database.argtypes = [C.c_void_p]
+        L.lsnh_commit_find_table.argtypes = [C.c_void_p, C.c_uint16]
+        L.lsnh_commit_activation_reason.argtypes = [C.c_void_p, C.c_uint16]
+        L.lsnh_commit_nof_tracked.restype = C.c_uint32
+        L.lsnh_commit_nof_tracked.argtypes = [C.c_void_p]
+        L.lsnh_commit_ue_config.argtypes = [C.c_void_p, C.c_uint16, C.c_void_p]
+        L.lsnh_commit_harq_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.lsnh_commit_subframe.argtypes = [C.c_void_p] + [C.c_uint32] * 4 + [C.c_void_p] * 3 + [C.c_uint32, C.c_void_p, C.c_uint32]
+
+    def open(self, life, dec):
+        name, nprb, ports, cid, cp, mode, harq, nrx, nsf, seed, fill = life
+        self.h = self.lib.lsnh_commit_new(nprb, ports, cid, cp, mode, harq, nrx)
+        self.lib.lsnh_commit_set_script(self.h, C.cast(dec.fn, C.c_void_p), None)
+
+    def close(self):
+        self.lib.lsnh_commit_free(self.h)
+
+    def now(self, k):
+        self.lib.lsnh_commit_set_now(self.h, k)
+
+    def age(self):
+        self.lib.lsnh_commit_update_database(self.h)
+
+    def subframe(self, sfn, sf_idx, cfi, dcis):
+        n = len(dcis)
+        meta = (C.c_uint32 * (6 * max(n, 1)))()
+        bits = (C.c_uint8 * (128 * max(n, 1)))()
+        for i, (rnti, fmt, L, ncce, hv, b) in enumerate(dcis):
+            meta[6 * i:6 * i + 6] = [rnti, fmt, L, ncce, hv, len(b)]
+            bits[128 * i:128 * i + len(b)] = b
+        recs, data = (C.c_uint32 * (5 * 64))(), (C.c_uint8 * (64 * 16384))()
+        k = self.lib.lsnh_commit_subframe(self.h, sfn, sf_idx, cfi, n, meta, bits, recs, 64, data, len(data))
+        assert k >= 0
+        raw = bytes(data)   # (the crc field of a record is 1 by construction: the walk emits a record only for a block whose CRC passed, as write_pcap's callers do)
+        return [(recs[5 * i], recs[5 * i + 1], recs[5 * i + 2], recs[5 * i + 3], 1, _fnv(raw[recs[5 * i + 4]:recs[5 * i + 4] + recs[5 * i + 3]])) for i in range(k)]
+
+    def harq_stats(self):
+        st = (C.c_uint32 * 5)()
+        self.lib.lsnh_commit_harq_stats(self.h, st)
+        return tuple(st)
+
+    def state(self, rntis):
+        out = []
+        for r in rntis:
+            w = (C.c_uint32 * 6)()
+            table = self.lib.lsnh_commit_find_table(self.h, r)
+            self.lib.lsnh_commit_ue_config(self.h, r, w)
+            out.append((r, table, self.lib.lsnh_commit_activation_reason(self.h, r), round(struct.unpack("<f", struct.pack("<I", w[0]))[0], 3), w[5], w[1], w[2], w[3], w[4]))
+        return (self.lib.lsnh_commit_nof_tracked(self.h), out)
+
+
+# A life of its own for the product's commit walk, run live against the oracle (tests/test_ref_decode.py): first blocks with I_MCS >= 28 stay in the script and
+# a third of the user grants beyond format 1A carries I_MCS 28 there, so undecided UEs pass blocks at the upper bound of the 64QAM table's learning rule; the
+# tracking clock makes `stride` subframes per step, so the 5 000-subframe idle limit passes between two ageing events - entries are deleted and learnt again all
+# the time, and a UE that only an uplink grant kept alive (the look-ups of format 0 DCIs) is told from one that nothing did
+WALK_PINS_LIFE = ("walk_pins", 100, 2, 4, 0, 1, 0, 2, 600, 41, 1)
+WALK_PINS = dict(reserved_first_block=True, stride=400, mcs28_share=0.33)
+
+
+def run(side, life, reserved_first_block=False, stride=1, mcs28_share=0.0):
+    """-> list of per-subframe (decode calls [(call16, p_a, verdicts)], records) + check points ("state", ...); stride: subframes of the tracking clock per step"""
+    ues, ev = script(life, reserved_first_block, mcs28_share)
     dec = ScriptedDecoder(life[9], ues)
     side.open(life, dec)
     out, k = [], 0
@@ -335,7 +415,7 @@ def run(side, life, reserved_first_block=False):
             out.append(("state", side.state(probe)))
             continue
         k += 1
-        side.now(k)
+        side.now(k * stride)
         dec.log = []
         recs = side.subframe(e[1], e[2], e[3], e[4])
         out.append((list(dec.log), recs))

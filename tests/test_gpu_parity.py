@@ -10,10 +10,10 @@ from parity import CfoLoop, compare_candidate_tables, compare_stage_c, compare_t
 pytestmark = pytest.mark.gpu
 
 
-def _run(scn, nsf, seed=1, batch=16, update_meta_period=0, exact_iters=False, cfo_correction=None, **over):
+def _run(scn, nsf, seed=1, batch=16, update_meta_period=0, exact_iters=False, cfo_correction=None, perf=None, **over):
     """stage-A taps, stage-C taps (int16 soft bits, de-rate-matched streams, per-code-block verdict + iterations), record stream and statistics
     of the HIP path against the oracle; exact_iters: the engine runs without first-block gating (LSN_NO_CB_SKIP=1), so every code block of
-    every decode call the oracle made carries a verdict and the iteration totals must agree"""
+    every decode call the oracle made carries a verdict and the iteration totals must agree; perf: a list that gets the engine's counters at the end"""
     import os
     sc = scenario(scn, seed=seed, **over)
     tti0, iq, truth = gen_subframes(sc, nsf)
@@ -54,6 +54,8 @@ def _run(scn, nsf, seed=1, batch=16, update_meta_period=0, exact_iters=False, cf
     for f in ("nof_locations", "nof_decoded_locations", "nof_cce", "nof_missed_cce", "nof_subframes",
               "nof_subframe_collisions_dw", "nof_subframe_collisions_up"):
         assert getattr(st, f) == getattr(ost, f), f
+    if perf is not None:
+        perf.append(phy.perf())
     phy.close()
     if loop:
         return len(o), loop

@@ -16,7 +16,9 @@ def test_connection_setup_p_a_feedback():
     decode decision behind it) equals the oracle's whether the decodes were planned before the connection setup was committed
     (one big chunk: planned with the old p-a, dropped and decoded again at commit) or chunk by chunk"""
     kw = dict(nof_prb=25, n_rnti=3, dl_min=3, dl_max=3, ul_min=0, ul_max=0, mcs_min=20, mcs_max=28, msg4_period=6, snr_db=36.0)
-    assert _run("cfg2", 40, seed=3, batch=40, msg4_p_a_idx=0, **kw) > 60
+    perf = []
+    assert _run("cfg2", 40, seed=3, batch=40, msg4_p_a_idx=0, perf=perf, **kw) > 60
+    assert perf[0].nof_ondemand_commit[0] > 0   # grants planned with the old p-a went through the commit's on-demand path (a planned job dropped and decoded again)
     _run("cfg2", 40, seed=3, batch=4, msg4_p_a_idx=7, **kw)
     _run("cfg3", 30, seed=4, batch=10, nof_prb=50, n_rnti=12, dl_min=4, dl_max=6, msg4_period=4, msg4_p_a_idx=8, update_meta_period=10)
 

@@ -374,6 +374,14 @@ def test_turbo_order_and_placement_under_sanitizers():
     assert out.startswith("OK")
 
 
+def test_commit_walk_under_sanitizers():
+    """the commit walk (csrc/host/lsn_commit.h) with a scripted decoder in a program of its own built with -fsanitize=address,undefined: random DCIs through
+    finishSubframe, the commit view and the walk, tracking database off / on / both tables, HARQ on"""
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "tests", "native"), "_build/test_commit_walk"], stdout=subprocess.DEVNULL)
+    out = subprocess.check_output([os.path.join(ROOT, "tests", "native", "_build", "test_commit_walk")]).decode()
+    assert out.startswith("OK")
+
+
 def _search_parity(scn, nsf, seed, update_meta_period=0, **over):
     """FALCON search of the product over oracle-decoded candidate tables == the oracle worker's own search."""
     h = hosttest()
