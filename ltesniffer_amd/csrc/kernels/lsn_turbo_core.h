@@ -12,6 +12,9 @@
 //   alpha recompute                27.3 / 28.3     23.3 / 25.3             23.6 / 25.6
 //   beta + soft output             50.9 / 49.9     44.9 / 44.5             37.7 / 37.3
 //   per step of a 64-step window   (forward sweep over 48 of the 64 steps)  85.8 / 89.9  ->  78.9 / 83.0
+//   The forward sweep runs over W - 16 steps of a window of W steps: the sub-block it leaves to the recompute is the last one, and the SHORT sub-block
+//   (W mod 16 steps) comes first, so that the one left out is always a full one (lsn_turbo_sb below).  Until round 6 the short one came last and the sweep ran
+//   over 16 (ceil(W / 16) - 1) steps: 32 instead of 20 at W = 36, 32 instead of 17 at W = 33 - 14.7 % of the forward-sweep steps of the metric's workload.
 //   round 5: operands of two steps built together (lsn_operands2), alpha normalised every second step in the recompute too, soft outputs of two steps on packed
 //   halves (lsn_ext_two), (g10, g11) with one add, lanes without a window masked instead of redirected per step;
 //   round 6: no shuffles inside a full-length sub-block (the cycle of seven register layouts, lsn_turbo_cyc.h: - 3.75 per step), beta normalised behind every
@@ -21,23 +24,34 @@
 //  * forward: butterfly k reads states 2k, 2k+1 and writes k, k+4 - with the operands taken as half-broadcasts (op_sel) layout C maps to
 //    itself: 8 v_pk_add + 4 v_pk_max per step.
 //  * backward: the pairs that meet alpha (k, k+4) need beta pairs (0,2) (4,6) (1,3) (5,7): four v_perm per step, then 8 v_pk_add
-//    (branch + beta), 8 v_pk_add (+ alpha), 6 + 4 v_pk_max; the result is layout C again.  (The short last sub-block of a window; the full-length ones
+//    (branch + beta), 8 v_pk_add (+ alpha), 6 + 4 v_pk_max; the result is layout C again.  (The short first sub-block of a window; the full-length ones
 //    walk through the seven layouts of lsn_turbo_cyc.h, in which neither direction shuffles.)
 // Word length (int16, no wrap-around anywhere - v_pk_max_i16 compares values, not residues):
 //   |gamma| <= |sys| + |ext| + |par| <= 512 + 2047 + 512 = 3071 per step.  Any state is reached from any state in 3 steps, so a metric
 //   vector normalised to state 0 spreads at most 3 * 3071 = 9213 once it is 3 steps away from its initialisation; the initialisations are
 //   (0, -12000 x 7), the termination metrics (<= 3 * 1022) and boundary metrics of the previous iteration (<= 9213).
-//   Alpha is normalised behind every ODD step (forward sweep and recompute; sub-blocks start at even steps).  In front of an even step t it is normalised:
-//   <= 9213 at t = 0 (boundary metrics), <= 15355 at t = 2 (two steps of growth), <= 9213 from t = 4 on; in front of an odd step it carries the growth of
-//   one more step: <= 12284 at t = 1, <= 18426 at t = 3, <= 12284 from t = 5 on.  The first window starts from (0, -12000 x 7) instead: 12000 at t = 0,
-//   <= 15071 at t = 1 and <= 18142 at t = 2 - on the NEGATIVE side only (the states that cannot be reached yet still carry the initial -12000, the reached
-//   ones are within 2 * 3071) -, and as every other window from t = 3 on.
-//   Beta (round 6, last session) is normalised behind every EVEN step of a full-length sub-block and behind every step of the short last one.  Let N(t) bound
-//   the NORMALISED vector that enters step t: N(W-1) = 9213 (the initialisation), N(W-2) = 12284, N(W-3) = 15355, N(t) = 9213 below (three steps away).
-//   A vector that enters an odd step is normalised (<= N(t)); one that enters an even step is at worst the raw result of the odd step behind it,
-//   <= N(t+1) + 3071 (<= 12284 in general, 18426 at t = W-4, 15355 at t = W-3, 12284 at t = W-2).  A window has at least 32 steps, so the young ends never meet:
-//     odd t:   |alpha| + |beta| + |gamma| <= max(12284 + 15355, 18426 + 9213) + 3071 = 30710
-//     even t:  <= max(9213 + 18426, 15355 + 12284) + 3071 = 30710;  first window, t = 0: 12000 + 12284 + 3071;  t = 2: 18142 + 12284 + 3071 = 33497 - beyond int16, but on the
+//   Both recursions are normalised by the step's position u INSIDE its sub-block, not by the parity of t: a window starts with a sub-block of s0 = W mod 16
+//   steps (16 when that is zero), so with an odd s0 the full sub-blocks start at odd steps.  What the argument needs is that neither vector ever goes more than
+//   one step without normalisation, and that the two are never both un-normalised in front of the same step:
+//    * alpha is normalised behind every odd u (forward sweep and recompute) and, in the forward sweep, behind the last step of sub-block 0 whatever its parity
+//      (what is check-pointed or carried into the next sub-block is normalised; check-points restart the recompute).  So alpha is normalised in front of every
+//      even u and carries the growth of one step in front of every odd u.
+//    * beta is normalised behind every even u of a full sub-block and behind every step of the short sub-block 0; the vector a sub-block receives from the one
+//      behind it left that one's step u = 0, normalised.  So beta is normalised when it enters an odd u (and any step of sub-block 0) and carries the growth of
+//      one step when it enters an even u of a full sub-block.
+//   A normalised vector is the vector of differences to state 0, which does not depend on where the normalisations fell.  Let Na(t) bound normalised alpha in front
+//   of step t and Nb(t) normalised beta entering step t: Na(0) = 9213 (boundary metrics), Na(1) = 12284, Na(2) = 15355 (one, two steps of growth on top of
+//   an arbitrary start), Na(t) = 9213 from t = 3 on; Nb(W-1) = 9213 (the initialisation), Nb(W-2) = 12284, Nb(W-3) = 15355, Nb(t) = 9213 below.  An un-normalised
+//   vector is the raw result of one step on a normalised one: alpha <= Na(t-1) + 3071 (12284 at t = 1, 15355 at t = 2, 18426 at t = 3, 12284 from t = 4 on),
+//   beta <= Nb(t+1) + 3071 (12284 at t = W-2, 15355 at t = W-3, 18426 at t = W-4, 12284 below).  The first window starts from (0, -12000 x 7) instead: the
+//   differences to state 0 of the states that cannot be reached yet are within 12000 + 3071 t on the NEGATIVE side (12000, 15071, 18142 in front of t = 0, 1, 2;
+//   one step grows a value and a difference by at most 3071 each, so this holds normalised or not), the reached ones within 3071 t, and from t = 3 on it is
+//   as every other window.  A window has at least 32 steps, so the young ends (t <= 3, t >= W-4) never meet, and the last four steps of a window lie in a full
+//   sub-block, u = 12 .. 15:
+//     alpha normalised, beta not (even u of a full sub-block):  |alpha| + |beta| + |gamma| <= max(15355 + 12284, 9213 + 18426) + 3071 = 30710
+//     beta normalised, alpha not (odd u):                       <= max(18426 + 9213, 12284 + 15355) + 3071 = 30710
+//     both normalised (sub-block 0, even u):                    <= 15355 + 9213 + 3071
+//     first window, t <= 2: 12000 + 3071 t + 12284 + 3071, at t = 2 18142 + 12284 + 3071 = 33497 - beyond int16, but on the
 //              negative side only and only in sums over states that cannot be reached yet.  The alpha + (beta + gamma) adds SATURATE (pka_sat: v_pk_add_i16 clamp):
 //              a saturated sum is below -32768 in exact arithmetic while the maximum it competes in is at least the state-0 term >= -(12284 + 3071), so it
 //              loses either way and every maximum equals the exact one.  beta + gamma alone stays within 18426 + 3071.
@@ -325,8 +339,41 @@ LSN_HD void lsn_operands2(uint32_t ws0, uint32_t ws1, uint32_t es0, uint32_t es1
 #define TB_CKPT_BYTES ((size_t)3584)
 static_assert(TB_S == 16, "the check-point area is sized for sub-blocks of 16 steps");
 
-// interleaver address table of one block size, two trellis steps per word: dst[(t / 2) * P + w] = a(t) | a(t + 1) << 16 for even t, with
-// a(t) = transposed address of pi(w * W + t), pi(x) = (f1 x + f2 x^2) mod K (36.212 5.1.3.2.3); lsn_turbo_il_words(K) words (lsn_rm.h)
+// Sub-blocks of a window of W steps: nsb = ceil(W / TB_S) of them, the SHORT one first.  Sub-block 0 has s0 = W mod TB_S steps (TB_S when that is zero), every
+// other one TB_S: the forward sweep runs over sub-blocks 0 .. nsb-2 and leaves the last one to the recompute of the backward pass, so the sub-block it skips is
+// always a full one - W - TB_S forward-sweep steps per pass.  (Until round 6 the short sub-block came last and was the one skipped: TB_S (nsb - 1) steps,
+// up to 31 of them for one step of progress.)  This is the one place that knows where a sub-block starts, how long it is and where its interleaver addresses
+// lie; a window has at least 32 steps (lsn_turbo_nwin), so there are always at least two sub-blocks.
+struct LsnSubBlock {
+  int start;  // first step of the sub-block
+  int len;    // its steps: s0 for sub-block 0, TB_S for the others
+  int word;   // first word of its steps in the window's column of the interleaver address table (lsn_turbo_il_fill)
+};
+LSN_HD int lsn_turbo_nsb(int W) { return (W + TB_S - 1) / TB_S; }
+LSN_HD LsnSubBlock lsn_turbo_sb(int W, int sb)
+{
+  const int d = -W & (TB_S - 1);   // TB_S - s0: what sub-block 0 lacks
+  const int start = sb * TB_S - d, word = sb * (TB_S / 2) - (d >> 1);   // (TB_S / 2 - (d >> 1) = ceil(s0 / 2) words hold sub-block 0)
+  return LsnSubBlock{start > 0 ? start : 0, sb ? TB_S : TB_S - d, word > 0 ? word : 0};
+}
+// forward-sweep steps of one pass over a window: the sub-blocks the sweep runs over, summed
+LSN_HD int lsn_turbo_fwd_steps(int W)
+{
+  int n = 0;
+  for (int sb = 0; sb + 1 < lsn_turbo_nsb(W); sb++) n += lsn_turbo_sb(W, sb).len;
+  return n;
+}
+// (a host test build counts the forward-sweep steps a pass really runs: tests/native/test_turbo_subblocks.cc)
+#ifndef LSN_FWD_SWEEP_COUNT
+#define LSN_FWD_SWEEP_COUNT(n) (void)0
+#endif
+// sub-block of step t of a window
+LSN_HD int lsn_turbo_sb_of(int W, int t) { return (t + (-W & (TB_S - 1))) / TB_S; }
+
+// interleaver address table of one block size, two trellis steps per word, paired INSIDE their sub-block (the pairs build2 consumes together): step t =
+// lsn_turbo_sb(W, sb).start + u lies in dst[(lsn_turbo_sb(W, sb).word + u / 2) * P + w], half u & 1, and holds a(t) = transposed address of pi(w * W + t),
+// pi(x) = (f1 x + f2 x^2) mod K (36.212 5.1.3.2.3).  With an odd s0 the upper half of the last word of sub-block 0 belongs to no step: it stays 0, a valid
+// address (the operand built from it is never used).  ceil(s0 / 2) + (TB_S / 2) (nsb - 1) = ceil(W / 2) words per window: lsn_turbo_il_words(K) words (lsn_rm.h)
 LSN_HD void lsn_turbo_il_fill(uint32_t* dst, int K, int f1, int f2)
 {
   const int P = lsn_turbo_nwin(K), W = K / P;
@@ -335,15 +382,17 @@ LSN_HD void lsn_turbo_il_fill(uint32_t* dst, int K, int f1, int f2)
     for (int t = 0; t < W; t++) {
       const long long x = (long long)w * W + t;
       const int pi = (int)(((long long)f1 * x + (long long)f2 * x % K * x) % K);
-      dst[(t >> 1) * P + w] |= (uint32_t)((pi % W) * P + pi / W) << (16 * (t & 1));
+      const LsnSubBlock b = lsn_turbo_sb(W, lsn_turbo_sb_of(W, t));
+      const int u = t - b.start;
+      dst[(b.word + (u >> 1)) * P + w] |= (uint32_t)((pi % W) * P + pi / W) << (16 * (u & 1));
     }
 }
 
 // One constituent decoder, the part of one lane (= window `wl`; only lanes with a window run it - the caller masks the others, they meet the working
 // lanes again at the caller's barriers).  nii_a / nii_b: boundary metrics of the previous iteration (layout C); beta_tail: termination metrics (layout C);
 // a_end / b_out: this window's metrics at its end / start, for the exchange between the lanes (the caller's business).
-// il (second decoder only): il[(t / 2) * P + w] = transposed LDS addresses of the positions the QPP interleaver gives steps t, t + 1 of
-// window w, 16 bits each (lsn_turbo_il_fill above; one table per block size, 1.1 MB for all 188 sizes, L2 resident).  The addresses of a sub-block are fetched one
+// il (second decoder only): transposed LDS addresses of the positions the QPP interleaver gives the steps of window w, 16 bits each, two steps of a
+// sub-block per word (lsn_turbo_il_fill above; one table per block size, 1.1 MB for all 188 sizes, L2 resident).  The addresses of a sub-block are fetched one
 // sub-block ahead of their use: the L2 latency hides behind the recursion of the sub-block in hand.  (Rounds 1-2 stepped the QPP recursion
 // pi += g, g += 2 f2 per lane and divided by W with a multiply: 14 instructions per step and direction instead of one load.)
 template <bool IL>
@@ -362,7 +411,7 @@ LSN_HD void lsn_map_pass_lane(const TurboLds& m, const uint32_t* il, int nt, int
 #define LSN_LOCAL_ADDR(x) (void)(x)
 #endif
   const uint32_t bias2 = (uint32_t)m.bias * 0x10001u;  // (addresses stay below 2^16: K + bias <= 2 * 2760)
-  const int nsb = (W + TB_S - 1) / TB_S;
+  const int nsb = lsn_turbo_nsb(W);
   s2 a[4], b[4];
   // the window's first alpha vector: wanted again when the backward pass reaches sub-block 0 (read from the caller's registers a second time rather than kept)
   auto a_start = [&]() {
@@ -376,18 +425,17 @@ LSN_HD void lsn_map_pass_lane(const TurboLds& m, const uint32_t* il, int nt, int
   a_start();
   uint32_t nx[TB_S / 2];   // interleaver addresses (two steps per word) of the sub-block that comes next
   uint32_t cur[TB_S / 2];  // ... of the sub-block in hand
-  const int wlast = (W - 1) >> 1;
+  // (always TB_S / 2 words: behind a short sub-block 0 they are words of sub-block 1 - a window has at least TB_S / 2 words after any sub-block's first)
   auto il_load = [&](int sb) {
+    const int w0 = lsn_turbo_sb(W, sb).word;
 #pragma unroll
-    for (int u = 0; u < TB_S / 2; u++) {
-      int t2 = sb * (TB_S / 2) + u;
-      t2 = t2 < wlast ? t2 : wlast;
-      nx[u] = (il + (uint32_t)(t2 * P))[wl] + bias2;  // uniform row address + lane offset; both 16-bit addresses of the word move by the block's index bias
-    }
+    for (int u = 0; u < TB_S / 2; u++)
+      nx[u] = (il + (uint32_t)((w0 + u) * P))[wl] + bias2;  // uniform row address + lane offset; both 16-bit addresses of the word move by the block's index bias
   };
   if (IL) il_load(0);
   uint32_t g[TB_S];  // operands of one sub-block: lsa (low half) | lp << 16
-  // operands of steps tb + u, tb + u + 1 (u even); a step past the end of the window (odd W, last pair) reads the spare entries behind the block
+  // operands of steps tb + u, tb + u + 1 (u even; tb = first step of the sub-block); a step past the end of a short sub-block 0 (odd length, last pair)
+  // reads the first step of sub-block 1 in the natural order and address 0 of the block in the interleaved one (lsn_turbo_il_fill) - and is not used
   auto build2 = [&](int tb, int u) {
     const int nat0 = (tb + u) * P + wlb, nat1 = nat0 + P;
     if (IL) {
@@ -398,22 +446,44 @@ LSN_HD void lsn_map_pass_lane(const TurboLds& m, const uint32_t* il, int nt, int
       lsn_operands2<10>(w0, w1, (uint16_t)m.ext[nat0], (uint16_t)m.ext[nat1], w0, w1, &g[u], &g[u + 1]);
     }
   };
-  // ---- forward sweep over sub-blocks 0 .. nsb-2 (the last one is covered by the recompute below) ----
+  // ---- forward sweep over sub-blocks 0 .. nsb-2 (the last one, always a full one, is covered by the recompute below) ----
   for (int sb = 0; sb + 1 < nsb; sb++) {
     LSN_LOCAL_ADDR(wlb);
     if (sb >= 1) lsn_ckpt_store(m.ckpt, nt, sb - 1, lane, a, m.cw, m.ch);
-    const int tb = sb * TB_S;
+    const LsnSubBlock s = lsn_turbo_sb(W, sb);
+    const int tb = s.start, n = s.len;
     if (IL) {
 #pragma unroll
       for (int u = 0; u < TB_S / 2; u++) cur[u] = nx[u];
       il_load(sb + 1);
     }
+    if (n == TB_S) {
 #pragma unroll
-    for (int u = 0; u < TB_S; u += 2) build2(tb, u);
+      for (int u = 0; u < TB_S; u += 2) build2(tb, u);
 #pragma unroll
-    for (int u = 0; u < TB_S; u += 2) {
-      lsn_step_fwd_pk<false>(a, pk_s2(g[u]));
-      lsn_step_fwd_pk<true>(a, pk_s2(g[u + 1]));
+      for (int u = 0; u < TB_S; u += 2) {
+        lsn_step_fwd_pk<false>(a, pk_s2(g[u]));
+        lsn_step_fwd_pk<true>(a, pk_s2(g[u + 1]));
+        LSN_FWD_SWEEP_COUNT(2);
+      }
+    } else {
+      // the short sub-block 0 (n is the same for every lane): guarded pair by pair.  What is check-pointed, or carried into the next sub-block, is normalised:
+      // behind the single last step of an odd n too (the full sub-blocks behind it then normalise behind the even steps of the window - word-length
+      // argument at the top)
+#pragma unroll
+      for (int u = 0; u < TB_S; u += 2)
+        if (u < n) build2(tb, u);
+#pragma unroll
+      for (int u = 0; u < TB_S; u += 2) {
+        if (u + 1 < n) {
+          lsn_step_fwd_pk<false>(a, pk_s2(g[u]));
+          lsn_step_fwd_pk<true>(a, pk_s2(g[u + 1]));
+          LSN_FWD_SWEEP_COUNT(2);
+        } else if (u < n) {
+          lsn_step_fwd_pk<true>(a, pk_s2(g[u]));
+          LSN_FWD_SWEEP_COUNT(1);
+        }
+      }
     }
   }
   if (wl == P - 1) {
@@ -427,7 +497,8 @@ LSN_HD void lsn_map_pass_lane(const TurboLds& m, const uint32_t* il, int nt, int
   auto ext_index = [&](int tb, int u) { return IL ? (int)((u & 1) ? cur[u >> 1] >> 16 : cur[u >> 1] & 0xFFFFu) : (tb + u) * P + wlb; };
   for (int sb = nsb - 1; sb >= 0; sb--) {
     LSN_LOCAL_ADDR(wlb);
-    const int tb = sb * TB_S, n = (tb + TB_S < W) ? TB_S : W - tb;
+    const LsnSubBlock s = lsn_turbo_sb(W, sb);
+    const int tb = s.start, n = s.len;
     if (sb + 1 < nsb) {
       if (sb == 0) {
         a_start();
@@ -440,7 +511,7 @@ LSN_HD void lsn_map_pass_lane(const TurboLds& m, const uint32_t* il, int nt, int
       for (int u = 0; u < TB_S / 2; u++) cur[u] = nx[u];
       if (sb > 0) il_load(sb - 1);
     }
-    // only the last sub-block of a window can be shorter than TB_S: the full-length variant carries no per-step guards
+    // only sub-block 0 of a window can be shorter than TB_S: the full-length variant carries no per-step guards
     auto subblock = [&](auto fullc) {
       constexpr bool FULL = decltype(fullc)::value;
       // operand burst
@@ -451,7 +522,7 @@ LSN_HD void lsn_map_pass_lane(const TurboLds& m, const uint32_t* il, int nt, int
       // odd steps carry the growth of one step (word-length argument at the top).
       // Full-length sub-block (round 6, last session): the alphas in front of step u are kept in register layout u mod 7 (lsn_turbo_cyc.h) - the forward step
       // from layout L to L + 1 and the backward step from L + 1 to L need no shuffle -, the beta vector enters through one conversion from layout C and
-      // leaves step 0 in layout C again, normalised (check-points, window boundaries and the short last sub-block stay in layout C).
+      // leaves step 0 in layout C again, normalised (check-points, window boundaries and the short sub-block 0 stay in layout C).
       if constexpr (FULL) {
         auto fwd1 = [&](auto uc) {
           constexpr int u = decltype(uc)::value;
@@ -492,12 +563,8 @@ LSN_HD void lsn_map_pass_lane(const TurboLds& m, const uint32_t* il, int nt, int
             if (u & 1) lsn_step_fwd_pk<true>(a, pk_s2(g[u])); else lsn_step_fwd_pk<false>(a, pk_s2(g[u]));
           }
         }
-        if (sb == nsb - 1) {
-          // (the caller wants a normalised vector: the next iteration starts a window from it)
-          const s2 nn = a[0];
-          for (int k = 0; k < 4; k++) a_end[k] = pks_sel<0, 1, 0, 0>(a[k], nn);
-        }
-        // beta recursion + LLR + extrinsic
+        // (the alpha vector behind the last step is not wanted: the window's end lies in the last sub-block, which is a full one)
+        // beta recursion + LLR + extrinsic, normalised behind every step
 #pragma unroll
         for (int u = TB_S - 1; u >= 0; u--) {
           if (u < n) {

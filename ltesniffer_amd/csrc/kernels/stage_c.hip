@@ -493,9 +493,11 @@ void lsn_launch_harq_combine(const LsnCbDev* cbs, uint32_t ncb, const uint32_t* 
 // parity 2), ext[K] holds extrinsic * 2 + hard decision.  Both are stored TRANSPOSED, idx(x) = (x % W) * P + x / W:
 // the in-order decoder reads consecutive lanes = consecutive addresses and the QPP-interleaved one is (nearly)
 // conflict free by the contention-free property of the QPP (36.212 5.1.3.2.3).
-// Schedule per constituent decoder: forward sweep in sub-blocks of TB_S steps (operands of a sub-block are fetched
-// from LDS in one burst, the recursion then runs on registers), alpha check-pointed at sub-block starts; backward
-// sub-block by sub-block: burst fetch, recompute the TB_S alphas into registers, beta + LLR + extrinsic.
+// Schedule per constituent decoder: a window is cut into sub-blocks of TB_S steps, the SHORT one (W mod TB_S steps, when
+// that is not zero) first (lsn_turbo_core.h: lsn_turbo_sb).  Forward sweep over all sub-blocks but the last (operands of
+// a sub-block are fetched from LDS in one burst, the recursion then runs on registers), alpha check-pointed at sub-block
+// starts: W - TB_S steps, the sub-block left to the recompute is always a full one.  Backward sub-block by sub-block:
+// burst fetch, recompute the alphas of the sub-block into registers, beta + LLR + extrinsic.
 // The interleaver addresses come from a table in global memory (L2), fetched one sub-block ahead.
 // Window-boundary metrics of the previous iteration (next-iteration initialisation) stay in registers and change lanes through the
 // check-point area.
