@@ -326,8 +326,8 @@ int lsn_phy_prepare_file(lsn_phy_t* phy, uint32_t nof_antennas);
  * to the recording's centre.  Input sample n (its index in the RECORDING) is multiplied by exp(-2 pi j Phi(n) / 2^64) before the filter sees it, Phi(n) =
  * n W mod 2^64, W = round(center_offset_hz / rate_in * 2^64) mod 2^64: integer phase, so pieces, block sizes and call boundaries still change no bit.  The
  * exponential is a two-table NCO (12 + 10 phase bits, float32).  Same filter, same tap counts.  Accepted when finite and |center_offset_hz| + passband_hz <=
- * rate_in / 2 (the cell lies inside the recording), otherwise LSN_ERROR_INVALID_INPUTS.  Open loop: nothing searches for carriers or tracks one (the sample clock
- * is measured ahead of the replay, lsn_clock_estimate); one cell per
+ * rate_in / 2 (the cell lies inside the recording), otherwise LSN_ERROR_INVALID_INPUTS.  Open loop: nothing tracks a carrier (lsn_carrier_scan FINDS the carriers of a
+ * recording and the sample clock is measured, lsn_clock_estimate, both ahead of the replay); one cell per
  * pass - two Phys replay two cells of one file.  0 runs the kernel without the mixer.  Unlike lsn_file_cfg_t.offset_freq_hz (a rotation of the OUTPUT samples
  * that restarts every subframe, behind the filter) this is a translation in front of it.
  *
@@ -445,6 +445,92 @@ int lsn_clock_estimate(int device, const void* iq, int iq_on_device, uint64_t no
  * rate->sample_rate_hz * (1 + eps).  sf_start of the answer counts samples of the FILE from its first one (the offset included): directly the offset of the replay. */
 int lsn_file_clock_estimate(int device, const char* path, const lsn_file_cfg_t* fcfg, const lsn_file_rate_t* rate, uint32_t antenna, const lsn_clock_cfg_t* cfg,
                             lsn_clock_t* out);
+
+/* ---- the LTE carriers of a wideband recording: carrier scan ----
+ * Given the head of a recording and its sample rate, lsn_carrier_scan reports every LTE carrier in it: the offset from the recording's centre in the form
+ * lsn_resample_cfg_t.center_offset_hz / lsn_file_rate_t.center_offset_hz take, and the cell search's answer (cell id, CP, subframe timing, CFO) on that carrier.
+ *   hypotheses  f_k = (double)k * raster_hz + raster_offset_hz for every integer k with |f_k| + 555 kHz <= rate_in_hz / 2 (555 kHz = 15 kHz * 37, the centre six
+ *               resource blocks, which carry PSS, SSS and PBCH of a cell of any bandwidth; the acceptance rule of center_offset_hz), narrowed to f_lo_hz <= f_k
+ *               <= f_hi_hz unless both are 0.  None, or more than 8192: LSN_ERROR_INVALID_INPUTS.  The tuning word of f_k is lsn_resample's W of that double.
+ *   channel     the resampler of section 3.1b from rate_in_hz to 1.92 MS/s with pass band 555 kHz, output sample 0 at input sample 0, with two limits lifted for
+ *               this caller: 1.92e6 <= rate_in_hz <= 122.88e6 (ratio up to 64) and up to 768 taps (382 at 61.44 MS/s, 764 at 122.88 MS/s).  k_chan_bank, one
+ *               launch for a batch of hypotheses; a channel sample is a function of (input, configuration, hypothesis, m) only.
+ *   metric      per hypothesis the cell search's PSS correlation on its channel (N = 128, 9600 lags, three roots, nof_periods periods added) and its
+ *               pss_p2avg: the first maximum in (root, lag) order over the mean of the winning root.
+ *   decision    hypotheses with p2avg >= threshold and peak >= threshold * nof_periods / 128 (the mean of the correlation on a white channel: a channel that
+ *               holds a strong neighbour only in its transition band has a far lower mean and a large p2avg on nothing), by metric descending (ties: lower |f_k|, then lower k), accepted greedily; one strictly closer than
+ *               min_spacing_hz to an accepted one is dropped (a hypothesis a whole number of sub-carriers off a real carrier sees a time-shifted PSS).
+ *   verification  lsn_cell_search's algorithm on the channel of every accepted carrier (6 resource blocks, same nof_periods, root free); found is the search's.
+ * The head must hold lsn_carrier_scan_plan_t.nof_input_samples samples.  Device scratch for channels and correlations is bounded by 256 MB whatever the number
+ * of hypotheses (they are processed in batches).  One antenna is scanned.  lsn_carrier_scan_plan and lsn_carrier_scan_decide need no GPU. */
+#define LSN_SCAN_MAX_HYPOTHESES 8192u
+typedef struct {
+  uint32_t struct_size;      /* sizeof(lsn_carrier_scan_cfg_t); every other size is refused */
+  uint32_t nof_antennas;     /* interleaved in the input (lsn_file_carrier_scan: taken from lsn_file_cfg_t) */
+  uint32_t antenna;          /* the one that is scanned */
+  uint32_t sample_format;    /* LSN_FILE_* (lsn_file_carrier_scan: from lsn_file_cfg_t, as sample_scale) */
+  float    sample_scale;
+  uint32_t nof_periods;      /* 5 ms periods added, 1..16; 0 = 2.  With the threshold of 20 one period leaves a false alarm in a few percent of the scans of a
+                                61.44 MS/s recording, two periods about 1e-9 */
+  double   rate_in_hz;       /* rate of the recording, 1.92e6 .. 122.88e6 */
+  double   raster_hz;        /* 0 = 100e3, the LTE channel raster */
+  double   raster_offset_hz; /* position of a raster point relative to the recording's centre */
+  double   f_lo_hz, f_hi_hz; /* both 0: every hypothesis inside the recording; else only f_lo_hz <= f_k <= f_hi_hz */
+  double   min_spacing_hz;   /* 0 = 1.4e6, the narrowest LTE channel */
+  float    threshold;        /* on p2avg; 0 = 20 */
+  uint32_t reserved;
+} lsn_carrier_scan_cfg_t;
+typedef struct {
+  uint32_t nof_hypotheses, taps /* T of the channel filter */, nof_periods, reserved;
+  uint64_t nof_channel_samples;  /* (nof_periods + 1) * 9600 + 128 at 1.92 MS/s */
+  uint64_t nof_input_samples;    /* the scan reads samples 0 .. nof_input_samples - 1 of the input */
+} lsn_carrier_scan_plan_t;
+typedef struct {
+  int32_t  k;
+  uint32_t root;             /* of the peak */
+  double   f_hz;             /* f_k */
+  uint64_t tuning_word;      /* W of f_k */
+  uint32_t lag;              /* of the peak, 0 .. 9599 */
+  float    peak, p2avg;
+  uint32_t reserved;
+} lsn_carrier_metric_t;
+typedef struct {
+  double   center_offset_hz; /* f_k of the carrier: center_offset_hz of lsn_resample / lsn_phy_process_file_rate / lsn_carrier_channel */
+  int32_t  k;
+  float    scan_p2avg;       /* the scan's own metric ... */
+  uint32_t scan_root, scan_lag;  /* ... and where its peak was */
+  lsn_cell_search_t search;  /* the cell search on the carrier's channel; pss_pos and sf_start count samples of the 1.92 MS/s channel */
+} lsn_carrier_t;
+/* the hypotheses (k, f_hz, tuning_word filled, the rest zero; hyp optional, cap >= their number), the bank of the channel filter (optional: [512][taps][2] floats,
+ * H[p][j] and H[p + 1][j] - H[p][j]) and what the scan reads */
+int lsn_carrier_scan_plan(const lsn_carrier_scan_cfg_t* cfg, lsn_carrier_scan_plan_t* out, lsn_carrier_metric_t* hyp, uint32_t cap, float* bank_out);
+/* the decision on n metrics -> number accepted; accepted_out: their indices into metric in the order of acceptance (the first cap of them) */
+int lsn_carrier_scan_decide(const lsn_carrier_scan_cfg_t* cfg, const lsn_carrier_metric_t* metric, uint32_t n, uint32_t* accepted_out, uint32_t cap);
+/* in: [sample][antenna] in sample_format, in[0] = sample 0 of the recording, host or device memory.  Returns the number of carriers (the first cap of them in
+ * carriers_out, in the order of acceptance), < 0 on error.  metric_out optional: one entry per hypothesis (lsn_carrier_scan_plan_t.nof_hypotheses) */
+int lsn_carrier_scan(int device, const void* in, int in_on_device, uint64_t n_in, const lsn_carrier_scan_cfg_t* cfg, lsn_carrier_t* carriers_out, uint32_t cap,
+                     lsn_carrier_metric_t* metric_out);
+/* the same on a recording: only the head the scan needs is read (pread), from fcfg->offset_time_samples on - that sample is sample 0 of the scan.  nof_antennas,
+ * sample_format and sample_scale are fcfg's (cf32 / sc16 / sc8 by the file source's rule); offset_freq_hz is not applied.  A file shorter than the head:
+ * LSN_ERROR_INVALID_INPUTS */
+int lsn_file_carrier_scan(int device, const char* path, const lsn_file_cfg_t* fcfg, const lsn_carrier_scan_cfg_t* cfg, lsn_carrier_t* carriers_out, uint32_t cap,
+                          lsn_carrier_metric_t* metric_out);
+/* The 1.92 MS/s channel of one offset, all antennas: out [antenna][n_out] cf32, out[0] = output sample out_first; output sample 0 sits at first_sample + first_frac,
+ * in[0] = sample in_base of the recording (fields as lsn_resample_cfg_t).  With first_sample = 0 and first_frac = 0 these are, bit for bit, the samples the scan
+ * correlated for that offset - what lsn_phy_mib_decode on a six-block Phy needs.  Pieces, batches and call boundaries change no bit. */
+typedef struct {
+  uint32_t struct_size;      /* sizeof(lsn_carrier_channel_cfg_t); every other size is refused */
+  uint32_t nof_antennas;
+  uint32_t sample_format;
+  float    sample_scale;
+  double   rate_in_hz, center_offset_hz;
+  uint64_t first_sample;
+  double   first_frac;
+  uint64_t in_base, out_first;
+} lsn_carrier_channel_cfg_t;
+int lsn_carrier_channel(int device, const void* in, int in_on_device, uint64_t n_in, const lsn_carrier_channel_cfg_t* cfg, float* out, int out_on_device,
+                        uint64_t n_out);
+int lsn_carrier_channel_span(const lsn_carrier_channel_cfg_t* cfg, uint64_t n_out, uint64_t in_end, lsn_resample_span_t* out);
 
 /* ---- security-API sink (the step behind the path: PDSCH_Decoder::run_api_dl_mode, DL_Sniffer_PDSCH.cc:804-879) ----
  * api_mode as ArgManager's -a (ArgManager.cc:63,218): -1 off (default), 0 identity mapping, 2 IMSI catching, 3 all.  For every CRC-ok

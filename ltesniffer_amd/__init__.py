@@ -41,7 +41,8 @@ EXPORTS = ["lsn_phy_create", "lsn_phy_destroy", "lsn_phy_set_cell", "lsn_phy_get
            "lsn_phy_set_cfo_correction", "lsn_phy_get_cfo_correction", "lsn_phy_set_candidate_pruning", "lsn_phy_set_stage_c_taps", "lsn_phy_prepare_file", "lsn_phy_get_meta_formats", "lsn_phy_nof_workers", "lsn_phy_worker",
            "lsn_phy_set_sampling", "lsn_phy_get_sampling", "lsn_symbol_sz", "lsn_sampling_freq_hz", "lsn_cell_search_rates",
            "lsn_resample", "lsn_resample_span", "lsn_phy_process_file_rate",
-           "lsn_clock_plan", "lsn_clock_fit", "lsn_clock_replica", "lsn_clock_track", "lsn_clock_estimate", "lsn_file_clock_estimate"]
+           "lsn_clock_plan", "lsn_clock_fit", "lsn_clock_replica", "lsn_clock_track", "lsn_clock_estimate", "lsn_file_clock_estimate",
+           "lsn_carrier_scan_plan", "lsn_carrier_scan_decide", "lsn_carrier_scan", "lsn_file_carrier_scan", "lsn_carrier_channel", "lsn_carrier_channel_span"]
 
 RATES_3GPP, RATES_SRSRAN = 0, 1   # LSN_RATES_*: sampling mode of a Phy / of a cell search
 
@@ -131,6 +132,32 @@ class ClockObs(C.Structure):   # lsn_clock_obs_t
 class Clock(C.Structure):   # lsn_clock_t
     _fields_ = [("found", C.c_uint32), ("nof_periods", C.c_uint32), ("nof_used", C.c_uint32), ("nof_rounds", C.c_uint32), ("eps", C.c_double),
                 ("sample_rate_hz", C.c_double), ("pss_pos0", C.c_double), ("rms_residual", C.c_double), ("max_residual", C.c_double), ("sf_start", C.c_double)]
+
+
+class CarrierScanCfg(C.Structure):   # lsn_carrier_scan_cfg_t
+    _fields_ = [("struct_size", C.c_uint32), ("nof_antennas", C.c_uint32), ("antenna", C.c_uint32), ("sample_format", C.c_uint32), ("sample_scale", C.c_float),
+                ("nof_periods", C.c_uint32), ("rate_in_hz", C.c_double), ("raster_hz", C.c_double), ("raster_offset_hz", C.c_double), ("f_lo_hz", C.c_double),
+                ("f_hi_hz", C.c_double), ("min_spacing_hz", C.c_double), ("threshold", C.c_float), ("reserved", C.c_uint32)]
+
+
+class CarrierScanPlan(C.Structure):   # lsn_carrier_scan_plan_t
+    _fields_ = [("nof_hypotheses", C.c_uint32), ("taps", C.c_uint32), ("nof_periods", C.c_uint32), ("reserved", C.c_uint32), ("nof_channel_samples", C.c_uint64),
+                ("nof_input_samples", C.c_uint64)]
+
+
+class CarrierMetric(C.Structure):   # lsn_carrier_metric_t
+    _fields_ = [("k", C.c_int32), ("root", C.c_uint32), ("f_hz", C.c_double), ("tuning_word", C.c_uint64), ("lag", C.c_uint32), ("peak", C.c_float),
+                ("p2avg", C.c_float), ("reserved", C.c_uint32)]
+
+
+class Carrier(C.Structure):   # lsn_carrier_t
+    _fields_ = [("center_offset_hz", C.c_double), ("k", C.c_int32), ("scan_p2avg", C.c_float), ("scan_root", C.c_uint32), ("scan_lag", C.c_uint32),
+                ("search", CellSearch)]
+
+
+class CarrierChannelCfg(C.Structure):   # lsn_carrier_channel_cfg_t
+    _fields_ = [("struct_size", C.c_uint32), ("nof_antennas", C.c_uint32), ("sample_format", C.c_uint32), ("sample_scale", C.c_float), ("rate_in_hz", C.c_double),
+                ("center_offset_hz", C.c_double), ("first_sample", C.c_uint64), ("first_frac", C.c_double), ("in_base", C.c_uint64), ("out_first", C.c_uint64)]
 
 
 class ApiEvent(C.Structure):
@@ -378,6 +405,12 @@ def lib():
         L.lsn_clock_track.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.POINTER(ClockCfg), C.POINTER(ClockObs), C.c_uint32, C.c_void_p]
         L.lsn_clock_estimate.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.POINTER(ClockCfg), C.POINTER(Clock), C.POINTER(ClockObs), C.c_uint32]
         L.lsn_file_clock_estimate.argtypes = [C.c_int, C.c_char_p, C.POINTER(FileCfg), C.POINTER(FileRate), C.c_uint32, C.POINTER(ClockCfg), C.POINTER(Clock)]
+        L.lsn_carrier_scan_plan.argtypes = [C.POINTER(CarrierScanCfg), C.POINTER(CarrierScanPlan), C.POINTER(CarrierMetric), C.c_uint32, C.c_void_p]
+        L.lsn_carrier_scan_decide.argtypes = [C.POINTER(CarrierScanCfg), C.POINTER(CarrierMetric), C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32]
+        L.lsn_carrier_scan.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.POINTER(CarrierScanCfg), C.POINTER(Carrier), C.c_uint32, C.POINTER(CarrierMetric)]
+        L.lsn_file_carrier_scan.argtypes = [C.c_int, C.c_char_p, C.POINTER(FileCfg), C.POINTER(CarrierScanCfg), C.POINTER(Carrier), C.c_uint32, C.POINTER(CarrierMetric)]
+        L.lsn_carrier_channel.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.POINTER(CarrierChannelCfg), C.c_void_p, C.c_int, C.c_uint64]
+        L.lsn_carrier_channel_span.argtypes = [C.POINTER(CarrierChannelCfg), C.c_uint64, C.c_uint64, C.POINTER(ResampleSpan)]
         _lib = L
     return _lib
 
@@ -924,6 +957,148 @@ def resample(iq, rate_in, rate_out, n_out=None, first_sample=0, first_frac=0.0, 
     out = np.zeros((nant, n_out), dtype=np.complex64)
     _check(lib().lsn_resample(device, iq.ctypes.data, 0, n_in, C.byref(cfg), out.ctypes.data, 0, n_out), "lsn_resample")
     return out
+
+
+SCAN_MAX_HYPOTHESES = 8192
+SCAN_RATE_HZ = 1.92e6   # rate of a carrier's channel: six resource blocks, 128 samples per symbol
+
+
+def carrier_scan_cfg(rate_in, nof_antennas=1, antenna=0, sample_format=FILE_CF32, sample_scale=0.0, nof_periods=2, raster_hz=100e3, raster_offset_hz=0.0,
+                     f_lo_hz=0.0, f_hi_hz=0.0, min_spacing_hz=1.4e6, threshold=20.0):
+    return CarrierScanCfg(C.sizeof(CarrierScanCfg), int(nof_antennas), int(antenna), int(sample_format), float(sample_scale), int(nof_periods), float(rate_in),
+                          float(raster_hz), float(raster_offset_hz), float(f_lo_hz), float(f_hi_hz), float(min_spacing_hz), float(threshold), 0)
+
+
+def carrier_scan_plan(rate_in, with_bank=False, **kw):
+    """lsn_carrier_scan_plan (needs no GPU): the hypotheses of a scan of a recording at rate_in, the channel filter and what the scan reads ->
+    dict(nof_hypotheses, taps, nof_periods, nof_channel_samples, nof_input_samples, k, f_hz, tuning_word[, bank[512, taps, 2]]); kw: carrier_scan_cfg.
+    Raises ValueError when the library refuses the configuration"""
+    cfg = carrier_scan_cfg(rate_in, **kw)
+    pl = CarrierScanPlan()
+    hyp = (CarrierMetric * SCAN_MAX_HYPOTHESES)()
+    rc = lib().lsn_carrier_scan_plan(C.byref(cfg), C.byref(pl), hyp, SCAN_MAX_HYPOTHESES, None)
+    if rc == LSN_ERROR_INVALID_INPUTS:
+        raise ValueError("carrier scan: configuration refused")
+    _check(rc, "lsn_carrier_scan_plan")
+    n = int(pl.nof_hypotheses)
+    d = {f: int(getattr(pl, f)) for f, _ in CarrierScanPlan._fields_ if f != "reserved"}
+    d.update(k=[int(h.k) for h in hyp[:n]], f_hz=[float(h.f_hz) for h in hyp[:n]], tuning_word=[int(h.tuning_word) for h in hyp[:n]])
+    if with_bank:
+        bank = np.zeros((512, d["taps"], 2), dtype=np.float32)
+        _check(lib().lsn_carrier_scan_plan(C.byref(cfg), C.byref(pl), None, 0, bank.ctypes.data), "lsn_carrier_scan_plan")
+        d["bank"] = bank
+    return d
+
+
+def carrier_scan_decide(metric, rate_in, **kw):
+    """lsn_carrier_scan_decide (needs no GPU): metric: CarrierMetric entries or (k, f_hz, p2avg, peak) tuples -> indices of the accepted ones, in the order of acceptance"""
+    cfg = carrier_scan_cfg(rate_in, **kw)
+    arr = (CarrierMetric * max(len(metric), 1))()
+    for i, m in enumerate(metric):
+        arr[i] = m if isinstance(m, CarrierMetric) else CarrierMetric(k=int(m[0]), f_hz=float(m[1]), p2avg=float(m[2]), peak=float(m[3]))
+    idx = (C.c_uint32 * max(len(metric), 1))()
+    n = _check_n(lib().lsn_carrier_scan_decide(C.byref(cfg), arr, len(metric), idx, len(metric)), "lsn_carrier_scan_decide")
+    return [int(i) for i in idx[:n]]
+
+
+def _scan_result(n, carriers, metric, nhyp, with_metric):
+    found = [Carrier.from_buffer_copy(c) for c in carriers[:min(n, len(carriers))]]
+    return (found, [CarrierMetric.from_buffer_copy(m) for m in metric[:nhyp]]) if with_metric else found
+
+
+def _scan_input(iq, sample_format):
+    iq = np.ascontiguousarray(iq)
+    if iq.ndim == (2 if sample_format != FILE_CF32 else 1):
+        iq = iq.reshape(iq.shape[0], 1, *iq.shape[1:])
+    return np.ascontiguousarray(iq, dtype=(np.complex64, np.int16, np.int8)[sample_format])
+
+
+def carrier_scan(iq, rate_in, with_metric=False, cap=64, device=0, sample_format=FILE_CF32, **kw):
+    """lsn_carrier_scan: every LTE carrier in the head of a recording made at rate_in, given nothing else.  iq: [sample][antenna] (or [sample]) numpy complex64, or
+    int16 / int8 with a last axis of 2 for FILE_SC16 / FILE_SC8; iq[0] is sample 0 of the recording; it must hold carrier_scan_plan(...)["nof_input_samples"].
+    -> [Carrier (center_offset_hz, k, scan_p2avg, scan_root, scan_lag, search: CellSearch on the carrier's 1.92 MS/s channel)] in the order of acceptance
+    [, the CarrierMetric of every hypothesis].  kw: carrier_scan_cfg (antenna, nof_periods, raster_hz, raster_offset_hz, f_lo_hz, f_hi_hz, min_spacing_hz, threshold)"""
+    iq = _scan_input(iq, sample_format)
+    cfg = carrier_scan_cfg(rate_in, nof_antennas=iq.shape[1], sample_format=sample_format, **kw)
+    carriers = (Carrier * cap)()
+    metric = (CarrierMetric * SCAN_MAX_HYPOTHESES)() if with_metric else None
+    n = _check_n(lib().lsn_carrier_scan(device, iq.ctypes.data, 0, iq.shape[0], C.byref(cfg), carriers, cap, metric), "lsn_carrier_scan")
+    nhyp = 0
+    if with_metric:
+        pl = CarrierScanPlan()
+        _check(lib().lsn_carrier_scan_plan(C.byref(cfg), C.byref(pl), None, 0, None), "lsn_carrier_scan_plan")
+        nhyp = int(pl.nof_hypotheses)
+    return _scan_result(n, carriers, metric, nhyp, with_metric)
+
+
+def file_carrier_scan(path, rate_in, nof_antennas=1, sample_format=FILE_CF32, sample_scale=0.0, offset_time=0, with_metric=False, cap=64, device=0, **kw):
+    """lsn_file_carrier_scan: carrier_scan on a recording, of which only the head the scan needs is read, from sample offset_time on"""
+    cfg = carrier_scan_cfg(rate_in, nof_antennas=nof_antennas, sample_format=sample_format, sample_scale=sample_scale, **kw)
+    fc = FileCfg(int(nof_antennas), int(offset_time), 0.0, int(sample_format), float(sample_scale))
+    carriers = (Carrier * cap)()
+    metric = (CarrierMetric * SCAN_MAX_HYPOTHESES)() if with_metric else None
+    n = _check_n(lib().lsn_file_carrier_scan(device, os.fsencode(path), C.byref(fc), C.byref(cfg), carriers, cap, metric), "lsn_file_carrier_scan")
+    nhyp = 0
+    if with_metric:
+        pl = CarrierScanPlan()
+        _check(lib().lsn_carrier_scan_plan(C.byref(cfg), C.byref(pl), None, 0, None), "lsn_carrier_scan_plan")
+        nhyp = int(pl.nof_hypotheses)
+    return _scan_result(n, carriers, metric, nhyp, with_metric)
+
+
+def _channel_cfg(nof_antennas, rate_in, center_offset_hz, first_sample, first_frac, in_base, out_first, sample_format, sample_scale):
+    return CarrierChannelCfg(C.sizeof(CarrierChannelCfg), int(nof_antennas), int(sample_format), float(sample_scale), float(rate_in), float(center_offset_hz),
+                             int(first_sample), float(first_frac), int(in_base), int(out_first))
+
+
+def carrier_channel_span(n_out, in_end, rate_in, first_sample=0, first_frac=0.0, out_first=0, center_offset_hz=0.0):
+    """lsn_carrier_channel_span -> dict(in_lo, in_hi, max_out, taps), as resample_span for the 1.92 MS/s channel of a carrier"""
+    cfg = _channel_cfg(1, rate_in, center_offset_hz, first_sample, first_frac, 0, out_first, FILE_CF32, 0.0)
+    sp = ResampleSpan()
+    _check(lib().lsn_carrier_channel_span(C.byref(cfg), int(n_out), int(in_end), C.byref(sp)), "lsn_carrier_channel_span")
+    return dict(in_lo=int(sp.in_lo), in_hi=int(sp.in_hi), max_out=int(sp.max_out), taps=int(sp.taps))
+
+
+def carrier_channel(iq, rate_in, center_offset_hz, n_out=None, first_sample=0, first_frac=0.0, in_base=0, out_first=0, sample_format=FILE_CF32, sample_scale=0.0,
+                    device=0):
+    """lsn_carrier_channel: the 1.92 MS/s channel (the centre six resource blocks) of the carrier center_offset_hz off the centre of a recording made at rate_in,
+    all antennas -> complex64 [antenna][n_out]; with first_sample = 0 and first_frac = 0 the samples the scan correlated, bit for bit.  iq and the other
+    arguments as resample"""
+    iq = _scan_input(iq, sample_format)
+    n_in, nant = iq.shape[0], iq.shape[1]
+    cfg = _channel_cfg(nant, rate_in, center_offset_hz, first_sample, first_frac, in_base, out_first, sample_format, sample_scale)
+    if n_out is None:
+        sp = ResampleSpan()
+        _check(lib().lsn_carrier_channel_span(C.byref(cfg), 0, int(in_base) + n_in, C.byref(sp)), "lsn_carrier_channel_span")
+        n_out = int(sp.max_out)
+    out = np.zeros((nant, n_out), dtype=np.complex64)
+    _check(lib().lsn_carrier_channel(device, iq.ctypes.data, 0, n_in, C.byref(cfg), out.ctypes.data, 0, n_out), "lsn_carrier_channel")
+    return out
+
+
+def carrier_mib(channel, search, max_batch=1, device=0):
+    """the MIB of a carrier the scan found, from public calls only: subframe 0 is cut out of the carrier's channel (carrier_channel: [antenna][n] at 1.92 MS/s)
+    at the search's sf_start / sf_idx, a six-block Phy is set to the search's cell id and CP and decodes the PBCH - with 1, 2 and 4 ports in turn until the
+    MIB's own nof_ports agrees.  A six-block Phy decodes the PBCH of a cell of any bandwidth: the CRS sequence is indexed from the largest bandwidth and the
+    centre 72 sub-carriers start at a multiple of 6 in it.  -> the dict of Phy.mib_decode (found, nof_prb, nof_ports, sfn, ...) or None"""
+    channel = np.ascontiguousarray(channel, dtype=np.complex64)
+    if channel.ndim == 1:
+        channel = channel.reshape(1, -1)
+    sflen = 1920
+    start = int(search.sf_start) + (0 if int(search.sf_idx) == 0 else 5 * sflen)
+    starts = [s for s in range(start % (10 * sflen), channel.shape[1] - sflen + 1, 10 * sflen)]
+    for ports in (1, 2, 4):
+        phy = Phy(nof_rx_antennas=channel.shape[0], max_batch=max_batch, device=device, pcapwriter=PcapWriter(None))
+        try:
+            if not phy.setCell(6, ports, int(search.cell_id), cp=int(search.cp)):
+                continue
+            for s in starts:
+                m = phy.mib_decode(channel[:, s:s + sflen])
+                if m["found"] and m["nof_ports"] == ports:
+                    return m
+        finally:
+            phy.close()
+    return None
 
 
 def mac_lte_record(ctx, pdu):

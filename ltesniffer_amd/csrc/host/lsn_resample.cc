@@ -16,7 +16,7 @@ namespace lsn {
 
 static constexpr double kAtten = 80.0;                          // design attenuation A of the Kaiser window, dB
 static constexpr double kBeta = 0.1102 * (kAtten - 8.7);        // Kaiser's beta for A > 50
-static constexpr uint32_t kPhases = 512, kMaxTaps = 192, kRun = 512;  // kRun = LSN_RS_RUN of the kernel
+static constexpr uint32_t kPhases = 512, kRun = 512;  // kRun = LSN_RS_RUN of the kernel
 
 static double bessel_i0(double x)
 {
@@ -30,12 +30,27 @@ static double bessel_i0(double x)
   return s;
 }
 
-int ResamplePlan::init(double rate_in, double rate_out, double passband_hz, uint64_t first_sample, double first_frac, double center_offset_hz)
+// W = floor(center_offset_hz / rate_in * 2^64 + 1/2) mod 2^64, the quotient of the two doubles taken exactly as for D: |quotient| <= 1/2, so ec <= ea and
+// mc << sw stays below 2^118
+uint64_t ResamplePlan::tuning(double center_offset_hz, double rate_in)
+{
+  if (center_offset_hz == 0.0) return 0;
+  int ea = 0, ec = 0;
+  const uint64_t ma = (uint64_t)std::ldexp(std::frexp(rate_in, &ea), 53), mc = (uint64_t)std::ldexp(std::frexp(std::fabs(center_offset_hz), &ec), 53);
+  const int sw = 64 + ec - ea;
+  if (sw < -1) return 0;   // below that the quotient times 2^64 is under 1/2 in magnitude: W = 0
+  const __int128 num = (__int128)((u128)mc << std::max(sw, 0)) * (center_offset_hz < 0.0 ? -2 : 2), den = (__int128)((u128)ma << std::max(-sw, 0)) * 2;
+  const __int128 a = num + den / 2;   // floor(a / den) = floor(quotient 2^64 + 1/2)
+  return (uint64_t)(a >= 0 ? a / den : -((-a + den - 1) / den));
+}
+
+int ResamplePlan::init(double rate_in, double rate_out, double passband_hz, uint64_t first_sample, double first_frac, double center_offset_hz, double max_ratio,
+                       uint32_t max_taps)
 {
   if (!(rate_in > 0.0 && rate_in < 1e12) || !(rate_out > 0.0 && rate_out < 1e12)) return LSN_ERROR_INVALID_INPUTS;
   if (!(first_frac >= 0.0 && first_frac < 1.0) || first_sample >= (1ull << 62)) return LSN_ERROR_INVALID_INPUTS;
   const double ratio = rate_in / rate_out;
-  if (!(ratio <= 4.0 && ratio >= 1.0 / 65536.0)) return LSN_ERROR_INVALID_INPUTS;
+  if (!(ratio <= max_ratio && ratio >= 1.0 / 65536.0)) return LSN_ERROR_INVALID_INPUTS;
   const double lo_rate = std::min(rate_in, rate_out), rho = std::max(1.0, ratio);
   if (passband_hz == 0.0) passband_hz = 0.44 * lo_rate;
   if (!(passband_hz > 0.0)) return LSN_ERROR_INVALID_INPUTS;
@@ -43,29 +58,18 @@ int ResamplePlan::init(double rate_in, double rate_out, double passband_hz, uint
   if (!(width > 0.0)) return LSN_ERROR_INVALID_INPUTS;
   if (!(std::fabs(center_offset_hz) + passband_hz <= 0.5 * rate_in)) return LSN_ERROR_INVALID_INPUTS;   // the cell lies inside the recording (NaN and infinity fail here)
   const double want = (kAtten - 7.95) / (14.36 * width) + 1.0;    // Kaiser's estimate of the filter length
-  if (!(want <= (double)kMaxTaps)) return LSN_ERROR_INVALID_INPUTS;
+  if (!(want <= (double)max_taps)) return LSN_ERROR_INVALID_INPUTS;
   taps = std::max(4u, 2u * (uint32_t)std::ceil(want / 2.0));
   // D = round(rate_in / rate_out * 2^64), exactly: the two doubles are integers ma 2^(ea - 53), mb 2^(eb - 53)
   int ea = 0, eb = 0;
   const uint64_t ma = (uint64_t)std::ldexp(std::frexp(rate_in, &ea), 53), mb = (uint64_t)std::ldexp(std::frexp(rate_out, &eb), 53);
-  const int sh = 65 + ea - eb;   // 47 .. 68 for the accepted ratios: ma << sh stays below 2^121
-  if (sh < 0 || sh > 70) return LSN_ERROR_INVALID_INPUTS;
+  const int sh = 65 + ea - eb;   // 47 .. 68 for ratios up to 4, up to 72 for the carrier scan's 64: ma << sh stays below 2^125
+  if (sh < 0 || sh > 72) return LSN_ERROR_INVALID_INPUTS;
   step = (((u128)ma << sh) + (u128)mb) / ((u128)mb << 1);
   if (step == 0) return LSN_ERROR_INVALID_INPUTS;
   start = ((u128)first_sample << 64) + (u128)(uint64_t)std::ldexp(first_frac, 64);
-  // W = floor(center_offset_hz / rate_in * 2^64 + 1/2) mod 2^64, the quotient taken exactly as for D: |quotient| <= 1/2, so ec <= ea and mc << sw stays below 2^118
-  tune = 0;
+  tune = tuning(center_offset_hz, rate_in);
   nco.clear();
-  if (center_offset_hz != 0.0) {
-    int ec = 0;
-    const uint64_t mc = (uint64_t)std::ldexp(std::frexp(std::fabs(center_offset_hz), &ec), 53);
-    const int sw = 64 + ec - ea;
-    if (sw >= -1) {   // below that the quotient times 2^64 is under 1/2 in magnitude: W = 0
-      const __int128 num = (__int128)((u128)mc << std::max(sw, 0)) * (center_offset_hz < 0.0 ? -2 : 2), den = (__int128)((u128)ma << std::max(-sw, 0)) * 2;
-      const __int128 a = num + den / 2;   // floor(a / den) = floor(quotient 2^64 + 1/2)
-      tune = (uint64_t)(a >= 0 ? a / den : -((-a + den - 1) / den));
-    }
-  }
   if (tune) {
     nco.resize((4096 + 1024) * 2);
     lsn_nco_tables((cf32*)nco.data(), (cf32*)nco.data() + 4096);

@@ -22,7 +22,11 @@ struct ResamplePlan {
 
   // LSN_SUCCESS, or LSN_ERROR_INVALID_INPUTS when the pair is outside what the filter meets, or the cell at center_offset_hz does not lie inside
   // the recording (accepted range)
-  int init(double rate_in, double rate_out, double passband_hz, uint64_t first_sample, double first_frac, double center_offset_hz);
+  // max_ratio, max_taps: the largest rate_in / rate_out and Kaiser estimate accepted; the defaults are lsn_resample's and the file source's, the carrier
+  // scan's narrow-band channel lifts them to 64 and 768
+  int init(double rate_in, double rate_out, double passband_hz, uint64_t first_sample, double first_frac, double center_offset_hz, double max_ratio = 4.0,
+           uint32_t max_taps = 192);
+  static uint64_t tuning(double center_offset_hz, double rate_in);   // W of one offset
   // device copy of bank and nco in one allocation (the caller frees d_bank); d_nco = null when the plan does not mix
   void upload(float*& d_bank, const cf32*& d_nco, hipStream_t s) const;
   u128 position(uint64_t m) const { return start + (u128)m * step; }

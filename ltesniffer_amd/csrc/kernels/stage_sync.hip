@@ -5,7 +5,7 @@
 //              each power divided by the energy of its window, the ratios of P consecutive periods added.  256 lags per workgroup; the 256 + N samples a workgroup needs live in
 //              LDS (lane t reads xs[t + k]: consecutive 8-byte words, conflict free), the replica taps are wave-uniform
 //              (scalar loads).  Every sum runs in index order with one rounding per operation, as the CPU statement of the same
-//              algorithm does, so results are bit-identical (compiled with -ffp-contract=off).
+//              algorithm does, so results are bit-identical (compiled with -ffp-contract=off).  blockIdx.y = channel of a bank (carrier scan, scan.hip).
 // k_sync_fin   one workgroup: (a) the matched filter in two halves at the winning lag for each of the P + 1 occurrences,
 //              (b) pick the strongest occurrence whose SSS symbol is inside the buffer, (c) 62-carrier DFT of its PSS and SSS
 //              symbols (twiddle table), channel from the PSS, (d) the 336 SSS hypotheses (168 N_id_1 x subframe 0 / 5).
@@ -19,8 +19,11 @@
 #define SYNC_TILE 256
 
 __global__ __launch_bounds__(SYNC_TILE) void k_pss_corr(const cf32* __restrict__ x, const cf32* __restrict__ p /* [nroots][N] */, uint32_t N, uint32_t W5,
-                                                        uint32_t P, uint32_t nroots, float* __restrict__ C /* [nroots][W5] */)
+                                                        uint32_t P, uint32_t nroots, float* __restrict__ C /* [nroots][W5] */, size_t x_stride, size_t c_stride)
 {
+  // blockIdx.y = channel (the carrier scan correlates a bank of channels in one launch, scan.hip; the cell search passes one channel and zero strides)
+  x += (size_t)blockIdx.y * x_stride;
+  C += (size_t)blockIdx.y * c_stride;
   __shared__ cf32 xs[SYNC_TILE + 2048];
   const cf32* __restrict__ ps = p;  // uniform index: scalar loads
   const uint32_t t = threadIdx.x, n0 = blockIdx.x * SYNC_TILE, n = n0 + t;
@@ -185,9 +188,17 @@ __global__ __launch_bounds__(512) void k_sync_fin(const cf32* __restrict__ x, co
   }
 }
 
+// nch channels, channel c at x + c x_stride with its correlations at C + c c_stride
+void lsn_launch_pss_corr_bank(const cf32* x, size_t x_stride, const cf32* p, uint32_t N, uint32_t W5, uint32_t P, uint32_t nroots, float* C, size_t c_stride, uint32_t nch,
+                              hipStream_t s)
+{
+  if (!nch) return;
+  if (N < 1 || N > 2048 || nch > 65535) throw std::runtime_error("k_pss_corr: bad geometry");
+  LSN_LAUNCH(k_pss_corr, dim3((W5 + SYNC_TILE - 1) / SYNC_TILE, nch), dim3(SYNC_TILE), 0, s, x, p, N, W5, P, nroots, C, x_stride, c_stride);
+}
 void lsn_launch_pss_corr(const cf32* x, const cf32* p, uint32_t N, uint32_t W5, uint32_t P, uint32_t nroots, float* C, hipStream_t s)
 {
-  LSN_LAUNCH(k_pss_corr, dim3((W5 + SYNC_TILE - 1) / SYNC_TILE), dim3(SYNC_TILE), 0, s, x, p, N, W5, P, nroots, C);
+  LSN_LAUNCH(k_pss_corr, dim3((W5 + SYNC_TILE - 1) / SYNC_TILE), dim3(SYNC_TILE), 0, s, x, p, N, W5, P, nroots, C, (size_t)0, (size_t)0);
 }
 // tab: nper entries of LsnTrackSlice (device); max_lag: the widest window.  The caller has checked every slice against the buffer.
 void lsn_launch_pss_track(const cf32* x, const void* tab, uint32_t nper, uint32_t max_lag, const cf32* p, uint32_t N, float* C, hipStream_t s)
