@@ -328,7 +328,7 @@ int lsn_phy_prepare_file(lsn_phy_t* phy, uint32_t nof_antennas);
  * exponential is a two-table NCO (12 + 10 phase bits, float32).  Same filter, same tap counts.  Accepted when finite and |center_offset_hz| + passband_hz <=
  * rate_in / 2 (the cell lies inside the recording), otherwise LSN_ERROR_INVALID_INPUTS.  Open loop: nothing tracks a carrier (lsn_carrier_scan FINDS the carriers of a
  * recording and the sample clock is measured, lsn_clock_estimate, both ahead of the replay); one cell per
- * pass - two Phys replay two cells of one file.  0 runs the kernel without the mixer.  Unlike lsn_file_cfg_t.offset_freq_hz (a rotation of the OUTPUT samples
+ * call - lsn_file_process_cells replays several cells of one file in one pass over it.  0 runs the kernel without the mixer.  Unlike lsn_file_cfg_t.offset_freq_hz (a rotation of the OUTPUT samples
  * that restarts every subframe, behind the filter) this is a translation in front of it.
  *
  * lsn_resample: needs no Phy.  in: [sample][antenna] in sample_format, in[0] = sample in_base of the recording; out: [antenna][n_out] cf32,
@@ -375,6 +375,58 @@ typedef struct {
 } lsn_file_rate_t;
 int lsn_phy_process_file_rate(lsn_phy_t* phy, const char* path, const lsn_file_cfg_t* cfg, const lsn_file_rate_t* rate, uint32_t start_tti, uint64_t max_subframes,
                               uint32_t update_meta_period, uint64_t* subframes_done);
+
+/* ---- every cell of a wideband recording in ONE pass over the file ----
+ * lsn_carrier_scan returns the carriers of a recording; replaying them one lsn_phy_process_file_rate call each reads and copies the whole file once per cell.
+ * Here every cell has its own Phy and its own resampler plan (formed exactly as lsn_phy_process_file_rate forms it: rate pair, pass band 15 kHz (6 nof_prb + 1),
+ * start position, tuning word), and block k of the replay - output subframes [first + k blk, first + (k + 1) blk) of EVERY cell - is fed from the union of the
+ * cells' input spans: one read, one host-to-device copy, one kernel launch (k_resample_cells) that writes each cell's subframes into its own Phy's block buffer,
+ * then one submit per Phy in the order of the list.  An output sample is a function of (input, configuration, m) only, so each Phy gets, bit for bit, the samples
+ * of its single-cell replay and produces its records.  The cells may differ in bandwidth, start position, start TTI (LSN_TTI_FROM_MIB is resolved per cell) and
+ * length; a cell that has run out takes no part in later blocks.  The block size starts from LSN_FILE_BLOCK and shrinks until the union fits the largest raw
+ * block buffer the Phys hold - no allocation grows.  All Phys live on one GPU; at most LSN_FILE_MAX_CELLS of them.
+ * Refused with LSN_ERROR_INVALID_INPUTS before a byte is read: n_cells 0 or above LSN_FILE_MAX_CELLS; a struct_size the library does not know; a null or
+ * repeated phy, one without a cell, one from lsn_phy_create_multi, Phys on different devices, a Phy whose antenna count is not cfg->nof_antennas; non-zero offset
+ * fields in cfg (the cells carry their own); a cell lsn_phy_process_file_rate would refuse; cells whose starts lie so far apart that one subframe of each does
+ * not fit one block (pass start positions closer together, or replay the cells separately).  A refusal decodes nothing and leaves every Phy usable.
+ * When one Phy fails during the replay, nothing more is submitted to any of them, all are waited for, and its code is returned; subframes_done and status are
+ * filled per cell either way. */
+#define LSN_FILE_MAX_CELLS 8u
+typedef struct {
+  uint32_t struct_size;          /* sizeof(lsn_file_cell_t); every other size is refused */
+  uint32_t nof_prb; int rates;   /* bandwidth and sampling mode of the cell: read only when phy is NULL (lsn_file_cells_span on a machine with no GPU) */
+  lsn_phy_t* phy;                /* its cell is set; one engine, not a lsn_phy_create_multi handle */
+  double center_offset_hz;       /* as lsn_file_rate_t; the field lsn_carrier_t.center_offset_hz goes into */
+  int64_t offset_time_samples; double offset_time_frac;   /* start of the cell's subframe 0 in the file, in samples of the file */
+  float offset_freq_hz;          /* -o rotation of this cell's output samples, as lsn_file_cfg_t */
+  uint32_t start_tti;            /* may be LSN_TTI_FROM_MIB */
+  uint32_t update_meta_period;
+  uint64_t max_subframes;        /* 0 = to the end */
+  uint64_t subframes_done;       /* out */
+  int status;                    /* out: this cell's engine's return code */
+} lsn_file_cell_t;
+int lsn_file_process_cells(const char* path, const lsn_file_cfg_t* cfg /* nof_antennas, sample_format, sample_scale; the offset fields must be 0 */, double sample_rate_hz,
+                           lsn_file_cell_t* cells, uint32_t n_cells);
+/* The plan of block `block` of that replay, without a device: the union [in_lo, in_hi) of input samples it reads (clamped at sample 0) and, per cell, the
+ * first output subframe (counted from the cell's start position; LSN_TTI_FROM_MIB counts as no subframes dropped), the number of subframes and the taps.
+ * blk_subframes stands for LSN_FILE_BLOCK: the raw block buffer holds blk_subframes subframes of cf32 of the widest cell; blk_used is what the block size shrank
+ * to.  A block behind the end of every cell has nof_active 0.  Same refusals as lsn_file_process_cells, phy aside: with phy NULL the cell's bandwidth comes from
+ * nof_prb / rates. */
+typedef struct {
+  int64_t in_lo, in_hi;
+  uint32_t blk_used, nof_active;
+  uint64_t first_subframe[LSN_FILE_MAX_CELLS];
+  uint32_t nof_subframes[LSN_FILE_MAX_CELLS];
+  uint32_t taps[LSN_FILE_MAX_CELLS];
+} lsn_file_cells_span_t;
+int lsn_file_cells_span(const lsn_file_cfg_t* cfg, double sample_rate_hz, const lsn_file_cell_t* cells, uint32_t n_cells, uint64_t in_end /* samples in the recording */,
+                        uint32_t block, uint32_t blk_subframes, lsn_file_cells_span_t* out);
+/* k_resample_cells without a Phy: several resamplings of ONE input in one upload and one launch - the sibling of lsn_carrier_channel for full-bandwidth carriers.
+ * cfgs[c] is validated exactly as lsn_resample validates it and outs[c] ([antenna][n_out[c]] cf32) equals lsn_resample with cfgs[c], bit for bit.  nof_antennas,
+ * sample_format, sample_scale, rate_in_hz and in_base must agree across cfgs and every cfg must have the full struct_size; n_cells 0 or above
+ * LSN_FILE_MAX_CELLS, n_out NULL: LSN_ERROR_INVALID_INPUTS, the outputs untouched.  in must hold what every cell reads (lsn_resample_span per cell). */
+int lsn_resample_cells(int device, const void* in, int in_on_device, uint64_t n_in, const lsn_resample_cfg_t* cfgs, uint32_t n_cells, float* const* outs,
+                       int out_on_device, const uint64_t* n_out);
 
 /* ---- the sample clock of a recording, measured from its PSS train ----
  * A recording made by a radio whose clock is off by eps runs at fs (1 + eps), fs = 15 kHz * N the nominal rate: PSS occurrence q (one every 5 ms, W5 = 75 N

@@ -40,7 +40,7 @@ EXPORTS = ["lsn_phy_create", "lsn_phy_destroy", "lsn_phy_set_cell", "lsn_phy_get
            "lsn_phy_set_mcs_update_interval", "lsn_phy_update_mcs_database", "lsn_phy_nof_tracked_rnti", "lsn_worker_buffers_offset", "lsn_pcap_digest", "lsn_pcap_set_store", "lsn_pcap_set_digest_blocks", "lsn_pcap_block_digests", "lsn_phy_create_multi", "lsn_phy_nof_devices",
            "lsn_phy_set_cfo_correction", "lsn_phy_get_cfo_correction", "lsn_phy_set_candidate_pruning", "lsn_phy_set_stage_c_taps", "lsn_phy_prepare_file", "lsn_phy_get_meta_formats", "lsn_phy_nof_workers", "lsn_phy_worker",
            "lsn_phy_set_sampling", "lsn_phy_get_sampling", "lsn_symbol_sz", "lsn_sampling_freq_hz", "lsn_cell_search_rates",
-           "lsn_resample", "lsn_resample_span", "lsn_phy_process_file_rate",
+           "lsn_resample", "lsn_resample_span", "lsn_phy_process_file_rate", "lsn_resample_cells", "lsn_file_cells_span", "lsn_file_process_cells",
            "lsn_clock_plan", "lsn_clock_fit", "lsn_clock_replica", "lsn_clock_track", "lsn_clock_estimate", "lsn_file_clock_estimate",
            "lsn_carrier_scan_plan", "lsn_carrier_scan_decide", "lsn_carrier_scan", "lsn_file_carrier_scan", "lsn_carrier_channel", "lsn_carrier_channel_span"]
 
@@ -107,6 +107,20 @@ FILE_CF32, FILE_SC16, FILE_SC8 = 0, 1, 2
 class FileRate(C.Structure):   # lsn_file_rate_t
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("sample_rate_hz", C.c_double), ("offset_time_frac", C.c_double),
                 ("center_offset_hz", C.c_double)]
+
+
+FILE_MAX_CELLS = 8
+
+
+class FileCell(C.Structure):   # lsn_file_cell_t
+    _fields_ = [("struct_size", C.c_uint32), ("nof_prb", C.c_uint32), ("rates", C.c_int), ("phy", C.c_void_p), ("center_offset_hz", C.c_double),
+                ("offset_time_samples", C.c_int64), ("offset_time_frac", C.c_double), ("offset_freq_hz", C.c_float), ("start_tti", C.c_uint32),
+                ("update_meta_period", C.c_uint32), ("max_subframes", C.c_uint64), ("subframes_done", C.c_uint64), ("status", C.c_int)]
+
+
+class FileCellsSpan(C.Structure):   # lsn_file_cells_span_t
+    _fields_ = [("in_lo", C.c_int64), ("in_hi", C.c_int64), ("blk_used", C.c_uint32), ("nof_active", C.c_uint32), ("first_subframe", C.c_uint64 * FILE_MAX_CELLS),
+                ("nof_subframes", C.c_uint32 * FILE_MAX_CELLS), ("taps", C.c_uint32 * FILE_MAX_CELLS)]
 
 
 class ResampleCfg(C.Structure):   # lsn_resample_cfg_t
@@ -376,6 +390,9 @@ def lib():
         L.lsn_phy_process_file_rate.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(FileCfg), C.POINTER(FileRate), C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]
         L.lsn_resample.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.POINTER(ResampleCfg), C.c_void_p, C.c_int, C.c_uint64]
         L.lsn_resample_span.argtypes = [C.POINTER(ResampleCfg), C.c_uint64, C.c_uint64, C.POINTER(ResampleSpan)]
+        L.lsn_resample_cells.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.POINTER(ResampleCfg), C.c_uint32, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_uint64)]
+        L.lsn_file_cells_span.argtypes = [C.POINTER(FileCfg), C.c_double, C.POINTER(FileCell), C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(FileCellsSpan)]
+        L.lsn_file_process_cells.argtypes = [C.c_char_p, C.POINTER(FileCfg), C.c_double, C.POINTER(FileCell), C.c_uint32]
         L.lsn_phy_set_prach_config.argtypes = [C.c_void_p, C.POINTER(PrachCfg)]
         L.lsn_phy_prach_detect.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(PrachDet), C.c_uint32]
         L.lsn_phy_set_prach_sink.argtypes = [C.c_void_p, PRACH_SINK, C.c_void_p]
@@ -957,6 +974,84 @@ def resample(iq, rate_in, rate_out, n_out=None, first_sample=0, first_frac=0.0, 
     out = np.zeros((nant, n_out), dtype=np.complex64)
     _check(lib().lsn_resample(device, iq.ctypes.data, 0, n_in, C.byref(cfg), out.ctypes.data, 0, n_out), "lsn_resample")
     return out
+
+
+def resample_cells(iq, rate_in, cells, n_out=None, in_base=0, sample_format=FILE_CF32, sample_scale=0.0, device=0):
+    """lsn_resample_cells: several resamplings of ONE input in one upload and one kernel launch (k_resample_cells).  iq and in_base as resample; cells: a list of
+    dicts with resample's per-cell arguments (rate_out, and optionally n_out, first_sample, first_frac, out_first, passband_hz, center_offset_hz; n_out None:
+    as many as iq carries, or the call's n_out).  -> a list of complex64 [antenna][n_out] arrays, each bit for bit resample's with that cell's arguments"""
+    iq = _scan_input(iq, sample_format)
+    n_in, nant = iq.shape[0], iq.shape[1]
+    n = len(cells)
+    cfgs = (ResampleCfg * max(n, 1))()
+    counts = (C.c_uint64 * max(n, 1))()
+    outs = []
+    for i, c in enumerate(cells):
+        cfgs[i] = _resample_cfg(nant, rate_in, c["rate_out"], c.get("first_sample", 0), c.get("first_frac", 0.0), in_base, c.get("out_first", 0), c.get("passband_hz", 0.0),
+                                sample_format, sample_scale, c.get("center_offset_hz", 0.0))
+        k = c.get("n_out", n_out)
+        if k is None:
+            sp = ResampleSpan()
+            _check(lib().lsn_resample_span(C.byref(cfgs[i]), 0, int(in_base) + n_in, C.byref(sp)), "lsn_resample_span")
+            k = int(sp.max_out)
+        counts[i] = int(k)
+        outs.append(np.zeros((nant, int(k)), dtype=np.complex64))
+    ptrs = (C.c_void_p * max(n, 1))(*[o.ctypes.data for o in outs])
+    _check(lib().lsn_resample_cells(device, iq.ctypes.data, 0, n_in, cfgs, n, ptrs, 0, counts), "lsn_resample_cells")
+    return outs
+
+
+def _file_cell(phy, kw):
+    """(phy or None, dict) -> FileCell.  center_offset_hz may be a Carrier of carrier_scan / file_carrier_scan: its center_offset_hz is taken as it is"""
+    kw = dict(kw)
+    f0 = kw.pop("center_offset_hz", 0.0)
+    if isinstance(f0, Carrier):
+        f0 = f0.center_offset_hz
+    start_tti = kw.pop("start_tti", 0)
+    cell = FileCell(C.sizeof(FileCell), int(kw.pop("nof_prb", 0)), int(kw.pop("rates", RATES_3GPP)), phy._h if phy is not None else None, float(f0),
+                    int(kw.pop("offset_time", 0)), float(kw.pop("offset_time_frac", 0.0)), float(kw.pop("offset_freq", 0.0)),
+                    start_tti if start_tti == TTI_FROM_MIB else start_tti % 10240, int(kw.pop("update_meta_period", 0)), int(kw.pop("max_subframes", 0)), 0, 0)
+    if kw:
+        raise TypeError("unknown cell argument(s): %s" % ", ".join(sorted(kw)))
+    return cell
+
+
+def file_cells_span(sample_rate, cells, in_end, block=0, blk_subframes=800, nof_antennas=1, sample_format=FILE_CF32, sample_scale=0.0):
+    """lsn_file_cells_span (needs no GPU): the plan of block `block` of process_file_cells.  cells: a list of dicts (nof_prb, rates, center_offset_hz, offset_time,
+    offset_time_frac, max_subframes, ...) or of (phy, dict) pairs.  -> dict(in_lo, in_hi: the union of input samples the block reads; blk_used; nof_active;
+    first_subframe, nof_subframes, taps: one entry per cell).  Raises ValueError when the library refuses the cells"""
+    arr = (FileCell * max(len(cells), 1))()
+    for i, c in enumerate(cells):
+        arr[i] = _file_cell(*c) if isinstance(c, tuple) else _file_cell(None, c)
+    fc = FileCfg(int(nof_antennas), 0, 0.0, int(sample_format), float(sample_scale))
+    sp = FileCellsSpan()
+    rc = lib().lsn_file_cells_span(C.byref(fc), float(sample_rate), arr, len(cells), int(in_end), int(block), int(blk_subframes), C.byref(sp))
+    if rc == LSN_ERROR_INVALID_INPUTS:
+        raise ValueError("file cells: refused")
+    _check(rc, "lsn_file_cells_span")
+    n = len(cells)
+    return dict(in_lo=int(sp.in_lo), in_hi=int(sp.in_hi), blk_used=int(sp.blk_used), nof_active=int(sp.nof_active), first_subframe=[int(v) for v in sp.first_subframe[:n]],
+                nof_subframes=[int(v) for v in sp.nof_subframes[:n]], taps=[int(v) for v in sp.taps[:n]])
+
+
+def process_file_cells(path, sample_rate, cells, nof_antennas=None, sample_format=FILE_CF32, sample_scale=0.0, with_status=False):
+    """lsn_file_process_cells: replay several cells of one recording made at sample_rate (Hz) in ONE pass over the file - one read and one host-to-device copy
+    per block, one kernel launch for all cells, each Phy fed with its own cell's subframes.  cells: a list of (phy, dict(center_offset_hz=, start_tti=, offset_time=,
+    offset_time_frac=, offset_freq=, max_subframes=, update_meta_period=)); center_offset_hz may be a Carrier of file_carrier_scan.  start_tti may be
+    TTI_FROM_MIB, per cell.  -> the list of subframes done, one per cell [, the list of per-cell status codes].  Raises ValueError when the library refuses
+    the cells (nothing is decoded, every Phy stays usable)"""
+    arr = (FileCell * max(len(cells), 1))()
+    for i, (phy, kw) in enumerate(cells):
+        arr[i] = _file_cell(phy, kw)
+    if nof_antennas is None:
+        nof_antennas = cells[0][0].nof_rx_antennas if cells else 1
+    fc = FileCfg(int(nof_antennas), 0, 0.0, int(sample_format), float(sample_scale))
+    rc = lib().lsn_file_process_cells(os.fsencode(path), C.byref(fc), float(sample_rate), arr, len(cells))
+    if rc == LSN_ERROR_INVALID_INPUTS:
+        raise ValueError("process_file_cells: refused")
+    _check(rc, "lsn_file_process_cells")
+    done = [int(c.subframes_done) for c in arr[:len(cells)]]
+    return (done, [int(c.status) for c in arr[:len(cells)]]) if with_status else done
 
 
 SCAN_MAX_HYPOTHESES = 8192

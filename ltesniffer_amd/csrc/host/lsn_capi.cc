@@ -11,6 +11,7 @@
 // commit / write stages of its subframe run on while the caller refills it.  Lossless file mode (blocking getAvail, LTESniffer_Core.cc:441)
 // lets batches grow towards half the pool; live mode (getAvailImmediate, :439) dispatches whatever is pending at once.
 #include "lsn_engine.h"
+#include "lsn_cells.h"
 #include <chrono>
 #include <condition_variable>
 #include <deque>
@@ -539,6 +540,89 @@ int lsn_phy_process_file_rate(lsn_phy_t* phy, const char* path, const lsn_file_c
   if (subframes_done) *subframes_done = 0;
   if (!phy || !path || !cfg || !rate) return LSN_ERROR_INVALID_INPUTS;
   return phy->engine->processFileRate(path, *cfg, *rate, start_tti, max_subframes, update_meta_period, subframes_done);
+}
+// What lsn_file_process_cells and lsn_file_cells_span check alike, and the cells' plans (formed by file_rate_plan, as lsn_phy_process_file_rate forms its one).
+// need_phy: every cell has a Phy (one engine, its cell set, fcfg's antennas, all on one device, none twice); otherwise a null phy takes nof_prb / rates.
+static int file_cells_plans(const lsn_file_cfg_t* fc, double sample_rate_hz, const lsn_file_cell_t* cells, uint32_t n, bool need_phy, std::vector<lsn::ResamplePlan>& plans,
+                            std::vector<uint32_t>& sflen)
+{
+  if (!fc || !cells || n < 1 || n > LSN_FILE_MAX_CELLS) return LSN_ERROR_INVALID_INPUTS;
+  if (fc->nof_antennas < 1 || fc->nof_antennas > 8 || fc->offset_time_samples != 0 || fc->offset_freq_hz != 0.0f || !lsn_sample_format(fc->sample_format, fc->sample_scale).valid)
+    return LSN_ERROR_INVALID_INPUTS;
+  plans.resize(n);
+  sflen.resize(n);
+  for (uint32_t c = 0; c < n; c++) {
+    const lsn_file_cell_t& k = cells[c];
+    if (k.struct_size != sizeof(lsn_file_cell_t)) return LSN_ERROR_INVALID_INPUTS;
+    uint32_t N = 0, nof_prb = 0;
+    if (c && !k.phy != !cells[0].phy) return LSN_ERROR_INVALID_INPUTS;   // all with a Phy or none
+    if (k.phy) {
+      lsn::Engine* e = k.phy->engine.get();
+      if (!k.phy->more.empty() || !e->hasCell() || e->iqAntennas() != fc->nof_antennas || e->device() != cells[0].phy->engine->device()) return LSN_ERROR_INVALID_INPUTS;
+      for (uint32_t d = 0; d < c; d++) if (cells[d].phy == k.phy) return LSN_ERROR_INVALID_INPUTS;
+      N = e->symbolSz(); nof_prb = e->nofPrb();
+    } else {
+      if (need_phy) return LSN_ERROR_INVALID_INPUTS;
+      N = lsn::symbol_size(k.nof_prb, k.rates); nof_prb = k.nof_prb;
+      if (!N) return LSN_ERROR_INVALID_INPUTS;
+    }
+    if (!std::isfinite(k.offset_freq_hz)) return LSN_ERROR_INVALID_INPUTS;
+    const int r = lsn::file_rate_plan(sample_rate_hz, N, nof_prb, k.offset_time_samples, k.offset_time_frac, k.center_offset_hz, plans[c]);
+    if (r != LSN_SUCCESS) return r;
+    sflen[c] = 15u * N;
+  }
+  return LSN_SUCCESS;
+}
+
+int lsn_file_cells_span(const lsn_file_cfg_t* cfg, double sample_rate_hz, const lsn_file_cell_t* cells, uint32_t n_cells, uint64_t in_end, uint32_t block, uint32_t blk_subframes,
+                        lsn_file_cells_span_t* out)
+{
+  return lsn::guarded([&]() -> int {
+    std::vector<lsn::ResamplePlan> plans;
+    std::vector<uint32_t> sflen;
+    const int r = file_cells_plans(cfg, sample_rate_hz, cells, n_cells, false, plans, sflen);
+    if (r != LSN_SUCCESS) return r;
+    if (!out || !blk_subframes || in_end >= (1ull << 62)) return LSN_ERROR_INVALID_INPUTS;
+    lsn::FileCellPlan cp[LSN_FILE_MAX_CELLS];
+    uint32_t widest = 0;
+    for (uint32_t c = 0; c < n_cells; c++) {
+      cp[c].rs = &plans[c]; cp[c].sflen = sflen[c]; cp[c].first_sf = 0;
+      cp[c].total = lsn::file_cell_total(plans[c].outputsInside(in_end) / sflen[c], 0, cells[c].max_subframes);
+      widest = std::max(widest, sflen[c]);
+    }
+    // the raw block buffer: blk_subframes subframes of cf32 of the widest cell, in samples of the file's format (Engine::reserveFileBuffers)
+    const uint64_t cap = (uint64_t)((lsn::u128)blk_subframes * widest * sizeof(cf32) / lsn_sample_format(cfg->sample_format, cfg->sample_scale).bytes);
+    const uint32_t blk = lsn::file_cells_fit(cp, n_cells, blk_subframes, cap);
+    if (!blk) return LSN_ERROR_INVALID_INPUTS;
+    lsn::FileCellsBlock b;
+    (void)lsn::file_cells_block(cp, n_cells, blk, block, b);
+    memset(out, 0, sizeof(*out));
+    out->in_lo = b.in_lo; out->in_hi = b.in_hi; out->blk_used = blk; out->nof_active = b.active;
+    for (uint32_t c = 0; c < n_cells; c++) { out->first_subframe[c] = b.sf0[c]; out->nof_subframes[c] = b.nsf[c]; out->taps[c] = plans[c].taps; }
+    return LSN_SUCCESS;
+  });
+}
+
+int lsn_file_process_cells(const char* path, const lsn_file_cfg_t* cfg, double sample_rate_hz, lsn_file_cell_t* cells, uint32_t n_cells)
+{
+  if (cells && n_cells >= 1 && n_cells <= LSN_FILE_MAX_CELLS)
+    for (uint32_t c = 0; c < n_cells; c++) { cells[c].subframes_done = 0; cells[c].status = LSN_ERROR_INVALID_INPUTS; }
+  if (!path) return LSN_ERROR_INVALID_INPUTS;
+  return lsn::guarded([&]() -> int {
+    std::vector<lsn::ResamplePlan> plans;
+    std::vector<uint32_t> sflen;
+    const int r = file_cells_plans(cfg, sample_rate_hz, cells, n_cells, true, plans, sflen);
+    if (r != LSN_SUCCESS) return r;
+    lsn::Engine::FileCellJob jobs[LSN_FILE_MAX_CELLS];
+    for (uint32_t c = 0; c < n_cells; c++) {
+      jobs[c].e = cells[c].phy->engine.get(); jobs[c].rs = &plans[c]; jobs[c].offset_freq_hz = cells[c].offset_freq_hz; jobs[c].start_tti = cells[c].start_tti;
+      jobs[c].update_meta_period = cells[c].update_meta_period; jobs[c].max_subframes = cells[c].max_subframes;
+      jobs[c].status = LSN_ERROR_INVALID_INPUTS;   // (stays when the replay is refused in front of the first block)
+    }
+    const int rc = lsn::Engine::replayFile(path, *cfg, jobs, n_cells);
+    for (uint32_t c = 0; c < n_cells; c++) { cells[c].subframes_done = jobs[c].done; cells[c].status = jobs[c].status; }
+    return rc;
+  });
 }
 int lsn_phy_prepare_file(lsn_phy_t* phy, uint32_t nof_antennas)
 {

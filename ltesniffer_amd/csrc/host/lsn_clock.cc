@@ -7,7 +7,7 @@
 #include "../kernels/lsn_dev.h"
 #include "lsn_clock.h"
 #include "lsn_rates.h"
-#include "lsn_resample.h"
+#include "lsn_resample_launch.h"
 #include <algorithm>
 #include <cmath>
 #include <cstddef>

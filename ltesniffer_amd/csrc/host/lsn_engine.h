@@ -266,6 +266,16 @@ public:
                   uint64_t* subframes_done);
   int processFileRate(const char* path, const lsn_file_cfg_t& fc, const lsn_file_rate_t& fr, uint32_t start_tti, uint64_t max_subframes, uint32_t update_meta_period,
                       uint64_t* subframes_done);   // lsn_phy_process_file_rate: the same through the polyphase resampler (lsn_resample.h)
+  // one cell of a file replay: its engine, its resampler plan (null: the file is at the engine's rate - single-cell call only), where and how it starts; out: done, status
+  struct FileCellJob {
+    Engine* e = nullptr; const struct ResamplePlan* rs = nullptr; float offset_freq_hz = 0.0f; uint32_t start_tti = 0, update_meta_period = 0; uint64_t max_subframes = 0;
+    uint64_t done = 0; int status = 0;
+  };
+  // lsn_file_process_cells: n cells (engines on one device, each with its cell set and fc.nof_antennas antennas) from one pass over the file; n = 1 is processFile[Rate]
+  static int replayFile(const char* path, const lsn_file_cfg_t& fc, FileCellJob* jobs, uint32_t n);
+  uint32_t symbolSz() const { return cd.N; }
+  uint32_t nofPrb() const { return cd.nof_prb; }
+  uint32_t iqAntennas() const { return cd.iq_nant; }
   int reserveFileBuffers(uint32_t nof_antennas);   // lsn_phy_prepare_file: pinned read blocks + device blocks of the file source, ahead of the first replay
   int processHost(const void* iq, uint32_t nsf, uint32_t start_tti, uint32_t update_meta_period, uint32_t sample_format = 0 /* LSN_FILE_* */, float sample_scale = 0.0f);
   void setSink(lsn_pdu_sink_t cb, void* user) { sink = cb; sink_user = user; }
@@ -550,7 +560,7 @@ private:
   int buildUlTables(const lsn_ul_cfg_t& u);             // DMRS base sequences, n_PN, u(ns) / v(ns), hopping offset: the device side of setUlConfig
   void syncUlConfig();                                    // commit turn: pick up a configuration another engine (or the caller) has set since
   // device / pinned blocks of the file source, kept between lsn_phy_process_file calls (allocating them costs more than replaying a short capture)
-  // the one replay loop behind processFile (rs == nullptr) and processFileRate (rs: the resampler's plan, lsn_resample.h)
+  // processFile (rs == nullptr) and processFileRate (rs: the resampler's plan, lsn_resample.h) as a one-cell replayFile
   int processFileImpl(const char* path, const lsn_file_cfg_t& fc, const struct ResamplePlan* rs, uint32_t start_tti, uint64_t max_subframes, uint32_t update_meta_period,
                       uint64_t* subframes_done);
   struct FileReplay;   // lsn_file.cc: what one replay opens and how it hands blocks to submit()

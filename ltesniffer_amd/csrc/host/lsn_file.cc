@@ -10,7 +10,8 @@
 // and crosses PCIe straight from the page cache; on the boxes measured the lock / unlock per block costs more than the copy it saves.
 // Product code: no CPU fallback, nothing from oracle/ is included or linked.
 #include "lsn_engine.h"
-#include "lsn_resample.h"
+#include "lsn_resample_launch.h"
+#include "lsn_cells.h"
 #include <deque>
 #include <cmath>
 #include <cstddef>
@@ -71,8 +72,9 @@ int Engine::processFile(const char* path, const lsn_file_cfg_t& fc, uint32_t sta
   return processFileImpl(path, fc, nullptr, start_tti, max_subframes, update_meta_period, subframes_done);
 }
 
-// lsn_phy_process_file_rate: a recording made at fr.sample_rate_hz.  The plan (step, start, taps, bank: lsn_resample.cc) is made here, in front of
-// everything else, so that a rate the filter does not meet is refused before a byte is read.
+// lsn_phy_process_file_rate: a recording made at fr.sample_rate_hz.  The plan (step, start, taps, bank: lsn_resample.cc; formed by file_rate_plan, the one
+// lsn_file_process_cells forms its cells' plans with) is made here, in front of everything else, so that a rate the filter does not meet is refused before a
+// byte is read.
 int Engine::processFileRate(const char* path, const lsn_file_cfg_t& fc, const lsn_file_rate_t& fr, uint32_t start_tti, uint64_t max_subframes,
                             uint32_t update_meta_period, uint64_t* subframes_done)
 {
@@ -82,50 +84,76 @@ int Engine::processFileRate(const char* path, const lsn_file_cfg_t& fc, const ls
   if (fr.struct_size != offsetof(lsn_file_rate_t, center_offset_hz) && fr.struct_size != sizeof(lsn_file_rate_t)) return LSN_ERROR_INVALID_INPUTS;
   const double center = fr.struct_size == sizeof(lsn_file_rate_t) ? fr.center_offset_hz : 0.0;
   if (fc.offset_time_samples < 0 || !(fr.offset_time_frac >= 0.0 && fr.offset_time_frac < 4.0e18)) return LSN_ERROR_INVALID_INPUTS;
-  const double rate_out = 15000.0 * (double)cd.N, whole = std::floor(fr.offset_time_frac);
-  if (fr.sample_rate_hz == rate_out && fr.offset_time_frac == 0.0 && center == 0.0) return processFileImpl(path, fc, nullptr, start_tti, max_subframes, update_meta_period, subframes_done);
-  const uint64_t first = (uint64_t)fc.offset_time_samples + (uint64_t)whole;
+  if (fr.sample_rate_hz == 15000.0 * (double)cd.N && fr.offset_time_frac == 0.0 && center == 0.0) return processFileImpl(path, fc, nullptr, start_tti, max_subframes, update_meta_period, subframes_done);
   ResamplePlan plan;
-  const int r = plan.init(fr.sample_rate_hz, rate_out, 15000.0 * (6.0 * (double)cd.nof_prb + 1.0), first, fr.offset_time_frac - whole, center);
+  const int r = file_rate_plan(fr.sample_rate_hz, cd.N, cd.nof_prb, fc.offset_time_samples, fr.offset_time_frac, center, plan);
   if (r != LSN_SUCCESS) return r;
   return processFileImpl(path, fc, &plan, start_tti, max_subframes, update_meta_period, subframes_done);
 }
 
-// One replay: rs is the resampler's plan (processFileRate), or null: the file is at the engine's rate.  With a plan, block k of OUTPUT subframes is fed
-// from the input samples it reads (ResamplePlan::inputSpan - neighbouring blocks overlap by the filter length), and k_resample takes the place of
-// k_file_unpack.  The struct owns what the replay opens (file, mapping, stream, rotation table, resampler bank, page-locked ranges, reader thread) and its
-// destructor gives it back, whichever way the replay ends.
+// One replay of one file into the engines of `cells`: one cell (lsn_phy_process_file[_rate]) or several (lsn_file_process_cells).  A cell's rs is
+// the resampler's plan, or null (single-cell call only): the file is at the engine's rate and k_file_unpack converts it.  With plans, block k of OUTPUT
+// subframes of every cell is fed from the union of the input samples the cells read (lsn_cells.h - neighbouring blocks overlap by the filter length), read once and
+// copied once, and k_resample (one cell) or k_resample_cells (several: one launch, each cell into its own engine's block buffer) takes the place of k_file_unpack.
+// The struct owns what the replay opens (file, mapping, stream, rotation tables, resampler banks, page-locked ranges, reader thread) and its destructor gives it
+// back, whichever way the replay ends.
 struct Engine::FileReplay {
   static constexpr int NSLOT_MAX = 8;
-  struct Slot { cf32* h_raw = nullptr; cf32* d_raw = nullptr; cf32* d_iq = nullptr; uint32_t nsf = 0; int state = 0; /* 0 free, 1 ready, 2 eof */ uint64_t mark = 0;
-                void* reg = nullptr; /* page-locked range of the file mapping this block is copied from */ };
-  Engine& e;
-  const ResamplePlan* const rs;
-  const uint32_t nant, sflen, fmt;
+  struct Cell {
+    Engine* e = nullptr;
+    const ResamplePlan* rs = nullptr;
+    uint32_t sflen = 0;
+    float offset_freq_hz = 0.0f;
+    uint32_t start_tti = 0, update_meta_period = 0;
+    uint64_t max_subframes = 0;
+    uint64_t sf_in_file = 0, first_sf = 0, done = 0;   // complete subframes in the file / in front of the replay (DECODE_MIB state of the reference) / submitted
+    cf32* d_rot = nullptr;
+    float* d_bank = nullptr;      // the resampler's bank (a few hundred kB, as short-lived as d_rot) ...
+    const cf32* d_nco = nullptr;  // ... and, behind it in the same allocation, the mixer's tables when the plan has a tuning word
+    int rc = LSN_SUCCESS;         // what this cell's engine answered (submit, then wait)
+  };
+  struct Slot { cf32* h_raw = nullptr; cf32* d_raw = nullptr; cf32* d_iq[kFileMaxCells] = {}; uint32_t nsf[kFileMaxCells] = {}; uint64_t mark[kFileMaxCells] = {};
+                int state = 0; /* 0 free, 1 ready, 2 eof */ void* reg = nullptr; /* page-locked range of the file mapping this block is copied from */ };
+  std::vector<Cell> cells;
+  Engine& e;                   // the first cell's: device, reader-thread pinning
+  Engine* big = nullptr;       // the engine whose block buffers are largest: the raw block (pinned and device) of a slot is its
+  const uint32_t nant, fmt;
   const LsnSampleFormat sfm;   // bytes of one complex sample in the file (the block buffers are sized for cf32, the widest) and the conversion's scale
-  const size_t sf_bytes, spb;  // bytes of one subframe / of one sample of all antennas
-  const uint64_t file_off0;
-  const float offset_freq_hz;
+  const size_t spb;            // bytes of one sample of all antennas
+  size_t sf_bytes = 0;         // single cell at the engine's rate: bytes of one subframe ...
+  const uint64_t file_off0;    // ... and where subframe 0 starts
   uint32_t blk, nrd;           // subframes per block, page-touch / pread threads per block
+  uint32_t blk_geom = 0;       // blk as file_geometry gave it: what the block buffers are sized for
+  size_t raw_bytes = 0;        // bytes a raw block buffer holds: blk_geom subframes of cf32 of the widest cell
   int NSLOT;                   // blocks in flight (round 2 held eight until their chunks were written - and paid 8 x 393 MB of pinned allocation on the first call)
   int fd = -1; size_t file_size = 0;
-  uint64_t sf_in_file = 0, first_sf = 0, done = 0;   // complete subframes in the file / in front of the replay (DECODE_MIB state of the reference) / submitted
   bool use_mmap = false;  // measured on MI355X boxes (page-cache file): pread into pinned blocks 60 k subframes/s, in-place locking 26 k (lock / unlock per block)
   uint8_t* map = nullptr; const long page = sysconf(_SC_PAGESIZE);
-  cf32* d_rot = nullptr;
-  float* d_bank = nullptr;      // the resampler's bank (a few hundred kB, as short-lived as d_rot) ...
-  const cf32* d_nco = nullptr;  // ... and, behind it in the same allocation, the mixer's tables when the plan has a tuning word
   hipStream_t st = nullptr;
   Slot slot[NSLOT_MAX];
+  std::vector<FileCellPlan> plans;              // what the reader cuts blocks from (plan(), behind scanMib)
   std::mutex fm; std::condition_variable fcv;   // slot states, reader <-> submit loop
   std::string rerr; bool abort_reader = false; std::thread reader;
   const bool fdebug = getenv("LSN_FILE_DEBUG") != nullptr;
   const double t_begin = now_ms();
 
-  FileReplay(Engine& eng, const lsn_file_cfg_t& fc, const ResamplePlan* plan)
-      : e(eng), rs(plan), nant(fc.nof_antennas), sflen(eng.cd.sflen), fmt(fc.sample_format), sfm(lsn_sample_format(fc.sample_format, fc.sample_scale)),
-        sf_bytes((size_t)sflen * nant * sfm.bytes), spb((size_t)nant * sfm.bytes), file_off0((uint64_t)fc.offset_time_samples * nant * sfm.bytes),
-        offset_freq_hz(fc.offset_freq_hz) { file_geometry(blk, nrd, NSLOT); }
+  FileReplay(const lsn_file_cfg_t& fc, const FileCellJob* jobs, uint32_t n)
+      : e(*jobs[0].e), nant(fc.nof_antennas), fmt(fc.sample_format), sfm(lsn_sample_format(fc.sample_format, fc.sample_scale)), spb((size_t)nant * sfm.bytes),
+        file_off0((uint64_t)fc.offset_time_samples * nant * sfm.bytes)
+  {
+    file_geometry(blk, nrd, NSLOT);
+    blk_geom = blk;
+    uint32_t widest = 0;
+    for (uint32_t c = 0; c < n; c++) {
+      Cell k;
+      k.e = jobs[c].e; k.rs = jobs[c].rs; k.sflen = k.e->cd.sflen; k.offset_freq_hz = jobs[c].offset_freq_hz; k.start_tti = jobs[c].start_tti;
+      k.update_meta_period = jobs[c].update_meta_period; k.max_subframes = jobs[c].max_subframes;
+      cells.push_back(k);
+      if (k.sflen > widest) { widest = k.sflen; big = k.e; }
+    }
+    sf_bytes = (size_t)cells[0].sflen * nant * sfm.bytes;
+    raw_bytes = (size_t)blk_geom * widest * nant * sizeof(cf32);
+  }
 
   ~FileReplay()
   {
@@ -133,14 +161,43 @@ struct Engine::FileReplay {
     fcv.notify_all();
     if (reader.joinable()) reader.join();
     for (auto& s : slot) if (s.reg) (void)hipHostUnregister(s.reg);
-    if (d_rot) (void)hipFree(d_rot);
-    if (d_bank) (void)hipFree(d_bank);
+    for (auto& c : cells) {
+      if (c.d_rot) (void)hipFree(c.d_rot);
+      if (c.d_bank) (void)hipFree(c.d_bank);
+    }
     if (st) (void)hipStreamDestroy(st);
     if (map) munmap(map, file_size);
     if (fd >= 0) close(fd);
   }
 
-  // the file, how many subframes it holds, the block size that fits, the mapping (LSN_FILE_MMAP)
+  bool resampled() const { return cells[0].rs != nullptr; }   // (several cells: every one has a plan)
+
+  // the cells as lsn_cells.h wants them, from where each one starts
+  void plan()
+  {
+    plans.clear();
+    for (auto& c : cells) {
+      FileCellPlan p;
+      p.rs = c.rs; p.sflen = c.sflen; p.first_sf = c.first_sf; p.total = file_cell_total(c.sf_in_file, c.first_sf, c.max_subframes);
+      plans.push_back(p);
+    }
+  }
+
+  // the block buffers are sized for blk_geom subframes of cf32 at the OUTPUT rate of the widest cell: a block carries as many subframes as have the union of their
+  // input fit.  false: not one subframe of every cell - the starts lie too far apart (or LSN_FILE_BLOCK is too small for one subframe's input)
+  bool fitBlock()
+  {
+    plan();
+    const uint32_t fit = file_cells_fit(plans.data(), (uint32_t)plans.size(), blk_geom, raw_bytes / spb);
+    if (!fit) {
+      if (cells.size() > 1) fprintf(stderr, "ltesniffer_amd: the cells' start positions lie too far apart for one block of %u subframes: pass start positions closer together, or replay the cells separately\n", blk_geom);
+      return false;
+    }
+    blk = fit;
+    return true;
+  }
+
+  // the file, how many subframes of every cell it holds, the block size that fits, the mapping (LSN_FILE_MMAP)
   int open(const char* path)
   {
     fd = ::open(path, O_RDONLY);
@@ -148,15 +205,11 @@ struct Engine::FileReplay {
     struct stat sb;
     if (fstat(fd, &sb)) return LSN_ERROR_INVALID_INPUTS;
     file_size = (size_t)sb.st_size;
-    sf_in_file = (uint64_t)file_size > file_off0 ? ((uint64_t)file_size - file_off0) / sf_bytes : 0;  // complete subframes only
-    if (rs) {
-      sf_in_file = rs->outputsInside((uint64_t)file_size / spb) / sflen;  // output subframes whose whole input span lies inside the file
-      // the block buffers are sized for blk subframes of cf32 at the OUTPUT rate: a block carries as many subframes as have their input fit
-      const u128 cap = (u128)blk * sflen * sizeof(cf32) / sfm.bytes;
-      const u128 fit = cap > rs->taps + 2 ? ((cap - rs->taps - 2) << 64) / ((u128)sflen * rs->step) : 0;
-      if (fit == 0) return LSN_ERROR_INVALID_INPUTS;
-      if (fit < blk) blk = (uint32_t)fit;
+    for (auto& c : cells) {
+      if (c.rs) c.sf_in_file = c.rs->outputsInside((uint64_t)file_size / spb) / c.sflen;  // output subframes whose whole input span lies inside the file
+      else c.sf_in_file = (uint64_t)file_size > file_off0 ? ((uint64_t)file_size - file_off0) / sf_bytes : 0;  // complete subframes only
     }
+    if (resampled() && !fitBlock()) return LSN_ERROR_INVALID_INPUTS;
     if (const char* v = getenv("LSN_FILE_MMAP")) use_mmap = atoi(v) != 0;
     if (use_mmap && file_size > 0) {
       void* m = mmap(nullptr, file_size, PROT_READ, MAP_SHARED, fd, 0);
@@ -167,68 +220,83 @@ struct Engine::FileReplay {
     return LSN_SUCCESS;
   }
 
-  // input of the output subframes [pos, pos + n): first sample (zeros in front of the file are the kernel's), number of samples
-  void rsSpan(uint64_t pos, uint64_t n, int64_t& lo, uint64_t& len) const
+  // k_resample for one cell: n subframes from output subframe pos, out of the raw samples [lo, lo + len) of the recording, queued on st
+  void queueResampleOne(const Cell& c, const void* raw, int64_t lo, uint64_t len, uint64_t pos, uint32_t n, cf32* out)
   {
-    int64_t hi;
-    rs->inputSpan(pos * sflen, n * sflen, lo, hi);
-    lo = std::max<int64_t>(lo, 0);
-    len = hi > lo ? (uint64_t)(hi - lo) : 0;
+    const u128 base = c.rs->position(pos * c.sflen);
+    lsn_launch_resample(raw, fmt, sfm.scale, lo, len, (uint64_t)(base >> 64), (uint64_t)base, (uint32_t)(c.rs->step >> 64), (uint64_t)c.rs->step, c.rs->taps, c.rs->span, c.d_bank,
+                        c.rs->tune, c.d_nco, c.d_rot, c.sflen, 0, nant, out, (uint64_t)n * c.sflen, st);
   }
 
-  // the conversion of n subframes from position pos, raw block -> [subframe][antenna][sample] cf32, queued on st
-  void queueConvert(const void* raw, int64_t lo, uint64_t len, uint64_t pos, uint32_t n, cf32* out)
+  // the conversion of a block, raw block -> [subframe][antenna][sample] cf32 of every cell that takes part, queued on st
+  void queueConvert(Slot& s, const FileCellsBlock& b)
   {
-    if (!rs) { lsn_launch_file_unpack(raw, fmt, sfm.scale, d_rot, sflen, nant, out, n, st); return; }
-    const u128 base = rs->position(pos * sflen);
-    lsn_launch_resample(raw, fmt, sfm.scale, lo, len, (uint64_t)(base >> 64), (uint64_t)base, (uint32_t)(rs->step >> 64), (uint64_t)rs->step, rs->taps, rs->span, d_bank, rs->tune,
-                        d_nco, d_rot, sflen, 0, nant, out, (uint64_t)n * sflen, st);
+    if (!resampled()) { lsn_launch_file_unpack(s.d_raw, fmt, sfm.scale, cells[0].d_rot, cells[0].sflen, nant, s.d_iq[0], b.nsf[0], st); return; }
+    const uint64_t len = (uint64_t)(b.in_hi - b.in_lo);
+    if (cells.size() == 1) { queueResampleOne(cells[0], s.d_raw, b.in_lo, len, b.sf0[0], b.nsf[0], s.d_iq[0]); return; }
+    LsnResampleCell k[kFileMaxCells];
+    for (size_t c = 0; c < cells.size(); c++) {
+      const Cell& q = cells[c];
+      const u128 base = q.rs->position(b.sf0[c] * q.sflen);
+      k[c].base_hi = (uint64_t)(base >> 64); k[c].base_lo = (uint64_t)base; k[c].d_lo = (uint64_t)q.rs->step; k[c].d_hi = (uint32_t)(q.rs->step >> 64);
+      k[c].taps = q.rs->taps; k[c].span = q.rs->span; k[c].sflen = q.sflen; k[c].sf_off = 0; k[c].bank = q.d_bank; k[c].w = q.rs->tune; k[c].nco = q.d_nco; k[c].rot = q.d_rot;
+      k[c].out = s.d_iq[c]; k[c].n_out = (uint64_t)b.nsf[c] * q.sflen;
+    }
+    lsn_launch_resample_cells(s.d_raw, fmt, sfm.scale, b.in_lo, len, nant, k, (uint32_t)cells.size(), st);
   }
 
-  // stream, block buffers (kept by the engine: no-op when lsn_phy_prepare_file or an earlier call made them), rotation table, resampler bank
+  // stream, block buffers (kept by the engines: no-op when lsn_phy_prepare_file or an earlier call made them), rotation tables, resampler banks and NCO tables -
+  // of all cells, once, in front of the first block
   void setup()
   {
     HIP_CHECK(hipSetDevice(e.cfg.device));
     HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    if (e.reserveFileBuffers(nant) != LSN_SUCCESS) throw std::runtime_error("file source: block buffers");
+    for (auto& c : cells)
+      if (c.e->reserveFileBuffers(nant) != LSN_SUCCESS) throw std::runtime_error("file source: block buffers");
     for (int si = 0; si < NSLOT; si++) {
       Slot& s = slot[si];
-      FileBuf& fb = e.file_buf[si];
-      s.h_raw = fb.h_raw; s.d_raw = fb.d_raw; s.d_iq = fb.d_iq;
+      FileBuf& fb = big->file_buf[si];
+      if (fb.bytes < raw_bytes) throw std::runtime_error("file source: raw block buffer");
+      s.h_raw = fb.h_raw; s.d_raw = fb.d_raw;
+      for (size_t c = 0; c < cells.size(); c++) s.d_iq[c] = cells[c].e->file_buf[si].d_iq;
     }
-    if (offset_freq_hz != 0.0f) {
-      std::vector<cf32> rot(sflen);
-      const double fs = 15000.0 * (double)e.cd.N;
-      for (uint32_t n = 0; n < sflen; n++) {
-        const double a = -2.0 * M_PI * (double)offset_freq_hz * (double)n / fs;
-        rot[n] = {(float)std::cos(a), (float)std::sin(a)};
+    for (auto& c : cells) {
+      if (c.offset_freq_hz != 0.0f) {
+        std::vector<cf32> rot(c.sflen);
+        const double fs = 15000.0 * (double)c.e->cd.N;
+        for (uint32_t n = 0; n < c.sflen; n++) {
+          const double a = -2.0 * M_PI * (double)c.offset_freq_hz * (double)n / fs;
+          rot[n] = {(float)std::cos(a), (float)std::sin(a)};
+        }
+        HIP_CHECK(hipMalloc((void**)&c.d_rot, c.sflen * sizeof(cf32)));
+        HIP_CHECK(hipMemcpy(c.d_rot, rot.data(), c.sflen * sizeof(cf32), hipMemcpyHostToDevice));
       }
-      HIP_CHECK(hipMalloc((void**)&d_rot, sflen * sizeof(cf32)));
-      HIP_CHECK(hipMemcpy(d_rot, rot.data(), sflen * sizeof(cf32), hipMemcpyHostToDevice));
+      if (c.rs) c.rs->upload(c.d_bank, c.d_nco, st);
     }
-    if (rs) {
-      rs->upload(d_bank, d_nco, st);
-      HIP_CHECK(hipStreamSynchronize(st));
-    }
+    if (resampled()) HIP_CHECK(hipStreamSynchronize(st));
   }
 
-  // LSN_TTI_FROM_MIB: the first subframe 0 within 64 radio frames whose MIB decodes -> first_sf and the TTI the replay starts with; false: none
-  bool scanMib(uint32_t& start_tti)
+  // LSN_TTI_FROM_MIB of cell ci: the first subframe 0 within 64 radio frames whose MIB decodes -> its first_sf and the TTI its replay starts with; false: none
+  bool scanMib(size_t ci)
   {
-    for (uint64_t i = 0; i < sf_in_file && i < 10 * 64; i += 10) {  // the file starts at subframe 0 of a radio frame (file mode has no sync)
-      int64_t lo = 0; uint64_t len = sflen;
-      if (rs) rsSpan(i, 1, lo, len);
-      const size_t bytes = rs ? (size_t)len * spb : sf_bytes;
+    Cell& c = cells[ci];
+    for (uint64_t i = 0; i < c.sf_in_file && i < 10 * 64; i += 10) {  // the file starts at subframe 0 of a radio frame (file mode has no sync)
+      int64_t lo = 0, hi = 0;
+      if (c.rs) { c.rs->inputSpan(i * c.sflen, c.sflen, lo, hi); lo = std::max<int64_t>(lo, 0); }
+      const uint64_t len = c.rs ? (uint64_t)(hi - lo) : c.sflen;
+      const size_t bytes = c.rs ? (size_t)len * spb : sf_bytes;
+      if (bytes > raw_bytes) throw std::runtime_error("file source: one subframe's input does not fit the block buffer");
       std::vector<uint8_t> one(bytes);
-      if (pread(fd, one.data(), bytes, (off_t)(rs ? (uint64_t)lo * spb : file_off0 + i * sf_bytes)) != (ssize_t)bytes) break;
+      if (pread(fd, one.data(), bytes, (off_t)(c.rs ? (uint64_t)lo * spb : file_off0 + i * sf_bytes)) != (ssize_t)bytes) break;
       HIP_CHECK(hipMemcpyAsync(slot[0].d_raw, one.data(), bytes, hipMemcpyHostToDevice, st));
       HIP_CHECK(hipStreamSynchronize(st));
-      queueConvert(slot[0].d_raw, lo, len, i, 1, slot[0].d_iq);
+      if (c.rs) queueResampleOne(c, slot[0].d_raw, lo, len, i, 1, slot[0].d_iq[ci]);
+      else lsn_launch_file_unpack(slot[0].d_raw, fmt, sfm.scale, c.d_rot, c.sflen, nant, slot[0].d_iq[ci], 1, st);
       HIP_CHECK(hipStreamSynchronize(st));
       lsn_mib_t mib;
-      const int r = e.mibDecode(slot[0].d_iq, true, &mib, nullptr);
+      const int r = c.e->mibDecode(slot[0].d_iq[ci], true, &mib, nullptr);
       if (r < 0) throw std::runtime_error("MIB decode failed");
-      if (r == 1) { first_sf = i; start_tti = mib.sfn * 10u; return true; }
+      if (r == 1) { c.first_sf = i; c.start_tti = mib.sfn * 10u; return true; }
     }
     return false;
   }
@@ -266,7 +334,7 @@ struct Engine::FileReplay {
       (void)hipGetLastError();  // this mapping cannot be page-locked: copy through pinned buffers from here on
       use_mmap = false;
     }
-    if (!s.h_raw) { FileBuf& fb = e.file_buf[&s - slot]; HIP_CHECK(hipHostMalloc((void**)&fb.h_raw, fb.bytes, hipHostMallocDefault)); s.h_raw = fb.h_raw; }
+    if (!s.h_raw) { FileBuf& fb = big->file_buf[&s - slot]; HIP_CHECK(hipHostMalloc((void**)&fb.h_raw, fb.bytes, hipHostMallocDefault)); s.h_raw = fb.h_raw; }
     // the page-cache copy of one thread tops out near 9 GB/s: split the block over a few pread()ers
     std::vector<int> bad(nrd, 0);
     splitOver(total, part, [&](uint32_t r, size_t b0, size_t b1) {
@@ -282,38 +350,41 @@ struct Engine::FileReplay {
     return (const uint8_t*)s.h_raw;
   }
 
-  // `got` subframes from position pos into slot s: read, then copy and conversion QUEUED on st - the submit is ordered behind them on the device, so the
-  // reader goes straight on to the next block while this one crosses PCIe
-  void queueBlock(Slot& s, uint64_t pos, uint32_t got)
+  // block b into slot s: ONE read, then ONE copy and the conversion QUEUED on st - the submits are ordered behind them on the device, so the reader goes
+  // straight on to the next block while this one crosses PCIe
+  void queueBlock(Slot& s, const FileCellsBlock& b)
   {
-    int64_t in_lo = 0; uint64_t in_len = 0;   // resampler: the block's input samples [in_lo, in_lo + in_len)
-    if (rs) rsSpan(pos, got, in_lo, in_len);
-    const size_t total = rs ? (size_t)in_len * spb : got * sf_bytes;
-    const uint8_t* src = readBlock(s, rs ? (uint64_t)in_lo * spb : file_off0 + pos * sf_bytes, total);
+    const bool rs = resampled();   // the block's input samples are [in_lo, in_hi) of the recording, else whole subframes from file_off0
+    const size_t total = rs ? (size_t)(b.in_hi - b.in_lo) * spb : b.nsf[0] * sf_bytes;
+    if (total > raw_bytes) throw std::runtime_error("file source: a block's input does not fit the block buffer");
+    const uint8_t* src = readBlock(s, rs ? (uint64_t)b.in_lo * spb : file_off0 + b.sf0[0] * sf_bytes, total);
     HIP_CHECK(hipMemcpyAsync(s.d_raw, src, total, hipMemcpyHostToDevice, st));
-    queueConvert(s.d_raw, in_lo, in_len, pos, got, s.d_iq);
+    queueConvert(s, b);
   }
 
-  // reader thread: fills the free slots in turn until the file (or max_subframes) is through; an empty block marks the end
-  void readerLoop(uint64_t max_subframes)
+  // reader thread: fills the free slots in turn until every cell is through the file (or its max_subframes); an empty block marks the end
+  void readerLoop()
   {
     try {
       (void)hipSetDevice(e.cfg.device);
       e.pinThisThread(nullptr);
-      uint64_t avail = sf_in_file - first_sf, left = max_subframes ? std::min<uint64_t>(max_subframes, avail) : avail, pos = first_sf;
-      for (int i = 0;; i = (i + 1) % NSLOT) {
+      uint64_t k = 0;
+      for (int i = 0;; i = (i + 1) % NSLOT, k++) {
         Slot& s = slot[i];
         {
           std::unique_lock<std::mutex> lk(fm);
           fcv.wait(lk, [&] { return s.state == 0 || abort_reader; });
           if (abort_reader) return;
         }
-        const uint32_t got = (uint32_t)std::min<uint64_t>(blk, left);
+        FileCellsBlock b;
+        const bool got = file_cells_block(plans.data(), (uint32_t)plans.size(), blk, k, b);
         if (s.reg) { (void)hipHostUnregister(s.reg); s.reg = nullptr; }  // the block this slot carried last has been committed
-        if (got) queueBlock(s, pos, got);
-        pos += got;
-        left -= got;
-        { std::unique_lock<std::mutex> lk(fm); s.nsf = got; s.state = got ? 1 : 2; }
+        if (got) queueBlock(s, b);
+        {
+          std::unique_lock<std::mutex> lk(fm);
+          for (size_t c = 0; c < cells.size(); c++) s.nsf[c] = b.nsf[c];
+          s.state = got ? 1 : 2;
+        }
         fcv.notify_all();
         if (!got) return;
       }
@@ -325,9 +396,9 @@ struct Engine::FileReplay {
     }
   }
 
-  // block i is submitted (searched, queued for decoding) while block i-1 drains; its slot goes back to the reader once every chunk
-  // of it has been through stage A
-  int submitLoop(uint32_t start_tti, uint32_t update_meta_period)
+  // block i is submitted (searched, queued for decoding) to every engine that takes part in it, in cell order, while block i-1 drains; its slot goes back to the
+  // reader once every chunk of it has been through stage A of every one of them.  An engine that fails ends the submitting for all; all are waited for.
+  int submitLoop()
   {
     int rc = LSN_SUCCESS;
     std::deque<int> inflight;  // submitted blocks whose slot the reader may not touch yet (pinned source + device buffers still in use)
@@ -338,23 +409,65 @@ struct Engine::FileReplay {
         fcv.wait(lk, [&] { return s.state != 0; });
         if (s.state == 2) break;
       }
-      rc = e.submit(s.d_iq, s.nsf, (uint32_t)((start_tti + done) % 10240u), update_meta_period, st);
-      s.mark = e.submitMark();
-      done += s.nsf;
+      for (size_t ci = 0; ci < cells.size(); ci++) {
+        Cell& c = cells[ci];
+        // behind a failure: not submitted, nothing to wait for.  The slot of the failing block goes into `inflight` like any other and the loop ends: it is never
+        // handed back to the reader - its copy and kernel may still be on the stream - and is given up with the replay (the destructor joins the reader first)
+        if (rc != LSN_SUCCESS) s.nsf[ci] = 0;
+        if (!s.nsf[ci]) continue;
+        c.rc = c.e->submit(s.d_iq[ci], s.nsf[ci], (uint32_t)((c.start_tti + c.done) % 10240u), c.update_meta_period, st);
+        s.mark[ci] = c.e->submitMark();
+        c.done += s.nsf[ci];
+        if (c.rc != LSN_SUCCESS) rc = c.rc;
+      }
       inflight.push_back(i);
       while ((int)inflight.size() > NSLOT - 2) {  // keep two slots for the reader, hand the oldest one back once its chunks are written
         const int o = inflight.front();
         inflight.pop_front();
-        e.waitIqConsumed(slot[o].mark);  // stage A has read the block (UL_MODE: its chunks are written): pinned source and device buffers are free
+        for (size_t ci = 0; ci < cells.size(); ci++)   // stage A has read the block (UL_MODE: its chunks are written): pinned source and device buffers are free
+          if (slot[o].nsf[ci]) cells[ci].e->waitIqConsumed(slot[o].mark[ci]);
         { std::unique_lock<std::mutex> lk(fm); slot[o].state = 0; }
         fcv.notify_all();
       }
       if (rc != LSN_SUCCESS) break;
     }
-    const int w = e.wait();
-    return rc == LSN_SUCCESS ? w : rc;
+    for (auto& c : cells) {
+      const int w = c.e->wait();
+      if (c.rc == LSN_SUCCESS) c.rc = w;
+      if (rc == LSN_SUCCESS) rc = c.rc;
+    }
+    return rc;
   }
 };
+
+// the replay of `n` cells (FileCellJob: engine, plan, start) of one file; the single-cell entry points are its n = 1 case
+int Engine::replayFile(const char* path, const lsn_file_cfg_t& fc, FileCellJob* jobs, uint32_t n)
+{
+  FileReplay f(fc, jobs, n);
+  int rc = f.open(path);
+  if (rc != LSN_SUCCESS) return rc;
+  try {
+    f.setup();
+    bool moved = false;
+    for (size_t c = 0; c < f.cells.size(); c++) {
+      if (f.cells[c].start_tti != LSN_TTI_FROM_MIB) continue;
+      if (!f.scanMib(c)) throw std::runtime_error("no MIB found in the first 64 radio frames of the file");
+      moved = true;
+    }
+    if (moved && f.resampled() && !f.fitBlock()) return LSN_ERROR_INVALID_INPUTS;   // the MIBs put the cells' starts too far apart
+    f.plan();
+    if (f.fdebug) fprintf(stderr, "lsn_file: setup %.1f ms, mmap %d, %zu cell(s), block %u subframes, %d slots, %u readers\n", now_ms() - f.t_begin, (int)f.use_mmap, f.cells.size(), f.blk, f.NSLOT, f.nrd);
+    f.reader = std::thread([&] { f.readerLoop(); });
+    rc = f.submitLoop();
+    if (f.fdebug) fprintf(stderr, "lsn_file: %llu subframes (first cell) done at %.1f ms\n", (unsigned long long)f.cells[0].done, now_ms() - f.t_begin);
+    if (!f.rerr.empty()) throw std::runtime_error(f.rerr);
+  } catch (const std::exception& ex) {
+    fprintf(stderr, "ltesniffer_amd: %s\n", ex.what());
+    rc = LSN_ERROR;
+  }
+  for (uint32_t c = 0; c < n; c++) { jobs[c].done = f.cells[c].done; jobs[c].status = f.cells[c].rc; }
+  return rc;
+}
 
 int Engine::processFileImpl(const char* path, const lsn_file_cfg_t& fc, const ResamplePlan* rs, uint32_t start_tti, uint64_t max_subframes, uint32_t update_meta_period,
                             uint64_t* subframes_done)
@@ -362,22 +475,10 @@ int Engine::processFileImpl(const char* path, const lsn_file_cfg_t& fc, const Re
   if (subframes_done) *subframes_done = 0;
   if (!cell_set) return LSN_ERROR;
   if (!path || fc.nof_antennas != cd.iq_nant || fc.offset_time_samples < 0 || !lsn_sample_format(fc.sample_format, fc.sample_scale).valid) return LSN_ERROR_INVALID_INPUTS;
-  FileReplay f(*this, fc, rs);
-  int rc = f.open(path);
-  if (rc != LSN_SUCCESS) return rc;
-  try {
-    f.setup();
-    if (start_tti == LSN_TTI_FROM_MIB && !f.scanMib(start_tti)) throw std::runtime_error("no MIB found in the first 64 radio frames of the file");
-    if (f.fdebug) fprintf(stderr, "lsn_file: setup %.1f ms, mmap %d, block %u subframes, %d slots, %u readers\n", now_ms() - f.t_begin, (int)f.use_mmap, f.blk, f.NSLOT, f.nrd);
-    f.reader = std::thread([&] { f.readerLoop(max_subframes); });
-    rc = f.submitLoop(start_tti, update_meta_period);
-    if (f.fdebug) fprintf(stderr, "lsn_file: %llu subframes done at %.1f ms\n", (unsigned long long)f.done, now_ms() - f.t_begin);
-    if (!f.rerr.empty()) throw std::runtime_error(f.rerr);
-  } catch (const std::exception& ex) {
-    fprintf(stderr, "ltesniffer_amd: %s\n", ex.what());
-    rc = LSN_ERROR;
-  }
-  if (subframes_done) *subframes_done = f.done;
+  FileCellJob job;
+  job.e = this; job.rs = rs; job.offset_freq_hz = fc.offset_freq_hz; job.start_tti = start_tti; job.update_meta_period = update_meta_period; job.max_subframes = max_subframes;
+  const int rc = replayFile(path, fc, &job, 1);
+  if (subframes_done) *subframes_done = job.done;
   return rc;
 }
 

@@ -4,10 +4,11 @@
 // Product code: no CPU fallback (the samples are computed by k_resample only), nothing from oracle/ is included or linked.
 #include "lsn_hip.h"
 #include "../kernels/lsn_dev.h"
-#include "lsn_resample.h"
+#include "lsn_resample_launch.h"
 #include <cmath>
 #include <cstddef>
 #include <cstdio>
+#include <algorithm>
 #include <cstring>
 #include <stdexcept>
 #include <string>
@@ -94,7 +95,8 @@ int ResamplePlan::init(double rate_in, double rate_out, double passband_hz, uint
   return LSN_SUCCESS;
 }
 
-void ResamplePlan::upload(float*& d_bank, const cf32*& d_nco, hipStream_t s) const
+template <class Stream>
+void ResamplePlan::upload(float*& d_bank, const cf32*& d_nco, Stream s) const
 {
   HIP_CHECK(hipMalloc((void**)&d_bank, (bank.size() + nco.size()) * sizeof(float)));
   HIP_CHECK(hipMemcpyAsync(d_bank, bank.data(), bank.size() * sizeof(float), hipMemcpyHostToDevice, s));
@@ -104,6 +106,8 @@ void ResamplePlan::upload(float*& d_bank, const cf32*& d_nco, hipStream_t s) con
     d_nco = (const cf32*)(d_bank + bank.size());
   }
 }
+
+template void ResamplePlan::upload<hipStream_t>(float*&, const cf32*&, hipStream_t) const;
 
 void ResamplePlan::inputSpan(uint64_t m0, uint64_t n, int64_t& lo, int64_t& hi) const
 {
@@ -201,6 +205,84 @@ int lsn_resample(int device, const void* in, int in_on_device, uint64_t n_in, co
   if (d_in) (void)hipFree(d_in);
   if (d_bank) (void)hipFree(d_bank);
   if (d_out) (void)hipFree(d_out);
+  return rc;
+}
+
+// several resamplings of one input: one upload of the union of what the cells read, one launch of k_resample_cells
+int lsn_resample_cells(int device, const void* in, int in_on_device, uint64_t n_in, const lsn_resample_cfg_t* cfgs, uint32_t n_cells, float* const* outs, int out_on_device,
+                       const uint64_t* n_out)
+{
+  if (!cfgs || !outs || !n_out || n_cells < 1 || n_cells > LSN_FILE_MAX_CELLS) return LSN_ERROR_INVALID_INPUTS;
+  std::vector<lsn::ResamplePlan> plans(n_cells);
+  const lsn_resample_cfg_t& c0 = cfgs[0];
+  int64_t need_lo = 0, need_hi = 0;
+  bool any = false;
+  for (uint32_t c = 0; c < n_cells; c++) {
+    const lsn_resample_cfg_t& k = cfgs[c];
+    const int r = resample_plan(&k, plans[c]);
+    if (r != LSN_SUCCESS) return r;
+    if (k.struct_size != sizeof(lsn_resample_cfg_t) || k.nof_antennas != c0.nof_antennas || k.sample_format != c0.sample_format || !(k.sample_scale == c0.sample_scale) ||
+        k.rate_in_hz != c0.rate_in_hz || k.in_base != c0.in_base)
+      return LSN_ERROR_INVALID_INPUTS;
+    if (!n_out[c]) continue;
+    if (!in || !outs[c] || n_out[c] >= (1ull << 32) || k.out_first >= (1ull << 40) || k.in_base >= (1ull << 62) || n_in >= (1ull << 62)) return LSN_ERROR_INVALID_INPUTS;
+    int64_t lo, hi;
+    plans[c].inputSpan(k.out_first, n_out[c], lo, hi);
+    if (hi >= (int64_t)1 << 62) return LSN_ERROR_INVALID_INPUTS;
+    lo = std::max<int64_t>(lo, 0);   // in front of the recording: zeros
+    if (lo < (int64_t)k.in_base || hi > (int64_t)(k.in_base + n_in)) return LSN_ERROR_INVALID_INPUTS;   // the input does not hold what these outputs read
+    need_lo = any ? std::min(need_lo, lo) : lo;
+    need_hi = any ? std::max(need_hi, hi) : hi;
+    any = true;
+  }
+  if (!any) return LSN_SUCCESS;
+  const uint32_t nant = c0.nof_antennas, fmt = c0.sample_format;
+  const LsnSampleFormat sfm = lsn_sample_format(fmt, c0.sample_scale);
+  const size_t smp = (size_t)sfm.bytes * nant;
+  const uint64_t len = need_hi > need_lo ? (uint64_t)(need_hi - need_lo) : 0;
+  const uint8_t* src = (const uint8_t*)in + ((uint64_t)need_lo - c0.in_base) * smp;
+  void* d_in = nullptr;
+  std::vector<float*> d_bank(n_cells, nullptr);
+  std::vector<void*> d_out(n_cells, nullptr);
+  hipStream_t st = nullptr;
+  int rc = LSN_SUCCESS;
+  try {
+    HIP_CHECK(hipSetDevice(device));
+    HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    const void* raw = src;
+    if (!in_on_device && len) {
+      HIP_CHECK(hipMalloc(&d_in, len * smp));
+      HIP_CHECK(hipMemcpyAsync(d_in, src, len * smp, hipMemcpyHostToDevice, st));
+      raw = d_in;
+    }
+    LsnResampleCell k[LSN_FILE_MAX_CELLS];
+    for (uint32_t c = 0; c < n_cells; c++) {
+      const lsn::ResamplePlan& p = plans[c];
+      const cf32* d_nco = nullptr;
+      p.upload(d_bank[c], d_nco, st);
+      cf32* dst = (cf32*)outs[c];
+      if (!out_on_device && n_out[c]) {
+        HIP_CHECK(hipMalloc(&d_out[c], (size_t)n_out[c] * nant * sizeof(cf32)));
+        dst = (cf32*)d_out[c];
+      }
+      const lsn::u128 base = p.position(cfgs[c].out_first);
+      k[c].base_hi = (uint64_t)(base >> 64); k[c].base_lo = (uint64_t)base; k[c].d_lo = (uint64_t)p.step; k[c].d_hi = (uint32_t)(p.step >> 64); k[c].taps = p.taps; k[c].span = p.span;
+      k[c].sflen = (uint32_t)std::max<uint64_t>(n_out[c], 1); k[c].sf_off = 0; k[c].bank = d_bank[c]; k[c].w = p.tune; k[c].nco = d_nco; k[c].rot = nullptr; k[c].out = dst;
+      k[c].n_out = n_out[c];
+    }
+    lsn_launch_resample_cells(raw, fmt, sfm.scale, need_lo, len, nant, k, n_cells, st);
+    if (!out_on_device)
+      for (uint32_t c = 0; c < n_cells; c++)
+        if (n_out[c]) HIP_CHECK(hipMemcpyAsync(outs[c], d_out[c], (size_t)n_out[c] * nant * sizeof(cf32), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+  } catch (const std::exception& ex) {
+    fprintf(stderr, "ltesniffer_amd: resample_cells: %s\n", ex.what());
+    rc = LSN_ERROR;
+  }
+  if (st) (void)hipStreamDestroy(st);
+  if (d_in) (void)hipFree(d_in);
+  for (float* b : d_bank) if (b) (void)hipFree(b);
+  for (void* o : d_out) if (o) (void)hipFree(o);
   return rc;
 }
 

@@ -1,10 +1,11 @@
-// lsn_resample.h - host side of the polyphase resampler (kernels/resample.hip): the plan of one rate pair - step, start, taps, bank, and the
+// lsn_resample.h - host side of the polyphase resampler (kernels/resample.hip; launchers: lsn_resample_launch.h): the plan of one rate pair - step, start, taps, bank, and the
 // tuning word and NCO tables of the mixer in front of the filter - and the 64.64 position arithmetic in 128-bit integers.  Definition: DESIGN.md section 3.1b.
 #pragma once
 #include <cstdint>
 #include <vector>
-#include <hip/hip_runtime.h>
 
+// no HIP header: the plan is plain host arithmetic, and lsn_cells.cc, which builds on it, stays HIP-free.  What needs the runtime's types - the kernel launchers -
+// is declared in lsn_resample_launch.h.
 struct cf32;
 
 namespace lsn {
@@ -28,7 +29,8 @@ struct ResamplePlan {
            uint32_t max_taps = 192);
   static uint64_t tuning(double center_offset_hz, double rate_in);   // W of one offset
   // device copy of bank and nco in one allocation (the caller frees d_bank); d_nco = null when the plan does not mix
-  void upload(float*& d_bank, const cf32*& d_nco, hipStream_t s) const;
+  // Stream = hipStream_t, the one instantiation (lsn_resample.cc); a template so that this header names no type of the runtime
+  template <class Stream> void upload(float*& d_bank, const cf32*& d_nco, Stream s) const;
   u128 position(uint64_t m) const { return start + (u128)m * step; }
   // input samples [lo, hi) that outputs m0 .. m0 + n - 1 read (lo may be negative: zeros in front of the recording)
   void inputSpan(uint64_t m0, uint64_t n, int64_t& lo, int64_t& hi) const;
@@ -37,7 +39,3 @@ struct ResamplePlan {
 };
 
 }  // namespace lsn
-
-void lsn_launch_resample(const void* raw, uint32_t fmt, float scale, int64_t buf_base, uint64_t buf_len, uint64_t base_hi, uint64_t base_lo, uint32_t d_hi,
-                         uint64_t d_lo, uint32_t taps, uint32_t span, const float* bank, uint64_t w, const cf32* nco, const cf32* rot, uint32_t sflen, uint32_t sf_off,
-                         uint32_t nant, cf32* out, uint64_t n_out, hipStream_t s);

@@ -16,6 +16,9 @@
 // exp(-2 pi j Phi(n) / 2^64), Phi(n) = n * W mod 2^64 with n the sample's index in the RECORDING, while it is staged - the one place every input
 // sample is touched once; the tap loop does not know.  The exponential is the two-table NCO of k_ofdm (4096 coarse x 1024 fine entries).
 #include "lsn_dsp.h"
+#include "../host/lsn_resample_launch.h"
+#include <algorithm>
+#include <cstring>
 
 #define LSN_RS_RUN 512u      // outputs per workgroup (256 lanes x 2)
 
@@ -40,67 +43,91 @@ struct LsnResampleArgs {
   const cf32* nco;       // ... and the NCO tables, [4096] coarse then [1024] fine
 };
 
+// One run of one antenna: the staging loop and the tap loop.  They exist ONCE in this file, as text: the body is a macro that k_resample and k_resample_cells
+// expand, over the names A (the run's LsnResampleArgs), rs_x (the dynamic LDS) and FMT, with MIXCOND the one thing that differs - k_resample's template flag, or
+// the cell's own "has NCO tables", uniform over the workgroup.  A macro and not an inlined __device__ function: the compiler simplifies a function on its own
+// before it inlines it, which reorders k_resample's instructions; expanded as text, all six k_resample instantiations are the instruction streams
+// they were when this was k_resample's body.
+#define LSN_RESAMPLE_RUN(MIXCOND) \
+  const uint32_t a = blockIdx.y, half = A.taps / 2;                                                                                                                     \
+  const uint64_t i0 = (uint64_t)blockIdx.x * LSN_RS_RUN;                                                                                                                \
+  /* position of the run's first output: base + i0 * D */                                                                                                               \
+  uint64_t lo = i0 * A.d_lo, hi = __umul64hi(i0, A.d_lo) + i0 * (uint64_t)A.d_hi;                                                                                       \
+  lo += A.base_lo;                                                                                                                                                      \
+  hi += A.base_hi + (lo < A.base_lo ? 1u : 0u);                                                                                                                         \
+  const int64_t n_lo = (int64_t)hi - (int64_t)half + 1;  /* input sample staged at rs_x[0] */                                                                           \
+  for (uint32_t s = threadIdx.x; s < A.span; s += 256) {                                                                                                                \
+    const int64_t n = n_lo + (int64_t)s, k = n - A.buf_base;                                                                                                            \
+    float2 x = make_float2(0.0f, 0.0f);                                                                                                                                 \
+    if (n >= 0 && k >= 0 && (uint64_t)k < A.buf_len) {                                                                                                                  \
+      const size_t src = (size_t)k * A.nant + a;                                                                                                                        \
+      if (FMT == 1) {                                                                                                                                                   \
+        const short2 q = ((const short2*)A.raw)[src];                                                                                                                   \
+        x.x = (float)q.x * A.scale; x.y = (float)q.y * A.scale;                                                                                                         \
+      } else if (FMT == 2) {                                                                                                                                            \
+        const char2 q = ((const char2*)A.raw)[src];                                                                                                                     \
+        x.x = (float)q.x * A.scale; x.y = (float)q.y * A.scale;                                                                                                         \
+      } else {                                                                                                                                                          \
+        x = ((const float2*)A.raw)[src];                                                                                                                                \
+      }                                                                                                                                                                 \
+      if (MIXCOND) {                                                                                                                                                    \
+        const uint64_t ph = (uint64_t)n * A.w;  /* low 64 bits of n W */                                                                                                \
+        const cf32 e = cmul(A.nco[ph >> 52], A.nco[4096u + (uint32_t)((ph >> 42) & 1023u)]);                                                                            \
+        cf32 v; v.r = x.x; v.i = x.y;                                                                                                                                   \
+        v = cmulconj(v, e);                                                                                                                                             \
+        x.x = v.r; x.y = v.i;                                                                                                                                           \
+      }                                                                                                                                                                 \
+    }                                                                                                                                                                   \
+    rs_x[s] = x;                                                                                                                                                        \
+  }                                                                                                                                                                     \
+  __syncthreads();                                                                                                                                                      \
+  for (uint32_t r = 0; r < LSN_RS_RUN / 256; r++) {                                                                                                                     \
+    const uint64_t i = i0 + r * 256 + threadIdx.x;                                                                                                                      \
+    if (i >= A.n_out) break;                                                                                                                                            \
+    uint64_t plo = i * A.d_lo, phi = __umul64hi(i, A.d_lo) + i * (uint64_t)A.d_hi;                                                                                      \
+    plo += A.base_lo;                                                                                                                                                   \
+    phi += A.base_hi + (plo < A.base_lo ? 1u : 0u);                                                                                                                     \
+    const uint32_t s0 = (uint32_t)((int64_t)phi - (int64_t)half + 1 - n_lo);  /* first of the T staged samples of this output */                                        \
+    const uint32_t p = (uint32_t)(plo >> 55);  /* 9 bits of phase */                                                                                                    \
+    const float f = (float)(uint32_t)((plo >> 31) & 0xFFFFFFu) * 0x1p-24f;  /* 24 bits inside the phase, exact */                                                       \
+    if (s0 + A.taps > A.span) continue;  /* cannot happen (the host sizes span); keeps the LDS reads inside */                                                          \
+    const float4* row = (const float4*)(A.bank + (size_t)p * A.taps);                                                                                                   \
+    const float2* x = rs_x + s0;                                                                                                                                        \
+    float yr = 0.0f, yi = 0.0f;                                                                                                                                         \
+    for (uint32_t j = 0; j < half; j++) {                                                                                                                               \
+      const float4 c = row[j];                                                                                                                                          \
+      const float c0 = __builtin_fmaf(f, c.y, c.x), c1 = __builtin_fmaf(f, c.w, c.z);                                                                                   \
+      const float2 x0 = x[2 * j], x1 = x[2 * j + 1];                                                                                                                    \
+      yr = __builtin_fmaf(c0, x0.x, yr); yi = __builtin_fmaf(c0, x0.y, yi);                                                                                             \
+      yr = __builtin_fmaf(c1, x1.x, yr); yi = __builtin_fmaf(c1, x1.y, yi);                                                                                             \
+    }                                                                                                                                                                   \
+    const uint32_t q = (uint32_t)i + A.sf_off, sf = q / A.sflen, n = q - sf * A.sflen;  /* the launcher keeps n_out + sf_off below 2^32 */                              \
+    cf32 y; y.r = yr; y.i = yi;                                                                                                                                         \
+    if (A.rot) y = cmul(y, A.rot[n]);                                                                                                                                   \
+    A.out[((size_t)sf * A.nant + a) * A.sflen + n] = y;                                                                                                                 \
+  }
+
 template <int FMT, bool MIX>
 __global__ __launch_bounds__(256) void k_resample(const LsnResampleArgs A)
 {
   extern __shared__ float2 rs_x[];
-  const uint32_t a = blockIdx.y, half = A.taps / 2;
-  const uint64_t i0 = (uint64_t)blockIdx.x * LSN_RS_RUN;
-  // position of the run's first output: base + i0 * D
-  uint64_t lo = i0 * A.d_lo, hi = __umul64hi(i0, A.d_lo) + i0 * (uint64_t)A.d_hi;
-  lo += A.base_lo;
-  hi += A.base_hi + (lo < A.base_lo ? 1u : 0u);
-  const int64_t n_lo = (int64_t)hi - (int64_t)half + 1;  // input sample staged at rs_x[0]
-  for (uint32_t s = threadIdx.x; s < A.span; s += 256) {
-    const int64_t n = n_lo + (int64_t)s, k = n - A.buf_base;
-    float2 x = make_float2(0.0f, 0.0f);
-    if (n >= 0 && k >= 0 && (uint64_t)k < A.buf_len) {
-      const size_t src = (size_t)k * A.nant + a;
-      if (FMT == 1) {
-        const short2 q = ((const short2*)A.raw)[src];
-        x.x = (float)q.x * A.scale; x.y = (float)q.y * A.scale;
-      } else if (FMT == 2) {
-        const char2 q = ((const char2*)A.raw)[src];
-        x.x = (float)q.x * A.scale; x.y = (float)q.y * A.scale;
-      } else {
-        x = ((const float2*)A.raw)[src];
-      }
-      if (MIX) {
-        const uint64_t ph = (uint64_t)n * A.w;   // low 64 bits of n W
-        const cf32 e = cmul(A.nco[ph >> 52], A.nco[4096u + (uint32_t)((ph >> 42) & 1023u)]);
-        cf32 v; v.r = x.x; v.i = x.y;
-        v = cmulconj(v, e);
-        x.x = v.r; x.y = v.i;
-      }
-    }
-    rs_x[s] = x;
-  }
-  __syncthreads();
-  for (uint32_t r = 0; r < LSN_RS_RUN / 256; r++) {
-    const uint64_t i = i0 + r * 256 + threadIdx.x;
-    if (i >= A.n_out) break;
-    uint64_t plo = i * A.d_lo, phi = __umul64hi(i, A.d_lo) + i * (uint64_t)A.d_hi;
-    plo += A.base_lo;
-    phi += A.base_hi + (plo < A.base_lo ? 1u : 0u);
-    const uint32_t s0 = (uint32_t)((int64_t)phi - (int64_t)half + 1 - n_lo);   // first of the T staged samples of this output
-    const uint32_t p = (uint32_t)(plo >> 55);                                  // 9 bits of phase
-    const float f = (float)(uint32_t)((plo >> 31) & 0xFFFFFFu) * 0x1p-24f;      // 24 bits inside the phase, exact
-    if (s0 + A.taps > A.span) continue;                                        // cannot happen (the host sizes span); keeps the LDS reads inside
-    const float4* row = (const float4*)(A.bank + (size_t)p * A.taps);
-    const float2* x = rs_x + s0;
-    float yr = 0.0f, yi = 0.0f;
-    for (uint32_t j = 0; j < half; j++) {
-      const float4 c = row[j];
-      const float c0 = __builtin_fmaf(f, c.y, c.x), c1 = __builtin_fmaf(f, c.w, c.z);
-      const float2 x0 = x[2 * j], x1 = x[2 * j + 1];
-      yr = __builtin_fmaf(c0, x0.x, yr); yi = __builtin_fmaf(c0, x0.y, yi);
-      yr = __builtin_fmaf(c1, x1.x, yr); yi = __builtin_fmaf(c1, x1.y, yi);
-    }
-    const uint32_t q = (uint32_t)i + A.sf_off, sf = q / A.sflen, n = q - sf * A.sflen;   // the launcher keeps n_out + sf_off below 2^32
-    cf32 y; y.r = yr; y.i = yi;
-    if (A.rot) y = cmul(y, A.rot[n]);
-    A.out[((size_t)sf * A.nant + a) * A.sflen + n] = y;
-  }
+  LSN_RESAMPLE_RUN(MIX)
+}
+
+// Several cells of one recording from ONE raw buffer in one launch (lsn_file_process_cells, lsn_resample_cells): grid (largest number of runs
+// of a cell, antennas, cells).  The cells' arguments travel in the kernel argument block (8 x 128 bytes) and are read with scalar loads - the cell index is
+// blockIdx.z, the same for every lane.  Cells differ in D, T, n_out, sflen, bank and output buffer, so a workgroup in front of which its cell has no run left is
+// the normal case: it returns before it touches LDS.  The dynamic LDS request is the largest span of the launch's cells.  A cell mixes when it has NCO tables.
+#define LSN_RS_MAX_CELLS 8u
+struct LsnResampleCellsArgs { LsnResampleArgs c[LSN_RS_MAX_CELLS]; };
+
+template <int FMT>
+__global__ __launch_bounds__(256) void k_resample_cells(const LsnResampleCellsArgs P)
+{
+  extern __shared__ float2 rs_x[];
+  const LsnResampleArgs& A = P.c[blockIdx.z];
+  if ((uint64_t)blockIdx.x * LSN_RS_RUN >= A.n_out) return;
+  LSN_RESAMPLE_RUN(A.nco != nullptr)
 }
 
 // n_out outputs per antenna from output position (base_hi, base_lo); span = samples a run of LSN_RS_RUN outputs needs (host: lsn_resample.cc).
@@ -128,4 +155,35 @@ void lsn_launch_resample(const void* raw, uint32_t fmt, float scale, int64_t buf
     else if (fmt == 2) LSN_LAUNCH((k_resample<2, false>), g, dim3(256), lds, s, A);
     else LSN_LAUNCH((k_resample<0, false>), g, dim3(256), lds, s, A);
   }
+}
+
+// the cells of one launch: raw, buf_base, buf_len, fmt, scale and nant are the recording's and shared; everything else is the cell's own (lsn_resample.h).
+// A cell with n_out = 0 takes no part.
+void lsn_launch_resample_cells(const void* raw, uint32_t fmt, float scale, int64_t buf_base, uint64_t buf_len, uint32_t nant, const LsnResampleCell* cells, uint32_t n_cells,
+                               hipStream_t s)
+{
+  if (n_cells > LSN_RS_MAX_CELLS || buf_base < 0) throw std::runtime_error("k_resample_cells: bad geometry");
+  LsnResampleCellsArgs P;
+  memset(&P, 0, sizeof(P));
+  uint32_t n = 0, span = 0;
+  uint64_t runs = 0;
+  for (uint32_t c = 0; c < n_cells; c++) {
+    const LsnResampleCell& k = cells[c];
+    if (!k.n_out) continue;
+    if (k.taps < 2 || (k.taps & 1) || k.span < k.taps || (size_t)k.span * sizeof(float2) > 64 * 1024 || !k.sflen) throw std::runtime_error("k_resample_cells: bad geometry");
+    const uint64_t r = (k.n_out + LSN_RS_RUN - 1) / LSN_RS_RUN;
+    if (r > 0x7FFFFFFFull || k.n_out + k.sf_off > 0xFFFFFFFFull) throw std::runtime_error("k_resample_cells: launch too long");
+    LsnResampleArgs& A = P.c[n++];
+    A.raw = raw; A.buf_base = buf_base; A.buf_len = buf_len; A.base_hi = k.base_hi; A.base_lo = k.base_lo; A.d_lo = k.d_lo; A.d_hi = k.d_hi; A.taps = k.taps; A.span = k.span;
+    A.nant = nant; A.sflen = k.sflen; A.sf_off = k.sf_off; A.n_out = k.n_out; A.scale = scale; A.bank = (const float2*)k.bank; A.rot = k.rot; A.out = k.out;
+    A.w = k.w; A.nco = k.nco;
+    runs = std::max(runs, r);
+    span = std::max(span, k.span);
+  }
+  if (!n) return;
+  const dim3 g((uint32_t)runs, nant, n);
+  const size_t lds = (size_t)span * sizeof(float2);
+  if (fmt == 1) LSN_LAUNCH((k_resample_cells<1>), g, dim3(256), lds, s, P);
+  else if (fmt == 2) LSN_LAUNCH((k_resample_cells<2>), g, dim3(256), lds, s, P);
+  else LSN_LAUNCH((k_resample_cells<0>), g, dim3(256), lds, s, P);
 }
