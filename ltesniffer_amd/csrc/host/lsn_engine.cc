@@ -631,7 +631,8 @@ void Engine::packJobs(Chunk& ch, JobRunner& r, DecodeLaunch& L)
       if (d.qm[q]) L.llr_n += ((size_t)g.nof_re * d.qm[q] + 7) & ~(size_t)7;
     }
     d.prefix_off = (uint32_t)L.prefix_n;
-    L.prefix_n += 14 * nprb + 16;
+    L.prefix_n += lsn_rows_prefix_len(nprb);
+    d.rg = lsn_rows_geom(d.prb_mask, d.l0, cd.nslot, nprb);
     // transport blocks -> code blocks (36.212 5.1.2, 5.1.4.1.2)
     j.cb_first = (uint32_t)r.h_cbs.size();
     for (int i = 0; i < 2; i++) {
@@ -651,8 +652,7 @@ void Engine::packJobs(Chunk& ch, JobRunner& r, DecodeLaunch& L)
       pf.nof_cb_decodes += (uint64_t)s.C;
       pf.algo_bytes += bytes[i];
     }
-    if (g.prb_lo <= g.prb_hi)
-      for (uint32_t grp = g.prb_lo / 16; grp <= std::min<uint32_t>(g.prb_hi, nprb - 1) / 16; grp++) r.h_items.push_back(((uint32_t)r.h_jobs.size() << 8) | grp);
+    for (uint32_t grp = 0, n = lsn_rows_items(d.rg); grp < n; grp++) r.h_items.push_back(((uint32_t)r.h_jobs.size() << 8) | grp);   // 16 rows each (lsn_rows.h)
     r.h_jobs.push_back(d);
     L.jid_of_hjob.push_back(jid);
   }

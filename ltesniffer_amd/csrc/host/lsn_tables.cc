@@ -156,7 +156,7 @@ void Engine::allocRunner(JobRunner& r)
       cap = n;
     };
     dev(r.d_jobs, r.jobs_cap, 16); dev(r.d_cbs, r.cbs_cap, 32); dev(r.d_cbres, r.cbres_cap, 32);
-    dev(r.d_prefix, r.prefix_cap, 16.0 * (14 * 100 + 16)); dev(r.d_llr16, r.llr16_cap, 512.0 * 1024); dev(r.d_payload, r.payload_cap, 24.0 * 1024);
+    dev(r.d_prefix, r.prefix_cap, 16.0 * lsn_rows_prefix_len(100)); dev(r.d_llr16, r.llr16_cap, 512.0 * 1024); dev(r.d_payload, r.payload_cap, 24.0 * 1024);
     dev(r.d_items, r.items_cap, 64); dev(r.d_spp, r.spp_cap, 128.0 * 1024);
     host(r.h_cbres_pinned, r.h_cbres_cap, 32); host(r.h_payload_pinned, r.h_payload_cap, 24.0 * 1024); host(r.h_jobs_pinned, r.h_jobs_cap, 16);
     host(r.h_cbs_pinned, r.h_cbs_cap, 32); host(r.h_items_pinned, r.h_items_cap, 64);

@@ -7,6 +7,7 @@
 #include <stdexcept>
 #include <string>
 #include "../host/lsn_types.h"
+#include "lsn_rows.h"
 
 // A launch the runtime rejects (LDS request above the function's limit on this device, an empty or oversized grid, no code object for the
 // device) does not fail at the call site: the kernel never runs and the error sits in the thread until some later runtime call reports it -
@@ -111,8 +112,9 @@ struct LsnGrantDev {
   uint32_t qm[2];       // per codeword, 0 = unused
   uint32_t cinit[2];
   uint32_t llr_off[2];  // int16 element offsets into the LLR arena
-  uint32_t prefix_off;  // u16 element offset into the prefix arena: [14][nof_prb] then [16] symbol offsets
+  uint32_t prefix_off;  // u16 element offset into the prefix arena: [14][nof_prb], [16] symbol offsets, then the per-slot PRB lists (lsn_rows.h)
   float inv_amp_a, inv_amp_b;
+  LsnRowGeom rg;        // the job's demodulator rows (host: lsn_rows_geom of prb_mask, l0, the cell's nslot and nof_prb)
 };
 
 // one PUSCH grant to decode
@@ -164,7 +166,6 @@ void lsn_launch_prach(const cf32* iq, const uint64_t* occ_off, uint32_t nocc, co
 void lsn_launch_pusch_chest(const LsnCellDev& c, const LsnUlGrantDev* g, const cf32* grid, cf32* hs, float* stat, uint32_t ngrants, hipStream_t s);
 void lsn_launch_pusch_demod(const LsnCellDev& c, const LsnUlGrantDev* g, const cf32* grid, const cf32* hs, const float* stat, int16_t* llr,
                             uint32_t ngrants, hipStream_t s);
-void lsn_launch_pdsch_prep(const LsnCellDev& c, const LsnGrantDev* g, uint16_t* prefix, uint32_t njobs, hipStream_t s);
 void lsn_launch_pdsch_demod(const LsnCellDev& c, const LsnGrantDev* g, const uint32_t* items, uint32_t nitems, const uint16_t* prefix, const cf32* grid, const cf32* ce,
                             const LsnChest* ch, int16_t* llr, hipStream_t s);
 void lsn_launch_rm(const LsnCbDev* cb, const int16_t* llr, uint32_t* spp, uint32_t ncb, uint32_t emax, hipStream_t s);

@@ -3,7 +3,7 @@
 // descrambling, and the per-code-block turbo decoder (gather rate de-matching, windowed max-log-MAP with
 // next-iteration boundary init, early stop on the code-block CRC).  They replace srsran_ue_dl_decode_pdsch as called
 // from /root/reference/src/src/DL_Sniffer_PDSCH.cc:997,1110,1207 (config /root/reference/src/src/SubframeWorker.cc:362-371).
-// Mapping: demod = one thread per resource element (coalesced float2 loads of grid / channel estimates, int16 LLR
+// Mapping: demod = one thread per resource element of a dense list of (symbol, allocated PRB) rows (coalesced float2 loads of grid / channel estimates, int16 LLR
 // stores); turbo = one wavefront per code block, lane = trellis window, all soft data of the block staged in LDS,
 // forward metrics check-pointed every 16 steps and recomputed so that the block fits 2 workgroups per CU.
 #include "lsn_dsp.h"
@@ -16,41 +16,10 @@
 #define LLR_Q 180.0f
 
 // ------------------------------------------------------------------------------------------------ RE bookkeeping
-// prefix[l][prb] = number of PDSCH REs of this grant in symbol l before PRB prb; prefix[14*nprb + l] = REs before symbol l.
+// prefix[l][prb] = number of PDSCH REs of this grant in symbol l before PRB prb; prefix[14*nprb + l] = REs before symbol l; behind them the two per-slot
+// lists of the allocated PRBs, ascending, one byte each (layout: lsn_rows.h) - the demodulator's row -> PRB table.
 // One wavefront per job: lanes are PRBs (two rounds cover 110), the exclusive prefix over the PRBs of a symbol is a shuffle scan.
-__global__ __launch_bounds__(64) void k_pdsch_prep(LsnCellDev c, const LsnGrantDev* __restrict__ jobs, uint16_t* __restrict__ prefix)
-{
-  const LsnGrantDev& g = jobs[blockIdx.x];
-  const int lane = threadIdx.x, nprb = (int)c.nof_prb;
-  uint16_t* pf = prefix + g.prefix_off;
-  const int cls = g.sf_idx == 0 ? 0 : (g.sf_idx == 5 ? 1 : 2);
-  uint32_t before = 0;  // REs of the symbols in front of l (wave-uniform)
-  for (int l = 0; l < 14; l++) {
-    uint32_t run = 0;   // REs of this symbol in front of the current round
-    for (int base = 0; base < nprb; base += 64) {
-      const int prb = base + lane;
-      uint32_t v = 0;
-      if (prb < nprb && l >= (int)g.l0 && ((g.prb_mask[l >= (int)c.nslot ? 1 : 0][prb >> 5] >> (prb & 31)) & 1u)) v = (uint32_t)__popc((unsigned)c.validmask[(cls * 14 + l) * nprb + prb]);
-      uint32_t inc = v;  // inclusive scan over the 64 lanes
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t t = __shfl_up(inc, off);
-        if (lane >= off) inc += t;
-      }
-      if (prb < nprb) pf[l * nprb + prb] = (uint16_t)(run + inc - v);
-      run += __shfl(inc, 63);
-    }
-    if (lane == 0) pf[14 * nprb + l] = (uint16_t)before;
-    before += run;
-  }
-  if (lane == 0) pf[14 * nprb + 14] = (uint16_t)before;
-}
-void lsn_launch_pdsch_prep(const LsnCellDev& c, const LsnGrantDev* g, uint16_t* prefix, uint32_t njobs, hipStream_t s)
-{
-  LSN_LAUNCH(k_pdsch_prep, dim3(njobs), dim3(64), 0, s, c, g, prefix);
-}
-
-// The same with the upload of the launch's descriptors folded in (one launch less in every decode chain - the chains' depth, not their work, bounds
+// The upload of the launch's descriptors is folded in (one launch less in every decode chain - the chains' depth, not their work, bounds
 // the engine: DESIGN 3.2): workgroup j < njobs reads job j from the PINNED HOST array, stores the device copy the later kernels read and computes its
 // prefix table; the workgroups behind copy the other descriptor arrays (work items, code blocks) host -> device.
 __global__ __launch_bounds__(64) void k_pdsch_prep_up(LsnCellDev c, const LsnGrantDev* __restrict__ jobs_h, LsnGrantDev* __restrict__ jobs_d, uint32_t njobs,
@@ -84,14 +53,14 @@ __global__ __launch_bounds__(64) void k_pdsch_prep_up(LsnCellDev c, const LsnGra
   const LsnGrantDev& g = gs;
   uint16_t* pf = prefix + g.prefix_off;
   const int cls = g.sf_idx == 0 ? 0 : (g.sf_idx == 5 ? 1 : 2);
-  uint32_t before = 0;
+  uint32_t before = 0;  // REs of the symbols in front of l (wave-uniform)
   for (int l = 0; l < 14; l++) {
-    uint32_t run = 0;
+    uint32_t run = 0;   // REs of this symbol in front of the current round
     for (int base = 0; base < nprb; base += 64) {
       const int prb = base + lane;
       uint32_t v = 0;
       if (prb < nprb && l >= (int)g.l0 && ((g.prb_mask[l >= (int)c.nslot ? 1 : 0][prb >> 5] >> (prb & 31)) & 1u)) v = (uint32_t)__popc((unsigned)c.validmask[(cls * 14 + l) * nprb + prb]);
-      uint32_t inc = v;
+      uint32_t inc = v;  // inclusive scan over the 64 lanes
 #pragma unroll
       for (int off = 1; off < 64; off <<= 1) {
         const uint32_t t = __shfl_up(inc, off);
@@ -100,10 +69,14 @@ __global__ __launch_bounds__(64) void k_pdsch_prep_up(LsnCellDev c, const LsnGra
       if (prb < nprb) pf[l * nprb + prb] = (uint16_t)(run + inc - v);
       run += __shfl(inc, 63);
     }
-    if (lane == 0) pf[14 * nprb + l] = (uint16_t)before;
+    if (lane == 0) pf[lsn_rows_sym_off((uint32_t)nprb) + l] = (uint16_t)before;
     before += run;
   }
-  if (lane == 0) pf[14 * nprb + 14] = (uint16_t)before;
+  if (lane == 0) pf[lsn_rows_sym_off((uint32_t)nprb) + 14] = (uint16_t)before;
+  uint8_t* pl = (uint8_t*)(pf + lsn_rows_list_off((uint32_t)nprb));
+  for (int s = 0; s < 2; s++)
+    for (int prb = lane; prb < nprb; prb += 64)
+      if ((g.prb_mask[s][prb >> 5] >> (prb & 31)) & 1u) pl[s * nprb + (int)lsn_rows_ordinal(g.prb_mask[s], (uint32_t)prb)] = (uint8_t)prb;
 }
 void lsn_launch_pdsch_prep_up(const LsnCellDev& c, const LsnGrantDev* jobs_host, LsnGrantDev* jobs_dev, uint32_t njobs, const LsnCopySegs& sg, uint16_t* prefix, hipStream_t s)
 {
@@ -186,8 +159,12 @@ __device__ __forceinline__ void emit(const LsnCellDev& c, int Qm, cf32 x, float 
   }
 }
 
-// grid = (work items, 14 symbols): an item is one group of 16 PRBs inside the PRB span of one job (items[i] = job << 8 | group), listed by the
-// host - a grid over all groups of all jobs would be mostly empty workgroups (a grant covers a few PRBs of the 100)
+// grid = work items: an item is one group of 16 consecutive ROWS of one job (items[i] = job << 8 | group), listed by the host; a row is one (symbol,
+// allocated PRB) of the job in mapping order (lsn_rows.h) and a lane is (row, subcarrier).  The rows of a job are dense whatever its place in the band and
+// whichever symbols it starts at: only the last workgroup of a job has rows to spare, and the idle lanes of a row are its CRS / PSS / SSS / PBCH elements
+// (a partly filled wavefront costs the instructions of a full one, and the engine's rate follows the instructions issued: DESIGN 5.6).  Symbol, PRB, row
+// offset, RE mask, prefix entries and the rho_A / rho_B choice are per-lane values; the rest of the job descriptor stays wave-uniform.  A job has at most
+// 14 x 110 rows = 97 groups, so the group fits the item's low byte.
 __global__ __launch_bounds__(192) void k_pdsch_demod(LsnCellDev c, const LsnGrantDev* __restrict__ jobs, const uint32_t* __restrict__ items,
                                                      const uint16_t* __restrict__ prefix,
                                                      const cf32* __restrict__ grid, const cf32* __restrict__ ce,
@@ -196,18 +173,21 @@ __global__ __launch_bounds__(192) void k_pdsch_demod(LsnCellDev c, const LsnGran
   const uint32_t item = items[blockIdx.x];
   const LsnGrantDev& g = jobs[item >> 8];
   const int nprb = (int)c.nof_prb, nre = (int)c.nre, A = (int)c.nof_rx;
-  const int l = blockIdx.y, prb = (int)(item & 255u) * 16 + (int)threadIdx.x / 12, kk = (int)threadIdx.x % 12;
-  if (l < (int)g.l0 || prb >= nprb) return;
-  if (!((g.prb_mask[l >= (int)c.nslot ? 1 : 0][prb >> 5] >> (prb & 31)) & 1u)) return;
+  const uint32_t rsub = threadIdx.x / 12u, row = (item & 255u) * LSN_ROWS_PER_ITEM + rsub;
+  const int kk = (int)(threadIdx.x - rsub * 12u);
+  if (row >= g.rg.rows) return;
+  uint32_t lu, slot, ord;
+  lsn_rows_locate(g.rg, g.l0, c.nslot, row, &lu, &slot, &ord);
+  const uint16_t* pf = prefix + g.prefix_off;
+  const int l = (int)lu, prb = (int)((const uint8_t*)(pf + lsn_rows_list_off((uint32_t)nprb)))[__umul24(slot, (uint32_t)nprb) + ord];
   const int cls = g.sf_idx == 0 ? 0 : (g.sf_idx == 5 ? 1 : 2);
   const unsigned mask = c.validmask[(cls * 14 + l) * nprb + prb];
   if (!((mask >> kk) & 1u)) return;
-  const uint16_t* pf = prefix + g.prefix_off;
-  const uint32_t idx = (uint32_t)pf[14 * nprb + l] + (uint32_t)pf[l * nprb + prb] + (uint32_t)__popc(mask & ((1u << kk) - 1u));
+  const uint32_t idx = (uint32_t)pf[lsn_rows_sym_off((uint32_t)nprb) + l] + (uint32_t)pf[l * nprb + prb] + (uint32_t)__popc(mask & ((1u << kk) - 1u));
   const int k = 12 * prb + kk;
   const LsnChest ch = chest[g.sf];
   const float noise = ch.noise_avg, chan_ref = ch.chan_ref;
-  const int lq = l >= (int)c.nslot ? l - (int)c.nslot : l;
+  const int lq = slot ? l - (int)c.nslot : l;
   const float inv_amp = (lq == 0 || lq == (int)c.nslot - 3) ? g.inv_amp_b : g.inv_amp_a;   // rho_B on the symbols with the CRS of ports 0, 1 (36.213 Table 5.2-2)
   const cf32* gr = grid + (size_t)g.sf * A * 14 * nre;                 // (wave-uniform: scalar arithmetic)
   const cf32* ch0 = ce + (size_t)g.sf * c.nof_ports * A * 14 * nre;
@@ -244,27 +224,34 @@ __global__ __launch_bounds__(192) void k_pdsch_demod(LsnCellDev c, const LsnGran
         for (uint32_t b = 0; b < g.qm[0]; b++) out0[n0 + b] = 0;
         return;
       }
-      if (idx & 1u) return;
-      const int k2 = k + 1 + (__ffs(hi) - 1);
-      float x0r = 0, x0i = 0, x1r = 0, x1i = 0, hh = 0;
+      // Every lane of a pair emits its own element, so that the soft-bit emission - the bulk of the kernel - runs at full lane occupancy.
+      // k = the lane's own RE, kp = its partner's.  With the pair's REs (k0, k1) and h00 h01 / h10 h11 the
+      // channels of the two ports at them, element 0 is r0 h00* + h11 r1* and element 1 is r1 h01* - h10 r0*: both are r_own h_pa,own* -+ h_pb,partner
+      // r_partner*, so the lanes differ in one sign (d - cc = d + (-cc) bit for bit) and in nothing else.  The weight's |h00|^2 + |h11|^2 is taken at
+      // (pa, k0), (pb, k1) for both lanes: the odd lane reads those two values as well - nothing is exchanged between lanes, a pair may straddle two wavefronts.
+      const bool odd = (idx & 1u) != 0u;
+      const int kp = 12 * prb + (odd ? 31 - __clz((int)(mask & ((1u << kk) - 1u))) : kk + __ffs(hi));
+      const uint32_t sgn = (idx & 1u) << 31;
+      float xr = 0, xi = 0, hh = 0;
       // four ports (SFBC-FSTD, 36.211 6.3.4.3): symbol pairs alternate between the port pairs (0, 2) and (1, 3); each pair sees half of the ports
       // chan_ref sums over, so its weight doubles
       const bool fstd = c.nof_ports == 4;
       const int pa = (fstd && (idx & 2u)) ? 1 : 0, pb = fstd ? pa + 2 : 1;
       for (int rx = 0; rx < A; rx++) {
-        cf32 r0 = GRID(rx, k), r1 = GRID(rx, k2);
-        cf32 h00 = CE(pa, rx, k), h01 = CE(pa, rx, k2), h10 = CE(pb, rx, k), h11 = CE(pb, rx, k2);
+        cf32 ro = GRID(rx, k), rp = GRID(rx, kp);
+        cf32 hao = CE(pa, rx, k), hap = CE(pa, rx, kp), hbo = CE(pb, rx, k), hbp = CE(pb, rx, kp);
+        cf32 h00 = odd ? hap : hao, h11 = odd ? hbo : hbp;
         float hp = cabs2(h00) + cabs2(h11);
-        cf32 a = cmulconj(r0, h00), b = cmulconj(h11, r1), cc = cmulconj(h10, r0), d = cmulconj(r1, h01);
-        float t0r = a.r + b.r, t0i = a.i + b.i, t1r = d.r - cc.r, t1i = d.i - cc.i;
-        if (rx == 0) { x0r = t0r; x0i = t0i; x1r = t1r; x1i = t1i; hh = hp; }
-        else { x0r = x0r + t0r; x0i = x0i + t0i; x1r = x1r + t1r; x1i = x1i + t1i; hh = hh + hp; }
+        cf32 u = cmulconj(ro, hao), v = cmulconj(hbp, rp);
+        v.r = __uint_as_float(__float_as_uint(v.r) ^ sgn); v.i = __uint_as_float(__float_as_uint(v.i) ^ sgn);
+        float tr = u.r + v.r, ti = u.i + v.i;
+        if (rx == 0) { xr = tr; xi = ti; hh = hp; }
+        else { xr = xr + tr; xi = xi + ti; hh = hh + hp; }
       }
-      cf32 x0, x1;
-      x0.r = x0r / hh * SQRT2F; x0.i = x0i / hh * SQRT2F; x1.r = x1r / hh * SQRT2F; x1.i = x1i / hh * SQRT2F;
+      cf32 x;
+      x.r = xr / hh * SQRT2F; x.i = xi / hh * SQRT2F;
       float w = hh * (fstd ? 2.0f : 1.0f) / chan_ref;
-      emit(c, (int)g.qm[0], x0, w, inv_amp, g.cinit[0], idx, out0);
-      emit(c, (int)g.qm[0], x1, w, inv_amp, g.cinit[0], idx + 1, out0);
+      emit(c, (int)g.qm[0], x, w, inv_amp, g.cinit[0], idx, out0);
       break;
     }
     default: {  // 2: closed-loop spatial multiplexing, 3: large-delay CDD
@@ -326,7 +313,7 @@ __global__ __launch_bounds__(192) void k_pdsch_demod(LsnCellDev c, const LsnGran
 void lsn_launch_pdsch_demod(const LsnCellDev& c, const LsnGrantDev* g, const uint32_t* items, uint32_t nitems, const uint16_t* prefix, const cf32* grid,
                             const cf32* ce, const LsnChest* ch, int16_t* llr, hipStream_t s)
 {
-  if (nitems) LSN_LAUNCH(k_pdsch_demod, dim3(nitems, 14), dim3(192), 0, s, c, g, items, prefix, grid, ce, ch, llr);
+  if (nitems) LSN_LAUNCH(k_pdsch_demod, dim3(nitems), dim3(192), 0, s, c, g, items, prefix, grid, ce, ch, llr);
 }
 
 // ------------------------------------------------------------------------------------------------ rate de-matching
