@@ -428,6 +428,52 @@ int lsn_file_cells_span(const lsn_file_cfg_t* cfg, double sample_rate_hz, const 
 int lsn_resample_cells(int device, const void* in, int in_on_device, uint64_t n_in, const lsn_resample_cfg_t* cfgs, uint32_t n_cells, float* const* outs,
                        int out_on_device, const uint64_t* n_out);
 
+/* ---- sharp channel filter in front of the resampler: a cell next to a much stronger carrier ----
+ * The resampler's filter has the transition band [B, min(rate) - B]: a neighbour carrier inside it reaches the FFT's guard bins undamped and leaks into the
+ * occupied bins at about -40 dB.  The channel filter is an opt-in stage 1 at the RECORDING's rate, the resampler becomes stage 2:
+ *   y1[n] = sum over k = n - L .. n + L, in that order, of g[n - k] xm[k]      (one fma per product into one float32 accumulator per component)
+ *   xm[n] = x[n] exp(-2 pi j (n W mod 2^64) / 2^64)  - the mixer of lsn_resample (same W, same NCO), n the index in the recording; xm[n] = 0 for n < 0
+ *   g[j]  = 2 fc sinc(2 fc j) I0(beta sqrt(1 - (j / (L + 1))^2)) / I0(beta), j = -L .. L, float32;   fc = (B + S) / (2 R),   beta = 0.1102 (80 - 8.7),
+ *   L     = ceil((80 - 7.95) / (14.36 (S - B) / R) / 2)
+ * with R the recording's rate, B = passband_hz and S = stopband_hz: from |f| >= S on, relative to the wanted carrier, everything is 80 dB down by design.  Stage 2
+ * is the resampler's plan of the same rate pair, pass band and start with center_offset_hz = 0, reading y1.  y1[n] is a function of (input, configuration, n) only:
+ * block sizes, pieces and call boundaries change no bit.  Accepted: S finite, B < S <= R / 2, L <= 512 (S - B >= 0.0049 R: 301 kHz at 61.44 MS/s), and the
+ * resampler's rule |center_offset_hz| + B <= R / 2; everything else is LSN_ERROR_INVALID_INPUTS.
+ *
+ * lsn_phy_set_channel_filter: stopband_hz of this Phy's file replays (lsn_phy_process_file, lsn_phy_process_file_rate, lsn_file_process_cells; LSN_TTI_FROM_MIB
+ * resamples through the same two stages); 0 = off, the default.  Sticky, like lsn_phy_set_sampling.  Negative, NaN or infinite: LSN_ERROR_INVALID_INPUTS; the
+ * value is checked against rate and bandwidth when a replay starts (a refused replay decodes nothing and leaves the Phy usable).  With the filter set a file at
+ * the Phy's own rate goes through both stages too.  In lsn_file_process_cells either every cell's Phy has a filter or none has: a mix is refused.
+ * lsn_file_cells_span reads the setting from a non-NULL phy (the block's input is L samples wider on both sides); with phy NULL it plans the unfiltered pass. */
+int lsn_phy_set_channel_filter(lsn_phy_t* phy, double stopband_hz);
+typedef struct {
+  uint32_t struct_size;      /* in: sizeof(lsn_channel_filter_design_t); every other size is refused */
+  uint32_t half_len;         /* L */
+  uint32_t nof_taps;         /* 2 L + 1 */
+  uint32_t reserved;
+  double   cutoff;           /* fc, cycles per input sample */
+} lsn_channel_filter_design_t;
+/* The design alone, no GPU: L, fc and (taps != NULL: cap >= 2 L + 1 floats) g[-L] .. g[L]. */
+int lsn_channel_filter_design(double rate_in_hz, double passband_hz, double stopband_hz, lsn_channel_filter_design_t* out, float* taps, uint32_t cap);
+typedef struct {
+  uint32_t struct_size;      /* sizeof(lsn_channel_filter_cfg_t); every other size is refused */
+  uint32_t nof_antennas;     /* interleaved in the input */
+  uint32_t sample_format;    /* LSN_FILE_* */
+  float    sample_scale;     /* as lsn_file_cfg_t */
+  double   rate_in_hz, passband_hz, stopband_hz, center_offset_hz;
+  uint64_t in_base;          /* index, in the recording, of in[0] */
+  uint64_t out_first;        /* index n of out[0] */
+} lsn_channel_filter_cfg_t;
+/* Stage 1 alone, no Phy.  in: [sample][antenna] in sample_format; out: [sample][antenna] cf32, out[0] = y1[out_first] - what lsn_resample takes as cf32 input with
+ * in_base = out_first and center_offset_hz = 0.  Samples in front of sample 0 of the recording read as zeros; every other sample in [out_first - L, out_first +
+ * n_out + L) must lie inside in, otherwise LSN_ERROR_INVALID_INPUTS. */
+int lsn_channel_filter(int device, const void* in, int in_on_device, uint64_t n_in, const lsn_channel_filter_cfg_t* cfg, float* out, int out_on_device, uint64_t n_out);
+/* in_lo / in_hi: the input samples n_out outputs from out_first read; max_out: outputs from out_first on whose input lies in front of in_end; taps = 2 L + 1.  No GPU. */
+int lsn_channel_filter_span(const lsn_channel_filter_cfg_t* cfg, uint64_t n_out, uint64_t in_end, lsn_resample_span_t* out);
+/* The stop band of every cell of a recording from its neighbours: S_i = min over j != i of (|f_j - f_i| - B_j), B_j = 15 kHz (6 nof_prb_j + 1), capped at
+ * rate_in / 2; 0 (no filter) for a cell without a neighbour or when that is not above B_i.  LSN_ERROR_INVALID_INPUTS when a cell's L would exceed 512. */
+int lsn_cells_stopbands(const double* carrier_hz, const uint32_t* nof_prb, uint32_t n, double rate_in_hz, double* stopband_hz);
+
 /* ---- the sample clock of a recording, measured from its PSS train ----
  * A recording made by a radio whose clock is off by eps runs at fs (1 + eps), fs = 15 kHz * N the nominal rate: PSS occurrence q (one every 5 ms, W5 = 75 N
  * nominal samples) starts at p_q = p_0 + q W5 (1 + eps).  lsn_clock_estimate correlates the PSS replica of the cell (rotated by cfo_hz) over a short window

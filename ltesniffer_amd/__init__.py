@@ -42,7 +42,8 @@ EXPORTS = ["lsn_phy_create", "lsn_phy_destroy", "lsn_phy_set_cell", "lsn_phy_get
            "lsn_phy_set_sampling", "lsn_phy_get_sampling", "lsn_symbol_sz", "lsn_sampling_freq_hz", "lsn_cell_search_rates",
            "lsn_resample", "lsn_resample_span", "lsn_phy_process_file_rate", "lsn_resample_cells", "lsn_file_cells_span", "lsn_file_process_cells",
            "lsn_clock_plan", "lsn_clock_fit", "lsn_clock_replica", "lsn_clock_track", "lsn_clock_estimate", "lsn_file_clock_estimate",
-           "lsn_carrier_scan_plan", "lsn_carrier_scan_decide", "lsn_carrier_scan", "lsn_file_carrier_scan", "lsn_carrier_channel", "lsn_carrier_channel_span"]
+           "lsn_carrier_scan_plan", "lsn_carrier_scan_decide", "lsn_carrier_scan", "lsn_file_carrier_scan", "lsn_carrier_channel", "lsn_carrier_channel_span",
+           "lsn_phy_set_channel_filter", "lsn_channel_filter_design", "lsn_channel_filter", "lsn_channel_filter_span", "lsn_cells_stopbands"]
 
 RATES_3GPP, RATES_SRSRAN = 0, 1   # LSN_RATES_*: sampling mode of a Phy / of a cell search
 
@@ -131,6 +132,16 @@ class ResampleCfg(C.Structure):   # lsn_resample_cfg_t
 
 class ResampleSpan(C.Structure):   # lsn_resample_span_t
     _fields_ = [("in_lo", C.c_int64), ("in_hi", C.c_int64), ("max_out", C.c_uint64), ("taps", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ChannelFilterDesign(C.Structure):   # lsn_channel_filter_design_t
+    _fields_ = [("struct_size", C.c_uint32), ("half_len", C.c_uint32), ("nof_taps", C.c_uint32), ("reserved", C.c_uint32), ("cutoff", C.c_double)]
+
+
+class ChannelFilterCfg(C.Structure):   # lsn_channel_filter_cfg_t
+    _fields_ = [("struct_size", C.c_uint32), ("nof_antennas", C.c_uint32), ("sample_format", C.c_uint32), ("sample_scale", C.c_float),
+                ("rate_in_hz", C.c_double), ("passband_hz", C.c_double), ("stopband_hz", C.c_double), ("center_offset_hz", C.c_double),
+                ("in_base", C.c_uint64), ("out_first", C.c_uint64)]
 
 
 class ClockCfg(C.Structure):   # lsn_clock_cfg_t
@@ -428,6 +439,11 @@ def lib():
         L.lsn_file_carrier_scan.argtypes = [C.c_int, C.c_char_p, C.POINTER(FileCfg), C.POINTER(CarrierScanCfg), C.POINTER(Carrier), C.c_uint32, C.POINTER(CarrierMetric)]
         L.lsn_carrier_channel.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.POINTER(CarrierChannelCfg), C.c_void_p, C.c_int, C.c_uint64]
         L.lsn_carrier_channel_span.argtypes = [C.POINTER(CarrierChannelCfg), C.c_uint64, C.c_uint64, C.POINTER(ResampleSpan)]
+        L.lsn_phy_set_channel_filter.argtypes = [C.c_void_p, C.c_double]
+        L.lsn_channel_filter_design.argtypes = [C.c_double, C.c_double, C.c_double, C.POINTER(ChannelFilterDesign), C.c_void_p, C.c_uint32]
+        L.lsn_channel_filter.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.POINTER(ChannelFilterCfg), C.c_void_p, C.c_int, C.c_uint64]
+        L.lsn_channel_filter_span.argtypes = [C.POINTER(ChannelFilterCfg), C.c_uint64, C.c_uint64, C.POINTER(ResampleSpan)]
+        L.lsn_cells_stopbands.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.c_uint32, C.c_double, C.POINTER(C.c_double)]
         _lib = L
     return _lib
 
@@ -569,6 +585,13 @@ class Phy:
 
     def get_sampling(self):
         return int(lib().lsn_phy_get_sampling(self._h))
+
+    def set_channel_filter(self, stopband_hz):
+        """lsn_phy_set_channel_filter: this Phy's file replays (process_file, process_file_rate, process_file_cells) run a sharp channel filter at the recording's
+        rate in front of the resampler - everything from stopband_hz on, relative to the cell's carrier, is 80 dB down (a neighbour carrier: the distance to its
+        nearest occupied edge, cells_stopbands).  0: off (the default).  Sticky; checked against rate and bandwidth when a replay starts.  False: refused
+        (negative or not finite)"""
+        return lib().lsn_phy_set_channel_filter(self._h, float(stopband_hz)) == LSN_SUCCESS
 
     def setCell(self, nof_prb, nof_ports, cell_id, phich_resources=0, cp=0):
         """cp: srsran_cell_t.cp - 0 normal, 1 extended cyclic prefix (downlink path)"""
@@ -1001,9 +1024,71 @@ def resample_cells(iq, rate_in, cells, n_out=None, in_base=0, sample_format=FILE
     return outs
 
 
+def channel_filter_design(rate_in, passband_hz, stopband_hz):
+    """lsn_channel_filter_design (needs no GPU) -> dict(L, fc, taps: float32 [2 L + 1], g[-L] .. g[L]).  Raises ValueError when the library refuses the filter"""
+    import numpy as np
+    d = ChannelFilterDesign(C.sizeof(ChannelFilterDesign), 0, 0, 0, 0.0)
+    taps = np.zeros(2 * 512 + 1, dtype=np.float32)
+    rc = lib().lsn_channel_filter_design(float(rate_in), float(passband_hz), float(stopband_hz), C.byref(d), taps.ctypes.data, taps.size)
+    if rc == LSN_ERROR_INVALID_INPUTS:
+        raise ValueError("channel filter: refused")
+    _check(rc, "lsn_channel_filter_design")
+    return dict(L=int(d.half_len), fc=float(d.cutoff), taps=taps[:d.nof_taps].copy())
+
+
+def _channel_filter_cfg(nof_antennas, rate_in, passband_hz, stopband_hz, center_offset_hz, in_base, out_first, sample_format, sample_scale):
+    return ChannelFilterCfg(C.sizeof(ChannelFilterCfg), int(nof_antennas), int(sample_format), float(sample_scale), float(rate_in), float(passband_hz), float(stopband_hz),
+                            float(center_offset_hz), int(in_base), int(out_first))
+
+
+def channel_filter_span(n_out, in_end, rate_in, passband_hz, stopband_hz, out_first=0, center_offset_hz=0.0):
+    """lsn_channel_filter_span (needs no GPU) -> dict(in_lo, in_hi, max_out, taps): the input samples [in_lo, in_hi) that y1[out_first .. out_first + n_out - 1]
+    read, and the number of outputs from out_first on that a recording of in_end samples carries.  Raises ValueError when the library refuses the filter"""
+    cfg = _channel_filter_cfg(1, rate_in, passband_hz, stopband_hz, center_offset_hz, 0, out_first, FILE_CF32, 0.0)
+    sp = ResampleSpan()
+    rc = lib().lsn_channel_filter_span(C.byref(cfg), int(n_out), int(in_end), C.byref(sp))
+    if rc == LSN_ERROR_INVALID_INPUTS:
+        raise ValueError("channel filter: refused")
+    _check(rc, "lsn_channel_filter_span")
+    return dict(in_lo=int(sp.in_lo), in_hi=int(sp.in_hi), max_out=int(sp.max_out), taps=int(sp.taps))
+
+
+def channel_filter(iq, rate_in, passband_hz, stopband_hz, n_out=None, center_offset_hz=0.0, in_base=0, out_first=0, sample_format=FILE_CF32, sample_scale=0.0, device=0):
+    """lsn_channel_filter (k_chan_fir, needs no Phy): stage 1 alone.  iq and in_base as resample.  -> y1[out_first .. out_first + n_out - 1] as complex64
+    [n_out][antenna] (n_out None: as many as iq carries) - what resample takes as input with in_base=out_first and no center_offset_hz"""
+    iq = _scan_input(iq, sample_format)
+    n_in, nant = iq.shape[0], iq.shape[1]
+    cfg = _channel_filter_cfg(nant, rate_in, passband_hz, stopband_hz, center_offset_hz, in_base, out_first, sample_format, sample_scale)
+    if n_out is None:
+        sp = ResampleSpan()
+        _check(lib().lsn_channel_filter_span(C.byref(cfg), 0, int(in_base) + n_in, C.byref(sp)), "lsn_channel_filter_span")
+        n_out = int(sp.max_out)
+    out = np.zeros((int(n_out), nant), dtype=np.complex64)
+    _check(lib().lsn_channel_filter(device, iq.ctypes.data, 0, n_in, C.byref(cfg), out.ctypes.data, 0, int(n_out)), "lsn_channel_filter")
+    return out
+
+
+def cells_stopbands(carriers_hz, nof_prb, rate_in):
+    """lsn_cells_stopbands (needs no GPU): the stopband_hz of every cell of a recording from its neighbours - the distance from its carrier to the nearest occupied
+    edge of another cell, capped at rate_in / 2; 0.0 (no filter) for a cell that has no neighbour.  Raises ValueError when a neighbour is too close for the filter"""
+    n = len(carriers_hz)
+    f = (C.c_double * max(n, 1))(*[float(c.center_offset_hz if isinstance(c, Carrier) else c) for c in carriers_hz])
+    prb = (C.c_uint32 * max(n, 1))(*[int(p) for p in nof_prb])
+    out = (C.c_double * max(n, 1))()
+    rc = lib().lsn_cells_stopbands(f, prb, n, float(rate_in), out)
+    if rc == LSN_ERROR_INVALID_INPUTS:
+        raise ValueError("cells_stopbands: refused")
+    _check(rc, "lsn_cells_stopbands")
+    return [float(v) for v in out[:n]]
+
+
 def _file_cell(phy, kw):
     """(phy or None, dict) -> FileCell.  center_offset_hz may be a Carrier of carrier_scan / file_carrier_scan: its center_offset_hz is taken as it is"""
     kw = dict(kw)
+    if "stopband_hz" in kw:   # the channel filter is a setting of the Phy (set_channel_filter): sticky, like the call
+        stop = kw.pop("stopband_hz")
+        if phy is None or not phy.set_channel_filter(stop):
+            raise ValueError("stopband_hz: %s" % ("needs a Phy" if phy is None else "refused"))
     f0 = kw.pop("center_offset_hz", 0.0)
     if isinstance(f0, Carrier):
         f0 = f0.center_offset_hz
@@ -1037,7 +1122,8 @@ def file_cells_span(sample_rate, cells, in_end, block=0, blk_subframes=800, nof_
 def process_file_cells(path, sample_rate, cells, nof_antennas=None, sample_format=FILE_CF32, sample_scale=0.0, with_status=False):
     """lsn_file_process_cells: replay several cells of one recording made at sample_rate (Hz) in ONE pass over the file - one read and one host-to-device copy
     per block, one kernel launch for all cells, each Phy fed with its own cell's subframes.  cells: a list of (phy, dict(center_offset_hz=, start_tti=, offset_time=,
-    offset_time_frac=, offset_freq=, max_subframes=, update_meta_period=)); center_offset_hz may be a Carrier of file_carrier_scan.  start_tti may be
+    offset_time_frac=, offset_freq=, max_subframes=, update_meta_period=, stopband_hz=)); center_offset_hz may be a Carrier of file_carrier_scan; stopband_hz
+    (cells_stopbands) is set on that Phy as set_channel_filter does - every cell or none.  start_tti may be
     TTI_FROM_MIB, per cell.  -> the list of subframes done, one per cell [, the list of per-cell status codes].  Raises ValueError when the library refuses
     the cells (nothing is decoded, every Phy stays usable)"""
     arr = (FileCell * max(len(cells), 1))()

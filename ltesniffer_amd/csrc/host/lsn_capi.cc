@@ -12,6 +12,7 @@
 // lets batches grow towards half the pool; live mode (getAvailImmediate, :439) dispatches whatever is pending at once.
 #include "lsn_engine.h"
 #include "lsn_cells.h"
+#include "lsn_chanfilt_launch.h"
 #include <chrono>
 #include <condition_variable>
 #include <deque>
@@ -543,14 +544,16 @@ int lsn_phy_process_file_rate(lsn_phy_t* phy, const char* path, const lsn_file_c
 }
 // What lsn_file_process_cells and lsn_file_cells_span check alike, and the cells' plans (formed by file_rate_plan, as lsn_phy_process_file_rate forms its one).
 // need_phy: every cell has a Phy (one engine, its cell set, fcfg's antennas, all on one device, none twice); otherwise a null phy takes nof_prb / rates.
+// filt[c].L != 0: the cell's Phy has a channel filter set - stage 1 carries the offset and plans[c] is the plan without it; all cells or none.
 static int file_cells_plans(const lsn_file_cfg_t* fc, double sample_rate_hz, const lsn_file_cell_t* cells, uint32_t n, bool need_phy, std::vector<lsn::ResamplePlan>& plans,
-                            std::vector<uint32_t>& sflen)
+                            std::vector<uint32_t>& sflen, std::vector<lsn::ChanFilter>& filt)
 {
   if (!fc || !cells || n < 1 || n > LSN_FILE_MAX_CELLS) return LSN_ERROR_INVALID_INPUTS;
   if (fc->nof_antennas < 1 || fc->nof_antennas > 8 || fc->offset_time_samples != 0 || fc->offset_freq_hz != 0.0f || !lsn_sample_format(fc->sample_format, fc->sample_scale).valid)
     return LSN_ERROR_INVALID_INPUTS;
   plans.resize(n);
   sflen.resize(n);
+  filt.assign(n, lsn::ChanFilter());
   for (uint32_t c = 0; c < n; c++) {
     const lsn_file_cell_t& k = cells[c];
     if (k.struct_size != sizeof(lsn_file_cell_t)) return LSN_ERROR_INVALID_INPUTS;
@@ -567,10 +570,16 @@ static int file_cells_plans(const lsn_file_cfg_t* fc, double sample_rate_hz, con
       if (!N) return LSN_ERROR_INVALID_INPUTS;
     }
     if (!std::isfinite(k.offset_freq_hz)) return LSN_ERROR_INVALID_INPUTS;
-    const int r = lsn::file_rate_plan(sample_rate_hz, N, nof_prb, k.offset_time_samples, k.offset_time_frac, k.center_offset_hz, plans[c]);
+    const double stop = k.phy ? k.phy->engine->channelFilter() : 0.0;
+    if (stop != 0.0) {
+      const int rf = filt[c].init(sample_rate_hz, 15000.0 * (6.0 * (double)nof_prb + 1.0), stop, k.center_offset_hz);
+      if (rf != LSN_SUCCESS) return rf;
+    }
+    const int r = lsn::file_rate_plan(sample_rate_hz, N, nof_prb, k.offset_time_samples, k.offset_time_frac, stop != 0.0 ? 0.0 : k.center_offset_hz, plans[c]);
     if (r != LSN_SUCCESS) return r;
     sflen[c] = 15u * N;
   }
+  for (uint32_t c = 1; c < n; c++) if (!filt[c].L != !filt[0].L) return LSN_ERROR_INVALID_INPUTS;   // a filtered / unfiltered mix of cells
   return LSN_SUCCESS;
 }
 
@@ -580,14 +589,15 @@ int lsn_file_cells_span(const lsn_file_cfg_t* cfg, double sample_rate_hz, const 
   return lsn::guarded([&]() -> int {
     std::vector<lsn::ResamplePlan> plans;
     std::vector<uint32_t> sflen;
-    const int r = file_cells_plans(cfg, sample_rate_hz, cells, n_cells, false, plans, sflen);
+    std::vector<lsn::ChanFilter> filt;
+    const int r = file_cells_plans(cfg, sample_rate_hz, cells, n_cells, false, plans, sflen, filt);
     if (r != LSN_SUCCESS) return r;
     if (!out || !blk_subframes || in_end >= (1ull << 62)) return LSN_ERROR_INVALID_INPUTS;
     lsn::FileCellPlan cp[LSN_FILE_MAX_CELLS];
     uint32_t widest = 0;
     for (uint32_t c = 0; c < n_cells; c++) {
-      cp[c].rs = &plans[c]; cp[c].sflen = sflen[c]; cp[c].first_sf = 0;
-      cp[c].total = lsn::file_cell_total(plans[c].outputsInside(in_end) / sflen[c], 0, cells[c].max_subframes);
+      cp[c].rs = &plans[c]; cp[c].sflen = sflen[c]; cp[c].first_sf = 0; cp[c].pre = filt[c].L;
+      cp[c].total = lsn::file_cell_total(plans[c].outputsInside(filt[c].insideEnd(in_end)) / sflen[c], 0, cells[c].max_subframes);
       widest = std::max(widest, sflen[c]);
     }
     // the raw block buffer: blk_subframes subframes of cf32 of the widest cell, in samples of the file's format (Engine::reserveFileBuffers)
@@ -611,11 +621,12 @@ int lsn_file_process_cells(const char* path, const lsn_file_cfg_t* cfg, double s
   return lsn::guarded([&]() -> int {
     std::vector<lsn::ResamplePlan> plans;
     std::vector<uint32_t> sflen;
-    const int r = file_cells_plans(cfg, sample_rate_hz, cells, n_cells, true, plans, sflen);
+    std::vector<lsn::ChanFilter> filt;
+    const int r = file_cells_plans(cfg, sample_rate_hz, cells, n_cells, true, plans, sflen, filt);
     if (r != LSN_SUCCESS) return r;
     lsn::Engine::FileCellJob jobs[LSN_FILE_MAX_CELLS];
     for (uint32_t c = 0; c < n_cells; c++) {
-      jobs[c].e = cells[c].phy->engine.get(); jobs[c].rs = &plans[c]; jobs[c].offset_freq_hz = cells[c].offset_freq_hz; jobs[c].start_tti = cells[c].start_tti;
+      jobs[c].e = cells[c].phy->engine.get(); jobs[c].rs = &plans[c]; jobs[c].cf = filt[c].L ? &filt[c] : nullptr; jobs[c].offset_freq_hz = cells[c].offset_freq_hz; jobs[c].start_tti = cells[c].start_tti;
       jobs[c].update_meta_period = cells[c].update_meta_period; jobs[c].max_subframes = cells[c].max_subframes;
       jobs[c].status = LSN_ERROR_INVALID_INPUTS;   // (stays when the replay is refused in front of the first block)
     }
@@ -623,6 +634,65 @@ int lsn_file_process_cells(const char* path, const lsn_file_cfg_t* cfg, double s
     for (uint32_t c = 0; c < n_cells; c++) { cells[c].subframes_done = jobs[c].done; cells[c].status = jobs[c].status; }
     return rc;
   });
+}
+int lsn_phy_set_channel_filter(lsn_phy_t* phy, double stopband_hz)
+{
+  if (!phy) return LSN_ERROR_INVALID_INPUTS;
+  return phy->engine->setChannelFilter(stopband_hz);
+}
+
+// stage 1 alone (k_chan_fir), no Phy
+int lsn_channel_filter(int device, const void* in, int in_on_device, uint64_t n_in, const lsn_channel_filter_cfg_t* cfg, float* out, int out_on_device, uint64_t n_out)
+{
+  lsn::ChanFilter f;
+  const int r = lsn_channel_filter_plan(cfg, f);
+  if (r != LSN_SUCCESS) return r;
+  if (!n_out) return LSN_SUCCESS;
+  if (!in || !out || n_out >= (1ull << 40) || n_in >= (1ull << 62)) return LSN_ERROR_INVALID_INPUTS;
+  int64_t lo = (int64_t)cfg->out_first, hi = (int64_t)(cfg->out_first + n_out);
+  f.widen(lo, hi);
+  const int64_t need_lo = std::max<int64_t>(lo, 0);   // in front of the recording: zeros
+  if (need_lo < (int64_t)cfg->in_base || hi > (int64_t)(cfg->in_base + n_in)) return LSN_ERROR_INVALID_INPUTS;   // the input does not hold what these outputs read
+  const uint32_t nant = cfg->nof_antennas, fmt = cfg->sample_format;
+  const LsnSampleFormat sfm = lsn_sample_format(fmt, cfg->sample_scale);
+  const size_t smp = (size_t)sfm.bytes * nant;
+  const uint64_t len = (uint64_t)(hi - need_lo);
+  const uint8_t* src = (const uint8_t*)in + ((uint64_t)need_lo - cfg->in_base) * smp;
+  void *d_in = nullptr, *d_out = nullptr;
+  float* d_taps = nullptr;
+  const cf32* d_nco = nullptr;
+  hipStream_t st = nullptr;
+  int rc = LSN_SUCCESS;
+  try {
+    HIP_CHECK(hipSetDevice(device));
+    HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    lsn_chan_fir_upload(f, d_taps, d_nco, st);
+    const void* raw = src;
+    if (!in_on_device) {
+      HIP_CHECK(hipMalloc(&d_in, len * smp));
+      HIP_CHECK(hipMemcpyAsync(d_in, src, len * smp, hipMemcpyHostToDevice, st));
+      raw = d_in;
+    }
+    cf32* dst = (cf32*)out;
+    const size_t out_bytes = (size_t)n_out * nant * sizeof(cf32);
+    if (!out_on_device) {
+      HIP_CHECK(hipMalloc(&d_out, out_bytes));
+      dst = (cf32*)d_out;
+    }
+    LsnChanFirCell k;
+    k.taps = d_taps; k.L = f.L; k.w = f.tune; k.nco = d_nco; k.out = dst; k.out_first = (int64_t)cfg->out_first; k.n_out = n_out;
+    lsn_launch_chan_fir(raw, fmt, sfm.scale, need_lo, len, nant, &k, 1, st);
+    if (!out_on_device) HIP_CHECK(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+  } catch (const std::exception& ex) {
+    fprintf(stderr, "ltesniffer_amd: channel_filter: %s\n", ex.what());
+    rc = LSN_ERROR;
+  }
+  if (st) (void)hipStreamDestroy(st);
+  if (d_in) (void)hipFree(d_in);
+  if (d_taps) (void)hipFree(d_taps);
+  if (d_out) (void)hipFree(d_out);
+  return rc;
 }
 int lsn_phy_prepare_file(lsn_phy_t* phy, uint32_t nof_antennas)
 {

@@ -38,6 +38,7 @@ bool file_cells_block(const FileCellPlan* cells, uint32_t n, uint32_t blk, uint6
     if (!p.rs) continue;
     int64_t lo, hi;
     p.rs->inputSpan(out.sf0[c] * p.sflen, (uint64_t)got * p.sflen, lo, hi);
+    lo -= (int64_t)p.pre; hi += (int64_t)p.pre;   // what stage 1 reads for the y1 stage 2 reads
     out.in_lo = have ? std::min(out.in_lo, lo) : lo;
     out.in_hi = have ? std::max(out.in_hi, hi) : hi;
     have = true;
@@ -55,6 +56,7 @@ uint32_t file_cells_fit(const FileCellPlan* cells, uint32_t n, uint32_t blk, uin
     for (uint32_t c = 0; c < n; c++) {
       int64_t l, h;
       cells[c].rs->inputSpan(cells[c].first_sf * cells[c].sflen, (uint64_t)b * cells[c].sflen, l, h);
+      l -= (int64_t)cells[c].pre; h += (int64_t)cells[c].pre;
       lo = c ? std::min(lo, l) : l;
       hi = c ? std::max(hi, h) : h;
     }

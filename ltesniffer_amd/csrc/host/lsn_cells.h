@@ -18,6 +18,7 @@ struct FileCellPlan {
   uint32_t sflen = 0;                 // output samples of one subframe
   uint64_t first_sf = 0;              // output subframe the replay starts with (LSN_TTI_FROM_MIB: the first whose MIB decoded)
   uint64_t total = 0;                 // subframes the cell replays: file_cell_total
+  uint32_t pre = 0;                   // half length L of the channel filter in front of rs (lsn_chanfilt.h): the cell's span is L samples wider on both sides; 0: none
 };
 // sf_in_file output subframes lie inside the recording, the replay starts at first_sf and stops after max_subframes (0: at the end)
 uint64_t file_cell_total(uint64_t sf_in_file, uint64_t first_sf, uint64_t max_subframes);

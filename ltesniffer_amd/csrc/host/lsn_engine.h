@@ -249,6 +249,15 @@ public:
     return LSN_SUCCESS;
   }
   int sampling() const { return rates; }
+  // stop band of the channel filter this engine's file replays run in front of the resampler (lsn_chanfilt.h); 0: none.  Checked against rate and
+  // bandwidth when a replay starts
+  int setChannelFilter(double stopband_hz)
+  {
+    if (!(stopband_hz >= 0.0 && stopband_hz < 1e12)) return LSN_ERROR_INVALID_INPUTS;
+    chan_stopband_hz = stopband_hz;
+    return LSN_SUCCESS;
+  }
+  double channelFilter() const { return chan_stopband_hz; }
   int process(const void* d_iq, uint32_t nsf, uint32_t start_tti, uint32_t update_meta_period, hipStream_t stream);
   int submit(const void* d_iq, uint32_t nsf, uint32_t start_tti, uint32_t update_meta_period, hipStream_t stream, bool force_meta_first = false);
   // `nrows` = nsf x antennas rows of one subframe each (sflen samples), `row_pitch` bytes apart in PINNED host memory (the worker pool's slab:
@@ -268,7 +277,7 @@ public:
                       uint64_t* subframes_done);   // lsn_phy_process_file_rate: the same through the polyphase resampler (lsn_resample.h)
   // one cell of a file replay: its engine, its resampler plan (null: the file is at the engine's rate - single-cell call only), where and how it starts; out: done, status
   struct FileCellJob {
-    Engine* e = nullptr; const struct ResamplePlan* rs = nullptr; float offset_freq_hz = 0.0f; uint32_t start_tti = 0, update_meta_period = 0; uint64_t max_subframes = 0;
+    Engine* e = nullptr; const struct ResamplePlan* rs = nullptr; const struct ChanFilter* cf = nullptr /* stage 1 in front of rs, or null */; float offset_freq_hz = 0.0f; uint32_t start_tti = 0, update_meta_period = 0; uint64_t max_subframes = 0;
     uint64_t done = 0; int status = 0;
   };
   // lsn_file_process_cells: n cells (engines on one device, each with its cell set and fc.nof_antennas antennas) from one pass over the file; n = 1 is processFile[Rate]
@@ -276,6 +285,8 @@ public:
   uint32_t symbolSz() const { return cd.N; }
   uint32_t nofPrb() const { return cd.nof_prb; }
   uint32_t iqAntennas() const { return cd.iq_nant; }
+  // the channel filter's intermediate (y1 of one block, cf32 [sample][antenna]): grows, never shrinks; kept like the block buffers
+  int reserveChanBuffer(size_t bytes);
   int reserveFileBuffers(uint32_t nof_antennas);   // lsn_phy_prepare_file: pinned read blocks + device blocks of the file source, ahead of the first replay
   int processHost(const void* iq, uint32_t nsf, uint32_t start_tti, uint32_t update_meta_period, uint32_t sample_format = 0 /* LSN_FILE_* */, float sample_scale = 0.0f);
   void setSink(lsn_pdu_sink_t cb, void* user) { sink = cb; sink_user = user; }
@@ -561,11 +572,13 @@ private:
   void syncUlConfig();                                    // commit turn: pick up a configuration another engine (or the caller) has set since
   // device / pinned blocks of the file source, kept between lsn_phy_process_file calls (allocating them costs more than replaying a short capture)
   // processFile (rs == nullptr) and processFileRate (rs: the resampler's plan, lsn_resample.h) as a one-cell replayFile
-  int processFileImpl(const char* path, const lsn_file_cfg_t& fc, const struct ResamplePlan* rs, uint32_t start_tti, uint64_t max_subframes, uint32_t update_meta_period,
+  int processFileImpl(const char* path, const lsn_file_cfg_t& fc, const struct ResamplePlan* rs, const struct ChanFilter* cf, uint32_t start_tti, uint64_t max_subframes, uint32_t update_meta_period,
                       uint64_t* subframes_done);
   struct FileReplay;   // lsn_file.cc: what one replay opens and how it hands blocks to submit()
   struct FileBuf { cf32* h_raw = nullptr; cf32* d_raw = nullptr; cf32* d_iq = nullptr; size_t bytes = 0; };
   FileBuf file_buf[8];
+  double chan_stopband_hz = 0.0;   // lsn_phy_set_channel_filter
+  cf32* d_chan = nullptr; size_t chan_bytes = 0;   // reserveChanBuffer
   std::atomic<uint32_t>& ul_cfg_epoch = sh->ul_cfg_epoch;  // bumped by every (re)configuration: chunks whose DCI 0 grants were converted earlier are converted again at commit
   bool& sib2_learned = sh->sib2_learned; Sib2Config& sib2 = sh->sib2;  // the SIB2 the UL-mode commit stage configured itself from (decode_SIB), if any
   bool decodeSib(Chunk& ch, JobRunner& r, uint32_t sf, Sib2Config& out, size_t& payload_off, uint32_t& len, uint8_t& tb);

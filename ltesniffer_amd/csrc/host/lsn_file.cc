@@ -11,6 +11,7 @@
 // Product code: no CPU fallback, nothing from oracle/ is included or linked.
 #include "lsn_engine.h"
 #include "lsn_resample_launch.h"
+#include "lsn_chanfilt_launch.h"
 #include "lsn_cells.h"
 #include <deque>
 #include <cmath>
@@ -39,6 +40,8 @@ static void file_geometry(uint32_t& blk, uint32_t& nrd, int& nslot)
 // 1.5 GB takes longer than replaying 10 000 subframes: rounds 2-4 paid it inside the first lsn_phy_process_file call (43.6 k subframes/s on the first
 // pass of a 20 000-subframe capture against 96 k on the second, round-4 review).  A caller that knows it will replay a file - the reference does
 // when it parses -i (LTESniffer_Core.cc:240-262) - reserves them up front with lsn_phy_prepare_file; processFile calls this as well (no-op then).
+static size_t chan_buffer_bytes(uint64_t raw_samples, uint32_t nant, uint32_t L);
+
 int Engine::reserveFileBuffers(uint32_t nof_antennas)
 {
   if (!cell_set) return LSN_ERROR;
@@ -47,6 +50,12 @@ int Engine::reserveFileBuffers(uint32_t nof_antennas)
   file_geometry(blk, nrd, nslot);
   const size_t sf_bytes = (size_t)cd.sflen * nof_antennas * sizeof(cf32);
   const bool use_mmap = getenv("LSN_FILE_MMAP") && atoi(getenv("LSN_FILE_MMAP")) != 0;
+  // the channel filter is set already: its intermediate for a cf32 recording and the longest filter (a replay of an integer format, whose raw block holds more
+  // samples, grows it in front of its first block)
+  if (chan_stopband_hz != 0.0) {
+    const int r = reserveChanBuffer(chan_buffer_bytes((uint64_t)blk * cd.sflen, nof_antennas, kChanMaxL));
+    if (r != LSN_SUCCESS) return r;
+  }
   return guarded([&]() -> int {
     HIP_CHECK(hipSetDevice(cfg.device));
     for (int si = 0; si < nslot; si++) {
@@ -66,10 +75,31 @@ int Engine::reserveFileBuffers(uint32_t nof_antennas)
   });
 }
 
+int Engine::reserveChanBuffer(size_t bytes)
+{
+  if (chan_bytes >= bytes) return LSN_SUCCESS;
+  return guarded([&]() -> int {
+    HIP_CHECK(hipSetDevice(cfg.device));
+    if (d_chan) { (void)hipFree(d_chan); d_chan = nullptr; }
+    chan_bytes = 0;
+    HIP_CHECK(hipMalloc((void**)&d_chan, bytes));
+    chan_bytes = bytes;
+    return LSN_SUCCESS;
+  });
+}
+
+// the intermediate of a block whose raw buffer holds raw_samples samples per antenna: as many cf32, plus 2L
+static size_t chan_buffer_bytes(uint64_t raw_samples, uint32_t nant, uint32_t L) { return (size_t)(raw_samples + 2 * (uint64_t)L) * nant * sizeof(cf32); }
+
 int Engine::processFile(const char* path, const lsn_file_cfg_t& fc, uint32_t start_tti, uint64_t max_subframes, uint32_t update_meta_period,
                         uint64_t* subframes_done)
 {
-  return processFileImpl(path, fc, nullptr, start_tti, max_subframes, update_meta_period, subframes_done);
+  if (chan_stopband_hz != 0.0) {   // the channel filter is set: the file is at the engine's rate and goes through both stages
+    lsn_file_rate_t fr;
+    fr.struct_size = sizeof(fr); fr.reserved = 0; fr.sample_rate_hz = 15000.0 * (double)cd.N; fr.offset_time_frac = 0.0; fr.center_offset_hz = 0.0;
+    return processFileRate(path, fc, fr, start_tti, max_subframes, update_meta_period, subframes_done);
+  }
+  return processFileImpl(path, fc, nullptr, nullptr, start_tti, max_subframes, update_meta_period, subframes_done);
 }
 
 // lsn_phy_process_file_rate: a recording made at fr.sample_rate_hz.  The plan (step, start, taps, bank: lsn_resample.cc; formed by file_rate_plan, the one
@@ -84,11 +114,19 @@ int Engine::processFileRate(const char* path, const lsn_file_cfg_t& fc, const ls
   if (fr.struct_size != offsetof(lsn_file_rate_t, center_offset_hz) && fr.struct_size != sizeof(lsn_file_rate_t)) return LSN_ERROR_INVALID_INPUTS;
   const double center = fr.struct_size == sizeof(lsn_file_rate_t) ? fr.center_offset_hz : 0.0;
   if (fc.offset_time_samples < 0 || !(fr.offset_time_frac >= 0.0 && fr.offset_time_frac < 4.0e18)) return LSN_ERROR_INVALID_INPUTS;
-  if (fr.sample_rate_hz == 15000.0 * (double)cd.N && fr.offset_time_frac == 0.0 && center == 0.0) return processFileImpl(path, fc, nullptr, start_tti, max_subframes, update_meta_period, subframes_done);
+  if (fr.sample_rate_hz == 15000.0 * (double)cd.N && fr.offset_time_frac == 0.0 && center == 0.0 && chan_stopband_hz == 0.0)
+    return processFileImpl(path, fc, nullptr, nullptr, start_tti, max_subframes, update_meta_period, subframes_done);
+  // with the channel filter set the mixer runs in stage 1 and the resampler, stage 2, is the plan of the same pair and start with no offset
+  ChanFilter filt;
+  const bool filtered = chan_stopband_hz != 0.0;
+  if (filtered) {
+    const int rf = filt.init(fr.sample_rate_hz, 15000.0 * (6.0 * (double)cd.nof_prb + 1.0), chan_stopband_hz, center);
+    if (rf != LSN_SUCCESS) return rf;
+  }
   ResamplePlan plan;
-  const int r = file_rate_plan(fr.sample_rate_hz, cd.N, cd.nof_prb, fc.offset_time_samples, fr.offset_time_frac, center, plan);
+  const int r = file_rate_plan(fr.sample_rate_hz, cd.N, cd.nof_prb, fc.offset_time_samples, fr.offset_time_frac, filtered ? 0.0 : center, plan);
   if (r != LSN_SUCCESS) return r;
-  return processFileImpl(path, fc, &plan, start_tti, max_subframes, update_meta_period, subframes_done);
+  return processFileImpl(path, fc, &plan, filtered ? &filt : nullptr, start_tti, max_subframes, update_meta_period, subframes_done);
 }
 
 // One replay of one file into the engines of `cells`: one cell (lsn_phy_process_file[_rate]) or several (lsn_file_process_cells).  A cell's rs is
@@ -102,6 +140,10 @@ struct Engine::FileReplay {
   struct Cell {
     Engine* e = nullptr;
     const ResamplePlan* rs = nullptr;
+    const ChanFilter* cf = nullptr;   // stage 1 in front of rs: raw block -> mid (y1 over the span rs reads) -> rs; null: rs reads the raw block
+    cf32* mid = nullptr;              // the cell's engine's intermediate (Engine::reserveChanBuffer)
+    float* d_taps = nullptr;          // the filter's taps ...
+    const cf32* d_mix = nullptr;      // ... and, behind them, its mixer's tables when it has a tuning word
     uint32_t sflen = 0;
     float offset_freq_hz = 0.0f;
     uint32_t start_tti = 0, update_meta_period = 0;
@@ -146,7 +188,7 @@ struct Engine::FileReplay {
     uint32_t widest = 0;
     for (uint32_t c = 0; c < n; c++) {
       Cell k;
-      k.e = jobs[c].e; k.rs = jobs[c].rs; k.sflen = k.e->cd.sflen; k.offset_freq_hz = jobs[c].offset_freq_hz; k.start_tti = jobs[c].start_tti;
+      k.e = jobs[c].e; k.rs = jobs[c].rs; k.cf = jobs[c].cf; k.sflen = k.e->cd.sflen; k.offset_freq_hz = jobs[c].offset_freq_hz; k.start_tti = jobs[c].start_tti;
       k.update_meta_period = jobs[c].update_meta_period; k.max_subframes = jobs[c].max_subframes;
       cells.push_back(k);
       if (k.sflen > widest) { widest = k.sflen; big = k.e; }
@@ -164,6 +206,7 @@ struct Engine::FileReplay {
     for (auto& c : cells) {
       if (c.d_rot) (void)hipFree(c.d_rot);
       if (c.d_bank) (void)hipFree(c.d_bank);
+      if (c.d_taps) (void)hipFree(c.d_taps);
     }
     if (st) (void)hipStreamDestroy(st);
     if (map) munmap(map, file_size);
@@ -171,6 +214,7 @@ struct Engine::FileReplay {
   }
 
   bool resampled() const { return cells[0].rs != nullptr; }   // (several cells: every one has a plan)
+  bool filtered() const { return cells[0].cf != nullptr; }    // (several cells: all or none, lsn_file_process_cells)
 
   // the cells as lsn_cells.h wants them, from where each one starts
   void plan()
@@ -178,7 +222,7 @@ struct Engine::FileReplay {
     plans.clear();
     for (auto& c : cells) {
       FileCellPlan p;
-      p.rs = c.rs; p.sflen = c.sflen; p.first_sf = c.first_sf; p.total = file_cell_total(c.sf_in_file, c.first_sf, c.max_subframes);
+      p.rs = c.rs; p.pre = c.cf ? c.cf->L : 0; p.sflen = c.sflen; p.first_sf = c.first_sf; p.total = file_cell_total(c.sf_in_file, c.first_sf, c.max_subframes);
       plans.push_back(p);
     }
   }
@@ -206,7 +250,8 @@ struct Engine::FileReplay {
     if (fstat(fd, &sb)) return LSN_ERROR_INVALID_INPUTS;
     file_size = (size_t)sb.st_size;
     for (auto& c : cells) {
-      if (c.rs) c.sf_in_file = c.rs->outputsInside((uint64_t)file_size / spb) / c.sflen;  // output subframes whose whole input span lies inside the file
+      const uint64_t in_end = (uint64_t)file_size / spb;
+      if (c.rs) c.sf_in_file = c.rs->outputsInside(c.cf ? c.cf->insideEnd(in_end) : in_end) / c.sflen;  // output subframes whose whole input span lies inside the file
       else c.sf_in_file = (uint64_t)file_size > file_off0 ? ((uint64_t)file_size - file_off0) / sf_bytes : 0;  // complete subframes only
     }
     if (resampled() && !fitBlock()) return LSN_ERROR_INVALID_INPUTS;
@@ -220,10 +265,40 @@ struct Engine::FileReplay {
     return LSN_SUCCESS;
   }
 
+  // the y1 samples [lo2, hi2) stage 2 reads for n subframes from output subframe pos (in front of sample 0: zeros, the resampler's own)
+  void midSpan(const Cell& c, uint64_t pos, uint32_t n, int64_t& lo2, int64_t& hi2) const
+  {
+    c.rs->inputSpan(pos * c.sflen, (uint64_t)n * c.sflen, lo2, hi2);
+    lo2 = std::max<int64_t>(lo2, 0);
+    hi2 = std::max(hi2, lo2);
+  }
+
+  // stage 1 of the cells [c0, c1) in ONE k_chan_fir launch: raw samples [lo, lo + len) of the recording -> every cell's intermediate, for nsf[c] subframes from sf0[c]
+  void queueFilter(size_t c0, size_t c1, const void* raw, int64_t lo, uint64_t len, const uint64_t* sf0, const uint32_t* nsf)
+  {
+    LsnChanFirCell k[kFileMaxCells];
+    for (size_t c = c0; c < c1; c++) {
+      const Cell& q = cells[c];
+      LsnChanFirCell& f = k[c - c0];
+      int64_t lo2 = 0, hi2 = 0;
+      if (nsf[c]) midSpan(q, sf0[c], nsf[c], lo2, hi2);
+      if ((size_t)(hi2 - lo2) * nant * sizeof(cf32) > q.e->chan_bytes) throw std::runtime_error("file source: a block's filtered samples do not fit the intermediate buffer");
+      f.taps = q.d_taps; f.L = q.cf->L; f.w = q.cf->tune; f.nco = q.d_mix; f.out = q.mid; f.out_first = lo2; f.n_out = (uint64_t)(hi2 - lo2);
+    }
+    lsn_launch_chan_fir(raw, fmt, sfm.scale, lo, len, nant, k, (uint32_t)(c1 - c0), st);
+  }
+
   // k_resample for one cell: n subframes from output subframe pos, out of the raw samples [lo, lo + len) of the recording, queued on st
   void queueResampleOne(const Cell& c, const void* raw, int64_t lo, uint64_t len, uint64_t pos, uint32_t n, cf32* out)
   {
     const u128 base = c.rs->position(pos * c.sflen);
+    if (c.cf) {   // stage 2 of a filtered cell: the plain cf32 k_resample from the cell's intermediate, which queueFilter has filled for these subframes
+      int64_t lo2, hi2;
+      midSpan(c, pos, n, lo2, hi2);
+      lsn_launch_resample(c.mid, 0, 1.0f, lo2, (uint64_t)(hi2 - lo2), (uint64_t)(base >> 64), (uint64_t)base, (uint32_t)(c.rs->step >> 64), (uint64_t)c.rs->step, c.rs->taps,
+                          c.rs->span, c.d_bank, 0, nullptr, c.d_rot, c.sflen, 0, nant, out, (uint64_t)n * c.sflen, st);
+      return;
+    }
     lsn_launch_resample(raw, fmt, sfm.scale, lo, len, (uint64_t)(base >> 64), (uint64_t)base, (uint32_t)(c.rs->step >> 64), (uint64_t)c.rs->step, c.rs->taps, c.rs->span, c.d_bank,
                         c.rs->tune, c.d_nco, c.d_rot, c.sflen, 0, nant, out, (uint64_t)n * c.sflen, st);
   }
@@ -233,6 +308,14 @@ struct Engine::FileReplay {
   {
     if (!resampled()) { lsn_launch_file_unpack(s.d_raw, fmt, sfm.scale, cells[0].d_rot, cells[0].sflen, nant, s.d_iq[0], b.nsf[0], st); return; }
     const uint64_t len = (uint64_t)(b.in_hi - b.in_lo);
+    if (filtered()) {
+      // one k_chan_fir launch covers all cells; each cell then has an input of its own, and k_resample_cells takes ONE raw buffer per launch: stage 2 is one
+      // k_resample per cell (the same expressions - both kernels expand LSN_RESAMPLE_RUN)
+      queueFilter(0, cells.size(), s.d_raw, b.in_lo, len, b.sf0, b.nsf);
+      for (size_t c = 0; c < cells.size(); c++)
+        if (b.nsf[c]) queueResampleOne(cells[c], nullptr, 0, 0, b.sf0[c], b.nsf[c], s.d_iq[c]);
+      return;
+    }
     if (cells.size() == 1) { queueResampleOne(cells[0], s.d_raw, b.in_lo, len, b.sf0[0], b.nsf[0], s.d_iq[0]); return; }
     LsnResampleCell k[kFileMaxCells];
     for (size_t c = 0; c < cells.size(); c++) {
@@ -272,6 +355,11 @@ struct Engine::FileReplay {
         HIP_CHECK(hipMemcpy(c.d_rot, rot.data(), c.sflen * sizeof(cf32), hipMemcpyHostToDevice));
       }
       if (c.rs) c.rs->upload(c.d_bank, c.d_nco, st);
+      if (c.cf) {   // the intermediate: reserved by lsn_phy_prepare_file when the filter was set by then, otherwise here - in front of the first block, never inside the loop
+        lsn_chan_fir_upload(*c.cf, c.d_taps, c.d_mix, st);
+        if (c.e->reserveChanBuffer(chan_buffer_bytes(raw_bytes / spb, nant, c.cf->L)) != LSN_SUCCESS) throw std::runtime_error("file source: channel filter buffer");
+        c.mid = c.e->d_chan;
+      }
     }
     if (resampled()) HIP_CHECK(hipStreamSynchronize(st));
   }
@@ -282,7 +370,7 @@ struct Engine::FileReplay {
     Cell& c = cells[ci];
     for (uint64_t i = 0; i < c.sf_in_file && i < 10 * 64; i += 10) {  // the file starts at subframe 0 of a radio frame (file mode has no sync)
       int64_t lo = 0, hi = 0;
-      if (c.rs) { c.rs->inputSpan(i * c.sflen, c.sflen, lo, hi); lo = std::max<int64_t>(lo, 0); }
+      if (c.rs) { c.rs->inputSpan(i * c.sflen, c.sflen, lo, hi); if (c.cf) c.cf->widen(lo, hi); lo = std::max<int64_t>(lo, 0); }
       const uint64_t len = c.rs ? (uint64_t)(hi - lo) : c.sflen;
       const size_t bytes = c.rs ? (size_t)len * spb : sf_bytes;
       if (bytes > raw_bytes) throw std::runtime_error("file source: one subframe's input does not fit the block buffer");
@@ -290,6 +378,7 @@ struct Engine::FileReplay {
       if (pread(fd, one.data(), bytes, (off_t)(c.rs ? (uint64_t)lo * spb : file_off0 + i * sf_bytes)) != (ssize_t)bytes) break;
       HIP_CHECK(hipMemcpyAsync(slot[0].d_raw, one.data(), bytes, hipMemcpyHostToDevice, st));
       HIP_CHECK(hipStreamSynchronize(st));
+      if (c.cf) { uint64_t sf0[kFileMaxCells] = {}; uint32_t one_sf[kFileMaxCells] = {}; sf0[ci] = i; one_sf[ci] = 1; queueFilter(ci, ci + 1, slot[0].d_raw, lo, len, sf0, one_sf); }
       if (c.rs) queueResampleOne(c, slot[0].d_raw, lo, len, i, 1, slot[0].d_iq[ci]);
       else lsn_launch_file_unpack(slot[0].d_raw, fmt, sfm.scale, c.d_rot, c.sflen, nant, slot[0].d_iq[ci], 1, st);
       HIP_CHECK(hipStreamSynchronize(st));
@@ -469,14 +558,14 @@ int Engine::replayFile(const char* path, const lsn_file_cfg_t& fc, FileCellJob* 
   return rc;
 }
 
-int Engine::processFileImpl(const char* path, const lsn_file_cfg_t& fc, const ResamplePlan* rs, uint32_t start_tti, uint64_t max_subframes, uint32_t update_meta_period,
+int Engine::processFileImpl(const char* path, const lsn_file_cfg_t& fc, const ResamplePlan* rs, const ChanFilter* cf, uint32_t start_tti, uint64_t max_subframes, uint32_t update_meta_period,
                             uint64_t* subframes_done)
 {
   if (subframes_done) *subframes_done = 0;
   if (!cell_set) return LSN_ERROR;
   if (!path || fc.nof_antennas != cd.iq_nant || fc.offset_time_samples < 0 || !lsn_sample_format(fc.sample_format, fc.sample_scale).valid) return LSN_ERROR_INVALID_INPUTS;
   FileCellJob job;
-  job.e = this; job.rs = rs; job.offset_freq_hz = fc.offset_freq_hz; job.start_tti = start_tti; job.update_meta_period = update_meta_period; job.max_subframes = max_subframes;
+  job.e = this; job.rs = rs; job.cf = cf; job.offset_freq_hz = fc.offset_freq_hz; job.start_tti = start_tti; job.update_meta_period = update_meta_period; job.max_subframes = max_subframes;
   const int rc = replayFile(path, fc, &job, 1);
   if (subframes_done) *subframes_done = job.done;
   return rc;

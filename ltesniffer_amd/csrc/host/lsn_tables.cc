@@ -87,6 +87,7 @@ void Engine::freeDevice(bool keep_file_buffers)
     // 10 000 subframes, and a caller that reserved them (lsn_phy_prepare_file) and then sets its cell must not pay for them a second time inside its first replay
     if (!keep_file_buffers)
       for (auto& fb : file_buf) { if (fb.h_raw) (void)hipHostFree(fb.h_raw); df(fb.d_raw); df(fb.d_iq); fb.h_raw = nullptr; fb.bytes = 0; }
+    if (!keep_file_buffers) { df(d_chan); chan_bytes = 0; }
   }
   d_iq_staging = nullptr;
   if (d_iq_raw) { (void)hipFree(d_iq_raw); d_iq_raw = nullptr; d_iq_raw_bytes = 0; }
