@@ -428,6 +428,83 @@ int lsn_file_cells_span(const lsn_file_cfg_t* cfg, double sample_rate_hz, const 
 int lsn_resample_cells(int device, const void* in, int in_on_device, uint64_t n_in, const lsn_resample_cfg_t* cfgs, uint32_t n_cells, float* const* outs,
                        int out_on_device, const uint64_t* n_out);
 
+/* k_resample_ring without a Phy, the sibling of lsn_resample_cells for the kernel a stream runs (below): the host input window in[0 .. n_in) = samples in_base ..
+ * in_base + n_in of the recording (in_base of the cfgs) is placed into a device ring of ring_samples samples per antenna, sample n at slot n mod ring_samples -
+ * two copies when the window crosses the end of the ring - and the cells are resampled out of the ring in one launch; outs[c] ([antenna][n_out[c]] cf32, host)
+ * equals lsn_resample_cells' with the same arguments, bit for bit.  Refused like lsn_resample_cells, and: ring_samples not a power of two or above 2^32,
+ * n_in > ring_samples.  A refusal leaves the outputs untouched. */
+int lsn_resample_cells_ring(int device, const void* in, uint64_t n_in, uint64_t ring_samples, const lsn_resample_cfg_t* cfgs, uint32_t n_cells, float* const* outs,
+                            const uint64_t* n_out);
+
+/* ---- a live wideband stream pushed in host buffers ----
+ * The file replays above take a path.  A stream takes the same samples as they arrive, in host buffers of any length, and feeds the same cells: per cell exactly
+ * the subframes a file of the samples pushed so far replays, and - an output sample being a function of (input, configuration, m) only - bit for bit the samples
+ * of lsn_file_process_cells on those bytes, however the stream was cut into pushes.
+ *   cells     lsn_file_cell_t as lsn_file_process_cells takes them: Phy, center_offset_hz, start of the cell's subframe 0 in samples of the stream counted from the
+ *             first sample ever pushed, start_tti, update_meta_period, max_subframes, offset_freq_hz; subframes_done and status are not written (status call).
+ *             Each cell's plan is the one lsn_phy_process_file_rate forms.  A stream starts at the cell's subframe 0.
+ *   storage   ONE device buffer of ring_samples samples per antenna, a power of two; sample n of the stream sits at slot n mod ring_samples.  A push copies its
+ *             samples host-to-device straight to their slots (two copies when it crosses the end of the ring, a long push in pieces): no host staging buffer, no
+ *             memcpy on the caller's thread.  A gap - the radio reported dropped samples - is a memset of the same slots: zeros arrive, positions stay.
+ *   when      after `pushed` samples cell c has floor(outputs whose whole input span lies in front of pushed / subframe length) complete subframes, capped by
+ *             max_subframes - the rule a file's subframes are counted by.  A cell is submitted when block_subframes of them are not submitted yet (fewer: the last
+ *             ones in front of max_subframes, or a flush): one k_resample_ring launch for all cells that are due, into block buffers of their Phys (those of
+ *             lsn_phy_prepare_file), then one submit per Phy in the order of the list.
+ *   ring      nothing at or behind the oldest sample a cell still needs - the first input sample of its next subframe, minimised over the cells that have not run
+ *             out - is overwritten; a piece that is written over slots an unfinished launch may still read waits for that launch, and for nothing else.
+ *             ring_samples = 0: the smallest power of two that holds four blocks of the union input (block_subframes of every cell from the oldest start to the
+ *             newest end, the filters' spans included).
+ * lsn_stream_push returns when its samples are in the ring - the caller's buffer is free again - and decoding goes on behind it; it blocks only while the Phys
+ * are more than their block buffers behind.  lsn_stream_flush submits every complete subframe and waits for every Phy; the stream goes on afterwards.
+ * lsn_stream_close flushes and frees; the Phys stay usable.  Close a stream before its Phys are destroyed (lsn_phy_destroy on a Phy of an open stream closes the stream first, with a line on
+ * stderr, and the stream's handle is dead from then on).  One call at a time per stream.
+ * When a Phy fails nothing more is submitted to any of them; the next push or flush returns its code and lsn_stream_status shows which cell it was.  Push, gap
+ * and flush on a failed stream return that code and do nothing; on a NULL (closed) stream LSN_ERROR_INVALID_INPUTS.
+ * Refused at open with LSN_ERROR_INVALID_INPUTS - nothing is allocated, every Phy stays usable: everything lsn_file_process_cells refuses; start_tti =
+ * LSN_TTI_FROM_MIB (the head of a live stream goes through lsn_carrier_scan and lsn_phy_mib_decode first, and that chain yields the TTI); a Phy with a channel
+ * filter set (k_chan_fir does not read the ring yet: refused, not dropped); a Phy that belongs to an open stream; cfg->device other than the Phys'; block_subframes
+ * above LSN_FILE_BLOCK; ring_samples not a power of two, above 2^32, or shorter than one block of every cell - which is also how cells whose starts lie further
+ * apart than the ring less one block are refused.
+ * Not on a stream: the channel filter, LSN_TTI_FROM_MIB, the worker pool, cells on several GPUs; rate and offsets are inputs, as for files - no loop tracks them. */
+typedef struct lsn_stream lsn_stream_t;
+typedef struct {
+  uint32_t struct_size;      /* sizeof(lsn_stream_cfg_t); every other size is refused */
+  int      device;           /* the Phys' */
+  double   sample_rate_hz;
+  uint32_t nof_antennas;     /* interleaved sample by sample in what is pushed */
+  uint32_t sample_format;    /* LSN_FILE_* */
+  float    sample_scale;     /* as lsn_file_cfg_t */
+  uint32_t block_subframes;  /* a cell is submitted once it has that many complete subframes; 0 = the file source's block size (LSN_FILE_BLOCK) */
+  uint64_t ring_samples;     /* 0 = chosen by the library */
+} lsn_stream_cfg_t;
+typedef struct {
+  uint64_t samples_pushed;
+  uint64_t ring_samples;
+  int64_t  oldest_needed;    /* the oldest sample of the stream a cell still needs; samples_pushed when none does */
+  uint32_t block_subframes, nof_cells;
+  int      failed;           /* LSN_SUCCESS, or the code every later push and flush returns */
+  int      status[LSN_FILE_MAX_CELLS];                 /* per cell: its Phy's return code */
+  uint64_t subframes_submitted[LSN_FILE_MAX_CELLS];
+} lsn_stream_status_t;
+/* The plan after pushed_samples samples in all, without a device (cells with phy NULL take nof_prb / rates, as lsn_file_cells_span).  subframes_complete: per
+ * cell, what a flush at that point has submitted in all; subframes_submitted: what a stream that was never flushed has submitted - whole blocks, and the last
+ * ones in front of max_subframes; oldest_needed belongs to the latter, oldest_needed_flushed to the former.  ring_samples: cfg's, or the default; block_input: the
+ * input samples of one block of every cell from the oldest start to the newest end, which the ring must hold.  Same refusals as the open, Phys and device aside. */
+typedef struct {
+  uint64_t ring_samples, block_input;
+  int64_t  oldest_needed, oldest_needed_flushed;
+  uint32_t block_subframes, reserved;
+  uint64_t subframes_complete[LSN_FILE_MAX_CELLS];
+  uint64_t subframes_submitted[LSN_FILE_MAX_CELLS];
+  uint32_t taps[LSN_FILE_MAX_CELLS];
+} lsn_stream_span_t;
+int lsn_stream_open(const lsn_stream_cfg_t* cfg, lsn_file_cell_t* cells, uint32_t n_cells, lsn_stream_t** out);
+int lsn_stream_push(lsn_stream_t* s, const void* iq /* [sample][antenna] in sample_format; NULL = a gap of n_samples zeros */, uint64_t n_samples);
+int lsn_stream_flush(lsn_stream_t* s);
+int lsn_stream_status(lsn_stream_t* s, lsn_stream_status_t* out);
+int lsn_stream_close(lsn_stream_t* s);
+int lsn_stream_span(const lsn_stream_cfg_t* cfg, const lsn_file_cell_t* cells, uint32_t n_cells, uint64_t pushed_samples, lsn_stream_span_t* out);
+
 /* ---- sharp channel filter in front of the resampler: a cell next to a much stronger carrier ----
  * The resampler's filter has the transition band [B, min(rate) - B]: a neighbour carrier inside it reaches the FFT's guard bins undamped and leaks into the
  * occupied bins at about -40 dB.  The channel filter is an opt-in stage 1 at the RECORDING's rate, the resampler becomes stage 2:

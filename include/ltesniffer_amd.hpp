@@ -264,4 +264,30 @@ inline int cellSearchRates(const cf_t* iq, uint64_t nof_samples, uint32_t nof_pr
   return lsn_cell_search_rates(device, iq, 0, nof_samples, nof_prb, rates, &c, &out, nullptr);
 }
 
+// A live wideband stream pushed in host buffers (lsn_stream_*): the place of the reference's receive loop (srsran_ue_sync_zerocopy per subframe,
+// LTESniffer_Core.cc:365) for a radio that delivers more than one cell's worth of bandwidth.  cells: lsn_file_cell_t, each with phy = Phy::handle().
+// Throws std::invalid_argument when the library refuses the stream; push / gap / flush return the library's code.  Destroy it before its Phys.
+class Stream {
+public:
+  Stream(const lsn_stream_cfg_t& cfg, std::vector<lsn_file_cell_t> cells)
+  {
+    lsn_stream_cfg_t c = cfg;
+    c.struct_size = sizeof(c);
+    for (auto& k : cells) k.struct_size = sizeof(k);
+    const int r = lsn_stream_open(&c, cells.data(), (uint32_t)cells.size(), &h);
+    if (r == LSN_ERROR_INVALID_INPUTS) throw std::invalid_argument("ltesniffer_amd: stream refused");
+    if (r != LSN_SUCCESS) throw std::runtime_error("lsn_stream_open failed");
+  }
+  Stream(const Stream&) = delete;
+  Stream& operator=(const Stream&) = delete;
+  ~Stream() { close(); }
+  int push(const void* iq, uint64_t n_samples) { return lsn_stream_push(h, iq, n_samples); }
+  int gap(uint64_t n_samples) { return lsn_stream_push(h, nullptr, n_samples); }
+  int flush() { return lsn_stream_flush(h); }
+  lsn_stream_status_t status() { lsn_stream_status_t s{}; lsn_stream_status(h, &s); return s; }
+  int close() { const int r = h ? lsn_stream_close(h) : LSN_SUCCESS; h = nullptr; return r; }
+private:
+  lsn_stream_t* h = nullptr;
+};
+
 }  // namespace lsn_amd

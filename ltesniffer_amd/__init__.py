@@ -43,7 +43,8 @@ EXPORTS = ["lsn_phy_create", "lsn_phy_destroy", "lsn_phy_set_cell", "lsn_phy_get
            "lsn_resample", "lsn_resample_span", "lsn_phy_process_file_rate", "lsn_resample_cells", "lsn_file_cells_span", "lsn_file_process_cells",
            "lsn_clock_plan", "lsn_clock_fit", "lsn_clock_replica", "lsn_clock_track", "lsn_clock_estimate", "lsn_file_clock_estimate",
            "lsn_carrier_scan_plan", "lsn_carrier_scan_decide", "lsn_carrier_scan", "lsn_file_carrier_scan", "lsn_carrier_channel", "lsn_carrier_channel_span",
-           "lsn_phy_set_channel_filter", "lsn_channel_filter_design", "lsn_channel_filter", "lsn_channel_filter_span", "lsn_cells_stopbands"]
+           "lsn_phy_set_channel_filter", "lsn_channel_filter_design", "lsn_channel_filter", "lsn_channel_filter_span", "lsn_cells_stopbands",
+           "lsn_resample_cells_ring", "lsn_stream_open", "lsn_stream_push", "lsn_stream_flush", "lsn_stream_status", "lsn_stream_close", "lsn_stream_span"]
 
 RATES_3GPP, RATES_SRSRAN = 0, 1   # LSN_RATES_*: sampling mode of a Phy / of a cell search
 
@@ -122,6 +123,22 @@ class FileCell(C.Structure):   # lsn_file_cell_t
 class FileCellsSpan(C.Structure):   # lsn_file_cells_span_t
     _fields_ = [("in_lo", C.c_int64), ("in_hi", C.c_int64), ("blk_used", C.c_uint32), ("nof_active", C.c_uint32), ("first_subframe", C.c_uint64 * FILE_MAX_CELLS),
                 ("nof_subframes", C.c_uint32 * FILE_MAX_CELLS), ("taps", C.c_uint32 * FILE_MAX_CELLS)]
+
+
+class StreamCfg(C.Structure):   # lsn_stream_cfg_t
+    _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int), ("sample_rate_hz", C.c_double), ("nof_antennas", C.c_uint32), ("sample_format", C.c_uint32),
+                ("sample_scale", C.c_float), ("block_subframes", C.c_uint32), ("ring_samples", C.c_uint64)]
+
+
+class StreamStatus(C.Structure):   # lsn_stream_status_t
+    _fields_ = [("samples_pushed", C.c_uint64), ("ring_samples", C.c_uint64), ("oldest_needed", C.c_int64), ("block_subframes", C.c_uint32), ("nof_cells", C.c_uint32),
+                ("failed", C.c_int), ("status", C.c_int * FILE_MAX_CELLS), ("subframes_submitted", C.c_uint64 * FILE_MAX_CELLS)]
+
+
+class StreamSpan(C.Structure):   # lsn_stream_span_t
+    _fields_ = [("ring_samples", C.c_uint64), ("block_input", C.c_uint64), ("oldest_needed", C.c_int64), ("oldest_needed_flushed", C.c_int64), ("block_subframes", C.c_uint32),
+                ("reserved", C.c_uint32), ("subframes_complete", C.c_uint64 * FILE_MAX_CELLS), ("subframes_submitted", C.c_uint64 * FILE_MAX_CELLS),
+                ("taps", C.c_uint32 * FILE_MAX_CELLS)]
 
 
 class ResampleCfg(C.Structure):   # lsn_resample_cfg_t
@@ -404,6 +421,13 @@ def lib():
         L.lsn_resample_cells.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.POINTER(ResampleCfg), C.c_uint32, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_uint64)]
         L.lsn_file_cells_span.argtypes = [C.POINTER(FileCfg), C.c_double, C.POINTER(FileCell), C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(FileCellsSpan)]
         L.lsn_file_process_cells.argtypes = [C.c_char_p, C.POINTER(FileCfg), C.c_double, C.POINTER(FileCell), C.c_uint32]
+        L.lsn_resample_cells_ring.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(ResampleCfg), C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        L.lsn_stream_open.argtypes = [C.POINTER(StreamCfg), C.POINTER(FileCell), C.c_uint32, C.POINTER(C.c_void_p)]
+        L.lsn_stream_push.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        L.lsn_stream_flush.argtypes = [C.c_void_p]
+        L.lsn_stream_status.argtypes = [C.c_void_p, C.POINTER(StreamStatus)]
+        L.lsn_stream_close.argtypes = [C.c_void_p]
+        L.lsn_stream_span.argtypes = [C.POINTER(StreamCfg), C.POINTER(FileCell), C.c_uint32, C.c_uint64, C.POINTER(StreamSpan)]
         L.lsn_phy_set_prach_config.argtypes = [C.c_void_p, C.POINTER(PrachCfg)]
         L.lsn_phy_prach_detect.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(PrachDet), C.c_uint32]
         L.lsn_phy_set_prach_sink.argtypes = [C.c_void_p, PRACH_SINK, C.c_void_p]
@@ -891,6 +915,13 @@ class Phy:
 
     def close(self):
         if self._h:
+            st = getattr(self, "_stream", None)     # a Stream this Phy is a cell of is closed first: its launches write this Phy's buffers
+            st = st() if st is not None else None
+            if st is not None:
+                try:
+                    st.close()
+                except (RuntimeError, ValueError):
+                    pass
             lib().lsn_phy_destroy(self._h)
             self._h = C.c_void_p()
 
@@ -1024,6 +1055,34 @@ def resample_cells(iq, rate_in, cells, n_out=None, in_base=0, sample_format=FILE
     return outs
 
 
+def resample_cells_ring(iq, rate_in, cells, ring_samples, n_out=None, in_base=0, sample_format=FILE_CF32, sample_scale=0.0, device=0):
+    """lsn_resample_cells_ring: resample_cells through the kernel a Stream runs (k_resample_ring).  The window iq = samples in_base .. in_base + len(iq) of the
+    recording is placed into a device ring of ring_samples samples (a power of two), sample n at slot n mod ring_samples, and the cells are resampled out of
+    the ring.  Arguments and result as resample_cells - the arrays are equal bit for bit.  Raises ValueError when the library refuses the call"""
+    iq = _scan_input(iq, sample_format)
+    n_in, nant = iq.shape[0], iq.shape[1]
+    n = len(cells)
+    cfgs = (ResampleCfg * max(n, 1))()
+    counts = (C.c_uint64 * max(n, 1))()
+    outs = []
+    for i, c in enumerate(cells):
+        cfgs[i] = _resample_cfg(nant, rate_in, c["rate_out"], c.get("first_sample", 0), c.get("first_frac", 0.0), in_base, c.get("out_first", 0), c.get("passband_hz", 0.0),
+                                sample_format, sample_scale, c.get("center_offset_hz", 0.0))
+        k = c.get("n_out", n_out)
+        if k is None:
+            sp = ResampleSpan()
+            _check(lib().lsn_resample_span(C.byref(cfgs[i]), 0, int(in_base) + n_in, C.byref(sp)), "lsn_resample_span")
+            k = int(sp.max_out)
+        counts[i] = int(k)
+        outs.append(np.zeros((nant, int(k)), dtype=np.complex64))
+    ptrs = (C.c_void_p * max(n, 1))(*[o.ctypes.data for o in outs])
+    rc = lib().lsn_resample_cells_ring(device, iq.ctypes.data, n_in, int(ring_samples), cfgs, n, ptrs, counts)
+    if rc == LSN_ERROR_INVALID_INPUTS:
+        raise ValueError("resample_cells_ring: refused")
+    _check(rc, "lsn_resample_cells_ring")
+    return outs
+
+
 def channel_filter_design(rate_in, passband_hz, stopband_hz):
     """lsn_channel_filter_design (needs no GPU) -> dict(L, fc, taps: float32 [2 L + 1], g[-L] .. g[L]).  Raises ValueError when the library refuses the filter"""
     import numpy as np
@@ -1138,6 +1197,119 @@ def process_file_cells(path, sample_rate, cells, nof_antennas=None, sample_forma
     _check(rc, "lsn_file_process_cells")
     done = [int(c.subframes_done) for c in arr[:len(cells)]]
     return (done, [int(c.status) for c in arr[:len(cells)]]) if with_status else done
+
+
+def _stream_cfg(sample_rate, nof_antennas, sample_format, sample_scale, block_subframes, ring_samples, device):
+    return StreamCfg(C.sizeof(StreamCfg), int(device), float(sample_rate), int(nof_antennas), int(sample_format), float(sample_scale), int(block_subframes), int(ring_samples))
+
+
+def stream_span(sample_rate, cells, pushed, nof_antennas=1, sample_format=FILE_CF32, sample_scale=0.0, block_subframes=0, ring_samples=0):
+    """lsn_stream_span (needs no GPU): the plan of a Stream after `pushed` samples in all.  cells as file_cells_span.  -> dict(ring_samples: the given one or the
+    default; block_input: input samples of one block of every cell, which the ring must hold; block_subframes; per cell subframes_complete - what a flush at that
+    point has submitted in all -, subframes_submitted - what a stream that was never flushed has - and taps; oldest_needed / oldest_needed_flushed: the oldest
+    sample a cell still needs in the two cases).  Raises ValueError when the library refuses cells or ring"""
+    arr = (FileCell * max(len(cells), 1))()
+    for i, c in enumerate(cells):
+        arr[i] = _file_cell(*c) if isinstance(c, tuple) else _file_cell(None, c)
+    cfg = _stream_cfg(sample_rate, nof_antennas, sample_format, sample_scale, block_subframes, ring_samples, 0)
+    sp = StreamSpan()
+    rc = lib().lsn_stream_span(C.byref(cfg), arr, len(cells), int(pushed), C.byref(sp))
+    if rc == LSN_ERROR_INVALID_INPUTS:
+        raise ValueError("stream: refused")
+    _check(rc, "lsn_stream_span")
+    n = len(cells)
+    return dict(ring_samples=int(sp.ring_samples), block_input=int(sp.block_input), block_subframes=int(sp.block_subframes), oldest_needed=int(sp.oldest_needed),
+                oldest_needed_flushed=int(sp.oldest_needed_flushed), subframes_complete=[int(v) for v in sp.subframes_complete[:n]],
+                subframes_submitted=[int(v) for v in sp.subframes_submitted[:n]], taps=[int(v) for v in sp.taps[:n]])
+
+
+class Stream:
+    """lsn_stream_*: the cells of a live wideband stream that arrives in host buffers.  cells: a list of (phy, dict(...)) with the keys of process_file_cells
+    (center_offset_hz, start_tti - not TTI_FROM_MIB -, offset_time / offset_time_frac: the start of the cell's subframe 0 counted from the first sample ever
+    pushed, offset_freq, max_subframes, update_meta_period).  The raw samples live in a device ring (ring_samples, a power of two; 0: chosen by the library);
+    a cell is submitted to its Phy whenever block_subframes complete subframes of it have arrived (0: the file source's block size).  The Phys' records are
+    those of process_file_cells on a file of the same bytes, however the stream is cut into pushes.  Raises ValueError when the library refuses the stream
+    (nothing is allocated, every Phy stays usable).  Close the stream before its Phys; a Phy that is closed first closes the stream."""
+
+    def __init__(self, sample_rate, cells, nof_antennas=None, sample_format=FILE_CF32, sample_scale=0.0, block_subframes=0, ring_samples=0, device=0):
+        self._h = None
+        self._phys = [phy for phy, _ in cells]     # kept alive as long as the stream
+        arr = (FileCell * max(len(cells), 1))()
+        for i, (phy, kw) in enumerate(cells):
+            arr[i] = _file_cell(phy, kw)
+        if nof_antennas is None:
+            nof_antennas = cells[0][0].nof_rx_antennas if cells else 1
+        self.nof_antennas, self.sample_format, self.nof_cells = int(nof_antennas), int(sample_format), len(cells)
+        cfg = _stream_cfg(sample_rate, nof_antennas, sample_format, sample_scale, block_subframes, ring_samples, device)
+        h = C.c_void_p()
+        rc = lib().lsn_stream_open(C.byref(cfg), arr, len(cells), C.byref(h))
+        if rc == LSN_ERROR_INVALID_INPUTS:
+            raise ValueError("Stream: refused")
+        _check(rc, "lsn_stream_open")
+        self._h = h
+        import weakref
+        for phy in self._phys:
+            phy._stream = weakref.ref(self)
+
+    def _call(self, rc, what):
+        if rc == LSN_ERROR_INVALID_INPUTS:
+            raise ValueError("%s: refused" % what)
+        _check(rc, what)
+
+    def push(self, iq):
+        """samples as resample takes them: [sample][antenna] complex64 (or [sample] for one antenna), int16 / int8 with a last axis of 2 for FILE_SC16 / FILE_SC8.
+        Returns when they are in the ring; a pinned (page-locked) array is copied without a detour"""
+        import numpy as np
+        dt = (np.complex64, np.int16, np.int8)[self.sample_format]
+        iq = np.ascontiguousarray(iq, dtype=dt)
+        per = self.nof_antennas * (1 if self.sample_format == FILE_CF32 else 2)
+        if iq.size % per:
+            raise ValueError("push: not a whole number of samples of %d antenna(s)" % self.nof_antennas)
+        self._call(lib().lsn_stream_push(self._h, iq.ctypes.data, iq.size // per), "lsn_stream_push")
+
+    def gap(self, n):
+        """n samples the radio dropped: zeros arrive, positions stay"""
+        self._call(lib().lsn_stream_push(self._h, None, int(n)), "lsn_stream_push")
+
+    def flush(self):
+        """submit every complete subframe, wait for every Phy -> subframes done per cell; the stream goes on afterwards"""
+        self._call(lib().lsn_stream_flush(self._h), "lsn_stream_flush")
+        return self.status()["subframes_submitted"]
+
+    def status(self):
+        st = StreamStatus()
+        self._call(lib().lsn_stream_status(self._h, C.byref(st)), "lsn_stream_status")
+        n = int(st.nof_cells)
+        return dict(samples_pushed=int(st.samples_pushed), ring_samples=int(st.ring_samples), oldest_needed=int(st.oldest_needed), block_subframes=int(st.block_subframes),
+                    failed=int(st.failed), status=[int(v) for v in st.status[:n]], subframes_submitted=[int(v) for v in st.subframes_submitted[:n]])
+
+    def close(self):
+        """flush, then free; the Phys stay usable -> subframes done per cell (None when the stream was closed already).  Every later call raises ValueError"""
+        if self._h is None:
+            return None
+        h, self._h = self._h, None
+        st = StreamStatus()
+        rc = lib().lsn_stream_flush(h)              # (the close's own flush finds nothing left: the counts are read between the two)
+        lib().lsn_stream_status(h, C.byref(st))
+        rc2 = lib().lsn_stream_close(h)
+        for phy in self._phys:
+            phy._stream = None
+        self._phys = []
+        self._call(rc if rc != LSN_SUCCESS else rc2, "lsn_stream_close")
+        return [int(v) for v in st.subframes_submitted[:int(st.nof_cells)]]
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 SCAN_MAX_HYPOTHESES = 8192

@@ -13,6 +13,7 @@
 #include "lsn_engine.h"
 #include "lsn_cells.h"
 #include "lsn_chanfilt_launch.h"
+#include "lsn_stream_ring.h"
 #include <chrono>
 #include <condition_variable>
 #include <deque>
@@ -51,6 +52,7 @@ struct lsn_phy {
   std::deque<InFlight> inflight;   // batches whose rows are crossing PCIe (dispatcher -> releaser)
   std::vector<hipEvent_t> ev_free;
   int last_error = 0;
+  lsn_stream* stream = nullptr;   // the open lsn_stream this Phy is a cell of
 
   void dispatch_loop();
   void release_loop();
@@ -227,6 +229,10 @@ uint32_t lsn_phy_nof_devices(lsn_phy_t* phy) { return phy ? (uint32_t)phy->neng(
 void lsn_phy_destroy(lsn_phy_t* phy)
 {
   if (!phy) return;
+  if (phy->stream) {   // the caller should have closed it: its launches write this Phy's block buffers, so it ends here, before they are freed (its handle is dead afterwards)
+    fprintf(stderr, "ltesniffer_amd: lsn_phy_destroy on a Phy of an open stream: the stream is closed first\n");
+    (void)lsn_stream_close(phy->stream);
+  }
   if (phy->dispatcher.joinable()) { (void)lsn_phy_join_pending(phy); phy->stop_threads(); }
   for (auto& w : phy->workers)
     for (auto& b : w->buf_offset) free(b);
@@ -635,6 +641,132 @@ int lsn_file_process_cells(const char* path, const lsn_file_cfg_t* cfg, double s
     return rc;
   });
 }
+
+// ---- a live stream pushed in host buffers (lsn_stream.h: the plan; lsn_stream_ring.h: the device ring) ----
+// What lsn_stream_open and lsn_stream_span check alike, through file_cells_plans - the file pass's own checks and plans - and the stream's refusals on top.
+static int stream_plans(const lsn_stream_cfg_t* cfg, const lsn_file_cell_t* cells, uint32_t n, bool need_phy, std::vector<lsn::ResamplePlan>& plans, std::vector<uint32_t>& sflen,
+                        uint32_t& blk, uint64_t& ring_samples)
+{
+  if (!cfg || cfg->struct_size != sizeof(lsn_stream_cfg_t)) return LSN_ERROR_INVALID_INPUTS;
+  lsn_file_cfg_t fc{};
+  fc.nof_antennas = cfg->nof_antennas; fc.offset_time_samples = 0; fc.offset_freq_hz = 0.0f; fc.sample_format = cfg->sample_format; fc.sample_scale = cfg->sample_scale;
+  std::vector<lsn::ChanFilter> filt;
+  const int r = file_cells_plans(&fc, cfg->sample_rate_hz, cells, n, need_phy, plans, sflen, filt);
+  if (r != LSN_SUCCESS) return r;
+  for (uint32_t c = 0; c < n; c++) {
+    if (cells[c].start_tti == LSN_TTI_FROM_MIB || filt[c].L) return LSN_ERROR_INVALID_INPUTS;
+    if (cells[c].phy && (cells[c].phy->stream || cells[c].phy->engine->device() != cfg->device)) return LSN_ERROR_INVALID_INPUTS;
+  }
+  uint32_t blk_geom;
+  int nslot;
+  lsn::Engine::fileBlockGeometry(blk_geom, nslot);
+  blk = cfg->block_subframes ? cfg->block_subframes : blk_geom;
+  if (blk > blk_geom) return LSN_ERROR_INVALID_INPUTS;
+  lsn::StreamCellPlan sp[LSN_FILE_MAX_CELLS];
+  for (uint32_t c = 0; c < n; c++) { sp[c].rs = &plans[c]; sp[c].sflen = sflen[c]; sp[c].max_subframes = cells[c].max_subframes; }
+  ring_samples = cfg->ring_samples;
+  return lsn::stream_ring_check(sp, n, blk, ring_samples);
+}
+
+struct lsn_stream {
+  std::unique_ptr<lsn::StreamRing> ring;
+  std::vector<lsn_phy*> phys;
+};
+
+int lsn_stream_span(const lsn_stream_cfg_t* cfg, const lsn_file_cell_t* cells, uint32_t n_cells, uint64_t pushed, lsn_stream_span_t* out)
+{
+  return lsn::guarded([&]() -> int {
+    std::vector<lsn::ResamplePlan> plans;
+    std::vector<uint32_t> sflen;
+    uint32_t blk = 0;
+    uint64_t ring = 0;
+    const int r = stream_plans(cfg, cells, n_cells, false, plans, sflen, blk, ring);
+    if (r != LSN_SUCCESS) return r;
+    if (!out || pushed >= (1ull << 62)) return LSN_ERROR_INVALID_INPUTS;
+    lsn::StreamCellPlan sp[LSN_FILE_MAX_CELLS];
+    uint64_t blocked[LSN_FILE_MAX_CELLS] = {}, complete[LSN_FILE_MAX_CELLS] = {};
+    memset(out, 0, sizeof(*out));
+    for (uint32_t c = 0; c < n_cells; c++) {
+      sp[c].rs = &plans[c]; sp[c].sflen = sflen[c]; sp[c].max_subframes = cells[c].max_subframes;
+      complete[c] = lsn::stream_cell_complete(sp[c], pushed);
+      // a stream that was never flushed: whole blocks, and the last subframes in front of max_subframes
+      blocked[c] = complete[c] / blk * blk;
+      blocked[c] += lsn::stream_cell_ready(sp[c], pushed, blocked[c], blk, false);
+      out->subframes_complete[c] = complete[c]; out->subframes_submitted[c] = blocked[c]; out->taps[c] = plans[c].taps;
+    }
+    out->ring_samples = ring; out->block_input = lsn::stream_block_input(sp, n_cells, blk); out->block_subframes = blk;
+    out->oldest_needed = lsn::stream_oldest_needed(sp, n_cells, blocked, pushed);
+    out->oldest_needed_flushed = lsn::stream_oldest_needed(sp, n_cells, complete, pushed);
+    return LSN_SUCCESS;
+  });
+}
+
+int lsn_stream_open(const lsn_stream_cfg_t* cfg, lsn_file_cell_t* cells, uint32_t n_cells, lsn_stream_t** out)
+{
+  if (!out) return LSN_ERROR_INVALID_INPUTS;
+  *out = nullptr;
+  return lsn::guarded([&]() -> int {
+    std::vector<lsn::ResamplePlan> plans;
+    std::vector<uint32_t> sflen;
+    uint32_t blk = 0;
+    uint64_t ring = 0;
+    const int r = stream_plans(cfg, cells, n_cells, true, plans, sflen, blk, ring);
+    if (r != LSN_SUCCESS) return r;
+    std::vector<lsn::StreamRing::CellSpec> specs(n_cells);
+    std::unique_ptr<lsn_stream> s(new lsn_stream());
+    for (uint32_t c = 0; c < n_cells; c++) {
+      specs[c].e = cells[c].phy->engine.get(); specs[c].plan = std::move(plans[c]); specs[c].offset_freq_hz = cells[c].offset_freq_hz; specs[c].start_tti = cells[c].start_tti;
+      specs[c].update_meta_period = cells[c].update_meta_period; specs[c].max_subframes = cells[c].max_subframes;
+      s->phys.push_back(cells[c].phy);
+    }
+    s->ring.reset(new lsn::StreamRing(cfg->device, cfg->nof_antennas, cfg->sample_format, cfg->sample_scale, blk, ring, std::move(specs)));
+    const int rs = s->ring->setup();
+    if (rs != LSN_SUCCESS) return rs;
+    for (auto* p : s->phys) p->stream = s.get();
+    *out = s.release();
+    return LSN_SUCCESS;
+  });
+}
+
+int lsn_stream_push(lsn_stream_t* s, const void* iq, uint64_t n_samples)
+{
+  if (!s) return LSN_ERROR_INVALID_INPUTS;
+  std::unique_lock<std::mutex> lk(s->ring->mtx);
+  return s->ring->push(iq, n_samples);
+}
+
+int lsn_stream_flush(lsn_stream_t* s)
+{
+  if (!s) return LSN_ERROR_INVALID_INPUTS;
+  std::unique_lock<std::mutex> lk(s->ring->mtx);
+  return s->ring->flush();
+}
+
+int lsn_stream_status(lsn_stream_t* s, lsn_stream_status_t* out)
+{
+  if (!s || !out) return LSN_ERROR_INVALID_INPUTS;
+  std::unique_lock<std::mutex> lk(s->ring->mtx);
+  const lsn::StreamRing& r = *s->ring;
+  memset(out, 0, sizeof(*out));
+  out->samples_pushed = r.pushedSamples(); out->ring_samples = r.ringSamples(); out->oldest_needed = r.oldestNeeded(); out->block_subframes = r.blockSubframes();
+  out->nof_cells = (uint32_t)r.nofCells(); out->failed = r.failedCode();
+  for (size_t c = 0; c < r.nofCells(); c++) { out->status[c] = r.cellStatus(c); out->subframes_submitted[c] = r.cellDone(c); }
+  return LSN_SUCCESS;
+}
+
+int lsn_stream_close(lsn_stream_t* s)
+{
+  if (!s) return LSN_ERROR_INVALID_INPUTS;
+  int rc;
+  {
+    std::unique_lock<std::mutex> lk(s->ring->mtx);
+    rc = s->ring->flush();
+  }
+  for (auto* p : s->phys) p->stream = nullptr;
+  delete s;   // (the ring waits for every Phy once more, whatever the flush answered, before it frees what their launches read)
+  return rc;
+}
+
 int lsn_phy_set_channel_filter(lsn_phy_t* phy, double stopband_hz)
 {
   if (!phy) return LSN_ERROR_INVALID_INPUTS;

@@ -288,6 +288,11 @@ public:
   // the channel filter's intermediate (y1 of one block, cf32 [sample][antenna]): grows, never shrinks; kept like the block buffers
   int reserveChanBuffer(size_t bytes);
   int reserveFileBuffers(uint32_t nof_antennas);   // lsn_phy_prepare_file: pinned read blocks + device blocks of the file source, ahead of the first replay
+  // what reserveFileBuffers sizes them by - subframes per block (LSN_FILE_BLOCK) and blocks in flight (LSN_FILE_SLOTS) - and the device block of slot si that a
+  // source fills with [subframe][antenna][sample] cf32 and hands to submit(): the file source's, and the pushed stream's (lsn_stream_ring.cc)
+  static void fileBlockGeometry(uint32_t& blk, int& nslot);
+  cf32* fileIqBlock(int si) const { return file_buf[si].d_iq; }
+  size_t fileIqBlockBytes(int si) const { return file_buf[si].d_iq ? file_buf[si].bytes : 0; }
   int processHost(const void* iq, uint32_t nsf, uint32_t start_tti, uint32_t update_meta_period, uint32_t sample_format = 0 /* LSN_FILE_* */, float sample_scale = 0.0f);
   void setSink(lsn_pdu_sink_t cb, void* user) { sink = cb; sink_user = user; }
   void setApi(int mode, lsn_api_sink_t cb, void* user, lsn_pdu_sink_t pcap_cb, void* pcap) { api_mode = mode; api_sink = cb; api_user = user; api_pcap_sink = pcap_cb; api_pcap = pcap; }

@@ -36,6 +36,12 @@ static void file_geometry(uint32_t& blk, uint32_t& nrd, int& nslot)
   if (const char* e = getenv("LSN_FILE_SLOTS")) nslot = std::max(3, std::min(8, atoi(e)));
 }
 
+void Engine::fileBlockGeometry(uint32_t& blk, int& nslot)
+{
+  uint32_t nrd;
+  file_geometry(blk, nrd, nslot);
+}
+
 // The pinned read blocks and the device blocks of the file source (4 x 393 MB page-locked + 8 x 393 MB of HBM at 20 MHz / 2 antennas).  Page-locking
 // 1.5 GB takes longer than replaying 10 000 subframes: rounds 2-4 paid it inside the first lsn_phy_process_file call (43.6 k subframes/s on the first
 // pass of a 20 000-subframe capture against 96 k on the second, round-4 review).  A caller that knows it will replay a file - the reference does

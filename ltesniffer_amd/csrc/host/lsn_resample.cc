@@ -208,9 +208,10 @@ int lsn_resample(int device, const void* in, int in_on_device, uint64_t n_in, co
   return rc;
 }
 
-// several resamplings of one input: one upload of the union of what the cells read, one launch of k_resample_cells
-int lsn_resample_cells(int device, const void* in, int in_on_device, uint64_t n_in, const lsn_resample_cfg_t* cfgs, uint32_t n_cells, float* const* outs, int out_on_device,
-                       const uint64_t* n_out)
+// several resamplings of one input: one upload of the union of what the cells read, one launch of k_resample_cells.  ring_samples != 0 (host input): the whole
+// window goes to its slots in a device ring of that many samples instead, and k_resample_ring reads it there
+static int resample_cells(int device, const void* in, int in_on_device, uint64_t n_in, uint64_t ring_samples, const lsn_resample_cfg_t* cfgs, uint32_t n_cells, float* const* outs,
+                          int out_on_device, const uint64_t* n_out)
 {
   if (!cfgs || !outs || !n_out || n_cells < 1 || n_cells > LSN_FILE_MAX_CELLS) return LSN_ERROR_INVALID_INPUTS;
   std::vector<lsn::ResamplePlan> plans(n_cells);
@@ -250,7 +251,14 @@ int lsn_resample_cells(int device, const void* in, int in_on_device, uint64_t n_
     HIP_CHECK(hipSetDevice(device));
     HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     const void* raw = src;
-    if (!in_on_device && len) {
+    if (ring_samples) {
+      // slots no sample of the window goes to keep a pattern (NaN as cf32) that a read outside the window would carry into the outputs
+      HIP_CHECK(hipMalloc(&d_in, ring_samples * smp));
+      HIP_CHECK(hipMemsetAsync(d_in, 0xFF, ring_samples * smp, st));
+      const uint64_t slot = c0.in_base & (ring_samples - 1), head = std::min(n_in, ring_samples - slot);
+      if (head) HIP_CHECK(hipMemcpyAsync((uint8_t*)d_in + slot * smp, in, head * smp, hipMemcpyHostToDevice, st));
+      if (n_in > head) HIP_CHECK(hipMemcpyAsync(d_in, (const uint8_t*)in + head * smp, (n_in - head) * smp, hipMemcpyHostToDevice, st));   // behind the end of the ring
+    } else if (!in_on_device && len) {
       HIP_CHECK(hipMalloc(&d_in, len * smp));
       HIP_CHECK(hipMemcpyAsync(d_in, src, len * smp, hipMemcpyHostToDevice, st));
       raw = d_in;
@@ -270,7 +278,8 @@ int lsn_resample_cells(int device, const void* in, int in_on_device, uint64_t n_
       k[c].sflen = (uint32_t)std::max<uint64_t>(n_out[c], 1); k[c].sf_off = 0; k[c].bank = d_bank[c]; k[c].w = p.tune; k[c].nco = d_nco; k[c].rot = nullptr; k[c].out = dst;
       k[c].n_out = n_out[c];
     }
-    lsn_launch_resample_cells(raw, fmt, sfm.scale, need_lo, len, nant, k, n_cells, st);
+    if (ring_samples) lsn_launch_resample_ring(d_in, ring_samples, fmt, sfm.scale, (int64_t)c0.in_base, n_in, nant, k, n_cells, st);
+    else lsn_launch_resample_cells(raw, fmt, sfm.scale, need_lo, len, nant, k, n_cells, st);
     if (!out_on_device)
       for (uint32_t c = 0; c < n_cells; c++)
         if (n_out[c]) HIP_CHECK(hipMemcpyAsync(outs[c], d_out[c], (size_t)n_out[c] * nant * sizeof(cf32), hipMemcpyDeviceToHost, st));
@@ -284,6 +293,19 @@ int lsn_resample_cells(int device, const void* in, int in_on_device, uint64_t n_
   for (float* b : d_bank) if (b) (void)hipFree(b);
   for (void* o : d_out) if (o) (void)hipFree(o);
   return rc;
+}
+
+int lsn_resample_cells(int device, const void* in, int in_on_device, uint64_t n_in, const lsn_resample_cfg_t* cfgs, uint32_t n_cells, float* const* outs, int out_on_device,
+                       const uint64_t* n_out)
+{
+  return resample_cells(device, in, in_on_device, n_in, 0, cfgs, n_cells, outs, out_on_device, n_out);
+}
+
+int lsn_resample_cells_ring(int device, const void* in, uint64_t n_in, uint64_t ring_samples, const lsn_resample_cfg_t* cfgs, uint32_t n_cells, float* const* outs,
+                            const uint64_t* n_out)
+{
+  if (!in || !ring_samples || (ring_samples & (ring_samples - 1)) || ring_samples > (1ull << 32) || n_in > ring_samples) return LSN_ERROR_INVALID_INPUTS;
+  return resample_cells(device, in, 0, n_in, ring_samples, cfgs, n_cells, outs, 0, n_out);
 }
 
 }  // extern "C"

@@ -22,3 +22,7 @@ struct LsnResampleCell {
 };
 void lsn_launch_resample_cells(const void* raw, uint32_t fmt, float scale, int64_t buf_base, uint64_t buf_len, uint32_t nant, const LsnResampleCell* cells, uint32_t n_cells,
                                hipStream_t s);
+// k_resample_ring: the same launch out of a device ring of ring_samples samples per antenna (a power of two), sample n of the recording at slot n & (ring_samples - 1);
+// [buf_base, buf_base + buf_len) are the recording indices whose samples the ring holds, buf_len <= ring_samples
+void lsn_launch_resample_ring(const void* ring, uint64_t ring_samples, uint32_t fmt, float scale, int64_t buf_base, uint64_t buf_len, uint32_t nant, const LsnResampleCell* cells,
+                              uint32_t n_cells, hipStream_t s);

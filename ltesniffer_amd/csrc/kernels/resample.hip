@@ -15,6 +15,9 @@
 // MIX instantiations (a cell off the recording's centre, DESIGN 3.1b "Frequency translation"): input sample n is multiplied by
 // exp(-2 pi j Phi(n) / 2^64), Phi(n) = n * W mod 2^64 with n the sample's index in the RECORDING, while it is staged - the one place every input
 // sample is touched once; the tap loop does not know.  The exponential is the two-table NCO of k_ofdm (4096 coarse x 1024 fine entries).
+//
+// Three kernels expand the one copy of that text: k_resample (one cell, a linear buffer), k_resample_cells (several cells, one linear buffer) and
+// k_resample_ring (several cells out of the device ring a pushed stream keeps its raw samples in).
 #include "lsn_dsp.h"
 #include "../host/lsn_resample_launch.h"
 #include <algorithm>
@@ -36,19 +39,23 @@ struct LsnResampleArgs {
   uint32_t sf_off;       // phase of launch output 0 inside its row (0 for the file source: launches start on a subframe)
   uint64_t n_out;        // outputs of the launch, per antenna
   float scale;
+  uint32_t ring_mask;    // k_resample_ring: raw is a ring of ring_mask + 1 samples (a power of two), recording sample n sits at slot n & ring_mask; else 0 and unread
   const float2* bank;    // [512][T] (H, dH)
   const cf32* rot;       // optional [sflen]
   cf32* out;
   uint64_t w;            // MIX: tuning word W ...
   const cf32* nco;       // ... and the NCO tables, [4096] coarse then [1024] fine
 };
+static_assert(sizeof(LsnResampleArgs) == 128, "eight of them are one kernel argument block; ring_mask sits in what was padding behind scale");
 
-// One run of one antenna: the staging loop and the tap loop.  They exist ONCE in this file, as text: the body is a macro that k_resample and k_resample_cells
+// One run of one antenna: the staging loop and the tap loop.  They exist ONCE in this file, as text: the body is a macro that the three kernels
 // expand, over the names A (the run's LsnResampleArgs), rs_x (the dynamic LDS) and FMT, with MIXCOND the one thing that differs - k_resample's template flag, or
 // the cell's own "has NCO tables", uniform over the workgroup.  A macro and not an inlined __device__ function: the compiler simplifies a function on its own
 // before it inlines it, which reorders k_resample's instructions; expanded as text, all six k_resample instantiations are the instruction streams
-// they were when this was k_resample's body.
-#define LSN_RESAMPLE_RUN(MIXCOND) \
+// they were when this was k_resample's body.  SRCSAMPLE is the second thing that differs: the index, in A.raw, of the sample the staging loop loads, over the
+// loop's names n (index in the recording) and k (n - buf_base).  k_resample and k_resample_cells read a linear buffer and pass k; k_resample_ring passes the slot
+// of n in its ring.  [buf_base, buf_base + buf_len) is the window of recording indices that hold samples either way.
+#define LSN_RESAMPLE_RUN(MIXCOND, SRCSAMPLE) \
   const uint32_t a = blockIdx.y, half = A.taps / 2;                                                                                                                     \
   const uint64_t i0 = (uint64_t)blockIdx.x * LSN_RS_RUN;                                                                                                                \
   /* position of the run's first output: base + i0 * D */                                                                                                               \
@@ -60,7 +67,7 @@ struct LsnResampleArgs {
     const int64_t n = n_lo + (int64_t)s, k = n - A.buf_base;                                                                                                            \
     float2 x = make_float2(0.0f, 0.0f);                                                                                                                                 \
     if (n >= 0 && k >= 0 && (uint64_t)k < A.buf_len) {                                                                                                                  \
-      const size_t src = (size_t)k * A.nant + a;                                                                                                                        \
+      const size_t src = (size_t)(SRCSAMPLE) * A.nant + a;                                                                                                              \
       if (FMT == 1) {                                                                                                                                                   \
         const short2 q = ((const short2*)A.raw)[src];                                                                                                                   \
         x.x = (float)q.x * A.scale; x.y = (float)q.y * A.scale;                                                                                                         \
@@ -111,7 +118,7 @@ template <int FMT, bool MIX>
 __global__ __launch_bounds__(256) void k_resample(const LsnResampleArgs A)
 {
   extern __shared__ float2 rs_x[];
-  LSN_RESAMPLE_RUN(MIX)
+  LSN_RESAMPLE_RUN(MIX, k)
 }
 
 // Several cells of one recording from ONE raw buffer in one launch (lsn_file_process_cells, lsn_resample_cells): grid (largest number of runs
@@ -127,7 +134,19 @@ __global__ __launch_bounds__(256) void k_resample_cells(const LsnResampleCellsAr
   extern __shared__ float2 rs_x[];
   const LsnResampleArgs& A = P.c[blockIdx.z];
   if ((uint64_t)blockIdx.x * LSN_RS_RUN >= A.n_out) return;
-  LSN_RESAMPLE_RUN(A.nco != nullptr)
+  LSN_RESAMPLE_RUN(A.nco != nullptr, k)
+}
+
+// The same launch out of a RING (lsn_stream, lsn_resample_cells_ring): raw holds ring_mask + 1 samples per antenna and sample n of the recording sits
+// at slot n & ring_mask, wherever the pushes that brought it were cut.  Grid, argument block and early exit are k_resample_cells'; a source index is below
+// (ring_mask + 1) * nant whatever n is, and the window test in front of it keeps a run from staging a slot that holds another lap's sample.
+template <int FMT>
+__global__ __launch_bounds__(256) void k_resample_ring(const LsnResampleCellsArgs P)
+{
+  extern __shared__ float2 rs_x[];
+  const LsnResampleArgs& A = P.c[blockIdx.z];
+  if ((uint64_t)blockIdx.x * LSN_RS_RUN >= A.n_out) return;
+  LSN_RESAMPLE_RUN(A.nco != nullptr, n & (int64_t)A.ring_mask)
 }
 
 // n_out outputs per antenna from output position (base_hi, base_lo); span = samples a run of LSN_RS_RUN outputs needs (host: lsn_resample.cc).
@@ -143,7 +162,7 @@ void lsn_launch_resample(const void* raw, uint32_t fmt, float scale, int64_t buf
   LsnResampleArgs A;
   A.raw = raw; A.buf_base = buf_base; A.buf_len = buf_len; A.base_hi = base_hi; A.base_lo = base_lo; A.d_lo = d_lo; A.d_hi = d_hi; A.taps = taps; A.span = span;
   A.nant = nant; A.sflen = sflen; A.sf_off = sf_off; A.n_out = n_out; A.scale = scale; A.bank = (const float2*)bank; A.rot = rot; A.out = out;
-  A.w = w; A.nco = nco;
+  A.w = w; A.nco = nco; A.ring_mask = 0;
   const dim3 g((uint32_t)runs, nant);
   const size_t lds = (size_t)span * sizeof(float2);
   if (nco) {
@@ -159,11 +178,11 @@ void lsn_launch_resample(const void* raw, uint32_t fmt, float scale, int64_t buf
 
 // the cells of one launch: raw, buf_base, buf_len, fmt, scale and nant are the recording's and shared; everything else is the cell's own (lsn_resample.h).
 // A cell with n_out = 0 takes no part.
-void lsn_launch_resample_cells(const void* raw, uint32_t fmt, float scale, int64_t buf_base, uint64_t buf_len, uint32_t nant, const LsnResampleCell* cells, uint32_t n_cells,
-                               hipStream_t s)
+// (the argument block of k_resample_cells and k_resample_ring: ring_mask = 0 for the former.  false: no cell takes part)
+static bool resample_cells_args(const void* raw, float scale, uint32_t ring_mask, int64_t buf_base, uint64_t buf_len, uint32_t nant, const LsnResampleCell* cells, uint32_t n_cells,
+                                LsnResampleCellsArgs& P, dim3& g, size_t& lds)
 {
   if (n_cells > LSN_RS_MAX_CELLS || buf_base < 0) throw std::runtime_error("k_resample_cells: bad geometry");
-  LsnResampleCellsArgs P;
   memset(&P, 0, sizeof(P));
   uint32_t n = 0, span = 0;
   uint64_t runs = 0;
@@ -176,14 +195,39 @@ void lsn_launch_resample_cells(const void* raw, uint32_t fmt, float scale, int64
     LsnResampleArgs& A = P.c[n++];
     A.raw = raw; A.buf_base = buf_base; A.buf_len = buf_len; A.base_hi = k.base_hi; A.base_lo = k.base_lo; A.d_lo = k.d_lo; A.d_hi = k.d_hi; A.taps = k.taps; A.span = k.span;
     A.nant = nant; A.sflen = k.sflen; A.sf_off = k.sf_off; A.n_out = k.n_out; A.scale = scale; A.bank = (const float2*)k.bank; A.rot = k.rot; A.out = k.out;
-    A.w = k.w; A.nco = k.nco;
+    A.w = k.w; A.nco = k.nco; A.ring_mask = ring_mask;
     runs = std::max(runs, r);
     span = std::max(span, k.span);
   }
-  if (!n) return;
-  const dim3 g((uint32_t)runs, nant, n);
-  const size_t lds = (size_t)span * sizeof(float2);
+  if (!n) return false;
+  g = dim3((uint32_t)runs, nant, n);
+  lds = (size_t)span * sizeof(float2);
+  return true;
+}
+
+void lsn_launch_resample_cells(const void* raw, uint32_t fmt, float scale, int64_t buf_base, uint64_t buf_len, uint32_t nant, const LsnResampleCell* cells, uint32_t n_cells,
+                               hipStream_t s)
+{
+  LsnResampleCellsArgs P;
+  dim3 g;
+  size_t lds;
+  if (!resample_cells_args(raw, scale, 0, buf_base, buf_len, nant, cells, n_cells, P, g, lds)) return;
   if (fmt == 1) LSN_LAUNCH((k_resample_cells<1>), g, dim3(256), lds, s, P);
   else if (fmt == 2) LSN_LAUNCH((k_resample_cells<2>), g, dim3(256), lds, s, P);
   else LSN_LAUNCH((k_resample_cells<0>), g, dim3(256), lds, s, P);
+}
+
+// ring: ring_samples samples per antenna, a power of two (at most 2^32); the samples [buf_base, buf_base + buf_len) of the recording are in their slots, so
+// buf_len <= ring_samples.  Everything else as lsn_launch_resample_cells.
+void lsn_launch_resample_ring(const void* ring, uint64_t ring_samples, uint32_t fmt, float scale, int64_t buf_base, uint64_t buf_len, uint32_t nant, const LsnResampleCell* cells,
+                              uint32_t n_cells, hipStream_t s)
+{
+  if (!ring_samples || (ring_samples & (ring_samples - 1)) || ring_samples > (1ull << 32) || buf_len > ring_samples) throw std::runtime_error("k_resample_ring: bad ring");
+  LsnResampleCellsArgs P;
+  dim3 g;
+  size_t lds;
+  if (!resample_cells_args(ring, scale, (uint32_t)(ring_samples - 1), buf_base, buf_len, nant, cells, n_cells, P, g, lds)) return;
+  if (fmt == 1) LSN_LAUNCH((k_resample_ring<1>), g, dim3(256), lds, s, P);
+  else if (fmt == 2) LSN_LAUNCH((k_resample_ring<2>), g, dim3(256), lds, s, P);
+  else LSN_LAUNCH((k_resample_ring<0>), g, dim3(256), lds, s, P);
 }
