@@ -465,7 +465,8 @@ int lsn_resample_cells_ring(int device, const void* in, uint64_t n_in, uint64_t 
  * filter set (k_chan_fir does not read the ring yet: refused, not dropped); a Phy that belongs to an open stream; cfg->device other than the Phys'; block_subframes
  * above LSN_FILE_BLOCK; ring_samples not a power of two, above 2^32, or shorter than one block of every cell - which is also how cells whose starts lie further
  * apart than the ring less one block are refused.
- * Not on a stream: the channel filter, LSN_TTI_FROM_MIB, the worker pool, cells on several GPUs; rate and offsets are inputs, as for files - no loop tracks them. */
+ * Not on a stream: the channel filter, LSN_TTI_FROM_MIB, the worker pool, cells on several GPUs.  Rate and offsets are inputs, as for files; a stream that asks
+ * for it (lsn_stream_track, below) follows the sample clock from there with a timing loop per cell.  File replays and the worker pool do not track. */
 typedef struct lsn_stream lsn_stream_t;
 typedef struct {
   uint32_t struct_size;      /* sizeof(lsn_stream_cfg_t); every other size is refused */
@@ -504,6 +505,79 @@ int lsn_stream_flush(lsn_stream_t* s);
 int lsn_stream_status(lsn_stream_t* s, lsn_stream_status_t* out);
 int lsn_stream_close(lsn_stream_t* s);
 int lsn_stream_span(const lsn_stream_cfg_t* cfg, const lsn_file_cell_t* cells, uint32_t n_cells, uint64_t pushed_samples, lsn_stream_span_t* out);
+/* lsn_stream_span describes the NOMINAL plan: a tracked stream (below) counts a cell's subframes by the positions its loop has decided, which leave the plan's by
+ * lsn_stream_track_status_t.position_drift. */
+
+/* ---- a stream that follows the sample clock: a PSS timing loop per cell ----
+ * Opt-in, per cell of an open stream, accepted only before the first sample is pushed.  A stream that does not ask for it runs exactly the launches described above.
+ * The resampler's position becomes piecewise linear in the output index.  The unit is a SEGMENT, one half frame (5 output subframes), anchored so that a segment
+ * starts at every output subframe whose TTI is a multiple of 5 (segment 0 may be shorter); segment h > 0 holds one PSS, in its first subframe.
+ *   position(m) = base_h + (m - m_h) step_h for the outputs of segment h;  base_(h+1) = base_h + n_h step_h in exact 128-bit integers: only the step changes, the
+ *   position never jumps, the FFT window never moves.
+ * The measurement taken in segment h decides the step of segment h + 2, whatever the pushes look like: no part of segment h + 2 is resampled before the measurement
+ * of segment h has come back (the host waits for that launch's event then, and nowhere else).  Segments 0 and 1 run at the opened rate times 1 + initial_ppm 1e-6.
+ * Every decision is a function of (input samples, configuration) only: the samples a Phy receives, its records and the loop's state do not depend on how the
+ * stream was cut into pushes, on the ring size or on block_subframes.  Resampling launches are per segment (or the part of one that fits the block buffer) and
+ * write into the Phy's block buffer at the segment's subframe offset; a block is still submitted once block_subframes subframes are in it.
+ *   detector  k_pss_timing: N the symbol size, d = max(1, N / 128), lags l_j = (j - 6) d, j = 0 .. 12, p = 13 N / 2 the index of the first useful sample of the PSS
+ *             symbol in the segment's first subframe, r the replica of lsn_clock_replica (unit energy, rotated by the cell's cfo_hz):
+ *               C_j = sum_a | sum_(k<N) x_a[p + l_j + k] conj r[k] |^2 / sum_a sum_(k<N) |x_a[p + l_j + k]|^2     (0 when the denominator is 0)
+ *             j* = first maximum; geometrically valid when 0 < j* < 12; frac = 0.5 (C[j*-1] - C[j*+1]) / (C[j*-1] - 2 C[j*] + C[j*+1]);
+ *             e = (j* - 6 + frac) d output samples, positive: the PSS arrived late.  Valid when geometrically valid and peak >= 0.25 mean(the last up to 8 valid
+ *             peaks); the first geometrically valid one is valid.  Invalid too: a segment without a PSS (a short segment 0), one whose first subframe reads
+ *             samples of a gap, a cell that is not enabled.
+ *   loop      valid: I += Ki e, c = Kp e + I;  invalid: c = I;  I and c clamped to +- lim = max_ppm 1e-6 seglen (seglen = 5 subframe lengths); anti-windup: a valid
+ *             step leaves I as it was when Kp e + clamp(I + Ki e) lies beyond +- lim on the side e pushes to (the correction is at its limit already);
+ *             step_(h+2) = step_nominal + (int128) nearbyint(ldexp(rate_in / rate_out, 64) * c / seglen), in doubles, one rounding per operation.
+ *             lost is set after lost_after consecutive invalid segments: the loop holds its rate and keeps measuring; the next valid measurement clears it.
+ * lsn_stream_track refuses with LSN_ERROR_INVALID_INPUTS, the stream unchanged and usable: after a push; gains not finite or not positive; max_ppm outside
+ * (0, 120]; |initial_ppm| > max_ppm or not finite; cfo_hz not finite; a ring shorter than block_input recomputed with every step widened by 1 + max_ppm 1e-6. */
+typedef struct {
+  uint32_t struct_size;      /* sizeof(lsn_stream_track_cfg_t); every other size is refused */
+  uint32_t lost_after;       /* 0 = 40 */
+  double   kp, ki;           /* 0 = 1/4, 1/32 */
+  double   max_ppm;          /* 0 = 100 */
+  float    cfo_hz[LSN_FILE_MAX_CELLS];        /* per cell: the replica is rotated by it (lsn_cell_search_t.cfo_hz) */
+  double   initial_ppm[LSN_FILE_MAX_CELLS];   /* per cell: the correction segments 0 and 1 run at, and the integrator's start */
+  uint32_t enable[LSN_FILE_MAX_CELLS];        /* per cell: 0 = this cell keeps the opened rate */
+} lsn_stream_track_cfg_t;
+typedef struct {
+  uint32_t struct_size;      /* in: sizeof(lsn_stream_track_status_t); every other size is refused */
+  uint32_t nof_cells;
+  uint64_t segments[LSN_FILE_MAX_CELLS];      /* segments decided */
+  uint64_t valid[LSN_FILE_MAX_CELLS], invalid[LSN_FILE_MAX_CELLS];   /* measurements that have come back */
+  uint32_t lost[LSN_FILE_MAX_CELLS];
+  double   last_error[LSN_FILE_MAX_CELLS];       /* e of the last valid measurement, output samples */
+  double   correction_ppm[LSN_FILE_MAX_CELLS];   /* c / seglen 1e6 of the segment decided last */
+  double   integrator_ppm[LSN_FILE_MAX_CELLS];
+  double   position_drift[LSN_FILE_MAX_CELLS];   /* position of the next output to resample minus the nominal plan's, input samples */
+} lsn_stream_track_status_t;
+int lsn_stream_track(lsn_stream_t* s, const lsn_stream_track_cfg_t* cfg);
+/* the measurements in flight are waited for first, so after a flush the answer is a function of the samples pushed */
+int lsn_stream_track_status(lsn_stream_t* s, lsn_stream_track_status_t* out);
+/* The loop without a GPU: one step on *state with the gains of cfg (its per-cell fields are not read) -> the new state and step - step_nominal as the two halves
+ * of a 128-bit two's complement integer.  seglen: output samples of a segment. */
+typedef struct {
+  double   integrator, correction;   /* I and c, output samples per segment */
+  uint32_t invalid_run, lost;
+} lsn_stream_track_state_t;
+int lsn_stream_track_step(const lsn_stream_track_cfg_t* cfg, double rate_in_hz, double rate_out_hz, uint32_t seglen, lsn_stream_track_state_t* state, double e, int valid,
+                          uint64_t* delta_hi, uint64_t* delta_lo);
+/* the observation of one window without a GPU: C[13] -> 1 and e, peak when geometrically valid, 0 (peak filled) when not */
+int lsn_pss_timing_error(const float* C, uint32_t d, double* e, double* peak);
+/* k_pss_timing without a Phy, the sibling of lsn_clock_track: per cell, blocks in the block-buffer layout [subframe][antenna][sflen] cf32 (host or device memory),
+ * a list of n_occ (subframe, p) pairs, the replica [N] cf32 (host) and d -> C [n_occ][13] (host).  All cells go into one launch when no cell has more than four
+ * occurrences (more: four per launch).  Refused: n_cells 0 or above LSN_FILE_MAX_CELLS, a struct_size the library does not know, N outside 128 .. 2048,
+ * d != max(1, N / 128), a subframe outside the blocks, a window [p - 6 d, p + 6 d + N) outside its subframe. */
+typedef struct {
+  uint32_t struct_size;      /* sizeof(lsn_pss_timing_cell_t) */
+  uint32_t N, d, sflen, nof_antennas, nof_subframes, n_occ, reserved;
+  const void* blocks;
+  const float* replica;
+  const uint32_t* occ;       /* [n_occ][2]: subframe, p */
+  float* C;                  /* out */
+} lsn_pss_timing_cell_t;
+int lsn_pss_timing(int device, int blocks_on_device, const lsn_pss_timing_cell_t* cells, uint32_t n_cells);
 
 /* ---- sharp channel filter in front of the resampler: a cell next to a much stronger carrier ----
  * The resampler's filter has the transition band [B, min(rate) - B]: a neighbour carrier inside it reaches the FFT's guard bins undamped and leaks into the

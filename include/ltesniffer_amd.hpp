@@ -285,6 +285,9 @@ public:
   int gap(uint64_t n_samples) { return lsn_stream_push(h, nullptr, n_samples); }
   int flush() { return lsn_stream_flush(h); }
   lsn_stream_status_t status() { lsn_stream_status_t s{}; lsn_stream_status(h, &s); return s; }
+  // the timing loop (before the first push): LSN_ERROR_INVALID_INPUTS when refused, the stream unchanged and usable
+  int track(lsn_stream_track_cfg_t cfg) { cfg.struct_size = sizeof(cfg); return lsn_stream_track(h, &cfg); }
+  lsn_stream_track_status_t track_status() { lsn_stream_track_status_t s{}; s.struct_size = sizeof(s); lsn_stream_track_status(h, &s); return s; }
   int close() { const int r = h ? lsn_stream_close(h) : LSN_SUCCESS; h = nullptr; return r; }
 private:
   lsn_stream_t* h = nullptr;

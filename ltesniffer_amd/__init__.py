@@ -44,7 +44,8 @@ EXPORTS = ["lsn_phy_create", "lsn_phy_destroy", "lsn_phy_set_cell", "lsn_phy_get
            "lsn_clock_plan", "lsn_clock_fit", "lsn_clock_replica", "lsn_clock_track", "lsn_clock_estimate", "lsn_file_clock_estimate",
            "lsn_carrier_scan_plan", "lsn_carrier_scan_decide", "lsn_carrier_scan", "lsn_file_carrier_scan", "lsn_carrier_channel", "lsn_carrier_channel_span",
            "lsn_phy_set_channel_filter", "lsn_channel_filter_design", "lsn_channel_filter", "lsn_channel_filter_span", "lsn_cells_stopbands",
-           "lsn_resample_cells_ring", "lsn_stream_open", "lsn_stream_push", "lsn_stream_flush", "lsn_stream_status", "lsn_stream_close", "lsn_stream_span"]
+           "lsn_resample_cells_ring", "lsn_stream_open", "lsn_stream_push", "lsn_stream_flush", "lsn_stream_status", "lsn_stream_close", "lsn_stream_span",
+           "lsn_stream_track", "lsn_stream_track_status", "lsn_stream_track_step", "lsn_pss_timing", "lsn_pss_timing_error"]
 
 RATES_3GPP, RATES_SRSRAN = 0, 1   # LSN_RATES_*: sampling mode of a Phy / of a cell search
 
@@ -133,6 +134,26 @@ class StreamCfg(C.Structure):   # lsn_stream_cfg_t
 class StreamStatus(C.Structure):   # lsn_stream_status_t
     _fields_ = [("samples_pushed", C.c_uint64), ("ring_samples", C.c_uint64), ("oldest_needed", C.c_int64), ("block_subframes", C.c_uint32), ("nof_cells", C.c_uint32),
                 ("failed", C.c_int), ("status", C.c_int * FILE_MAX_CELLS), ("subframes_submitted", C.c_uint64 * FILE_MAX_CELLS)]
+
+
+class StreamTrackCfg(C.Structure):   # lsn_stream_track_cfg_t
+    _fields_ = [("struct_size", C.c_uint32), ("lost_after", C.c_uint32), ("kp", C.c_double), ("ki", C.c_double), ("max_ppm", C.c_double),
+                ("cfo_hz", C.c_float * FILE_MAX_CELLS), ("initial_ppm", C.c_double * FILE_MAX_CELLS), ("enable", C.c_uint32 * FILE_MAX_CELLS)]
+
+
+class StreamTrackStatus(C.Structure):   # lsn_stream_track_status_t
+    _fields_ = [("struct_size", C.c_uint32), ("nof_cells", C.c_uint32), ("segments", C.c_uint64 * FILE_MAX_CELLS), ("valid", C.c_uint64 * FILE_MAX_CELLS),
+                ("invalid", C.c_uint64 * FILE_MAX_CELLS), ("lost", C.c_uint32 * FILE_MAX_CELLS), ("last_error", C.c_double * FILE_MAX_CELLS),
+                ("correction_ppm", C.c_double * FILE_MAX_CELLS), ("integrator_ppm", C.c_double * FILE_MAX_CELLS), ("position_drift", C.c_double * FILE_MAX_CELLS)]
+
+
+class StreamTrackState(C.Structure):   # lsn_stream_track_state_t
+    _fields_ = [("integrator", C.c_double), ("correction", C.c_double), ("invalid_run", C.c_uint32), ("lost", C.c_uint32)]
+
+
+class PssTimingCell(C.Structure):   # lsn_pss_timing_cell_t
+    _fields_ = [("struct_size", C.c_uint32), ("N", C.c_uint32), ("d", C.c_uint32), ("sflen", C.c_uint32), ("nof_antennas", C.c_uint32), ("nof_subframes", C.c_uint32),
+                ("n_occ", C.c_uint32), ("reserved", C.c_uint32), ("blocks", C.c_void_p), ("replica", C.c_void_p), ("occ", C.c_void_p), ("C", C.c_void_p)]
 
 
 class StreamSpan(C.Structure):   # lsn_stream_span_t
@@ -428,6 +449,12 @@ def lib():
         L.lsn_stream_status.argtypes = [C.c_void_p, C.POINTER(StreamStatus)]
         L.lsn_stream_close.argtypes = [C.c_void_p]
         L.lsn_stream_span.argtypes = [C.POINTER(StreamCfg), C.POINTER(FileCell), C.c_uint32, C.c_uint64, C.POINTER(StreamSpan)]
+        L.lsn_stream_track.argtypes = [C.c_void_p, C.POINTER(StreamTrackCfg)]
+        L.lsn_stream_track_status.argtypes = [C.c_void_p, C.POINTER(StreamTrackStatus)]
+        L.lsn_stream_track_step.argtypes = [C.POINTER(StreamTrackCfg), C.c_double, C.c_double, C.c_uint32, C.POINTER(StreamTrackState), C.c_double, C.c_int,
+                                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.lsn_pss_timing.argtypes = [C.c_int, C.c_int, C.POINTER(PssTimingCell), C.c_uint32]
+        L.lsn_pss_timing_error.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.lsn_phy_set_prach_config.argtypes = [C.c_void_p, C.POINTER(PrachCfg)]
         L.lsn_phy_prach_detect.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(PrachDet), C.c_uint32]
         L.lsn_phy_set_prach_sink.argtypes = [C.c_void_p, PRACH_SINK, C.c_void_p]
@@ -1223,6 +1250,71 @@ def stream_span(sample_rate, cells, pushed, nof_antennas=1, sample_format=FILE_C
                 subframes_submitted=[int(v) for v in sp.subframes_submitted[:n]], taps=[int(v) for v in sp.taps[:n]])
 
 
+def _track_cfg(n_cells, kp=0.0, ki=0.0, max_ppm=0.0, lost_after=0, cfo_hz=0.0, initial_ppm=0.0, enable=True):
+    cfg = StreamTrackCfg()
+    cfg.struct_size, cfg.lost_after, cfg.kp, cfg.ki, cfg.max_ppm = C.sizeof(StreamTrackCfg), int(lost_after), float(kp), float(ki), float(max_ppm)
+    for name, val, conv in (("cfo_hz", cfo_hz, float), ("initial_ppm", initial_ppm, float), ("enable", enable, lambda v: 1 if v else 0)):
+        vals = list(val) if isinstance(val, (list, tuple)) else [val] * n_cells
+        if len(vals) != n_cells:
+            raise ValueError("track: %s needs one value per cell" % name)
+        for i, v in enumerate(vals):
+            getattr(cfg, name)[i] = conv(v)
+    return cfg
+
+
+def stream_track_step(state, e, valid, rate_in, rate_out, seglen, kp=0.0, ki=0.0, max_ppm=0.0, lost_after=0):
+    """lsn_stream_track_step (needs no GPU): one step of the timing loop.  state: dict(integrator, correction, invalid_run, lost) -> (the new state, step -
+    step_nominal as a signed integer in units of 2^-64 input samples).  Raises ValueError when the library refuses the gains"""
+    cfg = _track_cfg(0, kp, ki, max_ppm, lost_after)
+    st = StreamTrackState(float(state["integrator"]), float(state["correction"]), int(state["invalid_run"]), int(state["lost"]))
+    hi, lo = C.c_uint64(), C.c_uint64()
+    rc = lib().lsn_stream_track_step(C.byref(cfg), float(rate_in), float(rate_out), int(seglen), C.byref(st), float(e), 1 if valid else 0, C.byref(hi), C.byref(lo))
+    if rc == LSN_ERROR_INVALID_INPUTS:
+        raise ValueError("stream_track_step: refused")
+    _check(rc, "lsn_stream_track_step")
+    delta = (hi.value << 64) | lo.value
+    if delta >> 127:
+        delta -= 1 << 128
+    return dict(integrator=float(st.integrator), correction=float(st.correction), invalid_run=int(st.invalid_run), lost=int(st.lost)), delta
+
+
+def pss_timing_error(Cv, d):
+    """lsn_pss_timing_error (needs no GPU): the 13 values of one window -> (geometrically valid, e in output samples, peak)"""
+    import numpy as np
+    Cv = np.ascontiguousarray(Cv, dtype=np.float32)
+    if Cv.shape != (13,):
+        raise ValueError("pss_timing_error: 13 values")
+    e, pk = C.c_double(), C.c_double()
+    rc = lib().lsn_pss_timing_error(Cv.ctypes.data, int(d), C.byref(e), C.byref(pk))
+    _check_n(rc, "lsn_pss_timing_error")
+    return bool(rc), float(e.value), float(pk.value)
+
+
+def pss_timing(cells, device=0):
+    """lsn_pss_timing: k_pss_timing without a Phy.  cells: a list of dict(blocks: complex64 [subframe][antenna][sflen], occ: [(subframe, p), ...], replica: complex64
+    [N], d) - all of them in one launch while no cell has more than four occurrences -> a list of float32 arrays [n_occ][13].  Raises ValueError when refused"""
+    import numpy as np
+    n = len(cells)
+    arr = (PssTimingCell * max(n, 1))()
+    keep, outs = [], []
+    for i, c in enumerate(cells):
+        x = np.ascontiguousarray(c["blocks"], dtype=np.complex64)
+        r = np.ascontiguousarray(c["replica"], dtype=np.complex64)
+        occ = np.ascontiguousarray(np.asarray(c["occ"], dtype=np.uint32).reshape(-1, 2))
+        if x.ndim != 3 or r.ndim != 1:
+            raise ValueError("pss_timing: blocks [subframe][antenna][sflen], replica [N]")
+        out = np.zeros((len(occ), 13), dtype=np.float32)
+        keep.append((x, r, occ))
+        outs.append(out)
+        arr[i] = PssTimingCell(C.sizeof(PssTimingCell), len(r), int(c["d"]), x.shape[2], x.shape[1], x.shape[0], len(occ), 0, x.ctypes.data, r.ctypes.data,
+                               occ.ctypes.data if len(occ) else None, out.ctypes.data if len(occ) else None)
+    rc = lib().lsn_pss_timing(int(device), 0, arr, n)
+    if rc == LSN_ERROR_INVALID_INPUTS:
+        raise ValueError("pss_timing: refused")
+    _check(rc, "lsn_pss_timing")
+    return outs
+
+
 class Stream:
     """lsn_stream_*: the cells of a live wideband stream that arrives in host buffers.  cells: a list of (phy, dict(...)) with the keys of process_file_cells
     (center_offset_hz, start_tti - not TTI_FROM_MIB -, offset_time / offset_time_frac: the start of the cell's subframe 0 counted from the first sample ever
@@ -1231,7 +1323,8 @@ class Stream:
     those of process_file_cells on a file of the same bytes, however the stream is cut into pushes.  Raises ValueError when the library refuses the stream
     (nothing is allocated, every Phy stays usable).  Close the stream before its Phys; a Phy that is closed first closes the stream."""
 
-    def __init__(self, sample_rate, cells, nof_antennas=None, sample_format=FILE_CF32, sample_scale=0.0, block_subframes=0, ring_samples=0, device=0):
+    def __init__(self, sample_rate, cells, nof_antennas=None, sample_format=FILE_CF32, sample_scale=0.0, block_subframes=0, ring_samples=0, device=0, track=None):
+        """track: None, or the keyword arguments of track() - the timing loop is set up before the first push.  A refused track closes the stream and raises"""
         self._h = None
         self._phys = [phy for phy, _ in cells]     # kept alive as long as the stream
         arr = (FileCell * max(len(cells), 1))()
@@ -1250,6 +1343,29 @@ class Stream:
         import weakref
         for phy in self._phys:
             phy._stream = weakref.ref(self)
+        if track is not None:
+            try:
+                self.track(**track)
+            except ValueError:
+                self.close()
+                raise
+
+    def track(self, kp=0.0, ki=0.0, max_ppm=0.0, lost_after=0, cfo_hz=0.0, initial_ppm=0.0, enable=True):
+        """lsn_stream_track: a PSS timing loop per cell follows the sample clock.  Only before the first push.  cfo_hz, initial_ppm, enable: one
+        value for every cell, or a list with one per cell; kp, ki, max_ppm, lost_after: 0 = the defaults (1/4, 1/32, 100, 40).  Raises ValueError when the
+        library refuses (the stream is unchanged and usable)"""
+        self._call(lib().lsn_stream_track(self._h, C.byref(_track_cfg(self.nof_cells, kp, ki, max_ppm, lost_after, cfo_hz, initial_ppm, enable))), "lsn_stream_track")
+
+    def track_status(self):
+        """lsn_stream_track_status -> dict of per-cell lists: segments, valid, invalid, lost, last_error (output samples), correction_ppm, integrator_ppm,
+        position_drift (input samples).  Behind a flush it is a function of the samples pushed"""
+        st = StreamTrackStatus()
+        st.struct_size = C.sizeof(StreamTrackStatus)
+        self._call(lib().lsn_stream_track_status(self._h, C.byref(st)), "lsn_stream_track_status")
+        n = int(st.nof_cells)
+        return dict(segments=[int(v) for v in st.segments[:n]], valid=[int(v) for v in st.valid[:n]], invalid=[int(v) for v in st.invalid[:n]],
+                    lost=[int(v) for v in st.lost[:n]], last_error=[float(v) for v in st.last_error[:n]], correction_ppm=[float(v) for v in st.correction_ppm[:n]],
+                    integrator_ppm=[float(v) for v in st.integrator_ppm[:n]], position_drift=[float(v) for v in st.position_drift[:n]])
 
     def _call(self, rc, what):
         if rc == LSN_ERROR_INVALID_INPUTS:

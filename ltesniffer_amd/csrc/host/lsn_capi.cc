@@ -671,6 +671,7 @@ static int stream_plans(const lsn_stream_cfg_t* cfg, const lsn_file_cell_t* cell
 struct lsn_stream {
   std::unique_ptr<lsn::StreamRing> ring;
   std::vector<lsn_phy*> phys;
+  double sample_rate_hz = 0.0;
 };
 
 int lsn_stream_span(const lsn_stream_cfg_t* cfg, const lsn_file_cell_t* cells, uint32_t n_cells, uint64_t pushed, lsn_stream_span_t* out)
@@ -719,6 +720,7 @@ int lsn_stream_open(const lsn_stream_cfg_t* cfg, lsn_file_cell_t* cells, uint32_
       specs[c].update_meta_period = cells[c].update_meta_period; specs[c].max_subframes = cells[c].max_subframes;
       s->phys.push_back(cells[c].phy);
     }
+    s->sample_rate_hz = cfg->sample_rate_hz;
     s->ring.reset(new lsn::StreamRing(cfg->device, cfg->nof_antennas, cfg->sample_format, cfg->sample_scale, blk, ring, std::move(specs)));
     const int rs = s->ring->setup();
     if (rs != LSN_SUCCESS) return rs;
@@ -752,6 +754,20 @@ int lsn_stream_status(lsn_stream_t* s, lsn_stream_status_t* out)
   out->nof_cells = (uint32_t)r.nofCells(); out->failed = r.failedCode();
   for (size_t c = 0; c < r.nofCells(); c++) { out->status[c] = r.cellStatus(c); out->subframes_submitted[c] = r.cellDone(c); }
   return LSN_SUCCESS;
+}
+
+int lsn_stream_track(lsn_stream_t* s, const lsn_stream_track_cfg_t* cfg)
+{
+  if (!s || !cfg || cfg->struct_size != sizeof(lsn_stream_track_cfg_t)) return LSN_ERROR_INVALID_INPUTS;
+  std::unique_lock<std::mutex> lk(s->ring->mtx);
+  return s->ring->track(*cfg, s->sample_rate_hz);
+}
+
+int lsn_stream_track_status(lsn_stream_t* s, lsn_stream_track_status_t* out)
+{
+  if (!s || !out) return LSN_ERROR_INVALID_INPUTS;
+  std::unique_lock<std::mutex> lk(s->ring->mtx);
+  return s->ring->trackStatus(out);
 }
 
 int lsn_stream_close(lsn_stream_t* s)

@@ -283,6 +283,7 @@ public:
   // lsn_file_process_cells: n cells (engines on one device, each with its cell set and fc.nof_antennas antennas) from one pass over the file; n = 1 is processFile[Rate]
   static int replayFile(const char* path, const lsn_file_cfg_t& fc, FileCellJob* jobs, uint32_t n);
   uint32_t symbolSz() const { return cd.N; }
+  uint32_t cellId() const { return cd.id; }
   uint32_t nofPrb() const { return cd.nof_prb; }
   uint32_t iqAntennas() const { return cd.iq_nant; }
   // the channel filter's intermediate (y1 of one block, cf32 [sample][antenna]): grows, never shrinks; kept like the block buffers

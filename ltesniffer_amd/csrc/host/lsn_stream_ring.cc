@@ -6,10 +6,15 @@
 // configuration, m) only (section 3.1b), so the Phys get the samples of the file replay of the same bytes however the stream was cut.
 // Two HIP streams: copies and memsets on one, launches on the other.  A launch waits for the copies queued so far; a piece that is written over slots an
 // unfinished launch may still read waits on the event recorded behind that launch, and on nothing else.  Product code: no CPU fallback.
+// A stream that asked for it (track()) follows the sample clock: runReadyTracked resamples segment by segment at the steps its timing loop
+// decides (lsn_track.h) and measures every segment's PSS with k_pss_timing; a stream that did not runs runReady exactly as before.
 #include "lsn_stream_ring.h"
 #include "lsn_resample_launch.h"
+#include "lsn_track_launch.h"
+#include "lsn_clock.h"
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 
 namespace lsn {
 
@@ -42,6 +47,9 @@ StreamRing::~StreamRing()
   for (auto& c : cells) {
     if (c.d_rot) (void)hipFree(c.d_rot);
     if (c.d_bank) (void)hipFree(c.d_bank);
+    if (c.d_rep) (void)hipFree(c.d_rep);
+    if (c.h_C) (void)hipHostFree(c.h_C);
+    for (auto& p : c.pending) if (p.ev) (void)hipEventDestroy(p.ev);
   }
   if (d_ring) (void)hipFree(d_ring);
   if (st_copy) (void)hipStreamDestroy(st_copy);
@@ -84,6 +92,15 @@ int StreamRing::setup()
 
 int64_t StreamRing::oldestNeeded() const
 {
+  if (tracking) {   // the first input sample of the next subframe to resample, at the position the loop has decided (the end of the last decided segment is one)
+    int64_t oldest = (int64_t)pushed;
+    for (const auto& c : cells) {
+      if (c.s.max_subframes && c.filled >= c.s.max_subframes) continue;
+      const int64_t lo = (int64_t)(uint64_t)(c.tk.position(c.filled) >> 64) - (int64_t)c.s.plan.taps / 2 + 1;
+      oldest = std::min(oldest, std::max<int64_t>(lo, 0));
+    }
+    return oldest;
+  }
   uint64_t done[kFileMaxCells];
   for (size_t c = 0; c < cells.size(); c++) done[c] = cells[c].done;
   return stream_oldest_needed(plans.data(), (uint32_t)plans.size(), done, pushed);
@@ -124,6 +141,7 @@ void StreamRing::writeRing(const uint8_t* src, uint64_t n)
 // every launch that is due: one k_resample_ring for the cells that have a block, then one submit per such cell in the order of the list
 int StreamRing::runReady(bool flush_all)
 {
+  if (tracking) return runReadyTracked(flush_all);
   for (;;) {
     if (failed != LSN_SUCCESS) return failed;
     uint32_t nsf[kFileMaxCells] = {};
@@ -181,6 +199,11 @@ int StreamRing::push(const void* iq, uint64_t n)
   const int r = guarded([&]() -> int {
     HIP_CHECK(hipSetDevice(device));
     const uint8_t* src = (const uint8_t*)iq;
+    if (tracking) {   // a gap is part of the input: a segment whose PSS subframe reads it has no measurement
+      const int64_t old = oldestNeeded();
+      gaps.erase(std::remove_if(gaps.begin(), gaps.end(), [old](const std::pair<int64_t, int64_t>& g) { return g.second <= old; }), gaps.end());
+      if (!src && n) gaps.emplace_back((int64_t)pushed, (int64_t)(pushed + n));
+    }
     while (n && failed == LSN_SUCCESS) {
       // a piece ends at the end of the ring, and in front of the slot of the oldest sample a cell still needs.  No cell has a block left to submit here, so the
       // cell that holds that sample waits for data inside its own block's span, which the ring holds (stream_ring_check): there is room
@@ -206,6 +229,7 @@ int StreamRing::flush()
   const int r = guarded([&]() -> int {
     HIP_CHECK(hipSetDevice(device));
     (void)runReady(true);
+    if (tracking) for (auto& c : cells) deliver(c, 0, true);
     for (auto& c : cells) {   // all are waited for, whatever one of them answered
       const int w = c.s.e->wait();
       if (c.rc == LSN_SUCCESS) c.rc = w;
@@ -215,6 +239,184 @@ int StreamRing::flush()
   });
   if (r != LSN_SUCCESS && failed == LSN_SUCCESS) failed = r;
   return r;
+}
+
+// ---- the timing loop (lsn_track.h) ----
+
+int StreamRing::track(const lsn_stream_track_cfg_t& tc, double rate_in)
+{
+  if (pushed || tracking || failed != LSN_SUCCESS) return LSN_ERROR_INVALID_INPUTS;
+  TrackCfg cfg;
+  const int r = track_cfg_resolve(tc.kp, tc.ki, tc.max_ppm, tc.lost_after, cfg);
+  if (r != LSN_SUCCESS) return r;
+  int64_t lo = 0, hi = 0;
+  for (size_t c = 0; c < cells.size(); c++) {
+    if (!std::isfinite(tc.cfo_hz[c]) || !std::isfinite(tc.initial_ppm[c]) || std::fabs(tc.initial_ppm[c]) > cfg.max_ppm) return LSN_ERROR_INVALID_INPUTS;
+    if (cells[c].s.e->symbolSz() < 128) return LSN_ERROR_INVALID_INPUTS;
+    // stream_block_input with every step widened by 1 + max_ppm 1e-6
+    const ResamplePlan& p = cells[c].s.plan;
+    const int64_t half = (int64_t)p.taps / 2;
+    const u128 last = p.start + (u128)((uint64_t)blk * cells[c].sflen - 1) * track_widened_step(p.step, cfg.max_ppm);
+    const int64_t l = (int64_t)(uint64_t)(p.start >> 64) - half + 1, h = (int64_t)(uint64_t)(last >> 64) + half + 1;
+    lo = c ? std::min(lo, l) : l;
+    hi = c ? std::max(hi, h) : h;
+  }
+  if ((uint64_t)(hi - lo) + 2 > ring_samples) return LSN_ERROR_INVALID_INPUTS;
+  return guarded([&]() -> int {
+    HIP_CHECK(hipSetDevice(device));
+    for (size_t c = 0; c < cells.size(); c++) {
+      Cell& q = cells[c];
+      const uint32_t N = q.s.e->symbolSz();
+      if (!q.d_rep) HIP_CHECK(hipMalloc((void**)&q.d_rep, (size_t)N * sizeof(cf32)));
+      if (!q.h_C) HIP_CHECK(hipHostMalloc((void**)&q.h_C, TRACK_SLOTS * kTrackLags * sizeof(float), hipHostMallocCoherent | hipHostMallocMapped));
+      std::vector<double> pd(2 * (size_t)N);
+      pss_replica_d(q.s.e->cellId() % 3, N, (double)tc.cfo_hz[c], pd.data());   // lsn_clock_replica's
+      std::vector<cf32> rep(N);
+      for (uint32_t k = 0; k < N; k++) rep[k] = {(float)pd[2 * k], (float)pd[2 * k + 1]};
+      HIP_CHECK(hipMemcpy(q.d_rep, rep.data(), (size_t)N * sizeof(cf32), hipMemcpyHostToDevice));
+    }
+    for (size_t c = 0; c < cells.size(); c++) {
+      Cell& q = cells[c];
+      q.tk.init(&q.s.plan, q.sflen, q.s.e->symbolSz(), q.s.start_tti, q.s.max_subframes, rate_in, cfg, tc.enable[c] != 0, tc.initial_ppm[c]);
+      q.filled = 0;
+    }
+    tracking = true;
+    return LSN_SUCCESS;
+  });
+}
+
+bool StreamRing::inGap(int64_t lo, int64_t hi) const
+{
+  for (const auto& g : gaps) if (g.first < hi && lo < g.second) return true;
+  return false;
+}
+
+void StreamRing::deliver(Cell& q, uint64_t upto_h, bool all)
+{
+  while (!q.pending.empty() && (all || q.pending.front().h <= upto_h)) {
+    const Cell::Pending p = q.pending.front();
+    q.pending.pop_front();
+    if (p.ev) {
+      const hipError_t e = hipEventSynchronize(p.ev);
+      ev_free.push_back(p.ev);
+      HIP_CHECK(e);
+      q.tk.measured(q.h_C + (size_t)p.slot * kTrackLags);
+    } else {
+      q.tk.measured(nullptr);
+    }
+  }
+}
+
+// runReady of a tracked stream: every cell's block buffer fills segment by segment (or by the part of one that fits the buffer), each piece at the step its segment
+// was entered with; the piece that holds a segment's first subframe is followed by the cell's window of k_pss_timing on the same stream.  One k_resample_ring launch
+// carries the pieces of all cells that are due.  A buffer is submitted when blk subframes are in it (fewer: a flush, or the last ones in front of max_subframes).
+int StreamRing::runReadyTracked(bool flush_all)
+{
+  for (;;) {
+    if (failed != LSN_SUCCESS) return failed;
+    LsnResampleCell k[kFileMaxCells];
+    uint32_t piece[kFileMaxCells] = {};
+    int64_t in_lo = 0, in_hi = 0;
+    bool any = false;
+    for (size_t c = 0; c < cells.size(); c++) {
+      Cell& q = cells[c];
+      TrackCell& t = q.tk;
+      k[c] = LsnResampleCell();
+      if (q.s.max_subframes && q.filled >= q.s.max_subframes) continue;   // run out
+      if (!t.entered || q.filled == t.segEnd()) {   // the next segment: the measurement of the segment two in front of it comes back first
+        if (t.needsMeasurement()) deliver(q, t.h - 1, false);
+        t.enter();
+      }
+      const uint64_t end = std::min<uint64_t>(t.segEnd(), q.done + blk);
+      const uint64_t upto = std::min<uint64_t>(t.completeInSegment(pushed), end);
+      if (upto <= q.filled || (upto < end && !flush_all)) continue;
+      piece[c] = (uint32_t)(upto - q.filled);
+      const int si = (int)(q.launches % (uint64_t)nslot);
+      if (q.filled == q.done && q.mark[si]) q.s.e->waitIqConsumed(q.mark[si]);   // the block this buffer carried last has been through stage A
+      const u128 base = t.position(q.filled);
+      k[c].base_hi = (uint64_t)(base >> 64); k[c].base_lo = (uint64_t)base; k[c].d_lo = (uint64_t)t.step; k[c].d_hi = (uint32_t)(t.step >> 64);
+      k[c].taps = q.s.plan.taps; k[c].span = t.span; k[c].sflen = q.sflen; k[c].sf_off = (uint32_t)(q.filled - q.done) * q.sflen; k[c].bank = q.d_bank; k[c].w = q.s.plan.tune;
+      k[c].nco = q.d_nco; k[c].rot = q.d_rot; k[c].out = q.s.e->fileIqBlock(si); k[c].n_out = (uint64_t)piece[c] * q.sflen;
+      int64_t lo, hi;
+      t.inputSpan(q.filled, upto, lo, hi);
+      in_lo = any ? std::min(in_lo, lo) : lo;
+      in_hi = any ? std::max(in_hi, hi) : hi;
+      any = true;
+    }
+    if (any) {
+      in_lo = std::max<int64_t>(in_lo, 0);
+      if (in_hi > (int64_t)pushed || (uint64_t)(in_hi - in_lo) > ring_samples || (int64_t)pushed - in_lo > (int64_t)ring_samples)
+        throw std::runtime_error("stream: a segment's input is not in the ring");
+      HIP_CHECK(hipEventRecord(ev_copy, st_copy));
+      HIP_CHECK(hipStreamWaitEvent(st_run, ev_copy, 0));
+      lsn_launch_resample_ring(d_ring, ring_samples, fmt, sfm.scale, in_lo, (uint64_t)(in_hi - in_lo), nant, k, (uint32_t)cells.size(), st_run);
+      Launch l;
+      l.ev = takeEvent(); l.lo = in_lo;
+      HIP_CHECK(hipEventRecord(l.ev, st_run));
+      inflight.push_back(l);
+      // the windows of the segments that began in this launch
+      LsnTimingCell tm[kFileMaxCells];
+      bool timing = false;
+      for (size_t c = 0; c < cells.size(); c++) {
+        Cell& q = cells[c];
+        TrackCell& t = q.tk;
+        tm[c] = LsnTimingCell();
+        if (!piece[c] || q.filled != t.sf0) continue;
+        int64_t lo, hi;
+        t.inputSpan(t.sf0, t.sf0 + 1, lo, hi);
+        Cell::Pending p = {t.h, nullptr, (uint32_t)(t.h % TRACK_SLOTS)};
+        if (t.enabled && t.hasPss() && !inGap(lo, hi)) {
+          tm[c].x = k[c].out; tm[c].rep = q.d_rep; tm[c].C = q.h_C + (size_t)p.slot * kTrackLags; tm[c].N = t.N; tm[c].d = track_lag_spacing(t.N); tm[c].sflen = q.sflen; tm[c].nant = nant;
+          tm[c].n_occ = 1; tm[c].sf[0] = (uint32_t)(q.filled - q.done); tm[c].p[0] = track_pss_index(t.N);
+          p.ev = takeEvent();
+          timing = true;
+        }
+        q.pending.push_back(p);
+      }
+      if (timing) {
+        lsn_launch_pss_timing(tm, (uint32_t)cells.size(), st_run);
+        for (size_t c = 0; c < cells.size(); c++)
+          if (tm[c].n_occ) HIP_CHECK(hipEventRecord(cells[c].pending.back().ev, st_run));
+      }
+      for (size_t c = 0; c < cells.size(); c++) cells[c].filled += piece[c];
+    }
+    bool submitted = false;
+    for (size_t c = 0; c < cells.size() && failed == LSN_SUCCESS; c++) {
+      Cell& q = cells[c];
+      const uint32_t n = (uint32_t)(q.filled - q.done);
+      if (!n || !(n == blk || (!any && flush_all) || (q.s.max_subframes && q.filled == q.s.max_subframes))) continue;
+      const int si = (int)(q.launches % (uint64_t)nslot);
+      q.rc = q.s.e->submit(q.s.e->fileIqBlock(si), n, (uint32_t)((q.s.start_tti + q.done) % 10240u), q.s.update_meta_period, st_run);
+      q.mark[si] = q.s.e->submitMark();
+      q.launches++;
+      q.done += n;
+      submitted = true;
+      if (q.rc != LSN_SUCCESS) failed = q.rc;
+    }
+    if (!any && !submitted) return LSN_SUCCESS;
+  }
+}
+
+int StreamRing::trackStatus(lsn_stream_track_status_t* out)
+{
+  if (!out || out->struct_size != sizeof(lsn_stream_track_status_t) || !tracking) return LSN_ERROR_INVALID_INPUTS;
+  return guarded([&]() -> int {
+    HIP_CHECK(hipSetDevice(device));
+    memset(out, 0, sizeof(*out));
+    out->struct_size = sizeof(*out);
+    out->nof_cells = (uint32_t)cells.size();
+    for (size_t c = 0; c < cells.size(); c++) {
+      Cell& q = cells[c];
+      deliver(q, 0, true);
+      const TrackCell& t = q.tk;
+      const double seglen = (double)(kTrackSegSubframes * q.sflen);
+      out->segments[c] = t.entered ? t.h + 1 : 0;
+      out->valid[c] = t.nvalid; out->invalid[c] = t.ninvalid; out->lost[c] = t.loop.lost; out->last_error[c] = t.last_e;
+      out->correction_ppm[c] = t.loop.corr / seglen * 1e6; out->integrator_ppm[c] = t.loop.integ / seglen * 1e6;
+      out->position_drift[c] = t.positionDrift(q.filled);
+    }
+    return LSN_SUCCESS;
+  });
 }
 
 }  // namespace lsn

@@ -1,8 +1,11 @@
 // lsn_stream_ring.h - the object behind lsn_stream_*: the raw input of a live stream in ONE device ring, the cells' Phys fed out of it by k_resample_ring
 // (DESIGN.md section 3.1g).  The counting is lsn_stream.h's; this is the part that speaks to the HIP runtime and to the engines.
+// A tracked stream (track(), section 3.1h) counts by the segments of lsn_track.h instead and measures every segment's PSS with k_pss_timing.
 #pragma once
 #include "lsn_engine.h"
 #include "lsn_stream.h"
+#include "lsn_track.h"
+#include <deque>
 #include <memory>
 #include <mutex>
 #include <vector>
@@ -24,6 +27,9 @@ public:
   int setup();                                  // ring, streams, block buffers, banks: every allocation of the stream's life
   int push(const void* iq, uint64_t n);         // iq null: a gap of n zero samples
   int flush();
+  // the timing loop (lsn_stream_track): accepted before the first sample only; a refusal leaves the stream as it was
+  int track(const lsn_stream_track_cfg_t& cfg, double rate_in /* the stream's sample rate */);
+  int trackStatus(lsn_stream_track_status_t* out);
   uint64_t pushedSamples() const { return pushed; }
   uint64_t ringSamples() const { return ring_samples; }
   uint32_t blockSubframes() const { return blk; }
@@ -46,10 +52,21 @@ private:
     const cf32* d_nco = nullptr;
     uint64_t launches = 0;               // block buffer of launch k: slot k mod nslot ...
     uint64_t mark[NSLOT_MAX] = {};       // ... free again when the engine has consumed the chunks up to this mark (0: never used)
+    // a tracked stream (runReadyTracked): the block buffer fills segment by segment
+    TrackCell tk;
+    uint64_t filled = 0;                 // subframes resampled into block buffers, done <= filled <= done + blk
+    cf32* d_rep = nullptr;               // the PSS replica, [N]
+    float* h_C = nullptr;                // pinned, [TRACK_SLOTS][13]: k_pss_timing writes, the host reads behind the event
+    struct Pending { uint64_t h; hipEvent_t ev; uint32_t slot; };   // the measurement of segment h: ev null = none could be taken
+    std::deque<Pending> pending;
   };
+  static constexpr uint32_t TRACK_SLOTS = 4;   // at most kTrackDelay measurements of a cell are in flight
   struct Launch { hipEvent_t ev; int64_t lo; };   // recorded behind a k_resample_ring launch that read the recording from sample lo on
   void writeRing(const uint8_t* src, uint64_t n);
   int runReady(bool flush_all);
+  int runReadyTracked(bool flush_all);
+  void deliver(Cell& q, uint64_t upto_h, bool all);   // the measurements of segments <= upto_h (all: every one in flight) go to the loop; waits for their events
+  bool inGap(int64_t lo, int64_t hi) const;
   hipEvent_t takeEvent();
   const int device;
   const uint32_t nant, fmt;
@@ -66,6 +83,8 @@ private:
   std::vector<Launch> inflight;
   std::vector<hipEvent_t> ev_free;
   uint64_t pushed = 0;
+  bool tracking = false;
+  std::vector<std::pair<int64_t, int64_t>> gaps;   // tracked: the gaps [lo, hi) a cell may still read
   int failed = LSN_SUCCESS;              // the first engine's failure: nothing more is submitted, every later call returns it
 };
 

@@ -1,0 +1,197 @@
+// lsn_track.cc - the timing loop of a pushed stream (lsn_track.h).  HIP-free host arithmetic, as lsn_stream.cc: it runs - and is tested
+// (tests/test_track_model.py, written from the definition in include/ltesniffer_amd.h, not from this file) - on a machine with no GPU.  The unit is compiled with
+// -ffp-contract=off like the rest of the library: every double expression below is one rounding per operation, in the order written.
+#include "../../../include/ltesniffer_amd.h"
+#include "lsn_track.h"
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <stdexcept>
+
+namespace lsn {
+
+int track_cfg_resolve(double kp, double ki, double max_ppm, uint32_t lost_after, TrackCfg& out)
+{
+  TrackCfg c;
+  if (kp != 0.0) c.kp = kp;
+  if (ki != 0.0) c.ki = ki;
+  if (max_ppm != 0.0) c.max_ppm = max_ppm;
+  if (lost_after) c.lost_after = lost_after;
+  if (!std::isfinite(c.kp) || !std::isfinite(c.ki) || !(c.kp > 0.0) || !(c.ki > 0.0) || !(c.max_ppm > 0.0 && c.max_ppm <= 120.0)) return LSN_ERROR_INVALID_INPUTS;
+  out = c;
+  return LSN_SUCCESS;
+}
+
+__int128 track_delta(double rate_in, double rate_out, uint32_t seglen, double c)
+{
+  const double scale = std::ldexp(rate_in / rate_out, 64);
+  const double v = scale * c;
+  return (__int128)std::nearbyint(v / (double)seglen);
+}
+
+__int128 track_step(const TrackCfg& cfg, double rate_in, double rate_out, uint32_t seglen, TrackLoop& s, double e, bool valid)
+{
+  const double lim = cfg.max_ppm * 1e-6 * (double)seglen;
+  auto clamp = [lim](double v) { return v > lim ? lim : (v < -lim ? -lim : v); };
+  if (valid) {
+    const double ie = cfg.ki * e, pe = cfg.kp * e;
+    const double in = clamp(s.integ + ie);
+    const double u = pe + in;
+    // anti-windup: while the correction sits at its limit and e pushes it further out, the integrator keeps its value - the error a limited correction cannot
+    // remove yet must not be integrated, or it comes back as overshoot once the limit lets go
+    if (!((u > lim && e > 0.0) || (u < -lim && e < 0.0))) s.integ = in;
+    s.corr = clamp(pe + s.integ);
+    s.invalid_run = 0;
+    s.lost = 0;
+  } else {
+    s.corr = s.integ;
+    if (s.invalid_run < 0xFFFFFFFFu) s.invalid_run++;
+    if (s.invalid_run >= cfg.lost_after) s.lost = 1;
+  }
+  return track_delta(rate_in, rate_out, seglen, s.corr);
+}
+
+bool track_observe(const float* C, uint32_t d, double& e, double& peak)
+{
+  uint32_t b = 0;
+  for (uint32_t j = 1; j < kTrackLags; j++) if (C[j] > C[b]) b = j;
+  e = 0.0;
+  peak = (double)C[b];
+  if (b == 0 || b + 1 >= kTrackLags) return false;
+  const double cm = (double)C[b - 1], c0 = (double)C[b], cp = (double)C[b + 1], den = (cm - 2.0 * c0) + cp;
+  if (!(den < 0.0)) return false;
+  const double frac = 0.5 * (cm - cp) / den;
+  e = (((double)b - 6.0) + frac) * (double)d;
+  return true;
+}
+
+bool TrackPeaks::accept(double peak)
+{
+  if (n) {
+    double sum = 0.0;
+    for (uint32_t i = 0; i < n; i++) sum = sum + hist[(at + 8 - n + i) % 8];   // oldest first
+    if (!(peak >= 0.25 * (sum / (double)n))) return false;
+  }
+  hist[at] = peak;
+  at = (at + 1) % 8;
+  if (n < 8) n++;
+  return true;
+}
+
+u128 track_widened_step(u128 step, double max_ppm)
+{
+  // step (1 + max_ppm 1e-6), rounded up: the product of the top 64 bits of a step below 2^67 with a factor in 2^-32 units is exact enough and errs upwards
+  const uint64_t f = (uint64_t)std::ceil(max_ppm * 1e-6 * 4294967296.0) + 1;   // units of 2^-32
+  return step + (((step >> 32) + 1) * f);
+}
+
+void TrackCell::init(const ResamplePlan* plan, uint32_t sflen_, uint32_t N_, uint32_t start_tti, uint64_t max_sf, double r_in, const TrackCfg& c, bool enable, double initial_ppm)
+{
+  rs = plan; sflen = sflen_; N = N_; max_subframes = max_sf; rate_in = r_in; rate_out = 15000.0 * (double)N_; cfg = c; enabled = enable;
+  const uint32_t ph = start_tti % kTrackSegSubframes;
+  first_nsf = ph ? kTrackSegSubframes - ph : kTrackSegSubframes;
+  first_has_pss = ph == 0;
+  loop = TrackLoop();
+  if (enabled) loop.integ = loop.corr = initial_ppm * 1e-6 * (double)(kTrackSegSubframes * sflen);
+  peaks = TrackPeaks();
+  entered = false; h = 0; nq = 0; nvalid = ninvalid = 0; last_e = 0.0;
+}
+
+void TrackCell::enter()
+{
+  const uint32_t seglen = kTrackSegSubframes * sflen;
+  const u128 b = endBase();
+  const uint64_t s0 = segEnd();
+  __int128 delta;
+  if (needsMeasurement()) {
+    if (!nq) throw std::runtime_error("track: a segment entered before its measurement came back");
+    const Meas m = q[0];
+    q[0] = q[1];
+    nq--;
+    delta = enabled ? track_step(cfg, rate_in, rate_out, seglen, loop, m.e, m.valid) : 0;
+  } else {
+    delta = enabled ? track_delta(rate_in, rate_out, seglen, loop.corr) : 0;   // segments 0 and 1: the opened rate times 1 + initial_ppm 1e-6
+  }
+  h = entered ? h + 1 : 0;
+  entered = true;
+  sf0 = s0;
+  nsf = h ? kTrackSegSubframes : first_nsf;
+  if (max_subframes && sf0 + nsf > max_subframes) nsf = sf0 < max_subframes ? (uint32_t)(max_subframes - sf0) : 0;
+  base = b;
+  step = (u128)((__int128)rs->step + delta);
+  span = (uint32_t)(((u128)512 * step) >> 64) + rs->taps + 2;   // ResamplePlan::init's rule (512 = LSN_RS_RUN, outputs of one run) at this segment's step
+  if (span < rs->span) span = rs->span;
+}
+
+void TrackCell::measured(const float* C)
+{
+  Meas m = {false, 0.0};
+  if (C && enabled) {
+    double e, peak;
+    if (track_observe(C, track_lag_spacing(N), e, peak) && peaks.accept(peak)) { m.valid = true; m.e = e; last_e = e; }
+  }
+  if (m.valid) nvalid++; else ninvalid++;
+  if (nq >= kTrackDelay) throw std::runtime_error("track: more measurements than the loop's delay");
+  q[nq++] = m;
+}
+
+uint64_t TrackCell::completeInSegment(uint64_t pushed) const
+{
+  if (!entered || !nsf) return segEnd();
+  const uint64_t half = rs->taps / 2;
+  if (pushed <= half) return sf0;
+  const u128 lim = (u128)(pushed - half) << 64;   // positions below lim read no sample at or behind `pushed` (ResamplePlan::outputsInside)
+  if (base >= lim) return sf0;
+  const u128 n = (lim - 1 - base) / step + 1;
+  const u128 sf = n / sflen;
+  return sf0 + (sf >= nsf ? nsf : (uint64_t)sf);
+}
+
+void TrackCell::inputSpan(uint64_t sf_lo, uint64_t sf_hi, int64_t& lo, int64_t& hi) const
+{
+  const int64_t half = (int64_t)rs->taps / 2;
+  const u128 first = position(sf_lo), last = sf_hi > sf_lo ? position(sf_hi) - step : first;
+  lo = (int64_t)(uint64_t)(first >> 64) - half + 1;
+  hi = (int64_t)(uint64_t)(last >> 64) + half + 1;
+}
+
+double TrackCell::positionDrift(uint64_t next_sf) const
+{
+  const u128 real = position(next_sf), nominal = rs->position(next_sf * sflen);
+  const __int128 diff = (__int128)(real - nominal);
+  return std::ldexp((double)diff, -64);
+}
+
+}  // namespace lsn
+
+extern "C" {
+
+static int track_cfg_of(const lsn_stream_track_cfg_t* cfg, lsn::TrackCfg& out)
+{
+  if (!cfg || cfg->struct_size != sizeof(lsn_stream_track_cfg_t)) return LSN_ERROR_INVALID_INPUTS;
+  return lsn::track_cfg_resolve(cfg->kp, cfg->ki, cfg->max_ppm, cfg->lost_after, out);
+}
+
+int lsn_stream_track_step(const lsn_stream_track_cfg_t* cfg, double rate_in_hz, double rate_out_hz, uint32_t seglen, lsn_stream_track_state_t* state, double e, int valid,
+                          uint64_t* delta_hi, uint64_t* delta_lo)
+{
+  lsn::TrackCfg c;
+  const int r = track_cfg_of(cfg, c);
+  if (r != LSN_SUCCESS) return r;
+  if (!state || !delta_hi || !delta_lo || !seglen || !(rate_in_hz > 0.0) || !(rate_out_hz > 0.0) || !std::isfinite(rate_in_hz / rate_out_hz) || !std::isfinite(e)) return LSN_ERROR_INVALID_INPUTS;
+  lsn::TrackLoop s;
+  s.integ = state->integrator; s.corr = state->correction; s.invalid_run = state->invalid_run; s.lost = state->lost;
+  const __int128 d = lsn::track_step(c, rate_in_hz, rate_out_hz, seglen, s, e, valid != 0);
+  state->integrator = s.integ; state->correction = s.corr; state->invalid_run = s.invalid_run; state->lost = s.lost;
+  *delta_hi = (uint64_t)((unsigned __int128)d >> 64);
+  *delta_lo = (uint64_t)(unsigned __int128)d;
+  return LSN_SUCCESS;
+}
+
+int lsn_pss_timing_error(const float* C, uint32_t d, double* e, double* peak)
+{
+  if (!C || !d || !e || !peak) return LSN_ERROR_INVALID_INPUTS;
+  return lsn::track_observe(C, d, *e, *peak) ? 1 : 0;
+}
+
+}  // extern "C"

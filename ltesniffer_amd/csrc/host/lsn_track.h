@@ -1,0 +1,97 @@
+// lsn_track.h - the timing loop of a pushed stream (lsn_stream_track): the segments that make a cell's resampler position piecewise linear
+// in the output index, the observation taken from the 13 values of k_pss_timing, and the proportional-integral loop that turns it into the step of a later segment.
+// Plain host arithmetic in doubles and 128-bit integers, no HIP header (like lsn_stream.h): it runs - and is tested (tests/test_track_model.py) - on a machine with
+// no GPU.  Every decision here is a function of (input samples, configuration) only; nothing depends on when a push arrived.
+#pragma once
+#include "lsn_resample.h"
+
+namespace lsn {
+
+static constexpr uint32_t kTrackLags = 13;        // l_j = (j - 6) d
+static constexpr uint32_t kTrackSegSubframes = 5; // one half frame: a PSS in the first subframe of every segment behind the first
+static constexpr uint32_t kTrackDelay = 2;        // the measurement of segment h decides the step of segment h + 2
+
+inline uint32_t track_lag_spacing(uint32_t N) { return N / 128 ? N / 128 : 1; }
+// index, inside a subframe 0 / 5, of the first useful sample of the PSS symbol: symbol 6 of slot 0 with the normal prefix, symbol 5 with the extended one - 13 N / 2
+// either way (160 + 6 144 = 1024 = 2048 / 2 at N = 2048; 6 512 / 4 + 5 at the extended prefix)
+inline uint32_t track_pss_index(uint32_t N) { return 13 * N / 2; }
+
+struct TrackCfg {   // defaults resolved
+  double kp = 0.25, ki = 1.0 / 32.0, max_ppm = 100.0;
+  uint32_t lost_after = 40;
+};
+
+struct TrackLoop {
+  double integ = 0.0;   // I, output samples per segment
+  double corr = 0.0;    // c, output samples to recover per segment: what the step in force was formed from
+  uint32_t invalid_run = 0, lost = 0;
+};
+
+// one step of the loop, in this order of operations (the unit is compiled without fused contraction):
+//   valid:   I' = clamp(I + Ki e); I = I' unless Kp e + I' lies beyond the limit on the side e pushes to; c = clamp(Kp e + I)          invalid:  c = I
+//   clamp to +- lim = max_ppm 1e-6 seglen;  delta = (int128) nearbyint(ldexp(rate_in / rate_out, 64) * c / seglen)
+// -> delta: step = step_nom + delta
+__int128 track_step(const TrackCfg& cfg, double rate_in, double rate_out, uint32_t seglen, TrackLoop& s, double e, bool valid);
+// the step delta of a correction c alone (the loop's last line)
+__int128 track_delta(double rate_in, double rate_out, uint32_t seglen, double c);
+
+// the observation of one window: j* = first maximum; geometrically valid when 0 < j* < 12 and the parabola through the three values opens downwards;
+// e = (j* - 6 + 0.5 (C[j*-1] - C[j*+1]) / (C[j*-1] - 2 C[j*] + C[j*+1])) d, peak = C[j*]
+bool track_observe(const float* C, uint32_t d, double& e, double& peak);
+
+// peak >= 0.25 mean(the last up to 8 valid peaks); the first one is valid.  A valid peak joins the history
+struct TrackPeaks {
+  double hist[8] = {};
+  uint32_t n = 0, at = 0;
+  bool accept(double peak);
+};
+
+// One cell's segments.  Segment h holds output subframes [sf0_h, sf0_h + n_h); position(m) = base_h + (m - sf0_h sflen) step_h, base_(h+1) = base_h + n_h sflen step_h.
+// Only the segment that holds the next subframe to resample is kept: a segment is entered when the one in front of it is complete, with the measurement of the
+// segment two in front of it (enter()).
+struct TrackCell {
+  const ResamplePlan* rs = nullptr;
+  uint32_t sflen = 0, N = 0;
+  uint64_t max_subframes = 0;
+  double rate_in = 0.0, rate_out = 0.0;
+  bool enabled = false;
+  uint32_t first_nsf = kTrackSegSubframes;   // subframes of segment 0: up to the first TTI that is a multiple of 5
+  bool first_has_pss = true;
+  TrackCfg cfg;
+  TrackLoop loop;
+  TrackPeaks peaks;
+  // the current segment
+  uint64_t h = 0;            // its index; valid once entered
+  bool entered = false;
+  uint64_t sf0 = 0; uint32_t nsf = 0;
+  u128 base = 0, step = 0;
+  uint32_t span = 0;         // samples one run of the kernel stages at this step
+  // measurements: those of segments h - 2 and h - 1 wait in q[] until their turn
+  struct Meas { bool valid; double e; };
+  Meas q[kTrackDelay] = {};
+  uint32_t nq = 0;
+  uint64_t nvalid = 0, ninvalid = 0;
+  double last_e = 0.0;
+
+  void init(const ResamplePlan* plan, uint32_t sflen_, uint32_t N_, uint32_t start_tti, uint64_t max_sf, double r_in, const TrackCfg& c, bool enable, double initial_ppm);
+  uint64_t segEnd() const { return entered ? sf0 + nsf : 0; }       // first subframe behind the current segment (0 before segment 0 is entered)
+  bool hasPss() const { return h ? true : first_has_pss; }
+  u128 endBase() const { return entered ? base + (u128)nsf * sflen * step : rs->start; }
+  u128 position(uint64_t sf) const { return entered ? base + (u128)(sf - sf0) * sflen * step : rs->start; }   // sf inside the current segment, or its end
+  // the next segment begins at subframe segEnd().  needs(): it takes a measurement out of q first (segments 2 ...)
+  bool needsMeasurement() const { return entered && h + 1 >= kTrackDelay; }
+  void enter();
+  // the measurement of the current segment, taken from its first subframe: C null = none could be taken (no PSS, a gap, the cell not enabled)
+  void measured(const float* C);
+  // subframes [.., n) of the cell that are complete once `pushed` samples have arrived, counted up to the end of the current segment
+  uint64_t completeInSegment(uint64_t pushed) const;
+  void inputSpan(uint64_t sf_lo, uint64_t sf_hi, int64_t& lo, int64_t& hi) const;   // subframes [sf_lo, sf_hi) of the current segment
+  double positionDrift(uint64_t next_sf) const;   // real minus nominal position of the first output of subframe next_sf, input samples
+};
+
+// LSN_SUCCESS and the resolved configuration, or LSN_ERROR_INVALID_INPUTS: gains not finite or not positive, max_ppm outside (0, 120]
+int track_cfg_resolve(double kp, double ki, double max_ppm, uint32_t lost_after, TrackCfg& out);
+// the plan's step widened by 1 + max_ppm 1e-6, rounded up: the fastest a tracked cell moves through the ring
+u128 track_widened_step(u128 step, double max_ppm);
+
+}  // namespace lsn
