@@ -180,12 +180,6 @@ int slices_of(const lsn_clock_obs_t* w, uint32_t n, uint32_t N, uint64_t nof_sam
   return LSN_SUCCESS;
 }
 
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  template <typename T> T* alloc(size_t n) { HIP_CHECK(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T))); return (T*)p; }
-};
-
 // device, stream and the replica of one estimate; correlate() is one launch of k_pss_track
 struct Tracker {
   const uint32_t N;
@@ -198,8 +192,7 @@ struct Tracker {
 
   int open(int device, const lsn_clock_cfg_t& cfg)
   {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return LSN_ERROR_NO_DEVICE;
+    if (!have_device(device)) return LSN_ERROR_NO_DEVICE;
     HIP_CHECK(hipSetDevice(device));
     HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     std::vector<cf32> rep(N);
@@ -454,11 +447,9 @@ int lsn_file_clock_estimate(int device, const char* path, const lsn_file_cfg_t* 
     Tracker T(g.N);
     const int ro = T.open(device, *cfg);
     if (ro != LSN_SUCCESS) return ro;
-    float* d_bank = nullptr;
-    const cf32* d_nco = nullptr;
-    struct BankGuard { float*& p; ~BankGuard() { if (p) (void)hipFree(p); } } bg{d_bank};
+    ResampleTables tb;
     if (rate) {
-      plan.upload(d_bank, d_nco, T.st);
+      tb.upload(plan, T.st);
       HIP_CHECK(hipStreamSynchronize(T.st));
     }
     std::vector<uint8_t> tmp, raw;
@@ -503,9 +494,7 @@ int lsn_file_clock_estimate(int device, const char* path, const lsn_file_cfg_t* 
         size_t o = 0;
         for (uint32_t i = 0; i < n; i++) {
           const uint64_t len = (uint64_t)tab[i].nlag + g.N - 1;
-          const u128 base = plan.position(tab[i].off);
-          lsn_launch_resample(d_raw + in[i].at, fc->sample_format, sfm.scale, in[i].lo, in[i].len, (uint64_t)(base >> 64), (uint64_t)base, (uint32_t)(plan.step >> 64),
-                              (uint64_t)plan.step, plan.taps, plan.span, d_bank, plan.tune, d_nco, nullptr, (uint32_t)len, 0, 1, d_x + o, len, T.st);
+          lsn_launch_resample({d_raw + in[i].at, fc->sample_format, sfm.scale, in[i].lo, in[i].len, 1, 0}, plan.cell(tab[i].off, (uint32_t)len, tb, d_x + o, len), T.st);
           tab[i].off = o;
           o += len;
         }

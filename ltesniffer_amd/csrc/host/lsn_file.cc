@@ -155,9 +155,7 @@ struct Engine::FileReplay {
     uint32_t start_tti = 0, update_meta_period = 0;
     uint64_t max_subframes = 0;
     uint64_t sf_in_file = 0, first_sf = 0, done = 0;   // complete subframes in the file / in front of the replay (DECODE_MIB state of the reference) / submitted
-    cf32* d_rot = nullptr;
-    float* d_bank = nullptr;      // the resampler's bank (a few hundred kB, as short-lived as d_rot) ...
-    const cf32* d_nco = nullptr;  // ... and, behind it in the same allocation, the mixer's tables when the plan has a tuning word
+    ResampleTables tb;            // the -o rotation and, with rs, the resampler's bank and NCO tables (a few hundred kB, as short-lived as the replay)
     int rc = LSN_SUCCESS;         // what this cell's engine answered (submit, then wait)
   };
   struct Slot { cf32* h_raw = nullptr; cf32* d_raw = nullptr; cf32* d_iq[kFileMaxCells] = {}; uint32_t nsf[kFileMaxCells] = {}; uint64_t mark[kFileMaxCells] = {};
@@ -196,8 +194,8 @@ struct Engine::FileReplay {
       Cell k;
       k.e = jobs[c].e; k.rs = jobs[c].rs; k.cf = jobs[c].cf; k.sflen = k.e->cd.sflen; k.offset_freq_hz = jobs[c].offset_freq_hz; k.start_tti = jobs[c].start_tti;
       k.update_meta_period = jobs[c].update_meta_period; k.max_subframes = jobs[c].max_subframes;
-      cells.push_back(k);
       if (k.sflen > widest) { widest = k.sflen; big = k.e; }
+      cells.push_back(std::move(k));
     }
     sf_bytes = (size_t)cells[0].sflen * nant * sfm.bytes;
     raw_bytes = (size_t)blk_geom * widest * nant * sizeof(cf32);
@@ -209,11 +207,9 @@ struct Engine::FileReplay {
     fcv.notify_all();
     if (reader.joinable()) reader.join();
     for (auto& s : slot) if (s.reg) (void)hipHostUnregister(s.reg);
-    for (auto& c : cells) {
-      if (c.d_rot) (void)hipFree(c.d_rot);
-      if (c.d_bank) (void)hipFree(c.d_bank);
+    for (auto& c : cells)
       if (c.d_taps) (void)hipFree(c.d_taps);
-    }
+    cells.clear();   // the cells' tables go before the stream does
     if (st) (void)hipStreamDestroy(st);
     if (map) munmap(map, file_size);
     if (fd >= 0) close(fd);
@@ -297,22 +293,21 @@ struct Engine::FileReplay {
   // k_resample for one cell: n subframes from output subframe pos, out of the raw samples [lo, lo + len) of the recording, queued on st
   void queueResampleOne(const Cell& c, const void* raw, int64_t lo, uint64_t len, uint64_t pos, uint32_t n, cf32* out)
   {
-    const u128 base = c.rs->position(pos * c.sflen);
-    if (c.cf) {   // stage 2 of a filtered cell: the plain cf32 k_resample from the cell's intermediate, which queueFilter has filled for these subframes
+    const LsnResampleCell k = c.rs->cell(pos * c.sflen, c.sflen, c.tb, out, (uint64_t)n * c.sflen);
+    if (c.cf) {   // stage 2 of a filtered cell: the plain cf32 k_resample from the cell's intermediate, which queueFilter has filled for these subframes.  Its plan
+                  // was formed with no centre offset (processFileRate, lsn_file_process_cells): tune = 0, no NCO tables - the mixer ran in stage 1
       int64_t lo2, hi2;
       midSpan(c, pos, n, lo2, hi2);
-      lsn_launch_resample(c.mid, 0, 1.0f, lo2, (uint64_t)(hi2 - lo2), (uint64_t)(base >> 64), (uint64_t)base, (uint32_t)(c.rs->step >> 64), (uint64_t)c.rs->step, c.rs->taps,
-                          c.rs->span, c.d_bank, 0, nullptr, c.d_rot, c.sflen, 0, nant, out, (uint64_t)n * c.sflen, st);
+      lsn_launch_resample({c.mid, 0, 1.0f, lo2, (uint64_t)(hi2 - lo2), nant, 0}, k, st);
       return;
     }
-    lsn_launch_resample(raw, fmt, sfm.scale, lo, len, (uint64_t)(base >> 64), (uint64_t)base, (uint32_t)(c.rs->step >> 64), (uint64_t)c.rs->step, c.rs->taps, c.rs->span, c.d_bank,
-                        c.rs->tune, c.d_nco, c.d_rot, c.sflen, 0, nant, out, (uint64_t)n * c.sflen, st);
+    lsn_launch_resample({raw, fmt, sfm.scale, lo, len, nant, 0}, k, st);
   }
 
   // the conversion of a block, raw block -> [subframe][antenna][sample] cf32 of every cell that takes part, queued on st
   void queueConvert(Slot& s, const FileCellsBlock& b)
   {
-    if (!resampled()) { lsn_launch_file_unpack(s.d_raw, fmt, sfm.scale, cells[0].d_rot, cells[0].sflen, nant, s.d_iq[0], b.nsf[0], st); return; }
+    if (!resampled()) { lsn_launch_file_unpack(s.d_raw, fmt, sfm.scale, cells[0].tb.d_rot, cells[0].sflen, nant, s.d_iq[0], b.nsf[0], st); return; }
     const uint64_t len = (uint64_t)(b.in_hi - b.in_lo);
     if (filtered()) {
       // one k_chan_fir launch covers all cells; each cell then has an input of its own, and k_resample_cells takes ONE raw buffer per launch: stage 2 is one
@@ -326,12 +321,9 @@ struct Engine::FileReplay {
     LsnResampleCell k[kFileMaxCells];
     for (size_t c = 0; c < cells.size(); c++) {
       const Cell& q = cells[c];
-      const u128 base = q.rs->position(b.sf0[c] * q.sflen);
-      k[c].base_hi = (uint64_t)(base >> 64); k[c].base_lo = (uint64_t)base; k[c].d_lo = (uint64_t)q.rs->step; k[c].d_hi = (uint32_t)(q.rs->step >> 64);
-      k[c].taps = q.rs->taps; k[c].span = q.rs->span; k[c].sflen = q.sflen; k[c].sf_off = 0; k[c].bank = q.d_bank; k[c].w = q.rs->tune; k[c].nco = q.d_nco; k[c].rot = q.d_rot;
-      k[c].out = s.d_iq[c]; k[c].n_out = (uint64_t)b.nsf[c] * q.sflen;
+      k[c] = q.rs->cell(b.sf0[c] * q.sflen, q.sflen, q.tb, s.d_iq[c], (uint64_t)b.nsf[c] * q.sflen);
     }
-    lsn_launch_resample_cells(s.d_raw, fmt, sfm.scale, b.in_lo, len, nant, k, (uint32_t)cells.size(), st);
+    lsn_launch_resample_cells({s.d_raw, fmt, sfm.scale, b.in_lo, len, nant, 0}, k, (uint32_t)cells.size(), st);
   }
 
   // stream, block buffers (kept by the engines: no-op when lsn_phy_prepare_file or an earlier call made them), rotation tables, resampler banks and NCO tables -
@@ -350,17 +342,8 @@ struct Engine::FileReplay {
       for (size_t c = 0; c < cells.size(); c++) s.d_iq[c] = cells[c].e->file_buf[si].d_iq;
     }
     for (auto& c : cells) {
-      if (c.offset_freq_hz != 0.0f) {
-        std::vector<cf32> rot(c.sflen);
-        const double fs = 15000.0 * (double)c.e->cd.N;
-        for (uint32_t n = 0; n < c.sflen; n++) {
-          const double a = -2.0 * M_PI * (double)c.offset_freq_hz * (double)n / fs;
-          rot[n] = {(float)std::cos(a), (float)std::sin(a)};
-        }
-        HIP_CHECK(hipMalloc((void**)&c.d_rot, c.sflen * sizeof(cf32)));
-        HIP_CHECK(hipMemcpy(c.d_rot, rot.data(), c.sflen * sizeof(cf32), hipMemcpyHostToDevice));
-      }
-      if (c.rs) c.rs->upload(c.d_bank, c.d_nco, st);
+      c.tb.rotation(c.offset_freq_hz, c.sflen, 15000.0 * (double)c.e->cd.N);
+      if (c.rs) c.tb.upload(*c.rs, st);
       if (c.cf) {   // the intermediate: reserved by lsn_phy_prepare_file when the filter was set by then, otherwise here - in front of the first block, never inside the loop
         lsn_chan_fir_upload(*c.cf, c.d_taps, c.d_mix, st);
         if (c.e->reserveChanBuffer(chan_buffer_bytes(raw_bytes / spb, nant, c.cf->L)) != LSN_SUCCESS) throw std::runtime_error("file source: channel filter buffer");
@@ -386,7 +369,7 @@ struct Engine::FileReplay {
       HIP_CHECK(hipStreamSynchronize(st));
       if (c.cf) { uint64_t sf0[kFileMaxCells] = {}; uint32_t one_sf[kFileMaxCells] = {}; sf0[ci] = i; one_sf[ci] = 1; queueFilter(ci, ci + 1, slot[0].d_raw, lo, len, sf0, one_sf); }
       if (c.rs) queueResampleOne(c, slot[0].d_raw, lo, len, i, 1, slot[0].d_iq[ci]);
-      else lsn_launch_file_unpack(slot[0].d_raw, fmt, sfm.scale, c.d_rot, c.sflen, nant, slot[0].d_iq[ci], 1, st);
+      else lsn_launch_file_unpack(slot[0].d_raw, fmt, sfm.scale, c.tb.d_rot, c.sflen, nant, slot[0].d_iq[ci], 1, st);
       HIP_CHECK(hipStreamSynchronize(st));
       lsn_mib_t mib;
       const int r = c.e->mibDecode(slot[0].d_iq[ci], true, &mib, nullptr);

@@ -1,4 +1,5 @@
-// lsn_hip.h - what every host file that talks to the HIP runtime shares: the one HIP_CHECK, the one clock and the one entry guard.
+// lsn_hip.h - what every host file that talks to the HIP runtime shares: the one HIP_CHECK, the one clock, the one entry guard, and the scope guards of a
+// stream and of a device allocation.
 #pragma once
 #include "../../../include/ltesniffer_amd.h"
 #include "lsn_types.h"
@@ -41,6 +42,33 @@ int guarded(F&& f)
     return LSN_ERROR;
   }
 }
+
+// the stand-alone entry points' test in front of their first allocation (the engine's own check, lsn_engine.cc / lsn_capi.cc, asks a different question)
+inline bool have_device(int device)
+{
+  int ndev = 0;
+  return hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0 && device >= 0 && device < ndev;
+}
+
+// a stream of the current device, destroyed with its scope
+struct OwnedStream {
+  hipStream_t s = nullptr;
+  OwnedStream() { hip_check(hipStreamCreateWithFlags(&s, hipStreamNonBlocking), "hipStreamCreateWithFlags"); }
+  ~OwnedStream() { (void)hipStreamDestroy(s); }
+  OwnedStream(const OwnedStream&) = delete;
+  OwnedStream& operator=(const OwnedStream&) = delete;
+  operator hipStream_t() const { return s; }
+};
+
+// one device allocation, freed with its scope
+struct DevBuf {
+  void* p = nullptr;
+  DevBuf() = default;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  template <typename T> T* alloc(size_t n) { hip_check(hipMalloc(&p, (n ? n : 1) * sizeof(T)), "hipMalloc"); return (T*)p; }
+};
 
 }  // namespace lsn
 

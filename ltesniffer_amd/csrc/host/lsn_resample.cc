@@ -1,5 +1,6 @@
 // lsn_resample.cc - host side of the polyphase resampler: the plan of a rate pair (step and start in 64.64 fixed point, formed in 128-bit
-// integers; number of taps; the bank of 512 phases; the tuning word and tables of the mixer) and lsn_resample, the stand-alone entry point (needs no Phy, like lsn_cell_search).
+// integers; number of taps; the bank of 512 phases; the tuning word and tables of the mixer), ResampleTables, the owner of a cell's device copies of them, and
+// lsn_resample / lsn_resample_cells, the stand-alone entry points (they need no Phy, like lsn_cell_search).
 // The filter is DESIGN.md section 3.1b, restated there as a formula; tests/resample_model.py is written from that formula, not from this file.
 // Product code: no CPU fallback (the samples are computed by k_resample only), nothing from oracle/ is included or linked.
 #include "lsn_hip.h"
@@ -95,19 +96,34 @@ int ResamplePlan::init(double rate_in, double rate_out, double passband_hz, uint
   return LSN_SUCCESS;
 }
 
-template <class Stream>
-void ResamplePlan::upload(float*& d_bank, const cf32*& d_nco, Stream s) const
+void ResampleTables::upload(const ResamplePlan& p, hipStream_t s)
 {
-  HIP_CHECK(hipMalloc((void**)&d_bank, (bank.size() + nco.size()) * sizeof(float)));
-  HIP_CHECK(hipMemcpyAsync(d_bank, bank.data(), bank.size() * sizeof(float), hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMalloc((void**)&d_bank, (p.bank.size() + p.nco.size()) * sizeof(float)));
+  HIP_CHECK(hipMemcpyAsync(d_bank, p.bank.data(), p.bank.size() * sizeof(float), hipMemcpyHostToDevice, s));
   d_nco = nullptr;
-  if (!nco.empty()) {
-    HIP_CHECK(hipMemcpyAsync(d_bank + bank.size(), nco.data(), nco.size() * sizeof(float), hipMemcpyHostToDevice, s));
-    d_nco = (const cf32*)(d_bank + bank.size());
+  if (!p.nco.empty()) {
+    HIP_CHECK(hipMemcpyAsync(d_bank + p.bank.size(), p.nco.data(), p.nco.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    d_nco = (const cf32*)(d_bank + p.bank.size());
   }
 }
 
-template void ResamplePlan::upload<hipStream_t>(float*&, const cf32*&, hipStream_t) const;
+void ResampleTables::rotation(float offset_freq_hz, uint32_t sflen, double fs)
+{
+  if (offset_freq_hz == 0.0f) return;
+  std::vector<cf32> rot(sflen);
+  for (uint32_t n = 0; n < sflen; n++) {
+    const double a = -2.0 * M_PI * (double)offset_freq_hz * (double)n / fs;
+    rot[n] = {(float)std::cos(a), (float)std::sin(a)};
+  }
+  HIP_CHECK(hipMalloc((void**)&d_rot, sflen * sizeof(cf32)));
+  HIP_CHECK(hipMemcpy(d_rot, rot.data(), sflen * sizeof(cf32), hipMemcpyHostToDevice));
+}
+
+ResampleTables::~ResampleTables()
+{
+  if (d_rot) (void)hipFree(d_rot);
+  if (d_bank) (void)hipFree(d_bank);
+}
 
 void ResamplePlan::inputSpan(uint64_t m0, uint64_t n, int64_t& lo, int64_t& hi) const
 {
@@ -172,14 +188,13 @@ int lsn_resample(int device, const void* in, int in_on_device, uint64_t n_in, co
   const uint64_t len = hi > need_lo ? (uint64_t)(hi - need_lo) : 0;
   const uint8_t* src = (const uint8_t*)in + ((uint64_t)need_lo - cfg->in_base) * smp;
   void *d_in = nullptr, *d_out = nullptr;
-  float* d_bank = nullptr;
-  const cf32* d_nco = nullptr;
+  lsn::ResampleTables tb;
   hipStream_t st = nullptr;
   int rc = LSN_SUCCESS;
   try {
     HIP_CHECK(hipSetDevice(device));
     HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    plan.upload(d_bank, d_nco, st);
+    tb.upload(plan, st);
     const void* raw = src;
     if (!in_on_device && len) {
       HIP_CHECK(hipMalloc(&d_in, len * smp));
@@ -192,9 +207,7 @@ int lsn_resample(int device, const void* in, int in_on_device, uint64_t n_in, co
       HIP_CHECK(hipMalloc(&d_out, out_bytes));
       dst = (cf32*)d_out;
     }
-    const lsn::u128 base = plan.position(cfg->out_first);
-    lsn_launch_resample(raw, fmt, scale, need_lo, len, (uint64_t)(base >> 64), (uint64_t)base, (uint32_t)(plan.step >> 64), (uint64_t)plan.step, plan.taps, plan.span,
-                        d_bank, plan.tune, d_nco, nullptr, (uint32_t)n_out, 0, nant, dst, n_out, st);
+    lsn_launch_resample({raw, fmt, scale, need_lo, len, nant, 0}, plan.cell(cfg->out_first, (uint32_t)n_out, tb, dst, n_out), st);
     if (!out_on_device) HIP_CHECK(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
   } catch (const std::exception& ex) {
@@ -203,7 +216,6 @@ int lsn_resample(int device, const void* in, int in_on_device, uint64_t n_in, co
   }
   if (st) (void)hipStreamDestroy(st);
   if (d_in) (void)hipFree(d_in);
-  if (d_bank) (void)hipFree(d_bank);
   if (d_out) (void)hipFree(d_out);
   return rc;
 }
@@ -243,7 +255,7 @@ static int resample_cells(int device, const void* in, int in_on_device, uint64_t
   const uint64_t len = need_hi > need_lo ? (uint64_t)(need_hi - need_lo) : 0;
   const uint8_t* src = (const uint8_t*)in + ((uint64_t)need_lo - c0.in_base) * smp;
   void* d_in = nullptr;
-  std::vector<float*> d_bank(n_cells, nullptr);
+  std::vector<lsn::ResampleTables> tb(n_cells);
   std::vector<void*> d_out(n_cells, nullptr);
   hipStream_t st = nullptr;
   int rc = LSN_SUCCESS;
@@ -265,21 +277,16 @@ static int resample_cells(int device, const void* in, int in_on_device, uint64_t
     }
     LsnResampleCell k[LSN_FILE_MAX_CELLS];
     for (uint32_t c = 0; c < n_cells; c++) {
-      const lsn::ResamplePlan& p = plans[c];
-      const cf32* d_nco = nullptr;
-      p.upload(d_bank[c], d_nco, st);
+      tb[c].upload(plans[c], st);
       cf32* dst = (cf32*)outs[c];
       if (!out_on_device && n_out[c]) {
         HIP_CHECK(hipMalloc(&d_out[c], (size_t)n_out[c] * nant * sizeof(cf32)));
         dst = (cf32*)d_out[c];
       }
-      const lsn::u128 base = p.position(cfgs[c].out_first);
-      k[c].base_hi = (uint64_t)(base >> 64); k[c].base_lo = (uint64_t)base; k[c].d_lo = (uint64_t)p.step; k[c].d_hi = (uint32_t)(p.step >> 64); k[c].taps = p.taps; k[c].span = p.span;
-      k[c].sflen = (uint32_t)std::max<uint64_t>(n_out[c], 1); k[c].sf_off = 0; k[c].bank = d_bank[c]; k[c].w = p.tune; k[c].nco = d_nco; k[c].rot = nullptr; k[c].out = dst;
-      k[c].n_out = n_out[c];
+      k[c] = plans[c].cell(cfgs[c].out_first, (uint32_t)std::max<uint64_t>(n_out[c], 1), tb[c], dst, n_out[c]);
     }
-    if (ring_samples) lsn_launch_resample_ring(d_in, ring_samples, fmt, sfm.scale, (int64_t)c0.in_base, n_in, nant, k, n_cells, st);
-    else lsn_launch_resample_cells(raw, fmt, sfm.scale, need_lo, len, nant, k, n_cells, st);
+    if (ring_samples) lsn_launch_resample_cells({d_in, fmt, sfm.scale, (int64_t)c0.in_base, n_in, nant, ring_samples}, k, n_cells, st);
+    else lsn_launch_resample_cells({raw, fmt, sfm.scale, need_lo, len, nant, 0}, k, n_cells, st);
     if (!out_on_device)
       for (uint32_t c = 0; c < n_cells; c++)
         if (n_out[c]) HIP_CHECK(hipMemcpyAsync(outs[c], d_out[c], (size_t)n_out[c] * nant * sizeof(cf32), hipMemcpyDeviceToHost, st));
@@ -290,7 +297,6 @@ static int resample_cells(int device, const void* in, int in_on_device, uint64_t
   }
   if (st) (void)hipStreamDestroy(st);
   if (d_in) (void)hipFree(d_in);
-  for (float* b : d_bank) if (b) (void)hipFree(b);
   for (void* o : d_out) if (o) (void)hipFree(o);
   return rc;
 }

@@ -1,16 +1,37 @@
 // lsn_resample.h - host side of the polyphase resampler (kernels/resample.hip; launchers: lsn_resample_launch.h): the plan of one rate pair - step, start, taps, bank, and the
-// tuning word and NCO tables of the mixer in front of the filter - and the 64.64 position arithmetic in 128-bit integers.  Definition: DESIGN.md section 3.1b.
+// tuning word and NCO tables of the mixer in front of the filter - the 64.64 position arithmetic in 128-bit integers, and the launch record of a cell, which
+// ResamplePlan::cell alone forms.  Definition: DESIGN.md section 3.1b.
 #pragma once
 #include <cstdint>
 #include <vector>
 
-// no HIP header: the plan is plain host arithmetic, and lsn_cells.cc, which builds on it, stays HIP-free.  What needs the runtime's types - the kernel launchers -
-// is declared in lsn_resample_launch.h.
+// no HIP header: the plan is plain host arithmetic, and lsn_cells.cc, which builds on it, stays HIP-free.  What needs the runtime's types - the kernel launchers and
+// the owner of a cell's device tables - is declared in lsn_resample_launch.h.
 struct cf32;
+
+// what one cell brings to a launch of its own (the launch's other arguments - raw buffer, format, scale, antennas - are the recording's: LsnResampleSource)
+struct LsnResampleCell {
+  uint64_t base_hi, base_lo;   // position of the cell's output 0 in this launch
+  uint64_t d_lo; uint32_t d_hi;
+  uint32_t taps, span;
+  uint32_t sflen, sf_off;
+  const float* bank;
+  uint64_t w; const cf32* nco; // nco null: the cell is not translated
+  const cf32* rot;
+  cf32* out;
+  uint64_t n_out;              // 0: the cell takes no part in this launch
+};
 
 namespace lsn {
 
 typedef unsigned __int128 u128;
+
+// a cell's device tables as a launch record names them; ResampleTables (lsn_resample_launch.h) owns them
+struct ResampleTablePtrs {
+  float* d_bank = nullptr;      // the bank ...
+  const cf32* d_nco = nullptr;  // ... and, behind it in the same allocation, the mixer's tables when the plan has a tuning word
+  cf32* d_rot = nullptr;        // the optional -o rotation of the outputs, [sflen]
+};
 
 struct ResamplePlan {
   u128 step = 0;       // D = round(rate_in / rate_out * 2^64)
@@ -28,10 +49,18 @@ struct ResamplePlan {
   int init(double rate_in, double rate_out, double passband_hz, uint64_t first_sample, double first_frac, double center_offset_hz, double max_ratio = 4.0,
            uint32_t max_taps = 192);
   static uint64_t tuning(double center_offset_hz, double rate_in);   // W of one offset
-  // device copy of bank and nco in one allocation (the caller frees d_bank); d_nco = null when the plan does not mix
-  // Stream = hipStream_t, the one instantiation (lsn_resample.cc); a template so that this header names no type of the runtime
-  template <class Stream> void upload(float*& d_bank, const cf32*& d_nco, Stream s) const;
   u128 position(uint64_t m) const { return start + (u128)m * step; }
+  // the launch record of n_out outputs from position `base` on, `step_` apart - the ONE place a position and a step are split into the kernel's words.  A tracked
+  // segment passes its own base, step and span; sf_off is the phase of output 0 inside its row of sflen outputs
+  LsnResampleCell cell(u128 base, u128 step_, uint32_t span_, uint32_t sflen, uint32_t sf_off, const ResampleTablePtrs& t, cf32* out, uint64_t n_out) const
+  {
+    LsnResampleCell k;
+    k.base_hi = (uint64_t)(base >> 64); k.base_lo = (uint64_t)base; k.d_lo = (uint64_t)step_; k.d_hi = (uint32_t)(step_ >> 64);
+    k.taps = taps; k.span = span_; k.sflen = sflen; k.sf_off = sf_off; k.bank = t.d_bank; k.w = tune; k.nco = t.d_nco; k.rot = t.d_rot; k.out = out; k.n_out = n_out;
+    return k;
+  }
+  // outputs [m0, m0 + n_out) of this plan, output m0 at the start of a row
+  LsnResampleCell cell(uint64_t m0, uint32_t sflen, const ResampleTablePtrs& t, cf32* out, uint64_t n_out) const { return cell(position(m0), step, span, sflen, 0, t, out, n_out); }
   // input samples [lo, hi) that outputs m0 .. m0 + n - 1 read (lo may be negative: zeros in front of the recording)
   void inputSpan(uint64_t m0, uint64_t n, int64_t& lo, int64_t& hi) const;
   // number of outputs m = 0, 1, ... whose taps all lie in front of input sample in_end

@@ -5,6 +5,7 @@
 #include "lsn_hip.h"
 #include "../kernels/lsn_dev.h"
 #include "lsn_scan.h"
+#include "lsn_resample_launch.h"
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
@@ -106,23 +107,8 @@ std::vector<uint32_t> scan_decide(const lsn_carrier_scan_cfg_t& cfg, const lsn_c
 }
 
 namespace {
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  template <typename T> T* alloc(size_t n) { HIP_CHECK(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T))); return (T*)p; }
-};
-struct Stream {
-  hipStream_t s = nullptr;
-  ~Stream() { if (s) (void)hipStreamDestroy(s); }
-};
 struct ScanPeak { double sum; float peak; uint32_t lag; uint32_t pad[2]; };   // LsnScanPeak of scan.hip
 static_assert(sizeof(ScanPeak) == 24, "24 bytes per (hypothesis, root)");
-
-bool have_device(int device)
-{
-  int ndev = 0;
-  return hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0 && device >= 0 && device < ndev;
-}
 }  // namespace
 
 static int carrier_scan(int device, const void* in, bool in_on_device, uint64_t n_in, const lsn_carrier_scan_cfg_t* ucfg, lsn_carrier_t* carriers_out, uint32_t cap,
@@ -137,24 +123,21 @@ static int carrier_scan(int device, const void* in, bool in_on_device, uint64_t 
     return LSN_ERROR_INVALID_INPUTS;
   if (!have_device(device)) return LSN_ERROR_NO_DEVICE;
   HIP_CHECK(hipSetDevice(device));
-  Stream st;
-  HIP_CHECK(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+  OwnedStream st;
   const ResamplePlan& rs = sp.rs;
   const uint32_t H = (uint32_t)sp.hyp.size(), P = cfg.nof_periods, N = kScanN, W5 = kScanW5;
   const size_t smp = (size_t)sfm.bytes * cfg.nof_antennas, nch = (size_t)sp.n_chan;
   uint32_t run, span;
   chan_geometry(rs, run, span);
 
-  DevBuf bin, bbank, btune, brep, bchan, bcorr, bpeak;
+  DevBuf bin, btune, brep, bchan, bcorr, bpeak;
+  ResampleTables tb;
   const void* d_in = in;
   if (!in_on_device) {
     d_in = bin.alloc<uint8_t>(sp.n_in * smp);
     HIP_CHECK(hipMemcpyAsync((void*)d_in, in, sp.n_in * smp, hipMemcpyHostToDevice, st.s));
   }
-  float* d_bank = nullptr;
-  const cf32* d_nco = nullptr;
-  rs.upload(d_bank, d_nco, st.s);
-  bbank.p = d_bank;
+  tb.upload(rs, st.s);
   std::vector<uint64_t> tunes(H);
   for (uint32_t i = 0; i < H; i++) tunes[i] = sp.hyp[i].tuning_word;
   uint64_t* d_tune = btune.alloc<uint64_t>(H);
@@ -179,7 +162,7 @@ static int carrier_scan(int device, const void* in, bool in_on_device, uint64_t 
   std::vector<ScanPeak> peaks((size_t)batch * 3);
   std::vector<lsn_carrier_metric_t> metric = sp.hyp;
   auto channels = [&](uint32_t h0, uint32_t n) {
-    lsn_launch_chan_bank(d_in, cfg.sample_format, sfm.scale, 0, sp.n_in, 0, 0, (uint32_t)(rs.step >> 64), (uint64_t)rs.step, rs.taps, span, run, d_bank, d_tune + h0, 1, d_nco,
+    lsn_launch_chan_bank(d_in, cfg.sample_format, sfm.scale, 0, sp.n_in, 0, 0, (uint32_t)(rs.step >> 64), (uint64_t)rs.step, rs.taps, span, run, tb.d_bank, d_tune + h0, 1, tb.d_nco,
                          cfg.nof_antennas, cfg.antenna, 0, n, d_chan, nch, nch, st.s);
   };
   for (uint32_t h0 = 0; h0 < H; h0 += batch) {
@@ -258,13 +241,10 @@ static int carrier_channel(int device, const void* in, bool in_on_device, uint64
   const uint64_t len = hi > need_lo ? (uint64_t)(hi - need_lo) : 0;
   const uint8_t* src = (const uint8_t*)in + ((uint64_t)need_lo - cfg->in_base) * smp;
   HIP_CHECK(hipSetDevice(device));
-  Stream st;
-  HIP_CHECK(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-  DevBuf bin, bbank, btune, bout;
-  float* d_bank = nullptr;
-  const cf32* d_nco = nullptr;
-  plan.upload(d_bank, d_nco, st.s);
-  bbank.p = d_bank;
+  OwnedStream st;
+  DevBuf bin, btune, bout;
+  ResampleTables tb;
+  tb.upload(plan, st.s);
   uint64_t* d_tune = btune.alloc<uint64_t>(1);
   HIP_CHECK(hipMemcpyAsync(d_tune, &plan.tune, sizeof(uint64_t), hipMemcpyHostToDevice, st.s));
   const void* raw = src;
@@ -279,7 +259,7 @@ static int carrier_channel(int device, const void* in, bool in_on_device, uint64
   chan_geometry(plan, run, span);
   const u128 base = plan.position(cfg->out_first);
   lsn_launch_chan_bank(raw, cfg->sample_format, sfm.scale, need_lo, len, (uint64_t)(base >> 64), (uint64_t)base, (uint32_t)(plan.step >> 64), (uint64_t)plan.step, plan.taps, span,
-                       run, d_bank, d_tune, 0, d_nco, nant, 0, 1, nant, dst, n_out, n_out, st.s);
+                       run, tb.d_bank, d_tune, 0, tb.d_nco, nant, 0, 1, nant, dst, n_out, n_out, st.s);
   if (!out_on_device) HIP_CHECK(hipMemcpyAsync(out, dst, out_bytes, hipMemcpyDeviceToHost, st.s));
   HIP_CHECK(hipStreamSynchronize(st.s));
   return LSN_SUCCESS;

@@ -7,9 +7,9 @@
 // Two HIP streams: copies and memsets on one, launches on the other.  A launch waits for the copies queued so far; a piece that is written over slots an
 // unfinished launch may still read waits on the event recorded behind that launch, and on nothing else.  Product code: no CPU fallback.
 // A stream that asked for it (track()) follows the sample clock: runReadyTracked resamples segment by segment at the steps its timing loop
-// decides (lsn_track.h) and measures every segment's PSS with k_pss_timing; a stream that did not runs runReady exactly as before.
+// decides (lsn_track.h) and measures every segment's PSS with k_pss_timing; a stream that did not runs runReady exactly as before.  The two loops differ in how a
+// block buffer fills; what they do alike - bufferFor, launchRing, submitBlock - exists once.
 #include "lsn_stream_ring.h"
-#include "lsn_resample_launch.h"
 #include "lsn_track_launch.h"
 #include "lsn_clock.h"
 #include <algorithm>
@@ -45,8 +45,6 @@ StreamRing::~StreamRing()
   for (auto& e : ev_free) (void)hipEventDestroy(e);
   if (ev_copy) (void)hipEventDestroy(ev_copy);
   for (auto& c : cells) {
-    if (c.d_rot) (void)hipFree(c.d_rot);
-    if (c.d_bank) (void)hipFree(c.d_bank);
     if (c.d_rep) (void)hipFree(c.d_rep);
     if (c.h_C) (void)hipHostFree(c.h_C);
     for (auto& p : c.pending) if (p.ev) (void)hipEventDestroy(p.ev);
@@ -73,17 +71,8 @@ int StreamRing::setup()
       if (r != LSN_SUCCESS) return r;
       for (int si = 0; si < nslot; si++)
         if (c.s.e->fileIqBlockBytes(si) < (size_t)blk * c.sflen * nant * sizeof(cf32)) throw std::runtime_error("stream: block buffer");
-      if (c.s.offset_freq_hz != 0.0f) {   // the -o rotation of the cell's output samples, as the file source forms it
-        std::vector<cf32> rot(c.sflen);
-        const double fs = 15000.0 * (double)c.s.e->symbolSz();
-        for (uint32_t n = 0; n < c.sflen; n++) {
-          const double a = -2.0 * M_PI * (double)c.s.offset_freq_hz * (double)n / fs;
-          rot[n] = {(float)std::cos(a), (float)std::sin(a)};
-        }
-        HIP_CHECK(hipMalloc((void**)&c.d_rot, c.sflen * sizeof(cf32)));
-        HIP_CHECK(hipMemcpy(c.d_rot, rot.data(), c.sflen * sizeof(cf32), hipMemcpyHostToDevice));
-      }
-      c.s.plan.upload(c.d_bank, c.d_nco, st_run);
+      c.tb.rotation(c.s.offset_freq_hz, c.sflen, 15000.0 * (double)c.s.e->symbolSz());   // the -o rotation of the cell's output samples, the file source's
+      c.tb.upload(c.s.plan, st_run);
     }
     HIP_CHECK(hipStreamSynchronize(st_run));
     return LSN_SUCCESS;
@@ -157,39 +146,47 @@ int StreamRing::runReady(bool flush_all)
       any = true;
     }
     if (!any) return LSN_SUCCESS;
-    in_lo = std::max<int64_t>(in_lo, 0);   // zeros in front of the stream are the kernel's
-    if (in_hi > (int64_t)pushed || (uint64_t)(in_hi - in_lo) > ring_samples || (int64_t)pushed - in_lo > (int64_t)ring_samples)
-      throw std::runtime_error("stream: a block's input is not in the ring");
     LsnResampleCell k[kFileMaxCells];
     for (size_t c = 0; c < cells.size(); c++) {
       Cell& q = cells[c];
       k[c] = LsnResampleCell();
-      if (!nsf[c]) continue;
-      const int si = (int)(q.launches % (uint64_t)nslot);
-      if (q.mark[si]) q.s.e->waitIqConsumed(q.mark[si]);   // the block this buffer carried last has been through stage A
-      const u128 base = q.s.plan.position(q.done * q.sflen);
-      k[c].base_hi = (uint64_t)(base >> 64); k[c].base_lo = (uint64_t)base; k[c].d_lo = (uint64_t)q.s.plan.step; k[c].d_hi = (uint32_t)(q.s.plan.step >> 64);
-      k[c].taps = q.s.plan.taps; k[c].span = q.s.plan.span; k[c].sflen = q.sflen; k[c].sf_off = 0; k[c].bank = q.d_bank; k[c].w = q.s.plan.tune; k[c].nco = q.d_nco; k[c].rot = q.d_rot;
-      k[c].out = q.s.e->fileIqBlock(si); k[c].n_out = (uint64_t)nsf[c] * q.sflen;
+      if (nsf[c]) k[c] = q.s.plan.cell(q.done * q.sflen, q.sflen, q.tb, bufferFor(q), (uint64_t)nsf[c] * q.sflen);
     }
-    HIP_CHECK(hipEventRecord(ev_copy, st_copy));
-    HIP_CHECK(hipStreamWaitEvent(st_run, ev_copy, 0));   // the samples pushed so far are in their slots
-    lsn_launch_resample_ring(d_ring, ring_samples, fmt, sfm.scale, in_lo, (uint64_t)(in_hi - in_lo), nant, k, (uint32_t)cells.size(), st_run);
-    Launch l;
-    l.ev = takeEvent(); l.lo = in_lo;
-    HIP_CHECK(hipEventRecord(l.ev, st_run));
-    inflight.push_back(l);
-    for (size_t c = 0; c < cells.size() && failed == LSN_SUCCESS; c++) {
-      Cell& q = cells[c];
-      if (!nsf[c]) continue;
-      const int si = (int)(q.launches % (uint64_t)nslot);
-      q.rc = q.s.e->submit(k[c].out, nsf[c], (uint32_t)((q.s.start_tti + q.done) % 10240u), q.s.update_meta_period, st_run);
-      q.mark[si] = q.s.e->submitMark();
-      q.launches++;
-      q.done += nsf[c];
-      if (q.rc != LSN_SUCCESS) failed = q.rc;   // nothing more is submitted to any Phy
-    }
+    launchRing(k, in_lo, in_hi, "block");
+    for (size_t c = 0; c < cells.size() && failed == LSN_SUCCESS; c++)
+      if (nsf[c]) submitBlock(cells[c], nsf[c]);
   }
+}
+
+void StreamRing::launchRing(const LsnResampleCell* k, int64_t in_lo, int64_t in_hi, const char* what)
+{
+  in_lo = std::max<int64_t>(in_lo, 0);   // zeros in front of the stream are the kernel's
+  if (in_hi > (int64_t)pushed || (uint64_t)(in_hi - in_lo) > ring_samples || (int64_t)pushed - in_lo > (int64_t)ring_samples)
+    throw std::runtime_error(std::string("stream: a ") + what + "'s input is not in the ring");
+  HIP_CHECK(hipEventRecord(ev_copy, st_copy));
+  HIP_CHECK(hipStreamWaitEvent(st_run, ev_copy, 0));   // the samples pushed so far are in their slots
+  lsn_launch_resample_cells({d_ring, fmt, sfm.scale, in_lo, (uint64_t)(in_hi - in_lo), nant, ring_samples}, k, (uint32_t)cells.size(), st_run);
+  Launch l;
+  l.ev = takeEvent(); l.lo = in_lo;
+  HIP_CHECK(hipEventRecord(l.ev, st_run));
+  inflight.push_back(l);
+}
+
+cf32* StreamRing::bufferFor(Cell& q, bool empty)
+{
+  const int si = (int)(q.launches % (uint64_t)nslot);
+  if (empty && q.mark[si]) q.s.e->waitIqConsumed(q.mark[si]);   // the block this buffer carried last has been through stage A
+  return q.s.e->fileIqBlock(si);
+}
+
+void StreamRing::submitBlock(Cell& q, uint32_t nsf)
+{
+  const int si = (int)(q.launches % (uint64_t)nslot);
+  q.rc = q.s.e->submit(q.s.e->fileIqBlock(si), nsf, (uint32_t)((q.s.start_tti + q.done) % 10240u), q.s.update_meta_period, st_run);
+  q.mark[si] = q.s.e->submitMark();
+  q.launches++;
+  q.done += nsf;
+  if (q.rc != LSN_SUCCESS) failed = q.rc;   // nothing more is submitted to any Phy
 }
 
 int StreamRing::push(const void* iq, uint64_t n)
@@ -331,12 +328,8 @@ int StreamRing::runReadyTracked(bool flush_all)
       const uint64_t upto = std::min<uint64_t>(t.completeInSegment(pushed), end);
       if (upto <= q.filled || (upto < end && !flush_all)) continue;
       piece[c] = (uint32_t)(upto - q.filled);
-      const int si = (int)(q.launches % (uint64_t)nslot);
-      if (q.filled == q.done && q.mark[si]) q.s.e->waitIqConsumed(q.mark[si]);   // the block this buffer carried last has been through stage A
-      const u128 base = t.position(q.filled);
-      k[c].base_hi = (uint64_t)(base >> 64); k[c].base_lo = (uint64_t)base; k[c].d_lo = (uint64_t)t.step; k[c].d_hi = (uint32_t)(t.step >> 64);
-      k[c].taps = q.s.plan.taps; k[c].span = t.span; k[c].sflen = q.sflen; k[c].sf_off = (uint32_t)(q.filled - q.done) * q.sflen; k[c].bank = q.d_bank; k[c].w = q.s.plan.tune;
-      k[c].nco = q.d_nco; k[c].rot = q.d_rot; k[c].out = q.s.e->fileIqBlock(si); k[c].n_out = (uint64_t)piece[c] * q.sflen;
+      k[c] = q.s.plan.cell(t.position(q.filled), t.step, t.span, q.sflen, (uint32_t)(q.filled - q.done) * q.sflen, q.tb, bufferFor(q, q.filled == q.done),
+                           (uint64_t)piece[c] * q.sflen);
       int64_t lo, hi;
       t.inputSpan(q.filled, upto, lo, hi);
       in_lo = any ? std::min(in_lo, lo) : lo;
@@ -344,16 +337,7 @@ int StreamRing::runReadyTracked(bool flush_all)
       any = true;
     }
     if (any) {
-      in_lo = std::max<int64_t>(in_lo, 0);
-      if (in_hi > (int64_t)pushed || (uint64_t)(in_hi - in_lo) > ring_samples || (int64_t)pushed - in_lo > (int64_t)ring_samples)
-        throw std::runtime_error("stream: a segment's input is not in the ring");
-      HIP_CHECK(hipEventRecord(ev_copy, st_copy));
-      HIP_CHECK(hipStreamWaitEvent(st_run, ev_copy, 0));
-      lsn_launch_resample_ring(d_ring, ring_samples, fmt, sfm.scale, in_lo, (uint64_t)(in_hi - in_lo), nant, k, (uint32_t)cells.size(), st_run);
-      Launch l;
-      l.ev = takeEvent(); l.lo = in_lo;
-      HIP_CHECK(hipEventRecord(l.ev, st_run));
-      inflight.push_back(l);
+      launchRing(k, in_lo, in_hi, "segment");
       // the windows of the segments that began in this launch
       LsnTimingCell tm[kFileMaxCells];
       bool timing = false;
@@ -385,13 +369,8 @@ int StreamRing::runReadyTracked(bool flush_all)
       Cell& q = cells[c];
       const uint32_t n = (uint32_t)(q.filled - q.done);
       if (!n || !(n == blk || (!any && flush_all) || (q.s.max_subframes && q.filled == q.s.max_subframes))) continue;
-      const int si = (int)(q.launches % (uint64_t)nslot);
-      q.rc = q.s.e->submit(q.s.e->fileIqBlock(si), n, (uint32_t)((q.s.start_tti + q.done) % 10240u), q.s.update_meta_period, st_run);
-      q.mark[si] = q.s.e->submitMark();
-      q.launches++;
-      q.done += n;
+      submitBlock(q, n);
       submitted = true;
-      if (q.rc != LSN_SUCCESS) failed = q.rc;
     }
     if (!any && !submitted) return LSN_SUCCESS;
   }

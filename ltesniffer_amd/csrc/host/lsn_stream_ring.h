@@ -3,6 +3,7 @@
 // A tracked stream (track(), section 3.1h) counts by the segments of lsn_track.h instead and measures every segment's PSS with k_pss_timing.
 #pragma once
 #include "lsn_engine.h"
+#include "lsn_resample_launch.h"
 #include "lsn_stream.h"
 #include "lsn_track.h"
 #include <deque>
@@ -47,10 +48,8 @@ private:
     uint32_t sflen = 0;
     uint64_t done = 0;
     int rc = LSN_SUCCESS;
-    cf32* d_rot = nullptr;
-    float* d_bank = nullptr;
-    const cf32* d_nco = nullptr;
-    uint64_t launches = 0;               // block buffer of launch k: slot k mod nslot ...
+    ResampleTables tb;                   // the plan's bank and NCO tables, the -o rotation
+    uint64_t launches = 0;              // block buffer of launch k: slot k mod nslot ...
     uint64_t mark[NSLOT_MAX] = {};       // ... free again when the engine has consumed the chunks up to this mark (0: never used)
     // a tracked stream (runReadyTracked): the block buffer fills segment by segment
     TrackCell tk;
@@ -65,6 +64,12 @@ private:
   void writeRing(const uint8_t* src, uint64_t n);
   int runReady(bool flush_all);
   int runReadyTracked(bool flush_all);
+  // the steps the two loops share.  launchRing: one k_resample_ring launch of the cells in k out of the recording samples [in_lo, in_hi), behind the copies queued
+  // so far, and its event into `inflight`; `what` names the input in the refusal.  bufferFor: the block buffer the cell fills next; empty (nothing of the next
+  // block is in it yet): waits until the block it carried last has been through stage A.  submitBlock: the first nsf subframes of that buffer go to the cell's Phy
+  void launchRing(const LsnResampleCell* k, int64_t in_lo, int64_t in_hi, const char* what);
+  cf32* bufferFor(Cell& q, bool empty = true);
+  void submitBlock(Cell& q, uint32_t nsf);
   void deliver(Cell& q, uint64_t upto_h, bool all);   // the measurements of segments <= upto_h (all: every one in flight) go to the loop; waits for their events
   bool inGap(int64_t lo, int64_t hi) const;
   hipEvent_t takeEvent();

@@ -100,14 +100,6 @@ static void sss_table(uint32_t n_id_2, int8_t* out /* [336][62] */)
   }
 }
 
-namespace {
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  template <typename T> T* alloc(size_t n) { HIP_CHECK(hipMalloc(&p, n * sizeof(T))); return (T*)p; }
-};
-}  // namespace
-
 int cell_search(int device, const cf32* iq, bool on_device, uint64_t nsamples, uint32_t nof_prb, int rates, const lsn_cell_search_cfg_t& cfg,
                 lsn_cell_search_t& out, float* corr_out)
 {
@@ -118,12 +110,9 @@ int cell_search(int device, const cf32* iq, bool on_device, uint64_t nsamples, u
   const uint32_t W5 = 75 * N;
   const uint64_t need = (uint64_t)(P + 1) * W5 + N;
   if (nsamples < need) return LSN_ERROR_INVALID_INPUTS;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return LSN_ERROR_NO_DEVICE;
+  if (!have_device(device)) return LSN_ERROR_NO_DEVICE;
   HIP_CHECK(hipSetDevice(device));
-  hipStream_t st = nullptr;
-  HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } sg{st};
+  OwnedStream st;
 
   const uint32_t nroots = cfg.force_n_id_2 >= 0 ? 1u : 3u;
   std::vector<cf32> rep((size_t)nroots * N);

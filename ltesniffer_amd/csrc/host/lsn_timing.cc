@@ -34,12 +34,9 @@ extern "C" int lsn_pss_timing(int device, int blocks_on_device, const lsn_pss_ti
       most = std::max(most, k.n_occ);
     }
     if (!most) return LSN_SUCCESS;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return LSN_ERROR_NO_DEVICE;
+    if (!lsn::have_device(device)) return LSN_ERROR_NO_DEVICE;
     HIP_CHECK(hipSetDevice(device));
-    hipStream_t st = nullptr;
-    HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } sg{st};
+    lsn::OwnedStream st;
     std::vector<DevMem> mem(3 * (size_t)n_cells);
     LsnTimingCell base[LSN_TIMING_MAX_CELLS];
     for (uint32_t c = 0; c < n_cells; c++) {

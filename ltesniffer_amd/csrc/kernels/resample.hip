@@ -1,5 +1,6 @@
 // resample.hip - polyphase Kaiser-windowed-sinc resampler of the file source and of lsn_resample (gfx950).  The filter, the bank and the
-// position arithmetic are defined in DESIGN.md section 3.1b; the host side (plan, bank, spans) is host/lsn_resample.cc.
+// position arithmetic are defined in DESIGN.md section 3.1b; the host side (plan, bank, spans, the launch record of a cell) is host/lsn_resample.{h,cc}, and
+// the launchers at the end of this file take that record as it is.
 //
 // Output sample m of a replay sits at input position P0 + m * D, a 64.64 fixed-point number (integer part = input sample index, 64 bits of
 // fraction).  The launch is handed the position of ITS first output (base = P0 + m0 * D, formed on the host in 128-bit integers) and D; a
@@ -149,85 +150,64 @@ __global__ __launch_bounds__(256) void k_resample_ring(const LsnResampleCellsArg
   LSN_RESAMPLE_RUN(A.nco != nullptr, n & (int64_t)A.ring_mask)
 }
 
-// n_out outputs per antenna from output position (base_hi, base_lo); span = samples a run of LSN_RS_RUN outputs needs (host: lsn_resample.cc).
-// nco != null: the mixing instantiations with tuning word w; null: the plain ones, as before the mixer existed
-void lsn_launch_resample(const void* raw, uint32_t fmt, float scale, int64_t buf_base, uint64_t buf_len, uint64_t base_hi, uint64_t base_lo, uint32_t d_hi,
-                         uint64_t d_lo, uint32_t taps, uint32_t span, const float* bank, uint64_t w, const cf32* nco, const cf32* rot, uint32_t sflen, uint32_t sf_off,
-                         uint32_t nant, cf32* out, uint64_t n_out, hipStream_t s)
+// ---- host side: one function forms a run's arguments, two launchers (lsn_resample_launch.h) ----
+
+// the arguments of cell k's runs out of src, checked: span = samples a run of LSN_RS_RUN outputs needs (host: lsn_resample.cc), n_out + sf_off below 2^32 (the
+// kernel's row arithmetic).  -> the cell's number of runs.  `kernel` names the launch in a refusal
+static uint64_t resample_args(const char* kernel, const LsnResampleSource& src, const LsnResampleCell& k, LsnResampleArgs& A)
 {
-  if (!n_out) return;
-  if (taps < 2 || (taps & 1) || span < taps || (size_t)span * sizeof(float2) > 64 * 1024 || buf_base < 0 || !sflen) throw std::runtime_error("k_resample: bad geometry");
-  const uint64_t runs = (n_out + LSN_RS_RUN - 1) / LSN_RS_RUN;
-  if (runs > 0x7FFFFFFFull || n_out + sf_off > 0xFFFFFFFFull) throw std::runtime_error("k_resample: launch too long");
-  LsnResampleArgs A;
-  A.raw = raw; A.buf_base = buf_base; A.buf_len = buf_len; A.base_hi = base_hi; A.base_lo = base_lo; A.d_lo = d_lo; A.d_hi = d_hi; A.taps = taps; A.span = span;
-  A.nant = nant; A.sflen = sflen; A.sf_off = sf_off; A.n_out = n_out; A.scale = scale; A.bank = (const float2*)bank; A.rot = rot; A.out = out;
-  A.w = w; A.nco = nco; A.ring_mask = 0;
-  const dim3 g((uint32_t)runs, nant);
-  const size_t lds = (size_t)span * sizeof(float2);
-  if (nco) {
-    if (fmt == 1) LSN_LAUNCH((k_resample<1, true>), g, dim3(256), lds, s, A);
-    else if (fmt == 2) LSN_LAUNCH((k_resample<2, true>), g, dim3(256), lds, s, A);
-    else LSN_LAUNCH((k_resample<0, true>), g, dim3(256), lds, s, A);
-  } else {
-    if (fmt == 1) LSN_LAUNCH((k_resample<1, false>), g, dim3(256), lds, s, A);
-    else if (fmt == 2) LSN_LAUNCH((k_resample<2, false>), g, dim3(256), lds, s, A);
-    else LSN_LAUNCH((k_resample<0, false>), g, dim3(256), lds, s, A);
-  }
+  if (k.taps < 2 || (k.taps & 1) || k.span < k.taps || (size_t)k.span * sizeof(float2) > 64 * 1024 || src.buf_base < 0 || !k.sflen)
+    throw std::runtime_error(std::string(kernel) + ": bad geometry");
+  const uint64_t runs = (k.n_out + LSN_RS_RUN - 1) / LSN_RS_RUN;
+  if (runs > 0x7FFFFFFFull || k.n_out + k.sf_off > 0xFFFFFFFFull) throw std::runtime_error(std::string(kernel) + ": launch too long");
+  A.raw = src.raw; A.buf_base = src.buf_base; A.buf_len = src.buf_len; A.base_hi = k.base_hi; A.base_lo = k.base_lo; A.d_lo = k.d_lo; A.d_hi = k.d_hi; A.taps = k.taps; A.span = k.span;
+  A.nant = src.nant; A.sflen = k.sflen; A.sf_off = k.sf_off; A.n_out = k.n_out; A.scale = src.scale; A.bank = (const float2*)k.bank; A.rot = k.rot; A.out = k.out;
+  A.w = k.w; A.nco = k.nco; A.ring_mask = src.ring_samples ? (uint32_t)(src.ring_samples - 1) : 0;
+  return runs;
 }
 
-// the cells of one launch: raw, buf_base, buf_len, fmt, scale and nant are the recording's and shared; everything else is the cell's own (lsn_resample.h).
-// A cell with n_out = 0 takes no part.
-// (the argument block of k_resample_cells and k_resample_ring: ring_mask = 0 for the former.  false: no cell takes part)
-static bool resample_cells_args(const void* raw, float scale, uint32_t ring_mask, int64_t buf_base, uint64_t buf_len, uint32_t nant, const LsnResampleCell* cells, uint32_t n_cells,
-                                LsnResampleCellsArgs& P, dim3& g, size_t& lds)
+// the instantiation of kernel template K for sample format fmt (K<FMT, REST...>)
+#define LSN_RS_LAUNCH_FMT(K, REST, fmt, g, lds, s, args)                    \
+  do {                                                                      \
+    if ((fmt) == 1) LSN_LAUNCH((K<1 REST>), g, dim3(256), lds, s, args);    \
+    else if ((fmt) == 2) LSN_LAUNCH((K<2 REST>), g, dim3(256), lds, s, args); \
+    else LSN_LAUNCH((K<0 REST>), g, dim3(256), lds, s, args);               \
+  } while (0)
+#define LSN_RS_COMMA ,
+
+// one cell out of a linear buffer.  cell.nco != null: the mixing instantiations with tuning word w; null: the plain ones, as before the mixer existed
+void lsn_launch_resample(const LsnResampleSource& src, const LsnResampleCell& cell, hipStream_t s)
 {
-  if (n_cells > LSN_RS_MAX_CELLS || buf_base < 0) throw std::runtime_error("k_resample_cells: bad geometry");
+  if (!cell.n_out) return;
+  if (src.ring_samples) throw std::runtime_error("k_resample: reads a linear buffer");
+  LsnResampleArgs A;
+  const dim3 g((uint32_t)resample_args("k_resample", src, cell, A), src.nant);
+  const size_t lds = (size_t)cell.span * sizeof(float2);
+  if (cell.nco) LSN_RS_LAUNCH_FMT(k_resample, LSN_RS_COMMA true, src.fmt, g, lds, s, A);
+  else LSN_RS_LAUNCH_FMT(k_resample, LSN_RS_COMMA false, src.fmt, g, lds, s, A);
+}
+
+// the cells of one launch: the source is the recording's and shared, everything else is the cell's own.  A cell with n_out = 0 takes no part; no launch when
+// none does.  Out of a ring: ring_samples a power of two (at most 2^32) that holds the window
+void lsn_launch_resample_cells(const LsnResampleSource& src, const LsnResampleCell* cells, uint32_t n_cells, hipStream_t s)
+{
+  const uint64_t rn = src.ring_samples;
+  const char* kernel = rn ? "k_resample_ring" : "k_resample_cells";
+  if (rn && ((rn & (rn - 1)) || rn > (1ull << 32) || src.buf_len > rn)) throw std::runtime_error("k_resample_ring: bad ring");
+  if (n_cells > LSN_RS_MAX_CELLS || src.buf_base < 0) throw std::runtime_error(std::string(kernel) + ": bad geometry");
+  LsnResampleCellsArgs P;
   memset(&P, 0, sizeof(P));
   uint32_t n = 0, span = 0;
   uint64_t runs = 0;
   for (uint32_t c = 0; c < n_cells; c++) {
-    const LsnResampleCell& k = cells[c];
-    if (!k.n_out) continue;
-    if (k.taps < 2 || (k.taps & 1) || k.span < k.taps || (size_t)k.span * sizeof(float2) > 64 * 1024 || !k.sflen) throw std::runtime_error("k_resample_cells: bad geometry");
-    const uint64_t r = (k.n_out + LSN_RS_RUN - 1) / LSN_RS_RUN;
-    if (r > 0x7FFFFFFFull || k.n_out + k.sf_off > 0xFFFFFFFFull) throw std::runtime_error("k_resample_cells: launch too long");
-    LsnResampleArgs& A = P.c[n++];
-    A.raw = raw; A.buf_base = buf_base; A.buf_len = buf_len; A.base_hi = k.base_hi; A.base_lo = k.base_lo; A.d_lo = k.d_lo; A.d_hi = k.d_hi; A.taps = k.taps; A.span = k.span;
-    A.nant = nant; A.sflen = k.sflen; A.sf_off = k.sf_off; A.n_out = k.n_out; A.scale = scale; A.bank = (const float2*)k.bank; A.rot = k.rot; A.out = k.out;
-    A.w = k.w; A.nco = k.nco; A.ring_mask = ring_mask;
-    runs = std::max(runs, r);
-    span = std::max(span, k.span);
+    if (!cells[c].n_out) continue;
+    runs = std::max(runs, resample_args(kernel, src, cells[c], P.c[n++]));
+    span = std::max(span, cells[c].span);
   }
-  if (!n) return false;
-  g = dim3((uint32_t)runs, nant, n);
-  lds = (size_t)span * sizeof(float2);
-  return true;
+  if (!n) return;
+  const dim3 g((uint32_t)runs, src.nant, n);
+  const size_t lds = (size_t)span * sizeof(float2);
+  if (!rn) LSN_RS_LAUNCH_FMT(k_resample_cells, , src.fmt, g, lds, s, P);
+  else LSN_RS_LAUNCH_FMT(k_resample_ring, , src.fmt, g, lds, s, P);
 }
 
-void lsn_launch_resample_cells(const void* raw, uint32_t fmt, float scale, int64_t buf_base, uint64_t buf_len, uint32_t nant, const LsnResampleCell* cells, uint32_t n_cells,
-                               hipStream_t s)
-{
-  LsnResampleCellsArgs P;
-  dim3 g;
-  size_t lds;
-  if (!resample_cells_args(raw, scale, 0, buf_base, buf_len, nant, cells, n_cells, P, g, lds)) return;
-  if (fmt == 1) LSN_LAUNCH((k_resample_cells<1>), g, dim3(256), lds, s, P);
-  else if (fmt == 2) LSN_LAUNCH((k_resample_cells<2>), g, dim3(256), lds, s, P);
-  else LSN_LAUNCH((k_resample_cells<0>), g, dim3(256), lds, s, P);
-}
-
-// ring: ring_samples samples per antenna, a power of two (at most 2^32); the samples [buf_base, buf_base + buf_len) of the recording are in their slots, so
-// buf_len <= ring_samples.  Everything else as lsn_launch_resample_cells.
-void lsn_launch_resample_ring(const void* ring, uint64_t ring_samples, uint32_t fmt, float scale, int64_t buf_base, uint64_t buf_len, uint32_t nant, const LsnResampleCell* cells,
-                              uint32_t n_cells, hipStream_t s)
-{
-  if (!ring_samples || (ring_samples & (ring_samples - 1)) || ring_samples > (1ull << 32) || buf_len > ring_samples) throw std::runtime_error("k_resample_ring: bad ring");
-  LsnResampleCellsArgs P;
-  dim3 g;
-  size_t lds;
-  if (!resample_cells_args(ring, scale, (uint32_t)(ring_samples - 1), buf_base, buf_len, nant, cells, n_cells, P, g, lds)) return;
-  if (fmt == 1) LSN_LAUNCH((k_resample_ring<1>), g, dim3(256), lds, s, P);
-  else if (fmt == 2) LSN_LAUNCH((k_resample_ring<2>), g, dim3(256), lds, s, P);
-  else LSN_LAUNCH((k_resample_ring<0>), g, dim3(256), lds, s, P);
-}
