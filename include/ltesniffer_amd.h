@@ -447,7 +447,7 @@ int lsn_resample_cells_ring(int device, const void* in, uint64_t n_in, uint64_t 
  *             samples host-to-device straight to their slots (two copies when it crosses the end of the ring, a long push in pieces): no host staging buffer, no
  *             memcpy on the caller's thread.  A gap - the radio reported dropped samples - is a memset of the same slots: zeros arrive, positions stay.
  *   when      after `pushed` samples cell c has floor(outputs whose whole input span lies in front of pushed / subframe length) complete subframes, capped by
- *             max_subframes - the rule a file's subframes are counted by.  A cell is submitted when block_subframes of them are not submitted yet (fewer: the last
+ *             max_subframes - the rule a file's subframes are counted by (with a channel filter: in front of pushed - L, lsn_file_cells_span's rule).  A cell is submitted when block_subframes of them are not submitted yet (fewer: the last
  *             ones in front of max_subframes, or a flush): one k_resample_ring launch for all cells that are due, into block buffers of their Phys (those of
  *             lsn_phy_prepare_file), then one submit per Phy in the order of the list.
  *   ring      nothing at or behind the oldest sample a cell still needs - the first input sample of its next subframe, minimised over the cells that have not run
@@ -461,11 +461,16 @@ int lsn_resample_cells_ring(int device, const void* in, uint64_t n_in, uint64_t 
  * When a Phy fails nothing more is submitted to any of them; the next push or flush returns its code and lsn_stream_status shows which cell it was.  Push, gap
  * and flush on a failed stream return that code and do nothing; on a NULL (closed) stream LSN_ERROR_INVALID_INPUTS.
  * Refused at open with LSN_ERROR_INVALID_INPUTS - nothing is allocated, every Phy stays usable: everything lsn_file_process_cells refuses; start_tti =
- * LSN_TTI_FROM_MIB (the head of a live stream goes through lsn_carrier_scan and lsn_phy_mib_decode first, and that chain yields the TTI); a Phy with a channel
- * filter set (k_chan_fir does not read the ring yet: refused, not dropped); a Phy that belongs to an open stream; cfg->device other than the Phys'; block_subframes
+ * LSN_TTI_FROM_MIB (the head of a live stream goes through lsn_carrier_scan and lsn_phy_mib_decode first, and that chain yields the TTI); a channel filter
+ * (below) on some of the Phys but not on all, or a stop band the filter's design refuses; a Phy that belongs to an open stream; cfg->device other than the Phys'; block_subframes
  * above LSN_FILE_BLOCK; ring_samples not a power of two, above 2^32, or shorter than one block of every cell - which is also how cells whose starts lie further
  * apart than the ring less one block are refused.
- * Not on a stream: the channel filter, LSN_TTI_FROM_MIB, the worker pool, cells on several GPUs.  Rate and offsets are inputs, as for files; a stream that asks
+ * The channel filter (lsn_phy_set_channel_filter): a stream opened on Phys that have it set runs the file pass's two stages - ONE
+ * k_chan_fir_ring launch reads the ring for all cells that are due and writes every cell's y1 into an intermediate of its Phy, then one k_resample per cell reads
+ * that - and submits, per cell, exactly the subframes and records of lsn_file_process_cells with the filter on the same bytes.  A cell's input span is L samples
+ * wider on both sides: oldest_needed, block_input, the default ring and the ring checks (lsn_stream_track's too) count with the widened spans.  The setting is read
+ * at open; changing it on a Phy of an open stream leaves that stream as it was opened and counts for the next open or file replay.
+ * Not on a stream: LSN_TTI_FROM_MIB, the worker pool, cells on several GPUs, a mix of filtered and unfiltered cells.  Rate and offsets are inputs, as for files; a stream that asks
  * for it (lsn_stream_track, below) follows the sample clock from there with a timing loop per cell.  File replays and the worker pool do not track. */
 typedef struct lsn_stream lsn_stream_t;
 typedef struct {
@@ -505,6 +510,11 @@ int lsn_stream_flush(lsn_stream_t* s);
 int lsn_stream_status(lsn_stream_t* s, lsn_stream_status_t* out);
 int lsn_stream_close(lsn_stream_t* s);
 int lsn_stream_span(const lsn_stream_cfg_t* cfg, const lsn_file_cell_t* cells, uint32_t n_cells, uint64_t pushed_samples, lsn_stream_span_t* out);
+/* lsn_stream_span reads the channel filter's setting from a non-NULL phy, as lsn_file_cells_span does.  The plan of a filtered stream without a Phy: the same call
+ * with stopband_hz[n_cells], a non-zero entry being that cell's stop band (lsn_phy_set_channel_filter's value); NULL or all zero: lsn_stream_span.  Every cell
+ * or none; a stop band the design refuses is refused. */
+int lsn_stream_span_filtered(const lsn_stream_cfg_t* cfg, const lsn_file_cell_t* cells, uint32_t n_cells, const double* stopband_hz, uint64_t pushed_samples,
+                             lsn_stream_span_t* out);
 /* lsn_stream_span describes the NOMINAL plan: a tracked stream (below) counts a cell's subframes by the positions its loop has decided, which leave the plan's by
  * lsn_stream_track_status_t.position_drift. */
 
@@ -531,7 +541,8 @@ int lsn_stream_span(const lsn_stream_cfg_t* cfg, const lsn_file_cell_t* cells, u
  *             step_(h+2) = step_nominal + (int128) nearbyint(ldexp(rate_in / rate_out, 64) * c / seglen), in doubles, one rounding per operation.
  *             lost is set after lost_after consecutive invalid segments: the loop holds its rate and keeps measuring; the next valid measurement clears it.
  * lsn_stream_track refuses with LSN_ERROR_INVALID_INPUTS, the stream unchanged and usable: after a push; gains not finite or not positive; max_ppm outside
- * (0, 120]; |initial_ppm| > max_ppm or not finite; cfo_hz not finite; a ring shorter than block_input recomputed with every step widened by 1 + max_ppm 1e-6. */
+ * (0, 120]; |initial_ppm| > max_ppm or not finite; cfo_hz not finite; a ring shorter than block_input recomputed with every step widened by 1 + max_ppm 1e-6
+ * (and, on a filtered stream, every cell's span by its 2 L). */
 typedef struct {
   uint32_t struct_size;      /* sizeof(lsn_stream_track_cfg_t); every other size is refused */
   uint32_t lost_after;       /* 0 = 40 */
@@ -592,7 +603,7 @@ int lsn_pss_timing(int device, int blocks_on_device, const lsn_pss_timing_cell_t
  * resampler's rule |center_offset_hz| + B <= R / 2; everything else is LSN_ERROR_INVALID_INPUTS.
  *
  * lsn_phy_set_channel_filter: stopband_hz of this Phy's file replays (lsn_phy_process_file, lsn_phy_process_file_rate, lsn_file_process_cells; LSN_TTI_FROM_MIB
- * resamples through the same two stages); 0 = off, the default.  Sticky, like lsn_phy_set_sampling.  Negative, NaN or infinite: LSN_ERROR_INVALID_INPUTS; the
+ * resamples through the same two stages) and of the streams opened on it from then on (lsn_stream_open); 0 = off, the default.  Sticky, like lsn_phy_set_sampling.  Negative, NaN or infinite: LSN_ERROR_INVALID_INPUTS; the
  * value is checked against rate and bandwidth when a replay starts (a refused replay decodes nothing and leaves the Phy usable).  With the filter set a file at
  * the Phy's own rate goes through both stages too.  In lsn_file_process_cells either every cell's Phy has a filter or none has: a mix is refused.
  * lsn_file_cells_span reads the setting from a non-NULL phy (the block's input is L samples wider on both sides); with phy NULL it plans the unfiltered pass. */
@@ -619,6 +630,15 @@ typedef struct {
  * in_base = out_first and center_offset_hz = 0.  Samples in front of sample 0 of the recording read as zeros; every other sample in [out_first - L, out_first +
  * n_out + L) must lie inside in, otherwise LSN_ERROR_INVALID_INPUTS. */
 int lsn_channel_filter(int device, const void* in, int in_on_device, uint64_t n_in, const lsn_channel_filter_cfg_t* cfg, float* out, int out_on_device, uint64_t n_out);
+/* k_chan_fir_ring without a Phy, the sibling of lsn_resample_cells_ring for stage 1 of a filtered stream: the host input window in[0 .. n_in) = samples in_base ..
+ * in_base + n_in of the recording is placed at its slots of a device ring of ring_samples samples per antenna (sample n at slot n mod ring_samples; every other
+ * slot holds a NaN pattern, so that a read outside the window shows in the outputs), and up to LSN_FILE_MAX_CELLS filters run out of the ring in ONE launch.
+ * cfgs[c]: the cell's filter and out_first; antennas, format, scale, rate and in_base are the recording's and must agree.  outs[c]: [n_out[c]][antenna] cf32
+ * (host), outs[c][0] = y1[out_first] - lsn_channel_filter's with the same arguments, bit for bit; n_out[c] = 0: the cell takes no part.  Refused
+ * (LSN_ERROR_INVALID_INPUTS, the outputs untouched): whatever lsn_channel_filter refuses, n_cells 0 or above LSN_FILE_MAX_CELLS, ring_samples not a power of two
+ * or above 2^32, n_in > ring_samples. */
+int lsn_channel_filter_ring(int device, const void* in, uint64_t n_in, uint64_t ring_samples, const lsn_channel_filter_cfg_t* cfgs, uint32_t n_cells, float* const* outs,
+                            const uint64_t* n_out);
 /* in_lo / in_hi: the input samples n_out outputs from out_first read; max_out: outputs from out_first on whose input lies in front of in_end; taps = 2 L + 1.  No GPU. */
 int lsn_channel_filter_span(const lsn_channel_filter_cfg_t* cfg, uint64_t n_out, uint64_t in_end, lsn_resample_span_t* out);
 /* The stop band of every cell of a recording from its neighbours: S_i = min over j != i of (|f_j - f_i| - B_j), B_j = 15 kHz (6 nof_prb_j + 1), capped at

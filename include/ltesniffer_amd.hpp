@@ -267,6 +267,7 @@ inline int cellSearchRates(const cf_t* iq, uint64_t nof_samples, uint32_t nof_pr
 // A live wideband stream pushed in host buffers (lsn_stream_*): the place of the reference's receive loop (srsran_ue_sync_zerocopy per subframe,
 // LTESniffer_Core.cc:365) for a radio that delivers more than one cell's worth of bandwidth.  cells: lsn_file_cell_t, each with phy = Phy::handle().
 // Throws std::invalid_argument when the library refuses the stream; push / gap / flush return the library's code.  Destroy it before its Phys.
+// Phys with a channel filter set (lsn_phy_set_channel_filter on Phy::handle(), every cell's or none's) get the file pass's two stages out of the ring.
 class Stream {
 public:
   Stream(const lsn_stream_cfg_t& cfg, std::vector<lsn_file_cell_t> cells)
@@ -289,6 +290,14 @@ public:
   int track(lsn_stream_track_cfg_t cfg) { cfg.struct_size = sizeof(cfg); return lsn_stream_track(h, &cfg); }
   lsn_stream_track_status_t track_status() { lsn_stream_track_status_t s{}; s.struct_size = sizeof(s); lsn_stream_track_status(h, &s); return s; }
   int close() { const int r = h ? lsn_stream_close(h) : LSN_SUCCESS; h = nullptr; return r; }
+  // the plan without a device or a Phy; stopband_hz: empty, or one entry per cell (lsn_stream_span_filtered)
+  static int span(lsn_stream_cfg_t cfg, std::vector<lsn_file_cell_t> cells, const std::vector<double>& stopband_hz, uint64_t pushed_samples, lsn_stream_span_t& out)
+  {
+    cfg.struct_size = sizeof(cfg);
+    for (auto& k : cells) k.struct_size = sizeof(k);
+    if (!stopband_hz.empty() && stopband_hz.size() != cells.size()) return LSN_ERROR_INVALID_INPUTS;
+    return lsn_stream_span_filtered(&cfg, cells.data(), (uint32_t)cells.size(), stopband_hz.empty() ? nullptr : stopband_hz.data(), pushed_samples, &out);
+  }
 private:
   lsn_stream_t* h = nullptr;
 };

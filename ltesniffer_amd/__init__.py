@@ -45,7 +45,8 @@ EXPORTS = ["lsn_phy_create", "lsn_phy_destroy", "lsn_phy_set_cell", "lsn_phy_get
            "lsn_carrier_scan_plan", "lsn_carrier_scan_decide", "lsn_carrier_scan", "lsn_file_carrier_scan", "lsn_carrier_channel", "lsn_carrier_channel_span",
            "lsn_phy_set_channel_filter", "lsn_channel_filter_design", "lsn_channel_filter", "lsn_channel_filter_span", "lsn_cells_stopbands",
            "lsn_resample_cells_ring", "lsn_stream_open", "lsn_stream_push", "lsn_stream_flush", "lsn_stream_status", "lsn_stream_close", "lsn_stream_span",
-           "lsn_stream_track", "lsn_stream_track_status", "lsn_stream_track_step", "lsn_pss_timing", "lsn_pss_timing_error"]
+           "lsn_stream_track", "lsn_stream_track_status", "lsn_stream_track_step", "lsn_pss_timing", "lsn_pss_timing_error",
+           "lsn_channel_filter_ring", "lsn_stream_span_filtered"]
 
 RATES_3GPP, RATES_SRSRAN = 0, 1   # LSN_RATES_*: sampling mode of a Phy / of a cell search
 
@@ -493,6 +494,8 @@ def lib():
         L.lsn_phy_set_channel_filter.argtypes = [C.c_void_p, C.c_double]
         L.lsn_channel_filter_design.argtypes = [C.c_double, C.c_double, C.c_double, C.POINTER(ChannelFilterDesign), C.c_void_p, C.c_uint32]
         L.lsn_channel_filter.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.POINTER(ChannelFilterCfg), C.c_void_p, C.c_int, C.c_uint64]
+        L.lsn_channel_filter_ring.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(ChannelFilterCfg), C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        L.lsn_stream_span_filtered.argtypes = [C.POINTER(StreamCfg), C.POINTER(FileCell), C.c_uint32, C.POINTER(C.c_double), C.c_uint64, C.POINTER(StreamSpan)]
         L.lsn_channel_filter_span.argtypes = [C.POINTER(ChannelFilterCfg), C.c_uint64, C.c_uint64, C.POINTER(ResampleSpan)]
         L.lsn_cells_stopbands.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.c_uint32, C.c_double, C.POINTER(C.c_double)]
         _lib = L
@@ -638,10 +641,10 @@ class Phy:
         return int(lib().lsn_phy_get_sampling(self._h))
 
     def set_channel_filter(self, stopband_hz):
-        """lsn_phy_set_channel_filter: this Phy's file replays (process_file, process_file_rate, process_file_cells) run a sharp channel filter at the recording's
-        rate in front of the resampler - everything from stopband_hz on, relative to the cell's carrier, is 80 dB down (a neighbour carrier: the distance to its
-        nearest occupied edge, cells_stopbands).  0: off (the default).  Sticky; checked against rate and bandwidth when a replay starts.  False: refused
-        (negative or not finite)"""
+        """lsn_phy_set_channel_filter: this Phy's file replays (process_file, process_file_rate, process_file_cells) and the Streams opened on it from then on run a
+        sharp channel filter at the recording's rate in front of the resampler - everything from stopband_hz on, relative to the cell's carrier, is 80 dB down (a
+        neighbour carrier: the distance to its nearest occupied edge, cells_stopbands).  0: off (the default).  Sticky; checked against rate and bandwidth when a
+        replay starts or a Stream opens; an open Stream stays as it was opened.  False: refused (negative or not finite)"""
         return lib().lsn_phy_set_channel_filter(self._h, float(stopband_hz)) == LSN_SUCCESS
 
     def setCell(self, nof_prb, nof_ports, cell_id, phich_resources=0, cp=0):
@@ -1154,6 +1157,32 @@ def channel_filter(iq, rate_in, passband_hz, stopband_hz, n_out=None, center_off
     return out
 
 
+def channel_filter_ring(iq, rate_in, cells, ring_samples, in_base=0, sample_format=FILE_CF32, sample_scale=0.0, device=0):
+    """lsn_channel_filter_ring: stage 1 through the kernel a filtered Stream runs (k_chan_fir_ring).  The window iq = samples in_base .. in_base + len(iq) of the
+    recording is placed into a device ring of ring_samples samples (a power of two), sample n at slot n mod ring_samples, every other slot holding a NaN pattern,
+    and up to 8 filters run out of the ring in ONE launch.  cells: a list of dict(passband_hz, stopband_hz, n_out[, center_offset_hz, out_first]) -> a list of
+    complex64 [n_out][antenna] arrays, each bit for bit channel_filter's with that cell's arguments.  Raises ValueError when the library refuses the call (the
+    outputs, available as the exception's .outs, are untouched)"""
+    iq = _scan_input(iq, sample_format)
+    n_in, nant = iq.shape[0], iq.shape[1]
+    n = len(cells)
+    cfgs = (ChannelFilterCfg * max(n, 1))()
+    counts = (C.c_uint64 * max(n, 1))()
+    outs = []
+    for i, c in enumerate(cells):
+        cfgs[i] = _channel_filter_cfg(nant, rate_in, c["passband_hz"], c["stopband_hz"], c.get("center_offset_hz", 0.0), in_base, c.get("out_first", 0), sample_format, sample_scale)
+        counts[i] = int(c["n_out"])
+        outs.append(np.zeros((int(c["n_out"]), nant), dtype=np.complex64))
+    ptrs = (C.c_void_p * max(n, 1))(*[o.ctypes.data for o in outs])
+    rc = lib().lsn_channel_filter_ring(device, iq.ctypes.data, n_in, int(ring_samples), cfgs, n, ptrs, counts)
+    if rc == LSN_ERROR_INVALID_INPUTS:
+        err = ValueError("channel_filter_ring: refused")
+        err.outs = outs
+        raise err
+    _check(rc, "lsn_channel_filter_ring")
+    return outs
+
+
 def cells_stopbands(carriers_hz, nof_prb, rate_in):
     """lsn_cells_stopbands (needs no GPU): the stopband_hz of every cell of a recording from its neighbours - the distance from its carrier to the nearest occupied
     edge of another cell, capped at rate_in / 2; 0.0 (no filter) for a cell that has no neighbour.  Raises ValueError when a neighbour is too close for the filter"""
@@ -1230,8 +1259,10 @@ def _stream_cfg(sample_rate, nof_antennas, sample_format, sample_scale, block_su
     return StreamCfg(C.sizeof(StreamCfg), int(device), float(sample_rate), int(nof_antennas), int(sample_format), float(sample_scale), int(block_subframes), int(ring_samples))
 
 
-def stream_span(sample_rate, cells, pushed, nof_antennas=1, sample_format=FILE_CF32, sample_scale=0.0, block_subframes=0, ring_samples=0):
-    """lsn_stream_span (needs no GPU): the plan of a Stream after `pushed` samples in all.  cells as file_cells_span.  -> dict(ring_samples: the given one or the
+def stream_span(sample_rate, cells, pushed, nof_antennas=1, sample_format=FILE_CF32, sample_scale=0.0, block_subframes=0, ring_samples=0, stopbands=None):
+    """lsn_stream_span (needs no GPU): the plan of a Stream after `pushed` samples in all.  cells as file_cells_span.  stopbands (lsn_stream_span_filtered): None,
+    or one stopband_hz per cell - the plan of the stream with the channel filter on, without a Phy: every span L samples wider on both sides, a cell's subframes
+    counted in front of pushed - L; every cell or none (0.0: none), and all 0.0 is None.  With (phy, dict) cells the Phys' own setting counts, as in file_cells_span.  -> dict(ring_samples: the given one or the
     default; block_input: input samples of one block of every cell, which the ring must hold; block_subframes; per cell subframes_complete - what a flush at that
     point has submitted in all -, subframes_submitted - what a stream that was never flushed has - and taps; oldest_needed / oldest_needed_flushed: the oldest
     sample a cell still needs in the two cases).  Raises ValueError when the library refuses cells or ring"""
@@ -1240,7 +1271,13 @@ def stream_span(sample_rate, cells, pushed, nof_antennas=1, sample_format=FILE_C
         arr[i] = _file_cell(*c) if isinstance(c, tuple) else _file_cell(None, c)
     cfg = _stream_cfg(sample_rate, nof_antennas, sample_format, sample_scale, block_subframes, ring_samples, 0)
     sp = StreamSpan()
-    rc = lib().lsn_stream_span(C.byref(cfg), arr, len(cells), int(pushed), C.byref(sp))
+    if stopbands is None:
+        rc = lib().lsn_stream_span(C.byref(cfg), arr, len(cells), int(pushed), C.byref(sp))
+    else:
+        if len(stopbands) != len(cells):
+            raise ValueError("stream_span: stopbands needs one value per cell")
+        stop = (C.c_double * max(len(cells), 1))(*[float(v) for v in stopbands])
+        rc = lib().lsn_stream_span_filtered(C.byref(cfg), arr, len(cells), stop, int(pushed), C.byref(sp))
     if rc == LSN_ERROR_INVALID_INPUTS:
         raise ValueError("stream: refused")
     _check(rc, "lsn_stream_span")
@@ -1318,7 +1355,9 @@ def pss_timing(cells, device=0):
 class Stream:
     """lsn_stream_*: the cells of a live wideband stream that arrives in host buffers.  cells: a list of (phy, dict(...)) with the keys of process_file_cells
     (center_offset_hz, start_tti - not TTI_FROM_MIB -, offset_time / offset_time_frac: the start of the cell's subframe 0 counted from the first sample ever
-    pushed, offset_freq, max_subframes, update_meta_period).  The raw samples live in a device ring (ring_samples, a power of two; 0: chosen by the library);
+    pushed, offset_freq, max_subframes, update_meta_period, stopband_hz).  stopband_hz (cells_stopbands) sets the channel filter on that Phy as
+    set_channel_filter does - every cell or none: the stream then runs the file pass's two stages out of the ring (k_chan_fir_ring, then k_resample per cell) and
+    the records are those of process_file_cells with the filter.  The raw samples live in a device ring (ring_samples, a power of two; 0: chosen by the library);
     a cell is submitted to its Phy whenever block_subframes complete subframes of it have arrived (0: the file source's block size).  The Phys' records are
     those of process_file_cells on a file of the same bytes, however the stream is cut into pushes.  Raises ValueError when the library refuses the stream
     (nothing is allocated, every Phy stays usable).  Close the stream before its Phys; a Phy that is closed first closes the stream."""

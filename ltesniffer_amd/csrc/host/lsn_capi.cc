@@ -551,8 +551,9 @@ int lsn_phy_process_file_rate(lsn_phy_t* phy, const char* path, const lsn_file_c
 // What lsn_file_process_cells and lsn_file_cells_span check alike, and the cells' plans (formed by file_rate_plan, as lsn_phy_process_file_rate forms its one).
 // need_phy: every cell has a Phy (one engine, its cell set, fcfg's antennas, all on one device, none twice); otherwise a null phy takes nof_prb / rates.
 // filt[c].L != 0: the cell's Phy has a channel filter set - stage 1 carries the offset and plans[c] is the plan without it; all cells or none.
+// stopband_hz (lsn_stream_span_filtered; null: none): a non-zero entry is the cell's stop band in place of its Phy's setting, so that a plan needs no Phy.
 static int file_cells_plans(const lsn_file_cfg_t* fc, double sample_rate_hz, const lsn_file_cell_t* cells, uint32_t n, bool need_phy, std::vector<lsn::ResamplePlan>& plans,
-                            std::vector<uint32_t>& sflen, std::vector<lsn::ChanFilter>& filt)
+                            std::vector<uint32_t>& sflen, std::vector<lsn::ChanFilter>& filt, const double* stopband_hz = nullptr)
 {
   if (!fc || !cells || n < 1 || n > LSN_FILE_MAX_CELLS) return LSN_ERROR_INVALID_INPUTS;
   if (fc->nof_antennas < 1 || fc->nof_antennas > 8 || fc->offset_time_samples != 0 || fc->offset_freq_hz != 0.0f || !lsn_sample_format(fc->sample_format, fc->sample_scale).valid)
@@ -576,7 +577,7 @@ static int file_cells_plans(const lsn_file_cfg_t* fc, double sample_rate_hz, con
       if (!N) return LSN_ERROR_INVALID_INPUTS;
     }
     if (!std::isfinite(k.offset_freq_hz)) return LSN_ERROR_INVALID_INPUTS;
-    const double stop = k.phy ? k.phy->engine->channelFilter() : 0.0;
+    const double stop = stopband_hz && stopband_hz[c] != 0.0 ? stopband_hz[c] : k.phy ? k.phy->engine->channelFilter() : 0.0;
     if (stop != 0.0) {
       const int rf = filt[c].init(sample_rate_hz, 15000.0 * (6.0 * (double)nof_prb + 1.0), stop, k.center_offset_hz);
       if (rf != LSN_SUCCESS) return rf;
@@ -644,17 +645,17 @@ int lsn_file_process_cells(const char* path, const lsn_file_cfg_t* cfg, double s
 
 // ---- a live stream pushed in host buffers (lsn_stream.h: the plan; lsn_stream_ring.h: the device ring) ----
 // What lsn_stream_open and lsn_stream_span check alike, through file_cells_plans - the file pass's own checks and plans - and the stream's refusals on top.
-static int stream_plans(const lsn_stream_cfg_t* cfg, const lsn_file_cell_t* cells, uint32_t n, bool need_phy, std::vector<lsn::ResamplePlan>& plans, std::vector<uint32_t>& sflen,
-                        uint32_t& blk, uint64_t& ring_samples)
+// filt: the cells' channel filters (L = 0: none; all cells or none, and a stop band ChanFilter::init refuses is refused here), DESIGN 3.1j.
+static int stream_plans(const lsn_stream_cfg_t* cfg, const lsn_file_cell_t* cells, uint32_t n, bool need_phy, const double* stopband_hz, std::vector<lsn::ResamplePlan>& plans,
+                        std::vector<uint32_t>& sflen, std::vector<lsn::ChanFilter>& filt, uint32_t& blk, uint64_t& ring_samples)
 {
   if (!cfg || cfg->struct_size != sizeof(lsn_stream_cfg_t)) return LSN_ERROR_INVALID_INPUTS;
   lsn_file_cfg_t fc{};
   fc.nof_antennas = cfg->nof_antennas; fc.offset_time_samples = 0; fc.offset_freq_hz = 0.0f; fc.sample_format = cfg->sample_format; fc.sample_scale = cfg->sample_scale;
-  std::vector<lsn::ChanFilter> filt;
-  const int r = file_cells_plans(&fc, cfg->sample_rate_hz, cells, n, need_phy, plans, sflen, filt);
+  const int r = file_cells_plans(&fc, cfg->sample_rate_hz, cells, n, need_phy, plans, sflen, filt, stopband_hz);
   if (r != LSN_SUCCESS) return r;
   for (uint32_t c = 0; c < n; c++) {
-    if (cells[c].start_tti == LSN_TTI_FROM_MIB || filt[c].L) return LSN_ERROR_INVALID_INPUTS;
+    if (cells[c].start_tti == LSN_TTI_FROM_MIB) return LSN_ERROR_INVALID_INPUTS;
     if (cells[c].phy && (cells[c].phy->stream || cells[c].phy->engine->device() != cfg->device)) return LSN_ERROR_INVALID_INPUTS;
   }
   uint32_t blk_geom;
@@ -663,7 +664,7 @@ static int stream_plans(const lsn_stream_cfg_t* cfg, const lsn_file_cell_t* cell
   blk = cfg->block_subframes ? cfg->block_subframes : blk_geom;
   if (blk > blk_geom) return LSN_ERROR_INVALID_INPUTS;
   lsn::StreamCellPlan sp[LSN_FILE_MAX_CELLS];
-  for (uint32_t c = 0; c < n; c++) { sp[c].rs = &plans[c]; sp[c].sflen = sflen[c]; sp[c].max_subframes = cells[c].max_subframes; }
+  for (uint32_t c = 0; c < n; c++) { sp[c].rs = &plans[c]; sp[c].sflen = sflen[c]; sp[c].max_subframes = cells[c].max_subframes; sp[c].pre = filt[c].L; }
   ring_samples = cfg->ring_samples;
   return lsn::stream_ring_check(sp, n, blk, ring_samples);
 }
@@ -676,19 +677,25 @@ struct lsn_stream {
 
 int lsn_stream_span(const lsn_stream_cfg_t* cfg, const lsn_file_cell_t* cells, uint32_t n_cells, uint64_t pushed, lsn_stream_span_t* out)
 {
+  return lsn_stream_span_filtered(cfg, cells, n_cells, nullptr, pushed, out);
+}
+
+int lsn_stream_span_filtered(const lsn_stream_cfg_t* cfg, const lsn_file_cell_t* cells, uint32_t n_cells, const double* stopband_hz, uint64_t pushed, lsn_stream_span_t* out)
+{
   return lsn::guarded([&]() -> int {
     std::vector<lsn::ResamplePlan> plans;
     std::vector<uint32_t> sflen;
+    std::vector<lsn::ChanFilter> filt;
     uint32_t blk = 0;
     uint64_t ring = 0;
-    const int r = stream_plans(cfg, cells, n_cells, false, plans, sflen, blk, ring);
+    const int r = stream_plans(cfg, cells, n_cells, false, stopband_hz, plans, sflen, filt, blk, ring);
     if (r != LSN_SUCCESS) return r;
     if (!out || pushed >= (1ull << 62)) return LSN_ERROR_INVALID_INPUTS;
     lsn::StreamCellPlan sp[LSN_FILE_MAX_CELLS];
     uint64_t blocked[LSN_FILE_MAX_CELLS] = {}, complete[LSN_FILE_MAX_CELLS] = {};
     memset(out, 0, sizeof(*out));
     for (uint32_t c = 0; c < n_cells; c++) {
-      sp[c].rs = &plans[c]; sp[c].sflen = sflen[c]; sp[c].max_subframes = cells[c].max_subframes;
+      sp[c].rs = &plans[c]; sp[c].sflen = sflen[c]; sp[c].max_subframes = cells[c].max_subframes; sp[c].pre = filt[c].L;
       complete[c] = lsn::stream_cell_complete(sp[c], pushed);
       // a stream that was never flushed: whole blocks, and the last subframes in front of max_subframes
       blocked[c] = complete[c] / blk * blk;
@@ -709,15 +716,16 @@ int lsn_stream_open(const lsn_stream_cfg_t* cfg, lsn_file_cell_t* cells, uint32_
   return lsn::guarded([&]() -> int {
     std::vector<lsn::ResamplePlan> plans;
     std::vector<uint32_t> sflen;
+    std::vector<lsn::ChanFilter> filt;
     uint32_t blk = 0;
     uint64_t ring = 0;
-    const int r = stream_plans(cfg, cells, n_cells, true, plans, sflen, blk, ring);
+    const int r = stream_plans(cfg, cells, n_cells, true, nullptr, plans, sflen, filt, blk, ring);
     if (r != LSN_SUCCESS) return r;
     std::vector<lsn::StreamRing::CellSpec> specs(n_cells);
     std::unique_ptr<lsn_stream> s(new lsn_stream());
     for (uint32_t c = 0; c < n_cells; c++) {
       specs[c].e = cells[c].phy->engine.get(); specs[c].plan = std::move(plans[c]); specs[c].offset_freq_hz = cells[c].offset_freq_hz; specs[c].start_tti = cells[c].start_tti;
-      specs[c].update_meta_period = cells[c].update_meta_period; specs[c].max_subframes = cells[c].max_subframes;
+      specs[c].update_meta_period = cells[c].update_meta_period; specs[c].max_subframes = cells[c].max_subframes; specs[c].filt = std::move(filt[c]);
       s->phys.push_back(cells[c].phy);
     }
     s->sample_rate_hz = cfg->sample_rate_hz;
@@ -829,7 +837,7 @@ int lsn_channel_filter(int device, const void* in, int in_on_device, uint64_t n_
     }
     LsnChanFirCell k;
     k.taps = d_taps; k.L = f.L; k.w = f.tune; k.nco = d_nco; k.out = dst; k.out_first = (int64_t)cfg->out_first; k.n_out = n_out;
-    lsn_launch_chan_fir(raw, fmt, sfm.scale, need_lo, len, nant, &k, 1, st);
+    lsn_launch_chan_fir(raw, fmt, sfm.scale, need_lo, len, nant, 0, &k, 1, st);
     if (!out_on_device) HIP_CHECK(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
   } catch (const std::exception& ex) {
@@ -840,6 +848,70 @@ int lsn_channel_filter(int device, const void* in, int in_on_device, uint64_t n_
   if (d_in) (void)hipFree(d_in);
   if (d_taps) (void)hipFree(d_taps);
   if (d_out) (void)hipFree(d_out);
+  return rc;
+}
+
+// stage 1 out of a ring (k_chan_fir_ring), no Phy: the whole window goes to its slots of a device ring, every cell's filter runs in ONE launch
+int lsn_channel_filter_ring(int device, const void* in, uint64_t n_in, uint64_t ring_samples, const lsn_channel_filter_cfg_t* cfgs, uint32_t n_cells, float* const* outs,
+                            const uint64_t* n_out)
+{
+  if (!in || !cfgs || !outs || !n_out || n_cells < 1 || n_cells > LSN_FILE_MAX_CELLS) return LSN_ERROR_INVALID_INPUTS;
+  if (!ring_samples || (ring_samples & (ring_samples - 1)) || ring_samples > (1ull << 32) || n_in > ring_samples || n_in >= (1ull << 62)) return LSN_ERROR_INVALID_INPUTS;
+  std::vector<lsn::ChanFilter> f(n_cells);
+  const lsn_channel_filter_cfg_t& c0 = cfgs[0];
+  bool any = false;
+  for (uint32_t c = 0; c < n_cells; c++) {
+    const lsn_channel_filter_cfg_t& k = cfgs[c];
+    const int r = lsn_channel_filter_plan(&k, f[c]);
+    if (r != LSN_SUCCESS) return r;
+    if (k.nof_antennas != c0.nof_antennas || k.sample_format != c0.sample_format || !(k.sample_scale == c0.sample_scale) || k.rate_in_hz != c0.rate_in_hz || k.in_base != c0.in_base)
+      return LSN_ERROR_INVALID_INPUTS;
+    if (!n_out[c]) continue;
+    if (!outs[c] || n_out[c] >= (1ull << 40)) return LSN_ERROR_INVALID_INPUTS;
+    int64_t lo = (int64_t)k.out_first, hi = (int64_t)(k.out_first + n_out[c]);
+    f[c].widen(lo, hi);
+    if (std::max<int64_t>(lo, 0) < (int64_t)k.in_base || hi > (int64_t)(k.in_base + n_in)) return LSN_ERROR_INVALID_INPUTS;   // the window does not hold what these outputs read
+    any = true;
+  }
+  if (!any) return LSN_SUCCESS;
+  const uint32_t nant = c0.nof_antennas, fmt = c0.sample_format;
+  const LsnSampleFormat sfm = lsn_sample_format(fmt, c0.sample_scale);
+  const size_t smp = (size_t)sfm.bytes * nant;
+  void* d_ring = nullptr;
+  std::vector<float*> d_taps(n_cells, nullptr);
+  std::vector<void*> d_out(n_cells, nullptr);
+  hipStream_t st = nullptr;
+  int rc = LSN_SUCCESS;
+  try {
+    HIP_CHECK(hipSetDevice(device));
+    HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    // slots no sample of the window goes to keep a pattern (NaN as cf32) that a read outside the window would carry into the outputs
+    HIP_CHECK(hipMalloc(&d_ring, ring_samples * smp));
+    HIP_CHECK(hipMemsetAsync(d_ring, 0xFF, ring_samples * smp, st));
+    const uint64_t slot = c0.in_base & (ring_samples - 1), head = std::min(n_in, ring_samples - slot);
+    if (head) HIP_CHECK(hipMemcpyAsync((uint8_t*)d_ring + slot * smp, in, head * smp, hipMemcpyHostToDevice, st));
+    if (n_in > head) HIP_CHECK(hipMemcpyAsync(d_ring, (const uint8_t*)in + head * smp, (n_in - head) * smp, hipMemcpyHostToDevice, st));   // behind the end of the ring
+    LsnChanFirCell k[LSN_FILE_MAX_CELLS];
+    for (uint32_t c = 0; c < n_cells; c++) {
+      k[c] = LsnChanFirCell();
+      if (!n_out[c]) continue;
+      const cf32* d_nco = nullptr;
+      lsn_chan_fir_upload(f[c], d_taps[c], d_nco, st);
+      HIP_CHECK(hipMalloc(&d_out[c], (size_t)n_out[c] * nant * sizeof(cf32)));
+      k[c].taps = d_taps[c]; k[c].L = f[c].L; k[c].w = f[c].tune; k[c].nco = d_nco; k[c].out = (cf32*)d_out[c]; k[c].out_first = (int64_t)cfgs[c].out_first; k[c].n_out = n_out[c];
+    }
+    lsn_launch_chan_fir(d_ring, fmt, sfm.scale, (int64_t)c0.in_base, n_in, nant, ring_samples, k, n_cells, st);
+    for (uint32_t c = 0; c < n_cells; c++)
+      if (n_out[c]) HIP_CHECK(hipMemcpyAsync(outs[c], d_out[c], (size_t)n_out[c] * nant * sizeof(cf32), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+  } catch (const std::exception& ex) {
+    fprintf(stderr, "ltesniffer_amd: channel_filter_ring: %s\n", ex.what());
+    rc = LSN_ERROR;
+  }
+  if (st) (void)hipStreamDestroy(st);
+  if (d_ring) (void)hipFree(d_ring);
+  for (float* t : d_taps) if (t) (void)hipFree(t);
+  for (void* o : d_out) if (o) (void)hipFree(o);
   return rc;
 }
 int lsn_phy_prepare_file(lsn_phy_t* phy, uint32_t nof_antennas)

@@ -288,6 +288,10 @@ public:
   uint32_t iqAntennas() const { return cd.iq_nant; }
   // the channel filter's intermediate (y1 of one block, cf32 [sample][antenna]): grows, never shrinks; kept like the block buffers
   int reserveChanBuffer(size_t bytes);
+  // the buffer as an open filtered stream holds it (lsn_stream_ring.cc keeps the pointer for its launches): growing frees and reallocates it, so while a stream
+  // holds it a call that would grow it is refused (LSN_ERROR_INVALID_INPUTS) and nothing is freed.  The stream itself grows it only in front of its first launch
+  cf32* chanBuffer() const { return d_chan; }
+  void holdChanBuffer(bool held) { chan_held = held; }
   int reserveFileBuffers(uint32_t nof_antennas);   // lsn_phy_prepare_file: pinned read blocks + device blocks of the file source, ahead of the first replay
   // what reserveFileBuffers sizes them by - subframes per block (LSN_FILE_BLOCK) and blocks in flight (LSN_FILE_SLOTS) - and the device block of slot si that a
   // source fills with [subframe][antenna][sample] cf32 and hands to submit(): the file source's, and the pushed stream's (lsn_stream_ring.cc)
@@ -585,6 +589,7 @@ private:
   FileBuf file_buf[8];
   double chan_stopband_hz = 0.0;   // lsn_phy_set_channel_filter
   cf32* d_chan = nullptr; size_t chan_bytes = 0;   // reserveChanBuffer
+  bool chan_held = false;                          // holdChanBuffer
   std::atomic<uint32_t>& ul_cfg_epoch = sh->ul_cfg_epoch;  // bumped by every (re)configuration: chunks whose DCI 0 grants were converted earlier are converted again at commit
   bool& sib2_learned = sh->sib2_learned; Sib2Config& sib2 = sh->sib2;  // the SIB2 the UL-mode commit stage configured itself from (decode_SIB), if any
   bool decodeSib(Chunk& ch, JobRunner& r, uint32_t sf, Sib2Config& out, size_t& payload_off, uint32_t& len, uint8_t& tb);

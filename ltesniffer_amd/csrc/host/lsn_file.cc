@@ -84,6 +84,7 @@ int Engine::reserveFileBuffers(uint32_t nof_antennas)
 int Engine::reserveChanBuffer(size_t bytes)
 {
   if (chan_bytes >= bytes) return LSN_SUCCESS;
+  if (chan_held) return LSN_ERROR_INVALID_INPUTS;   // an open stream's launches read and write d_chan
   return guarded([&]() -> int {
     HIP_CHECK(hipSetDevice(cfg.device));
     if (d_chan) { (void)hipFree(d_chan); d_chan = nullptr; }
@@ -287,7 +288,7 @@ struct Engine::FileReplay {
       if ((size_t)(hi2 - lo2) * nant * sizeof(cf32) > q.e->chan_bytes) throw std::runtime_error("file source: a block's filtered samples do not fit the intermediate buffer");
       f.taps = q.d_taps; f.L = q.cf->L; f.w = q.cf->tune; f.nco = q.d_mix; f.out = q.mid; f.out_first = lo2; f.n_out = (uint64_t)(hi2 - lo2);
     }
-    lsn_launch_chan_fir(raw, fmt, sfm.scale, lo, len, nant, k, (uint32_t)(c1 - c0), st);
+    lsn_launch_chan_fir(raw, fmt, sfm.scale, lo, len, nant, 0, k, (uint32_t)(c1 - c0), st);
   }
 
   // k_resample for one cell: n subframes from output subframe pos, out of the raw samples [lo, lo + len) of the recording, queued on st

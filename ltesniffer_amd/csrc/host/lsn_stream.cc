@@ -8,7 +8,7 @@ namespace lsn {
 
 uint64_t stream_cell_complete(const StreamCellPlan& c, uint64_t pushed)
 {
-  return file_cell_total(c.rs->outputsInside(pushed) / c.sflen, 0, c.max_subframes);
+  return file_cell_total(c.rs->outputsInside(pushed > c.pre ? pushed - c.pre : 0) / c.sflen, 0, c.max_subframes);   // (ChanFilter::insideEnd)
 }
 
 uint32_t stream_cell_ready(const StreamCellPlan& c, uint64_t pushed, uint64_t done, uint32_t blk, bool flush)
@@ -29,7 +29,7 @@ int64_t stream_oldest_needed(const StreamCellPlan* cells, uint32_t n, const uint
     if (p.max_subframes && done[c] >= p.max_subframes) continue;   // run out
     int64_t lo, hi;
     p.rs->inputSpan(done[c] * p.sflen, p.sflen, lo, hi);
-    oldest = std::min(oldest, std::max<int64_t>(lo, 0));
+    oldest = std::min(oldest, std::max<int64_t>(lo - (int64_t)p.pre, 0));
   }
   return oldest;
 }
@@ -40,6 +40,7 @@ uint64_t stream_block_input(const StreamCellPlan* cells, uint32_t n, uint32_t bl
   for (uint32_t c = 0; c < n; c++) {
     int64_t l, h;
     cells[c].rs->inputSpan(0, (uint64_t)blk * cells[c].sflen, l, h);
+    l -= (int64_t)cells[c].pre; h += (int64_t)cells[c].pre;   // what stage 1 reads for the y1 stage 2 reads
     lo = c ? std::min(lo, l) : l;
     hi = c ? std::max(hi, h) : h;
   }

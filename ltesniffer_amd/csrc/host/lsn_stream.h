@@ -11,17 +11,21 @@ struct StreamCellPlan {
   const ResamplePlan* rs = nullptr;   // formed by file_rate_plan, as every file replay's
   uint32_t sflen = 0;                 // output samples of one subframe
   uint64_t max_subframes = 0;         // 0: no end
+  uint32_t pre = 0;                   // half length L of the channel filter in front of rs (FileCellPlan::pre's meaning); 0: none
 };
 
 // complete subframes of the cell once `pushed` samples have arrived: file_cell_total of the subframes whose whole input span lies in front of `pushed` (a stream
-// starts at first_sf = 0)
+// starts at first_sf = 0).  With a filter the resampler reads y1, which `pushed` samples carry up to ChanFilter::insideEnd(pushed) = pushed - pre: the rule of
+// lsn_file_cells_span
 uint64_t stream_cell_complete(const StreamCellPlan& c, uint64_t pushed);
 // subframes of the cell that go out in the next launch, `done` being submitted already: a whole block of blk; fewer only behind a flush, or when they are the last
 // ones in front of max_subframes
 uint32_t stream_cell_ready(const StreamCellPlan& c, uint64_t pushed, uint64_t done, uint32_t blk, bool flush);
-// the oldest input sample any cell still needs: inputSpan's lo of subframe done[c], clamped at 0, minimised over the cells that have not run out; none left: pushed
+// the oldest input sample any cell still needs: inputSpan's lo of subframe done[c], less pre, clamped at 0, minimised over the cells that have not run out; none
+// left: pushed
 int64_t stream_oldest_needed(const StreamCellPlan* cells, uint32_t n, const uint64_t* done, uint64_t pushed);
-// input samples of one block of EVERY cell, from the oldest start to the newest end: the union of block 0 with all cells at blk subframes plus the two samples by
+// input samples of one block of EVERY cell, from the oldest start to the newest end: the union of block 0 with all cells at blk subframes - every cell's span
+// widened by pre on both sides, what its stage 1 reads - plus the two samples by
 // which the floor of a position moves the ends of a later block - file_cells_fit's rule.  A ring holds the stream when it is at least this long
 uint64_t stream_block_input(const StreamCellPlan* cells, uint32_t n, uint32_t blk);
 // the ring the library chooses: the smallest power of two that holds four such blocks; 0: above 2^32 samples

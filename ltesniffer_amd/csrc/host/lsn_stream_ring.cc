@@ -9,6 +9,8 @@
 // A stream that asked for it (track()) follows the sample clock: runReadyTracked resamples segment by segment at the steps its timing loop
 // decides (lsn_track.h) and measures every segment's PSS with k_pss_timing; a stream that did not runs runReady exactly as before.  The two loops differ in how a
 // block buffer fills; what they do alike - bufferFor, launchRing, submitBlock - exists once.
+// Cells with a channel filter: launchRing runs the file source's two stages instead - one k_chan_fir_ring launch out of the ring into the
+// cells' intermediates, one k_resample per cell out of those - and every span that guards the ring is L samples wider on both sides.  Without one, nothing differs.
 #include "lsn_stream_ring.h"
 #include "lsn_track_launch.h"
 #include "lsn_clock.h"
@@ -30,7 +32,7 @@ StreamRing::StreamRing(int device_, uint32_t nant_, uint32_t fmt_, float sample_
   // (the plans point into cells, which does not grow any more)
   for (auto& c : cells) {
     StreamCellPlan p;
-    p.rs = &c.s.plan; p.sflen = c.sflen; p.max_subframes = c.s.max_subframes;
+    p.rs = &c.s.plan; p.sflen = c.sflen; p.max_subframes = c.s.max_subframes; p.pre = c.s.filt.L;
     plans.push_back(p);
   }
 }
@@ -46,6 +48,8 @@ StreamRing::~StreamRing()
   if (ev_copy) (void)hipEventDestroy(ev_copy);
   for (auto& c : cells) {
     if (c.d_rep) (void)hipFree(c.d_rep);
+    if (c.d_taps) (void)hipFree(c.d_taps);
+    if (c.mid) c.s.e->holdChanBuffer(false);   // (mid is the Phy's: given back, not freed)
     if (c.h_C) (void)hipHostFree(c.h_C);
     for (auto& p : c.pending) if (p.ev) (void)hipEventDestroy(p.ev);
   }
@@ -73,10 +77,34 @@ int StreamRing::setup()
         if (c.s.e->fileIqBlockBytes(si) < (size_t)blk * c.sflen * nant * sizeof(cf32)) throw std::runtime_error("stream: block buffer");
       c.tb.rotation(c.s.offset_freq_hz, c.sflen, 15000.0 * (double)c.s.e->symbolSz());   // the -o rotation of the cell's output samples, the file source's
       c.tb.upload(c.s.plan, st_run);
+      if (c.s.filt.L) {
+        lsn_chan_fir_upload(c.s.filt, c.d_taps, c.d_mix, st_run);
+        const int rm = reserveMid(c, midSamples(c, c.s.plan.step));
+        if (rm != LSN_SUCCESS) return rm;
+      }
     }
     HIP_CHECK(hipStreamSynchronize(st_run));
     return LSN_SUCCESS;
   });
+}
+
+uint64_t StreamRing::midSamples(const Cell& c, u128 step) const
+{
+  const ResamplePlan& p = c.s.plan;
+  const u128 last = p.start + (u128)((uint64_t)blk * c.sflen - 1) * step;
+  return (uint64_t)(last >> 64) - (uint64_t)(p.start >> 64) + p.taps + 2;   // inputSpan's hi - lo of blk subframes, + 2
+}
+
+int StreamRing::reserveMid(Cell& c, uint64_t samples)
+{
+  // called from setup() and, in front of the first push, from track(): nothing of this stream's has been launched on the buffer yet, so it may still move
+  c.s.e->holdChanBuffer(false);
+  const int r = c.s.e->reserveChanBuffer((size_t)samples * nant * sizeof(cf32));
+  c.mid = c.s.e->chanBuffer();
+  if (r == LSN_SUCCESS) c.mid_samples = samples;
+  else if (!c.mid) c.mid_samples = 0;       // the old buffer went and no new one came: every later launch of this cell throws in front of stage 1
+  if (c.mid) c.s.e->holdChanBuffer(true);   // from here on nobody grows - frees - it under this stream
+  return r;
 }
 
 int64_t StreamRing::oldestNeeded() const
@@ -85,7 +113,7 @@ int64_t StreamRing::oldestNeeded() const
     int64_t oldest = (int64_t)pushed;
     for (const auto& c : cells) {
       if (c.s.max_subframes && c.filled >= c.s.max_subframes) continue;
-      const int64_t lo = (int64_t)(uint64_t)(c.tk.position(c.filled) >> 64) - (int64_t)c.s.plan.taps / 2 + 1;
+      const int64_t lo = (int64_t)(uint64_t)(c.tk.position(c.filled) >> 64) - (int64_t)c.s.plan.taps / 2 + 1 - (int64_t)c.s.filt.L;
       oldest = std::min(oldest, std::max<int64_t>(lo, 0));
     }
     return oldest;
@@ -134,15 +162,12 @@ int StreamRing::runReady(bool flush_all)
   for (;;) {
     if (failed != LSN_SUCCESS) return failed;
     uint32_t nsf[kFileMaxCells] = {};
-    int64_t in_lo = 0, in_hi = 0;
+    int64_t lo[kFileMaxCells] = {}, hi[kFileMaxCells] = {};
     bool any = false;
     for (size_t c = 0; c < cells.size(); c++) {
       nsf[c] = stream_cell_ready(plans[c], pushed, cells[c].done, blk, flush_all);
       if (!nsf[c]) continue;
-      int64_t lo, hi;
-      cells[c].s.plan.inputSpan(cells[c].done * cells[c].sflen, (uint64_t)nsf[c] * cells[c].sflen, lo, hi);
-      in_lo = any ? std::min(in_lo, lo) : lo;
-      in_hi = any ? std::max(in_hi, hi) : hi;
+      cells[c].s.plan.inputSpan(cells[c].done * cells[c].sflen, (uint64_t)nsf[c] * cells[c].sflen, lo[c], hi[c]);
       any = true;
     }
     if (!any) return LSN_SUCCESS;
@@ -152,20 +177,49 @@ int StreamRing::runReady(bool flush_all)
       k[c] = LsnResampleCell();
       if (nsf[c]) k[c] = q.s.plan.cell(q.done * q.sflen, q.sflen, q.tb, bufferFor(q), (uint64_t)nsf[c] * q.sflen);
     }
-    launchRing(k, in_lo, in_hi, "block");
+    launchRing(k, lo, hi, "block");
     for (size_t c = 0; c < cells.size() && failed == LSN_SUCCESS; c++)
       if (nsf[c]) submitBlock(cells[c], nsf[c]);
   }
 }
 
-void StreamRing::launchRing(const LsnResampleCell* k, int64_t in_lo, int64_t in_hi, const char* what)
+void StreamRing::launchRing(const LsnResampleCell* k, const int64_t* lo, const int64_t* hi, const char* what)
 {
+  // what the launch reads of the ring: the union of the cells' spans, each widened by its filter's L (0: none)
+  int64_t in_lo = 0, in_hi = 0;
+  bool any = false;
+  for (size_t c = 0; c < cells.size(); c++) {
+    if (!k[c].n_out) continue;
+    const int64_t L = (int64_t)cells[c].s.filt.L;
+    in_lo = any ? std::min(in_lo, lo[c] - L) : lo[c] - L;
+    in_hi = any ? std::max(in_hi, hi[c] + L) : hi[c] + L;
+    any = true;
+  }
   in_lo = std::max<int64_t>(in_lo, 0);   // zeros in front of the stream are the kernel's
   if (in_hi > (int64_t)pushed || (uint64_t)(in_hi - in_lo) > ring_samples || (int64_t)pushed - in_lo > (int64_t)ring_samples)
     throw std::runtime_error(std::string("stream: a ") + what + "'s input is not in the ring");
   HIP_CHECK(hipEventRecord(ev_copy, st_copy));
   HIP_CHECK(hipStreamWaitEvent(st_run, ev_copy, 0));   // the samples pushed so far are in their slots
-  lsn_launch_resample_cells({d_ring, fmt, sfm.scale, in_lo, (uint64_t)(in_hi - in_lo), nant, ring_samples}, k, (uint32_t)cells.size(), st_run);
+  if (filtered()) {
+    // stage 1, one launch for all cells: y1 over exactly the span each cell's resampler piece reads (in front of sample 0: zeros, the resampler's own - the file
+    // pass's midSpan); stage 2, per cell: the plain cf32 k_resample out of the cell's intermediate (k_resample_cells takes one source per launch)
+    LsnChanFirCell f[kFileMaxCells];
+    int64_t lo2[kFileMaxCells] = {}, hi2[kFileMaxCells] = {};
+    for (size_t c = 0; c < cells.size(); c++) {
+      const Cell& q = cells[c];
+      f[c] = LsnChanFirCell();
+      if (!k[c].n_out) continue;
+      lo2[c] = std::max<int64_t>(lo[c], 0);
+      hi2[c] = std::max(hi[c], lo2[c]);
+      if ((uint64_t)(hi2[c] - lo2[c]) > q.mid_samples) throw std::runtime_error(std::string("stream: a ") + what + "'s filtered samples do not fit the intermediate buffer");
+      f[c].taps = q.d_taps; f[c].L = q.s.filt.L; f[c].w = q.s.filt.tune; f[c].nco = q.d_mix; f[c].out = q.mid; f[c].out_first = lo2[c]; f[c].n_out = (uint64_t)(hi2[c] - lo2[c]);
+    }
+    lsn_launch_chan_fir(d_ring, fmt, sfm.scale, in_lo, (uint64_t)(in_hi - in_lo), nant, ring_samples, f, (uint32_t)cells.size(), st_run);
+    for (size_t c = 0; c < cells.size(); c++)
+      if (k[c].n_out) lsn_launch_resample({cells[c].mid, 0, 1.0f, lo2[c], (uint64_t)(hi2[c] - lo2[c]), nant, 0}, k[c], st_run);
+  } else {
+    lsn_launch_resample_cells({d_ring, fmt, sfm.scale, in_lo, (uint64_t)(in_hi - in_lo), nant, ring_samples}, k, (uint32_t)cells.size(), st_run);
+  }
   Launch l;
   l.ev = takeEvent(); l.lo = in_lo;
   HIP_CHECK(hipEventRecord(l.ev, st_run));
@@ -254,11 +308,20 @@ int StreamRing::track(const lsn_stream_track_cfg_t& tc, double rate_in)
     const ResamplePlan& p = cells[c].s.plan;
     const int64_t half = (int64_t)p.taps / 2;
     const u128 last = p.start + (u128)((uint64_t)blk * cells[c].sflen - 1) * track_widened_step(p.step, cfg.max_ppm);
-    const int64_t l = (int64_t)(uint64_t)(p.start >> 64) - half + 1, h = (int64_t)(uint64_t)(last >> 64) + half + 1;
+    const int64_t L = (int64_t)cells[c].s.filt.L;   // a filtered cell reads L more on both sides
+    const int64_t l = (int64_t)(uint64_t)(p.start >> 64) - half + 1 - L, h = (int64_t)(uint64_t)(last >> 64) + half + 1 + L;
     lo = c ? std::min(lo, l) : l;
     hi = c ? std::max(hi, h) : h;
   }
   if ((uint64_t)(hi - lo) + 2 > ring_samples) return LSN_ERROR_INVALID_INPUTS;
+  // the intermediates at the widened step: grown here, in front of the first push (nothing has been launched yet), or the call is refused
+  for (auto& q : cells) {
+    if (!q.s.filt.L) continue;
+    const uint64_t need = midSamples(q, track_widened_step(q.s.plan.step, cfg.max_ppm));
+    if (need <= q.mid_samples) continue;
+    const int rm = reserveMid(q, need);
+    if (rm != LSN_SUCCESS) return rm;
+  }
   return guarded([&]() -> int {
     HIP_CHECK(hipSetDevice(device));
     for (size_t c = 0; c < cells.size(); c++) {
@@ -313,7 +376,7 @@ int StreamRing::runReadyTracked(bool flush_all)
     if (failed != LSN_SUCCESS) return failed;
     LsnResampleCell k[kFileMaxCells];
     uint32_t piece[kFileMaxCells] = {};
-    int64_t in_lo = 0, in_hi = 0;
+    int64_t lo[kFileMaxCells] = {}, hi[kFileMaxCells] = {};
     bool any = false;
     for (size_t c = 0; c < cells.size(); c++) {
       Cell& q = cells[c];
@@ -325,19 +388,16 @@ int StreamRing::runReadyTracked(bool flush_all)
         t.enter();
       }
       const uint64_t end = std::min<uint64_t>(t.segEnd(), q.done + blk);
-      const uint64_t upto = std::min<uint64_t>(t.completeInSegment(pushed), end);
+      const uint64_t upto = std::min<uint64_t>(t.completeInSegment(insideEnd(q)), end);
       if (upto <= q.filled || (upto < end && !flush_all)) continue;
       piece[c] = (uint32_t)(upto - q.filled);
       k[c] = q.s.plan.cell(t.position(q.filled), t.step, t.span, q.sflen, (uint32_t)(q.filled - q.done) * q.sflen, q.tb, bufferFor(q, q.filled == q.done),
                            (uint64_t)piece[c] * q.sflen);
-      int64_t lo, hi;
-      t.inputSpan(q.filled, upto, lo, hi);
-      in_lo = any ? std::min(in_lo, lo) : lo;
-      in_hi = any ? std::max(in_hi, hi) : hi;
+      t.inputSpan(q.filled, upto, lo[c], hi[c]);
       any = true;
     }
     if (any) {
-      launchRing(k, in_lo, in_hi, "segment");
+      launchRing(k, lo, hi, "segment");
       // the windows of the segments that began in this launch
       LsnTimingCell tm[kFileMaxCells];
       bool timing = false;
@@ -346,10 +406,11 @@ int StreamRing::runReadyTracked(bool flush_all)
         TrackCell& t = q.tk;
         tm[c] = LsnTimingCell();
         if (!piece[c] || q.filled != t.sf0) continue;
-        int64_t lo, hi;
-        t.inputSpan(t.sf0, t.sf0 + 1, lo, hi);
+        int64_t g_lo, g_hi;
+        t.inputSpan(t.sf0, t.sf0 + 1, g_lo, g_hi);
+        q.s.filt.widen(g_lo, g_hi);   // (L = 0: as it is)
         Cell::Pending p = {t.h, nullptr, (uint32_t)(t.h % TRACK_SLOTS)};
-        if (t.enabled && t.hasPss() && !inGap(lo, hi)) {
+        if (t.enabled && t.hasPss() && !inGap(g_lo, g_hi)) {
           tm[c].x = k[c].out; tm[c].rep = q.d_rep; tm[c].C = q.h_C + (size_t)p.slot * kTrackLags; tm[c].N = t.N; tm[c].d = track_lag_spacing(t.N); tm[c].sflen = q.sflen; tm[c].nant = nant;
           tm[c].n_occ = 1; tm[c].sf[0] = (uint32_t)(q.filled - q.done); tm[c].p[0] = track_pss_index(t.N);
           p.ev = takeEvent();

@@ -1,9 +1,10 @@
 // lsn_stream_ring.h - the object behind lsn_stream_*: the raw input of a live stream in ONE device ring, the cells' Phys fed out of it by k_resample_ring
-// (DESIGN.md section 3.1g).  The counting is lsn_stream.h's; this is the part that speaks to the HIP runtime and to the engines.
+//  - or, when the cells have a channel filter, by k_chan_fir_ring and one k_resample per cell (section 3.1j).  The counting is lsn_stream.h's; this is the part that speaks to the HIP runtime and to the engines.
 // A tracked stream (track(), section 3.1h) counts by the segments of lsn_track.h instead and measures every segment's PSS with k_pss_timing.
 #pragma once
 #include "lsn_engine.h"
 #include "lsn_resample_launch.h"
+#include "lsn_chanfilt_launch.h"
 #include "lsn_stream.h"
 #include "lsn_track.h"
 #include <deque>
@@ -17,7 +18,8 @@ class StreamRing {
 public:
   struct CellSpec {
     Engine* e = nullptr;
-    ResamplePlan plan;            // file_rate_plan's
+    ResamplePlan plan;            // file_rate_plan's; of a filtered cell: the plan with no centre offset (tune = 0), as in the file source
+    ChanFilter filt;              // L != 0: stage 1 in front of plan (all cells or none: lsn_stream_open)
     float offset_freq_hz = 0.0f;
     uint32_t start_tti = 0, update_meta_period = 0;
     uint64_t max_subframes = 0;
@@ -25,7 +27,7 @@ public:
   // the caller (lsn_stream_open) has checked cells, block and ring: stream_ring_check passes and blk subframes fit the Phys' block buffers
   StreamRing(int device, uint32_t nant, uint32_t fmt, float sample_scale, uint32_t blk, uint64_t ring_samples, std::vector<CellSpec> cells);
   ~StreamRing();
-  int setup();                                  // ring, streams, block buffers, banks: every allocation of the stream's life
+  int setup();                                  // ring, streams, block buffers, banks, the filters' taps and intermediates: every allocation of the stream's life
   int push(const void* iq, uint64_t n);         // iq null: a gap of n zero samples
   int flush();
   // the timing loop (lsn_stream_track): accepted before the first sample only; a refusal leaves the stream as it was
@@ -49,6 +51,12 @@ private:
     uint64_t done = 0;
     int rc = LSN_SUCCESS;
     ResampleTables tb;                   // the plan's bank and NCO tables, the -o rotation
+    // a filtered cell: stage 1 writes y1 over the span one launch's resampler piece reads into mid, element 0 = y1[lo]; one mid serves every block-buffer slot,
+    // the launches being ordered on st_run
+    float* d_taps = nullptr;             // the filter's taps ...
+    const cf32* d_mix = nullptr;         // ... and, behind them, its mixer's tables when it has a tuning word
+    cf32* mid = nullptr;                 // the Phy's intermediate (Engine::reserveChanBuffer), at least mid_samples samples of all antennas
+    uint64_t mid_samples = 0;
     uint64_t launches = 0;              // block buffer of launch k: slot k mod nslot ...
     uint64_t mark[NSLOT_MAX] = {};       // ... free again when the engine has consumed the chunks up to this mark (0: never used)
     // a tracked stream (runReadyTracked): the block buffer fills segment by segment
@@ -60,14 +68,21 @@ private:
     std::deque<Pending> pending;
   };
   static constexpr uint32_t TRACK_SLOTS = 4;   // at most kTrackDelay measurements of a cell are in flight
-  struct Launch { hipEvent_t ev; int64_t lo; };   // recorded behind a k_resample_ring launch that read the recording from sample lo on
+  struct Launch { hipEvent_t ev; int64_t lo; };   // recorded behind a launch that read the ring from recording sample lo on (filtered: the widened span's)
   void writeRing(const uint8_t* src, uint64_t n);
   int runReady(bool flush_all);
   int runReadyTracked(bool flush_all);
-  // the steps the two loops share.  launchRing: one k_resample_ring launch of the cells in k out of the recording samples [in_lo, in_hi), behind the copies queued
-  // so far, and its event into `inflight`; `what` names the input in the refusal.  bufferFor: the block buffer the cell fills next; empty (nothing of the next
+  // the steps the two loops share.  launchRing: the cells in k (n_out != 0) resampled out of the ring, cell c reading the recording samples [lo[c], hi[c]), behind
+  // the copies queued so far, and the event behind it into `inflight`; `what` names the input in the refusal.  Unfiltered: ONE k_resample_ring launch over the
+  // union of the spans.  Filtered: ONE k_chan_fir_ring launch over the union of the spans widened by every cell's L writes each cell's y1[lo, hi) into its
+  // intermediate, then one k_resample per cell reads that (the file source's two stages, lsn_file.cc).  bufferFor: the block buffer the cell fills next; empty (nothing of the next
   // block is in it yet): waits until the block it carried last has been through stage A.  submitBlock: the first nsf subframes of that buffer go to the cell's Phy
-  void launchRing(const LsnResampleCell* k, int64_t in_lo, int64_t in_hi, const char* what);
+  void launchRing(const LsnResampleCell* k, const int64_t* lo, const int64_t* hi, const char* what);
+  bool filtered() const { return cells[0].s.filt.L != 0; }
+  // y1 samples the largest resampler piece of one launch reads at `step`: blk subframes, plus the two samples by which the floor of a position moves the ends
+  uint64_t midSamples(const Cell& c, u128 step) const;
+  int reserveMid(Cell& c, uint64_t samples);
+  uint64_t insideEnd(const Cell& c) const { return c.s.filt.insideEnd(pushed); }   // what of y1 the samples pushed so far carry (L = 0: pushed)
   cf32* bufferFor(Cell& q, bool empty = true);
   void submitBlock(Cell& q, uint32_t nsf);
   void deliver(Cell& q, uint64_t upto_h, bool all);   // the measurements of segments <= upto_h (all: every one in flight) go to the loop; waits for their events

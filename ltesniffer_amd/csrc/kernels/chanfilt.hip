@@ -44,10 +44,13 @@ struct LsnChanFirArgs {
   cf32* out;             // [sample][antenna]
   uint32_t L, nant;
   float scale;
-  uint32_t pad;
+  uint32_t ring_mask;    // k_chan_fir_ring: raw is a ring of ring_mask + 1 samples per antenna, sample n of the recording at slot n & ring_mask; otherwise 0, not read
 };
+static_assert(sizeof(LsnChanFirArgs) == 88, "the ring mask took the place of the padding: eight cells' arguments stay 704 bytes of the kernel argument block");
 
-template <int FMT>
+// RING: where sample n of the recording sits in raw - false: element n - buf_base of a linear buffer; true: slot n & ring_mask of a ring.  [buf_base, buf_base +
+// buf_len) is the window of valid recording indices either way, and the window test (not the mask) is what keeps a tile from staging another lap's sample.
+template <int FMT, bool RING>
 __device__ __forceinline__ void chan_fir_tile(const LsnChanFirArgs& A, const bool mix, float4* cf_lo, float4* cf_hi)
 {
   const uint32_t a = blockIdx.y, t = threadIdx.x, L2 = 2 * A.L;
@@ -61,7 +64,7 @@ __device__ __forceinline__ void chan_fir_tile(const LsnChanFirArgs& A, const boo
     const int64_t n = n_lo + (int64_t)s, k = n - A.buf_base;
     float2 x = make_float2(0.0f, 0.0f);
     if (s < need && n >= 0 && k >= 0 && (uint64_t)k < A.buf_len) {
-      const size_t src = (size_t)k * A.nant + a;
+      const size_t src = (size_t)(RING ? n & (int64_t)A.ring_mask : k) * A.nant + a;
       if (FMT == 1) {
         const short2 q = ((const short2*)A.raw)[src];
         x.x = (float)q.x * A.scale; x.y = (float)q.y * A.scale;
@@ -129,7 +132,7 @@ template <int FMT, bool MIX>
 __global__ __launch_bounds__(256) void k_chan_fir(const LsnChanFirArgs A)
 {
   __shared__ float4 cf_lo[LSN_CF_QUADS], cf_hi[LSN_CF_QUADS];
-  chan_fir_tile<FMT>(A, MIX, cf_lo, cf_hi);
+  chan_fir_tile<FMT, false>(A, MIX, cf_lo, cf_hi);
 }
 
 // Several cells of one recording from ONE raw buffer in one launch (the multi-cell pass): grid (largest number of tiles of a cell, antennas, cells).
@@ -142,7 +145,18 @@ __global__ __launch_bounds__(256) void k_chan_fir_cells(const LsnChanFirCellsArg
   __shared__ float4 cf_lo[LSN_CF_QUADS], cf_hi[LSN_CF_QUADS];
   const LsnChanFirArgs& A = P.c[blockIdx.z];
   if ((uint64_t)blockIdx.x * LSN_CF_TILE >= A.n_out) return;
-  chan_fir_tile<FMT>(A, A.nco != nullptr, cf_lo, cf_hi);
+  chan_fir_tile<FMT, false>(A, A.nco != nullptr, cf_lo, cf_hi);
+}
+
+// The same launch out of a RING (lsn_stream with the filter on, lsn_channel_filter_ring): raw holds ring_mask + 1 samples per antenna and sample n of
+// the recording sits at slot n & ring_mask.  Grid, argument block and early exit are k_chan_fir_cells'; a source index is below (ring_mask + 1) * nant whatever n is.
+template <int FMT>
+__global__ __launch_bounds__(256) void k_chan_fir_ring(const LsnChanFirCellsArgs P)
+{
+  __shared__ float4 cf_lo[LSN_CF_QUADS], cf_hi[LSN_CF_QUADS];
+  const LsnChanFirArgs& A = P.c[blockIdx.z];
+  if ((uint64_t)blockIdx.x * LSN_CF_TILE >= A.n_out) return;
+  chan_fir_tile<FMT, true>(A, A.nco != nullptr, cf_lo, cf_hi);
 }
 
 void lsn_chan_fir_upload(const lsn::ChanFilter& f, float*& d_taps, const cf32*& d_nco, hipStream_t s)
@@ -157,11 +171,14 @@ void lsn_chan_fir_upload(const lsn::ChanFilter& f, float*& d_taps, const cf32*& 
   d_nco = f.tune ? (const cf32*)(d_taps + nt) : nullptr;
 }
 
-// A cell with n_out = 0 takes no part.  One cell: k_chan_fir, the mixer a template flag; several: k_chan_fir_cells
-void lsn_launch_chan_fir(const void* raw, uint32_t fmt, float scale, int64_t buf_base, uint64_t buf_len, uint32_t nant, const LsnChanFirCell* cells, uint32_t n_cells,
-                         hipStream_t s)
+// A cell with n_out = 0 takes no part.  One cell: k_chan_fir, the mixer a template flag; several: k_chan_fir_cells.  Out of a ring (ring_samples != 0: a power
+// of two, at most 2^32, that holds the window): k_chan_fir_ring, also for one cell
+void lsn_launch_chan_fir(const void* raw, uint32_t fmt, float scale, int64_t buf_base, uint64_t buf_len, uint32_t nant, uint64_t ring_samples, const LsnChanFirCell* cells,
+                         uint32_t n_cells, hipStream_t s)
 {
+  const uint64_t rn = ring_samples;
   if (n_cells > LSN_CF_MAX_CELLS || buf_base < 0 || !nant) throw std::runtime_error("k_chan_fir: bad geometry");
+  if (rn && ((rn & (rn - 1)) || rn > (1ull << 32) || buf_len > rn)) throw std::runtime_error("k_chan_fir_ring: bad ring");
   LsnChanFirCellsArgs P;
   memset(&P, 0, sizeof(P));
   uint32_t n = 0;
@@ -174,11 +191,11 @@ void lsn_launch_chan_fir(const void* raw, uint32_t fmt, float scale, int64_t buf
     if (r > 0x7FFFFFFFull) throw std::runtime_error("k_chan_fir: launch too long");
     LsnChanFirArgs& A = P.c[n++];
     A.raw = raw; A.buf_base = buf_base; A.buf_len = buf_len; A.out_first = k.out_first; A.n_out = k.n_out; A.taps = k.taps; A.w = k.w; A.nco = k.nco; A.out = k.out;
-    A.L = k.L; A.nant = nant; A.scale = scale;
+    A.L = k.L; A.nant = nant; A.scale = scale; A.ring_mask = rn ? (uint32_t)(rn - 1) : 0;
     tiles = std::max(tiles, r);
   }
   if (!n) return;
-  if (n == 1) {
+  if (n == 1 && !rn) {
     const LsnChanFirArgs& A = P.c[0];
     const dim3 g((uint32_t)tiles, nant);
     if (A.nco) {
@@ -193,7 +210,13 @@ void lsn_launch_chan_fir(const void* raw, uint32_t fmt, float scale, int64_t buf
     return;
   }
   const dim3 g((uint32_t)tiles, nant, n);
-  if (fmt == 1) LSN_LAUNCH((k_chan_fir_cells<1>), g, dim3(256), 0, s, P);
-  else if (fmt == 2) LSN_LAUNCH((k_chan_fir_cells<2>), g, dim3(256), 0, s, P);
-  else LSN_LAUNCH((k_chan_fir_cells<0>), g, dim3(256), 0, s, P);
+  if (!rn) {
+    if (fmt == 1) LSN_LAUNCH((k_chan_fir_cells<1>), g, dim3(256), 0, s, P);
+    else if (fmt == 2) LSN_LAUNCH((k_chan_fir_cells<2>), g, dim3(256), 0, s, P);
+    else LSN_LAUNCH((k_chan_fir_cells<0>), g, dim3(256), 0, s, P);
+    return;
+  }
+  if (fmt == 1) LSN_LAUNCH((k_chan_fir_ring<1>), g, dim3(256), 0, s, P);
+  else if (fmt == 2) LSN_LAUNCH((k_chan_fir_ring<2>), g, dim3(256), 0, s, P);
+  else LSN_LAUNCH((k_chan_fir_ring<0>), g, dim3(256), 0, s, P);
 }
