@@ -3,8 +3,8 @@
 // These replace what DCISearch::search obtains from srsran_ue_dl_decode_fft_estimate
 // (/root/reference/src/src/DCISearch.cc:562) and every srsran_pdcch_decode_msg_limit_avg_llr_power call of the blind
 // search (/root/reference/src/src/DCISearch.cc:133 -> /root/reference/lib/src/phy/falcon_phch/falcon_pdcch.c:110-170).
-// Layout: one workgroup per (subframe, antenna, OFDM symbol) for the FFT (LDS-staged radix-2^3 passes, coalesced
-// float2 loads of the IQ); one workgroup per (subframe, antenna, port) for the estimator; one wavefront (64 lanes =
+// Layout: one workgroup per (subframe, antenna, OFDM symbol) for the FFT (radix-2^3 passes, the first on registers
+// straight from coalesced loads of the IQ, the others through a swizzled LDS image); one workgroup per (subframe, antenna, port) for the estimator; one wavefront (64 lanes =
 // the 64 trellis states) per (subframe, location, DCI size) for the tail-biting Viterbi with __ballot decision words.
 // Float arithmetic is written one rounding per operation (compiled with -ffp-contract=off) so that results are
 // bit-identical to the CPU oracle used by the tests.
@@ -18,13 +18,16 @@
 // ------------------------------------------------------------------------------------------------ OFDM
 // rbp_part (optional): [sf][14][128] - the per-symbol term of SubframePower::computePower (SubframePower.cc:26-30: mean |x|^2 over the 12 REs of every PRB of
 // antenna 0), written here from the symbol the workgroup has just produced; k_rb_power then only adds the 14 terms of a PRB in symbol order (rounds 1-4: a
-// kernel that read the whole grid a second time, 0.13 MB per subframe)
-__device__ __forceinline__ void ofdm_rb_power(const LsnCellDev& c, const cf32* out, float* __restrict__ rbp_part, int sf, int l, int tid)
+// kernel that read the whole grid a second time, 0.13 MB per subframe).  pw: |x|^2 of the nre carriers, left in LDS by the transform.
+__device__ __forceinline__ void ofdm_rb_power(const LsnCellDev& c, const float* pw, float* __restrict__ rbp_part, int sf, int l, int tid)
 {
-  __syncthreads();  // the row this workgroup stored is read back (L2)
+  __syncthreads();
   if (tid < (int)c.nof_prb) {
+    const float4* q = (const float4*)(pw + tid * 12);  // 48 bytes per PRB
+    const float4 q0 = q[0], q1 = q[1], q2 = q[2];
+    const float v[12] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w};
     float s = 0.0f;
-    for (int k = 0; k < 12; k++) { const cf32 x = out[tid * 12 + k]; s = s + (x.r * x.r + x.i * x.i); }
+    for (int k = 0; k < 12; k++) s = s + v[k];
     rbp_part[((size_t)sf * 14 + l) * 128 + tid] = s / 12.0f;
   }
 }
@@ -34,7 +37,6 @@ __global__ __launch_bounds__(256) void k_ofdm(LsnCellDev c, const cf32* __restri
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int N = (int)c.N, tid = threadIdx.x;
   cf32* a = (cf32*)smem;
-  cf32* w = a + N;
   const int nsym = (int)c.nsym;  // 14, or 12 with the extended cyclic prefix (rows 12, 13 of the grid are never written)
   const int blk = blockIdx.x, l = blk % nsym, rx = (blk / nsym) % (int)c.nof_rx, sf = blk / (nsym * (int)c.nof_rx);
   const int cp0 = 160 * N / 2048, cp1 = 144 * N / 2048;
@@ -54,13 +56,14 @@ __global__ __launch_bounds__(256) void k_ofdm(LsnCellDev c, const cf32* __restri
     }
     return x;
   };
-  lsn_symbol_fft(c, a, w, load, out, 1, tid);  // 1: the DC carrier is not part of the downlink grid
-  if (rbp_part && rx == 0) ofdm_rb_power(c, out, rbp_part, sf, l, tid);
+  float* pw = (rbp_part && rx == 0) ? (float*)smem : nullptr;  // over a: the transform is done with a when it writes pw
+  lsn_symbol_fft(c, a, load, out, pw, 1, tid);  // 1: the DC carrier is not part of the downlink grid
+  if (pw) ofdm_rb_power(c, pw, rbp_part, sf, l, tid);
 }
 
 void lsn_launch_ofdm(const LsnCellDev& c, const cf32* iq, const uint32_t* dphi, cf32* grid, uint32_t nsf, hipStream_t s, float* rbp_part)
 {
-  size_t lds = sizeof(cf32) * (c.N + c.N / 2);
+  size_t lds = sizeof(cf32) * lsn_fft_lds_slots((int)c.N);
   LSN_LAUNCH(k_ofdm, dim3(nsf * c.nof_rx * c.nsym), dim3(256), lds, s, c, iq, dphi, grid, rbp_part);
 }
 

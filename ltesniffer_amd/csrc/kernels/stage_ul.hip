@@ -15,7 +15,6 @@ __global__ __launch_bounds__(256) void k_ul_fft(LsnCellDev c, const cf32* __rest
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int N = (int)c.N, tid = threadIdx.x;
   cf32* a = (cf32*)smem;
-  cf32* w = a + N;
   const int nsym = (int)c.nsym;  // 14, or 12 with the extended cyclic prefix (rows 12, 13 of the grid stay zero)
   const int l = blockIdx.x % nsym, sf = blockIdx.x / nsym;
   const int cp0 = 160 * N / 2048, cp1 = 144 * N / 2048;
@@ -24,12 +23,12 @@ __global__ __launch_bounds__(256) void k_ul_fft(LsnCellDev c, const cf32* __rest
   const cf32* in = iq + ((size_t)sf * nant + ant) * c.sflen + pos;
   const int nre = (int)c.nre;
   cf32* out = grid + ((size_t)sf * 14 + l) * nre;
-  lsn_symbol_fft(c, a, w, [&](int n) { return cmul(in[n], c.ul_shift[n]); }, out, 0, tid);  // 0: no DC gap in the uplink grid
+  lsn_symbol_fft(c, a, [&](int n) { return cmul(in[n], c.ul_shift[n]); }, out, nullptr, 0, tid);  // 0: no DC gap in the uplink grid
 }
 
 void lsn_launch_ul_fft(const LsnCellDev& c, const cf32* iq, uint32_t nant, uint32_t ant, cf32* grid, uint32_t nsf, hipStream_t s)
 {
-  LSN_LAUNCH(k_ul_fft, dim3(nsf * c.nsym), dim3(256), sizeof(cf32) * (c.N + c.N / 2), s, c, iq, nant, ant, grid);
+  LSN_LAUNCH(k_ul_fft, dim3(nsf * c.nsym), dim3(256), sizeof(cf32) * lsn_fft_lds_slots((int)c.N), s, c, iq, nant, ant, grid);
 }
 
 // ------------------------------------------------------------------------------------------------ DMRS estimate
