@@ -879,8 +879,10 @@ int lsn_sib2_decode(const uint8_t* pdu, uint32_t len, lsn_sib2_t* out);
  * payloads (may be NULL): decoded transport blocks, tbs/8 bytes each at results[i].payload_off. */
 int lsn_phy_pusch_decode(lsn_phy_t* phy, const void* ul_iq, int iq_on_device, uint32_t n_subframes, uint32_t start_tti,
                          const lsn_pusch_grant_t* grants, uint32_t n_grants, lsn_pusch_result_t* results, uint8_t* payloads, size_t payload_cap);
-long lsn_phy_tap_ul(lsn_phy_t* phy, int what /* 0: uplink grid of subframe `index`, 1: LLRs of grant `index`, 2: PRACH correlation power of occasion `index` */,
-                    uint32_t index, void* out, size_t cap);
+/* Read-only taps of the last lsn_phy_pusch_decode / lsn_phy_prach_detect call; returns the bytes written.  what = 0: uplink grid of subframe `index`,
+ * 1: rate-matched LLRs of grant `index`, 2: PRACH correlation power of occasion `index`, 3: the code blocks of grant `index` in transport-block order, six
+ * uint32 each (K, F, E, rv, ok, iters), 4: for the same blocks in the same order the K + 12 words the rate de-matcher handed to the turbo decoder. */
+long lsn_phy_tap_ul(lsn_phy_t* phy, int what, uint32_t index, void* out, size_t cap);
 
 /* ---- uplink (PRACH) ----
  * lsn_phy_set_prach_config replaces PUSCH_Decoder::set_rach_config (UL_Sniffer_PUSCH.cc:640-653: srsran_prach_init,

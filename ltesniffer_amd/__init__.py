@@ -75,6 +75,22 @@ def turbo_nwin(K):
     return p2 if p2 >= 96 else p1
 
 
+def unpack_rm_words(w, K):
+    """the K + 12 uint32 words k_rm hands to k_turbo for one code block -> int16[3, K + 4], the de-rate-matched streams d0 | d1 | d2: word
+    (x % W) * P + x // W carries the three 10-bit fields of trellis position x, words K + 4 s + j the termination value j of stream s"""
+    w = np.asarray(w, dtype=np.uint32)
+    P = turbo_nwin(K)
+    W = K // P
+    x = np.arange(K)
+    ww = w[(x % W) * P + x // W]
+    d3 = np.zeros((3, K + 4), dtype=np.int16)
+    for s_ in range(3):
+        f = ((ww >> (10 * s_)) & 0x3FF).astype(np.int32)
+        d3[s_, :K] = np.where(f >= 512, f - 1024, f)
+        d3[s_, K:] = w[K + 4 * s_:K + 4 * s_ + 4].view(np.int32)
+    return d3
+
+
 PRACH_NCS = [0, 13, 15, 18, 22, 26, 32, 38, 46, 59, 76, 93, 119, 167, 279, 419]  # 36.211 Table 5.7.2-2
 
 
@@ -825,6 +841,24 @@ class Phy:
             raise RuntimeError("tap_ul failed: %d" % nb)
         return buf[: nb // 2]
 
+    def tap_ul_cbs(self, grant_index):
+        """code blocks of grant `grant_index` of the last pusch_decode call in transport-block order: list of dict(K, F, E, rv, ok, iters,
+        d3=int16[3, K + 4] (what k_rm wrote for k_turbo, unpacked as in stage_c_jobs)); raises for a grant that was not decoded"""
+        rec = np.zeros(6 * 32, dtype=np.uint32)   # a transport block has at most 32 code blocks
+        nb = lib().lsn_phy_tap_ul(self._h, 3, grant_index, rec.ctypes.data, rec.nbytes)
+        if nb < 0:
+            raise RuntimeError("tap_ul failed: %d" % nb)
+        rec = rec[: nb // 4].reshape(-1, 6)
+        words = np.zeros(int(sum(int(c[0]) + 12 for c in rec)), dtype=np.uint32)
+        nw = lib().lsn_phy_tap_ul(self._h, 4, grant_index, words.ctypes.data, words.nbytes)
+        if nw != words.nbytes:
+            raise RuntimeError("tap_ul failed: %d" % nw)
+        out, o = [], 0
+        for K, F, E, rv, ok, iters in rec.tolist():
+            out.append(dict(K=K, F=F, E=E, rv=rv, ok=ok, iters=iters, d3=unpack_rm_words(words[o:o + K + 12], K)))
+            o += K + 12
+        return out
+
     # ---- PRACH ----
     def setPrachConfig(self, config_idx, root_seq_idx, zero_corr_zone, freq_offset, hs_flag=0, detect_factor=0.0, zc_roots=None):
         """PUSCH_Decoder::set_rach_config; zc_roots: 838 uint16 (36.211 Table 5.7.2-4) or None"""
@@ -889,17 +923,8 @@ class Phy:
                 o = 0
                 for c in cbs:
                     K = int(c["K"])
-                    w = words[o:o + K + 12]
+                    d3 = unpack_rm_words(words[o:o + K + 12], K)
                     o += K + 12
-                    P = turbo_nwin(K)
-                    W = K // P
-                    x = np.arange(K)
-                    ww = w[(x % W) * P + x // W]
-                    d3 = np.zeros((3, K + 4), dtype=np.int16)
-                    for s_ in range(3):
-                        f = ((ww >> (10 * s_)) & 0x3FF).astype(np.int32)
-                        d3[s_, :K] = np.where(f >= 512, f - 1024, f)
-                        d3[s_, K:] = w[K + 4 * s_:K + 4 * s_ + 4].view(np.int32)
                     d["cbs"].append(dict(tb=int(c["tb"]), K=K, F=int(c["F"]), E=int(c["E"]), rv=int(c["rv"]), ok=int(c["ok"]), iters=int(c["iters"]), skipped=int(c["skipped"]), d3=d3))
             out.append(d)
         return out

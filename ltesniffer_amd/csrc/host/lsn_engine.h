@@ -608,6 +608,9 @@ private:
 
   UeSpecConfig ulUeConfig(uint16_t rnti) const { return (!ulmod.empty() && ulmod[rnti]) ? ul_uecfg[rnti] : mcs_tracking.default_config(); }
   std::vector<LsnUlGrantDev> ul_last_gd; std::vector<int> ul_last_idx;  // descriptors of the last puschDecode call (taps)
+  struct UlTapCb { uint32_t K, F, E, rv, ok, iters, spp_off; };       // one code block of that call: descriptor, verdict, place of its k_rm output in runner_u.d_spp
+  struct UlTapTb { uint32_t cb_first, cb_count; };                    // the blocks of ul_last_gd[i], in transport-block order
+  std::vector<UlTapCb> ul_last_cbs; std::vector<UlTapTb> ul_last_tbs;
   JobRunner runner_u;
   cf32 *ul_d_iq = nullptr, *ul_d_grid = nullptr, *ul_d_hs = nullptr; float* ul_d_stat = nullptr; LsnUlGrantDev* ul_d_grants = nullptr;
   size_t ul_iq_cap = 0, ul_grid_cap = 0, ul_hs_cap = 0, ul_stat_cap = 0, ul_grants_cap = 0;

@@ -250,6 +250,7 @@ void Engine::puschDecodeGrid(const cf32* d_grid, uint32_t nsf, uint32_t start_tt
     gidx.push_back((int)i);
   }
   ul_last_gd = gd; ul_last_idx = gidx;
+  ul_last_cbs.clear(); ul_last_tbs.clear();
   const uint32_t ng = (uint32_t)gd.size(), ncb = (uint32_t)r.h_cbs.size();
   if (!ng) { HIP_CHECK(hipStreamSynchronize(st)); return; }
   // (these arenas are runner_u's, written and read on its stream only - also when the UL_MODE commit calls in with a chunk's grid, which stage A finished long ago)
@@ -296,6 +297,16 @@ void Engine::puschDecodeGrid(const cf32* d_grid, uint32_t nsf, uint32_t start_tt
     res.payload_off = (uint32_t)payload_out.size();
     payload_out.insert(payload_out.end(), pl, pl + ref.tbs / 8);
   }
+  // taps 3 / 4: the blocks of every grant in transport-block order with their verdicts and where turbo_place put their de-rate-matched words (tbs[t] belongs to gd[t])
+  ul_last_cbs.reserve(ncb);
+  for (const TbRef& ref : tbs) {
+    ul_last_tbs.push_back({(uint32_t)ul_last_cbs.size(), ref.cb_count});
+    for (uint32_t q = ref.cb_first; q < ref.cb_first + ref.cb_count; q++) {
+      const LsnCbDev& cb = r.h_cbs[q];
+      const LsnCbRes& cr = cbres[cb.res_idx];
+      ul_last_cbs.push_back({cb.K, cb.F, cb.E, cb.rv, cr.ok, cr.iters, place.spp_of[q]});
+    }
+  }
 }
 
 long Engine::tapUl(int what, uint32_t index, void* out, size_t cap)
@@ -310,6 +321,22 @@ long Engine::tapUl(int what, uint32_t index, void* out, size_t cap)
       if ((uint32_t)ul_last_idx[i] == index) d = &ul_last_gd[i];
     if (!d) return LSN_ERROR_INVALID_INPUTS;
     n = ((size_t)2 * (cell.nslot() - 1) * 12 * d->L_prb - d->q_ri - d->q_cqi) * d->qm * sizeof(int16_t); src = runner_u.d_llr16 + d->llr_off;
+  } else if (what == 3 || what == 4) {  // code blocks of grant `index` of the last call in transport-block order: (K, F, E, rv, ok, iters) each / their K + 12 words from k_rm
+    const UlTapTb* tb = nullptr;
+    for (size_t i = 0; i < ul_last_idx.size() && i < ul_last_tbs.size(); i++)
+      if ((uint32_t)ul_last_idx[i] == index) tb = &ul_last_tbs[i];
+    if (!tb) return LSN_ERROR_INVALID_INPUTS;
+    const UlTapCb* cbs = ul_last_cbs.data() + tb->cb_first;
+    for (uint32_t q = 0; q < tb->cb_count; q++) n += what == 3 ? 6 * sizeof(uint32_t) : ((size_t)cbs[q].K + 12) * sizeof(uint32_t);
+    if (n > cap) return LSN_ERROR_INVALID_INPUTS;
+    uint32_t* o = (uint32_t*)out;
+    for (uint32_t q = 0; q < tb->cb_count; q++) {
+      const UlTapCb& c = cbs[q];
+      if (what == 3) { const uint32_t rec[6] = {c.K, c.F, c.E, c.rv, c.ok, c.iters}; std::memcpy(o, rec, sizeof(rec)); o += 6; continue; }
+      if (hipMemcpy(o, runner_u.d_spp + c.spp_off, ((size_t)c.K + 12) * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) return LSN_ERROR;
+      o += c.K + 12;
+    }
+    return (long)n;
   } else return LSN_ERROR_INVALID_INPUTS;
   if (n > cap) return LSN_ERROR_INVALID_INPUTS;
   if (hipMemcpy(out, src, n, hipMemcpyDeviceToHost) != hipSuccess) return LSN_ERROR;
