@@ -590,6 +590,64 @@ typedef struct {
 } lsn_pss_timing_cell_t;
 int lsn_pss_timing(int device, int blocks_on_device, const lsn_pss_timing_cell_t* cells, uint32_t n_cells);
 
+/* ---- a tracked stream that finds a cell's timing again after samples were lost ----
+ * k_pss_timing sees 13 lags, +- 6 d around the place where the PSS must be.  A radio that overflows drops (or repeats) a few thousand samples without saying how
+ * many; the PSS then lies outside that window for good and every segment is invalid.  Opt-in per stream, accepted only after lsn_stream_track and before the first
+ * push; a stream that does not ask runs exactly the launches it ran before.  Notation as above, W5 = 75 N (a half frame), sflen = 15 N.
+ *   metric    k_pss_acquire over the SPAN of segment h: the 6 sflen outputs m = 0 .. 6 sflen - 1 at the positions base_h + m step_h - segment h and one subframe
+ *             more, all at segment h's step -, resampled out of the ring into a scratch of the cell's; lags L_i = i d, i = 0 .. W5 / d - 1 (9600 at every N):
+ *               C_i = sum_a | sum_(k<N) x_a[L_i + k] conj r[k] |^2 / sum_a sum_(k<N) |x_a[L_i + k]|^2      (0 when the denominator is 0)
+ *             k_pss_timing's quantity, with its arithmetic: C[p / d + j - 6] of a span is bit for bit k_pss_timing's C_j on the span's first subframe.
+ *   decision  host, doubles: i* the first maximum, peak = C[i*]; far = the largest C_i whose circular distance from i* is above 8 lags.  Accepted when peak > 0,
+ *             peak >= min_ratio far, and peak >= 0.25 mean(the cell's valid-peak history as it stands behind the measurement of segment h + 1; empty: accepts).
+ *             o = ((i* d - p + W5 / 2) mod W5) - W5 / 2 output samples, signed: the nearest PSS, so a slip of up to +- 2.5 ms is repaired with the TTI intact.
+ *   when      on entering segment h, after the loop's step that consumed the measurement of segment h - 2 (and after a search's result was taken in): a search of
+ *             segment h is due when invalid_run >= after, no search of the cell is in flight and the cell is enabled.  It is launched once its span is complete in
+ *             the ring and its result is taken in on entering segment h + 3.  Accepted: base_(h+3) = end of segment h + 2 + o step_h, exact in the 64.64 integers,
+ *             invalid_run = 0, integrator and correction untouched; the measurements still queued from the old timing go through the loop as they are (the peak test
+ *             rejects them).  Rejected: nothing changes, the next search is due as soon as the rule allows.  A search whose span reads a declared gap is not
+ *             launched and counts as rejected.  Output subframes stay contiguous and the TTI keeps counting: only a position jumps, and only here.
+ *   ring      a cell with re-acquisition keeps 8 output subframes of input more (at the step widened by 1 + max_ppm 1e-6), behind what it keeps anyway: 6 for the
+ *             span of the segment behind, 2.5 for a backward jump, rounded up.  oldest_needed and the ring guards count with it; lsn_stream_span keeps describing
+ *             the nominal plan.
+ * Limits: a slip beyond +- 2.5 ms is repaired to the nearest PSS and leaves the TTI off by a multiple of 5 subframes (that needs the SSS and the MIB: not built);
+ * one search per cell in flight; streams only - file replays do not track -, and not on a stream with the channel filter.
+ * lsn_stream_reacquire refuses with LSN_ERROR_INVALID_INPUTS, the stream unchanged and usable: a struct_size it does not know, an untracked stream, a second call,
+ * after a push, min_ratio not finite or below 1 (0 = the default), a stream with the channel filter, a ring shorter than lsn_stream_track's bound plus the 8
+ * subframes. */
+typedef struct {
+  uint32_t struct_size;      /* sizeof(lsn_stream_reacquire_cfg_t); every other size is refused */
+  uint32_t after;            /* consecutive invalid segments that make a search due; 0 = the loop's lost_after */
+  double   min_ratio;        /* 0 = 3: the geometric mean of the ratio peak / far measured on noise (1.86) and with the cell present (5.1) */
+  uint32_t enable[LSN_FILE_MAX_CELLS];        /* per cell: 0 = this cell is never searched */
+} lsn_stream_reacquire_cfg_t;
+typedef struct {
+  uint32_t struct_size;      /* in: sizeof(lsn_stream_reacquire_status_t); every other size is refused */
+  uint32_t nof_cells;
+  uint64_t launched[LSN_FILE_MAX_CELLS], accepted[LSN_FILE_MAX_CELLS], rejected[LSN_FILE_MAX_CELLS];   /* rejected counts the searches a gap kept from being launched */
+  double   last_peak[LSN_FILE_MAX_CELLS], last_ratio[LSN_FILE_MAX_CELLS];   /* of the last search that came back */
+  int64_t  last_offset[LSN_FILE_MAX_CELLS];    /* o, output samples */
+  uint64_t jump_segment[LSN_FILE_MAX_CELLS];   /* the segment at which the last jump took force (0: none yet) */
+  double   jumps_total[LSN_FILE_MAX_CELLS];    /* the sum of all jumps, input samples */
+} lsn_stream_reacquire_status_t;
+int lsn_stream_reacquire(lsn_stream_t* s, const lsn_stream_reacquire_cfg_t* cfg);
+/* the measurements and the searches in flight are waited for first, so after a flush the answer is a function of the samples pushed */
+int lsn_stream_reacquire_status(lsn_stream_t* s, lsn_stream_reacquire_status_t* out);
+/* the decision without a GPU: C[n], n d = 75 N -> 1 accepted, 0 rejected (offset, peak and ratio = peak / far filled either way), or LSN_ERROR_INVALID_INPUTS.
+ * min_ratio 0 = the default; history_mean < 0: an empty history */
+int lsn_pss_acquire_decide(const float* C, uint32_t n, uint32_t d, uint32_t N, double min_ratio, double history_mean, int64_t* offset, double* peak, double* ratio);
+/* k_pss_acquire without a Phy, the sibling of lsn_pss_timing: per cell a span of 6 subframes in the block-buffer layout [6][antenna][sflen] cf32 (host or device
+ * memory), the replica [N] cf32 (host) and d -> C [75 N / d] (host).  All cells go into one launch.  Refused: n_cells 0 or above LSN_FILE_MAX_CELLS, a struct_size
+ * the library does not know, N outside 128 .. 2048, d != max(1, N / 128), sflen != 15 N. */
+typedef struct {
+  uint32_t struct_size;      /* sizeof(lsn_pss_acquire_cell_t) */
+  uint32_t N, d, sflen, nof_antennas, reserved;
+  const void* blocks;
+  const float* replica;
+  float* C;                  /* out */
+} lsn_pss_acquire_cell_t;
+int lsn_pss_acquire(int device, int blocks_on_device, const lsn_pss_acquire_cell_t* cells, uint32_t n_cells);
+
 /* ---- sharp channel filter in front of the resampler: a cell next to a much stronger carrier ----
  * The resampler's filter has the transition band [B, min(rate) - B]: a neighbour carrier inside it reaches the FFT's guard bins undamped and leaks into the
  * occupied bins at about -40 dB.  The channel filter is an opt-in stage 1 at the RECORDING's rate, the resampler becomes stage 2:

@@ -289,6 +289,9 @@ public:
   // the timing loop (before the first push): LSN_ERROR_INVALID_INPUTS when refused, the stream unchanged and usable
   int track(lsn_stream_track_cfg_t cfg) { cfg.struct_size = sizeof(cfg); return lsn_stream_track(h, &cfg); }
   lsn_stream_track_status_t track_status() { lsn_stream_track_status_t s{}; s.struct_size = sizeof(s); lsn_stream_track_status(h, &s); return s; }
+  // re-acquisition after a loss of samples (after track(), before the first push): LSN_ERROR_INVALID_INPUTS when refused, the stream unchanged and usable
+  int reacquire(lsn_stream_reacquire_cfg_t cfg) { cfg.struct_size = sizeof(cfg); return lsn_stream_reacquire(h, &cfg); }
+  lsn_stream_reacquire_status_t reacquire_status() { lsn_stream_reacquire_status_t s{}; s.struct_size = sizeof(s); lsn_stream_reacquire_status(h, &s); return s; }
   int close() { const int r = h ? lsn_stream_close(h) : LSN_SUCCESS; h = nullptr; return r; }
   // the plan without a device or a Phy; stopband_hz: empty, or one entry per cell (lsn_stream_span_filtered)
   static int span(lsn_stream_cfg_t cfg, std::vector<lsn_file_cell_t> cells, const std::vector<double>& stopband_hz, uint64_t pushed_samples, lsn_stream_span_t& out)

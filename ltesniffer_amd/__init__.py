@@ -46,7 +46,8 @@ EXPORTS = ["lsn_phy_create", "lsn_phy_destroy", "lsn_phy_set_cell", "lsn_phy_get
            "lsn_phy_set_channel_filter", "lsn_channel_filter_design", "lsn_channel_filter", "lsn_channel_filter_span", "lsn_cells_stopbands",
            "lsn_resample_cells_ring", "lsn_stream_open", "lsn_stream_push", "lsn_stream_flush", "lsn_stream_status", "lsn_stream_close", "lsn_stream_span",
            "lsn_stream_track", "lsn_stream_track_status", "lsn_stream_track_step", "lsn_pss_timing", "lsn_pss_timing_error",
-           "lsn_channel_filter_ring", "lsn_stream_span_filtered"]
+           "lsn_channel_filter_ring", "lsn_stream_span_filtered",
+           "lsn_stream_reacquire", "lsn_stream_reacquire_status", "lsn_pss_acquire", "lsn_pss_acquire_decide"]
 
 RATES_3GPP, RATES_SRSRAN = 0, 1   # LSN_RATES_*: sampling mode of a Phy / of a cell search
 
@@ -171,6 +172,21 @@ class StreamTrackState(C.Structure):   # lsn_stream_track_state_t
 class PssTimingCell(C.Structure):   # lsn_pss_timing_cell_t
     _fields_ = [("struct_size", C.c_uint32), ("N", C.c_uint32), ("d", C.c_uint32), ("sflen", C.c_uint32), ("nof_antennas", C.c_uint32), ("nof_subframes", C.c_uint32),
                 ("n_occ", C.c_uint32), ("reserved", C.c_uint32), ("blocks", C.c_void_p), ("replica", C.c_void_p), ("occ", C.c_void_p), ("C", C.c_void_p)]
+
+
+class StreamReacquireCfg(C.Structure):   # lsn_stream_reacquire_cfg_t
+    _fields_ = [("struct_size", C.c_uint32), ("after", C.c_uint32), ("min_ratio", C.c_double), ("enable", C.c_uint32 * FILE_MAX_CELLS)]
+
+
+class StreamReacquireStatus(C.Structure):   # lsn_stream_reacquire_status_t
+    _fields_ = [("struct_size", C.c_uint32), ("nof_cells", C.c_uint32), ("launched", C.c_uint64 * FILE_MAX_CELLS), ("accepted", C.c_uint64 * FILE_MAX_CELLS),
+                ("rejected", C.c_uint64 * FILE_MAX_CELLS), ("last_peak", C.c_double * FILE_MAX_CELLS), ("last_ratio", C.c_double * FILE_MAX_CELLS),
+                ("last_offset", C.c_int64 * FILE_MAX_CELLS), ("jump_segment", C.c_uint64 * FILE_MAX_CELLS), ("jumps_total", C.c_double * FILE_MAX_CELLS)]
+
+
+class PssAcquireCell(C.Structure):   # lsn_pss_acquire_cell_t
+    _fields_ = [("struct_size", C.c_uint32), ("N", C.c_uint32), ("d", C.c_uint32), ("sflen", C.c_uint32), ("nof_antennas", C.c_uint32), ("reserved", C.c_uint32),
+                ("blocks", C.c_void_p), ("replica", C.c_void_p), ("C", C.c_void_p)]
 
 
 class StreamSpan(C.Structure):   # lsn_stream_span_t
@@ -472,6 +488,11 @@ def lib():
                                             C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.lsn_pss_timing.argtypes = [C.c_int, C.c_int, C.POINTER(PssTimingCell), C.c_uint32]
         L.lsn_pss_timing_error.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.lsn_stream_reacquire.argtypes = [C.c_void_p, C.POINTER(StreamReacquireCfg)]
+        L.lsn_stream_reacquire_status.argtypes = [C.c_void_p, C.POINTER(StreamReacquireStatus)]
+        L.lsn_pss_acquire.argtypes = [C.c_int, C.c_int, C.POINTER(PssAcquireCell), C.c_uint32]
+        L.lsn_pss_acquire_decide.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_double),
+                                             C.POINTER(C.c_double)]
         L.lsn_phy_set_prach_config.argtypes = [C.c_void_p, C.POINTER(PrachCfg)]
         L.lsn_phy_prach_detect.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(PrachDet), C.c_uint32]
         L.lsn_phy_set_prach_sink.argtypes = [C.c_void_p, PRACH_SINK, C.c_void_p]
@@ -1377,6 +1398,56 @@ def pss_timing(cells, device=0):
     return outs
 
 
+def _reacquire_cfg(n_cells, after=0, min_ratio=0.0, enable=True):
+    cfg = StreamReacquireCfg()
+    cfg.struct_size, cfg.after, cfg.min_ratio = C.sizeof(StreamReacquireCfg), int(after), float(min_ratio)
+    vals = list(enable) if isinstance(enable, (list, tuple)) else [enable] * n_cells
+    if len(vals) != n_cells:
+        raise ValueError("reacquire: enable needs one value per cell")
+    for i, v in enumerate(vals):
+        cfg.enable[i] = 1 if v else 0
+    return cfg
+
+
+def pss_acquire_decide(Cv, d, N, min_ratio=0.0, history_mean=None):
+    """lsn_pss_acquire_decide (needs no GPU): the 75 N / d values of one search -> (accepted, offset in output samples, peak, peak / far).  history_mean None: an
+    empty history; min_ratio 0: the default.  Raises ValueError when refused"""
+    import numpy as np
+    Cv = np.ascontiguousarray(Cv, dtype=np.float32)
+    if Cv.ndim != 1:
+        raise ValueError("pss_acquire_decide: one row of values")
+    o, pk, ra = C.c_int64(), C.c_double(), C.c_double()
+    rc = lib().lsn_pss_acquire_decide(Cv.ctypes.data, len(Cv), int(d), int(N), float(min_ratio), -1.0 if history_mean is None else float(history_mean),
+                                      C.byref(o), C.byref(pk), C.byref(ra))
+    if rc == LSN_ERROR_INVALID_INPUTS:
+        raise ValueError("pss_acquire_decide: refused")
+    _check_n(rc, "lsn_pss_acquire_decide")
+    return bool(rc), int(o.value), float(pk.value), float(ra.value)
+
+
+def pss_acquire(cells, device=0):
+    """lsn_pss_acquire: k_pss_acquire without a Phy.  cells: a list of dict(blocks: complex64 [6][antenna][15 N], replica: complex64 [N], d), all of them in one
+    launch -> a list of float32 arrays [75 N / d].  Raises ValueError when refused"""
+    import numpy as np
+    n = len(cells)
+    arr = (PssAcquireCell * max(n, 1))()
+    keep, outs = [], []
+    for i, c in enumerate(cells):
+        x = np.ascontiguousarray(c["blocks"], dtype=np.complex64)
+        r = np.ascontiguousarray(c["replica"], dtype=np.complex64)
+        if x.ndim != 3 or x.shape[0] != 6 or r.ndim != 1:
+            raise ValueError("pss_acquire: blocks [6][antenna][sflen], replica [N]")
+        out = np.zeros(75 * len(r) // max(int(c["d"]), 1), dtype=np.float32)
+        keep.append((x, r))
+        outs.append(out)
+        arr[i] = PssAcquireCell(C.sizeof(PssAcquireCell), len(r), int(c["d"]), x.shape[2], x.shape[1], 0, x.ctypes.data, r.ctypes.data, out.ctypes.data)
+    rc = lib().lsn_pss_acquire(int(device), 0, arr, n)
+    if rc == LSN_ERROR_INVALID_INPUTS:
+        raise ValueError("pss_acquire: refused")
+    _check(rc, "lsn_pss_acquire")
+    return outs
+
+
 class Stream:
     """lsn_stream_*: the cells of a live wideband stream that arrives in host buffers.  cells: a list of (phy, dict(...)) with the keys of process_file_cells
     (center_offset_hz, start_tti - not TTI_FROM_MIB -, offset_time / offset_time_frac: the start of the cell's subframe 0 counted from the first sample ever
@@ -1387,8 +1458,10 @@ class Stream:
     those of process_file_cells on a file of the same bytes, however the stream is cut into pushes.  Raises ValueError when the library refuses the stream
     (nothing is allocated, every Phy stays usable).  Close the stream before its Phys; a Phy that is closed first closes the stream."""
 
-    def __init__(self, sample_rate, cells, nof_antennas=None, sample_format=FILE_CF32, sample_scale=0.0, block_subframes=0, ring_samples=0, device=0, track=None):
-        """track: None, or the keyword arguments of track() - the timing loop is set up before the first push.  A refused track closes the stream and raises"""
+    def __init__(self, sample_rate, cells, nof_antennas=None, sample_format=FILE_CF32, sample_scale=0.0, block_subframes=0, ring_samples=0, device=0, track=None,
+                 reacquire=None):
+        """track: None, or the keyword arguments of track() - the timing loop is set up before the first push.  reacquire: None, or the keyword arguments of
+        reacquire(), called behind track().  A refused track or reacquire closes the stream and raises"""
         self._h = None
         self._phys = [phy for phy, _ in cells]     # kept alive as long as the stream
         arr = (FileCell * max(len(cells), 1))()
@@ -1413,6 +1486,12 @@ class Stream:
             except ValueError:
                 self.close()
                 raise
+        if reacquire is not None:
+            try:
+                self.reacquire(**reacquire)
+            except ValueError:
+                self.close()
+                raise
 
     def track(self, kp=0.0, ki=0.0, max_ppm=0.0, lost_after=0, cfo_hz=0.0, initial_ppm=0.0, enable=True):
         """lsn_stream_track: a PSS timing loop per cell follows the sample clock.  Only before the first push.  cfo_hz, initial_ppm, enable: one
@@ -1430,6 +1509,23 @@ class Stream:
         return dict(segments=[int(v) for v in st.segments[:n]], valid=[int(v) for v in st.valid[:n]], invalid=[int(v) for v in st.invalid[:n]],
                     lost=[int(v) for v in st.lost[:n]], last_error=[float(v) for v in st.last_error[:n]], correction_ppm=[float(v) for v in st.correction_ppm[:n]],
                     integrator_ppm=[float(v) for v in st.integrator_ppm[:n]], position_drift=[float(v) for v in st.position_drift[:n]])
+
+    def reacquire(self, after=0, min_ratio=0.0, enable=True):
+        """lsn_stream_reacquire: a cell whose loop saw `after` invalid segments in a row (0: the loop's lost_after) is searched over a whole half frame and its
+        position moved once to the nearest PSS.  Only after track() and before the first push.  enable: one value for every cell, or a list.  Raises
+        ValueError when the library refuses (the stream is unchanged and usable)"""
+        self._call(lib().lsn_stream_reacquire(self._h, C.byref(_reacquire_cfg(self.nof_cells, after, min_ratio, enable))), "lsn_stream_reacquire")
+
+    def reacquire_status(self):
+        """lsn_stream_reacquire_status -> dict of per-cell lists: launched, accepted, rejected, last_peak, last_ratio, last_offset (output samples), jump_segment,
+        jumps_total (input samples).  Behind a flush it is a function of the samples pushed"""
+        st = StreamReacquireStatus()
+        st.struct_size = C.sizeof(StreamReacquireStatus)
+        self._call(lib().lsn_stream_reacquire_status(self._h, C.byref(st)), "lsn_stream_reacquire_status")
+        n = int(st.nof_cells)
+        return dict(launched=[int(v) for v in st.launched[:n]], accepted=[int(v) for v in st.accepted[:n]], rejected=[int(v) for v in st.rejected[:n]],
+                    last_peak=[float(v) for v in st.last_peak[:n]], last_ratio=[float(v) for v in st.last_ratio[:n]], last_offset=[int(v) for v in st.last_offset[:n]],
+                    jump_segment=[int(v) for v in st.jump_segment[:n]], jumps_total=[float(v) for v in st.jumps_total[:n]])
 
     def _call(self, rc, what):
         if rc == LSN_ERROR_INVALID_INPUTS:

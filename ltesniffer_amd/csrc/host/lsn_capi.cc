@@ -778,6 +778,20 @@ int lsn_stream_track_status(lsn_stream_t* s, lsn_stream_track_status_t* out)
   return s->ring->trackStatus(out);
 }
 
+int lsn_stream_reacquire(lsn_stream_t* s, const lsn_stream_reacquire_cfg_t* cfg)
+{
+  if (!s || !cfg || cfg->struct_size != sizeof(lsn_stream_reacquire_cfg_t)) return LSN_ERROR_INVALID_INPUTS;
+  std::unique_lock<std::mutex> lk(s->ring->mtx);
+  return s->ring->reacquire(*cfg);
+}
+
+int lsn_stream_reacquire_status(lsn_stream_t* s, lsn_stream_reacquire_status_t* out)
+{
+  if (!s || !out) return LSN_ERROR_INVALID_INPUTS;
+  std::unique_lock<std::mutex> lk(s->ring->mtx);
+  return s->ring->reacquireStatus(out);
+}
+
 int lsn_stream_close(lsn_stream_t* s)
 {
   if (!s) return LSN_ERROR_INVALID_INPUTS;

@@ -9,6 +9,9 @@
 // A stream that asked for it (track()) follows the sample clock: runReadyTracked resamples segment by segment at the steps its timing loop
 // decides (lsn_track.h) and measures every segment's PSS with k_pss_timing; a stream that did not runs runReady exactly as before.  The two loops differ in how a
 // block buffer fills; what they do alike - bufferFor, launchRing, submitBlock - exists once.
+// A tracked stream that asked for it too (reacquire()) searches a cell whose loop has lost the PSS over a whole half frame: launchSearches
+// resamples the span into a scratch of the cell's and runs k_pss_acquire on it - launches of their own, which a stream that loses nothing never issues -, and the
+// enter() of three segments later moves the position once.
 // Cells with a channel filter: launchRing runs the file source's two stages instead - one k_chan_fir_ring launch out of the ring into the
 // cells' intermediates, one k_resample per cell out of those - and every span that guards the ring is L samples wider on both sides.  Without one, nothing differs.
 #include "lsn_stream_ring.h"
@@ -51,6 +54,9 @@ StreamRing::~StreamRing()
     if (c.d_taps) (void)hipFree(c.d_taps);
     if (c.mid) c.s.e->holdChanBuffer(false);   // (mid is the Phy's: given back, not freed)
     if (c.h_C) (void)hipHostFree(c.h_C);
+    if (c.acq_x) (void)hipFree(c.acq_x);
+    if (c.acq_C) (void)hipHostFree(c.acq_C);
+    if (c.acq_ev) (void)hipEventDestroy(c.acq_ev);
     for (auto& p : c.pending) if (p.ev) (void)hipEventDestroy(p.ev);
   }
   if (d_ring) (void)hipFree(d_ring);
@@ -113,7 +119,8 @@ int64_t StreamRing::oldestNeeded() const
     int64_t oldest = (int64_t)pushed;
     for (const auto& c : cells) {
       if (c.s.max_subframes && c.filled >= c.s.max_subframes) continue;
-      const int64_t lo = (int64_t)(uint64_t)(c.tk.position(c.filled) >> 64) - (int64_t)c.s.plan.taps / 2 + 1 - (int64_t)c.s.filt.L;
+      // (a cell with re-acquisition keeps acq_keep samples more: the span of a search of the segment behind, and room for a backward jump)
+      const int64_t lo = (int64_t)(uint64_t)(c.tk.position(c.filled) >> 64) - (int64_t)c.s.plan.taps / 2 + 1 - (int64_t)c.s.filt.L - (int64_t)c.acq_keep;
       oldest = std::min(oldest, std::max<int64_t>(lo, 0));
     }
     return oldest;
@@ -300,20 +307,11 @@ int StreamRing::track(const lsn_stream_track_cfg_t& tc, double rate_in)
   TrackCfg cfg;
   const int r = track_cfg_resolve(tc.kp, tc.ki, tc.max_ppm, tc.lost_after, cfg);
   if (r != LSN_SUCCESS) return r;
-  int64_t lo = 0, hi = 0;
   for (size_t c = 0; c < cells.size(); c++) {
     if (!std::isfinite(tc.cfo_hz[c]) || !std::isfinite(tc.initial_ppm[c]) || std::fabs(tc.initial_ppm[c]) > cfg.max_ppm) return LSN_ERROR_INVALID_INPUTS;
     if (cells[c].s.e->symbolSz() < 128) return LSN_ERROR_INVALID_INPUTS;
-    // stream_block_input with every step widened by 1 + max_ppm 1e-6
-    const ResamplePlan& p = cells[c].s.plan;
-    const int64_t half = (int64_t)p.taps / 2;
-    const u128 last = p.start + (u128)((uint64_t)blk * cells[c].sflen - 1) * track_widened_step(p.step, cfg.max_ppm);
-    const int64_t L = (int64_t)cells[c].s.filt.L;   // a filtered cell reads L more on both sides
-    const int64_t l = (int64_t)(uint64_t)(p.start >> 64) - half + 1 - L, h = (int64_t)(uint64_t)(last >> 64) + half + 1 + L;
-    lo = c ? std::min(lo, l) : l;
-    hi = c ? std::max(hi, h) : h;
   }
-  if ((uint64_t)(hi - lo) + 2 > ring_samples) return LSN_ERROR_INVALID_INPUTS;
+  if ((uint64_t)trackedBlockInput(cfg.max_ppm) + 2 > ring_samples) return LSN_ERROR_INVALID_INPUTS;
   // the intermediates at the widened step: grown here, in front of the first push (nothing has been launched yet), or the call is refused
   for (auto& q : cells) {
     if (!q.s.filt.L) continue;
@@ -341,6 +339,121 @@ int StreamRing::track(const lsn_stream_track_cfg_t& tc, double rate_in)
       q.filled = 0;
     }
     tracking = true;
+    return LSN_SUCCESS;
+  });
+}
+
+int64_t StreamRing::trackedBlockInput(double max_ppm) const
+{
+  int64_t lo = 0, hi = 0;
+  for (size_t c = 0; c < cells.size(); c++) {
+    const ResamplePlan& p = cells[c].s.plan;
+    const int64_t half = (int64_t)p.taps / 2;
+    const u128 last = p.start + (u128)((uint64_t)blk * cells[c].sflen - 1) * track_widened_step(p.step, max_ppm);
+    const int64_t L = (int64_t)cells[c].s.filt.L;   // a filtered cell reads L more on both sides
+    const int64_t l = (int64_t)(uint64_t)(p.start >> 64) - half + 1 - L, h = (int64_t)(uint64_t)(last >> 64) + half + 1 + L;
+    lo = c ? std::min(lo, l) : l;
+    hi = c ? std::max(hi, h) : h;
+  }
+  return hi - lo;
+}
+
+// ---- re-acquisition (lsn_track.h) ----
+
+int StreamRing::reacquire(const lsn_stream_reacquire_cfg_t& rc)
+{
+  if (pushed || !tracking || reacquiring || failed != LSN_SUCCESS || filtered()) return LSN_ERROR_INVALID_INPUTS;
+  if (rc.min_ratio != 0.0 && (!std::isfinite(rc.min_ratio) || rc.min_ratio < 1.0)) return LSN_ERROR_INVALID_INPUTS;
+  // the ring holds what track() asked for and, behind it, the samples every searched cell keeps
+  const double max_ppm = cells[0].tk.cfg.max_ppm;   // (one configuration for all cells of a stream)
+  uint64_t keep[kFileMaxCells] = {}, most = 0;
+  for (size_t c = 0; c < cells.size(); c++) {
+    if (!rc.enable[c] || !cells[c].tk.enabled) continue;   // a cell whose loop is off has no measurement that could be lost
+    keep[c] = track_acquire_keep(cells[c].s.plan.step, max_ppm, cells[c].sflen);
+    most = std::max(most, keep[c]);
+  }
+  if ((uint64_t)trackedBlockInput(max_ppm) + 2 + most > ring_samples) return LSN_ERROR_INVALID_INPUTS;
+  return guarded([&]() -> int {
+    HIP_CHECK(hipSetDevice(device));
+    for (size_t c = 0; c < cells.size(); c++) {
+      Cell& q = cells[c];
+      if (!keep[c]) continue;
+      const uint32_t N = q.s.e->symbolSz();
+      if (!q.acq_x) HIP_CHECK(hipMalloc((void**)&q.acq_x, (size_t)kAcqSpanSubframes * nant * q.sflen * sizeof(cf32)));
+      if (!q.acq_C) HIP_CHECK(hipHostMalloc((void**)&q.acq_C, (size_t)(kTrackSegSubframes * q.sflen / track_lag_spacing(N)) * sizeof(float), hipHostMallocCoherent | hipHostMallocMapped));
+    }
+    for (size_t c = 0; c < cells.size(); c++) {
+      if (!keep[c]) continue;
+      cells[c].acq_keep = keep[c];
+      cells[c].tk.reacquire(rc.after, rc.min_ratio);
+    }
+    reacquiring = true;
+    return LSN_SUCCESS;
+  });
+}
+
+void StreamRing::launchSearches()
+{
+  LsnResampleCell k[kFileMaxCells];
+  LsnAcquireCell a[kFileMaxCells];
+  int64_t lo[kFileMaxCells] = {}, hi[kFileMaxCells] = {};
+  bool any = false;
+  for (size_t c = 0; c < cells.size(); c++) {
+    Cell& q = cells[c];
+    TrackCell& t = q.tk;
+    k[c] = LsnResampleCell();
+    a[c] = LsnAcquireCell();
+    if (!t.search.active || t.search.launched) continue;
+    t.searchInputSpan(lo[c], hi[c]);
+    if (hi[c] > (int64_t)pushed) continue;   // the span is not complete yet
+    t.search.launched = true;
+    if (inGap(lo[c], hi[c])) continue;       // not launched: it comes back rejected (acq_ev stays null)
+    k[c] = q.s.plan.cell(t.search.base, t.search.step, t.search.span, q.sflen, 0, q.tb, q.acq_x, (uint64_t)kAcqSpanSubframes * q.sflen);
+    a[c].x = q.acq_x; a[c].rep = q.d_rep; a[c].C = q.acq_C; a[c].N = t.N; a[c].d = track_lag_spacing(t.N); a[c].sflen = q.sflen; a[c].nant = nant;
+    a[c].n_lags = kTrackSegSubframes * q.sflen / a[c].d;
+    any = true;
+  }
+  if (!any) return;
+  launchRing(k, lo, hi, "search");   // a launch of its own: the scratches are no block buffers, and the decode path's launches stay what they are
+  lsn_launch_pss_acquire(a, (uint32_t)cells.size(), st_run);
+  for (size_t c = 0; c < cells.size(); c++) {
+    if (!a[c].n_lags) continue;
+    cells[c].acq_ev = takeEvent();
+    HIP_CHECK(hipEventRecord(cells[c].acq_ev, st_run));
+    cells[c].tk.acq_launched++;
+  }
+}
+
+void StreamRing::takeSearch(Cell& q)
+{
+  TrackCell& t = q.tk;
+  if (!t.search.active || !t.search.launched || t.search.done) return;
+  if (t.nvalid + t.ninvalid < t.search.h + 2) return;   // (a status call) the measurement of segment h + 1, whose history the decision reads, is not in yet
+  if (!q.acq_ev) { t.searched(nullptr); return; }
+  const hipError_t e = hipEventSynchronize(q.acq_ev);
+  ev_free.push_back(q.acq_ev);
+  q.acq_ev = nullptr;
+  HIP_CHECK(e);
+  t.searched(q.acq_C);
+}
+
+int StreamRing::reacquireStatus(lsn_stream_reacquire_status_t* out)
+{
+  if (!out || out->struct_size != sizeof(lsn_stream_reacquire_status_t) || !reacquiring) return LSN_ERROR_INVALID_INPUTS;
+  return guarded([&]() -> int {
+    HIP_CHECK(hipSetDevice(device));
+    memset(out, 0, sizeof(*out));
+    out->struct_size = sizeof(*out);
+    out->nof_cells = (uint32_t)cells.size();
+    for (size_t c = 0; c < cells.size(); c++) {
+      Cell& q = cells[c];
+      deliver(q, 0, true);   // the measurement of segment h + 1 comes in front of the search of segment h, as on entering h + 3
+      takeSearch(q);
+      const TrackCell& t = q.tk;
+      out->launched[c] = t.acq_launched; out->accepted[c] = t.acq_accepted; out->rejected[c] = t.acq_rejected;
+      out->last_peak[c] = t.acq_peak; out->last_ratio[c] = t.acq_ratio; out->last_offset[c] = t.acq_offset;
+      out->jump_segment[c] = t.acq_jump_segment; out->jumps_total[c] = std::ldexp((double)t.acq_jumps, -64);
+    }
     return LSN_SUCCESS;
   });
 }
@@ -385,6 +498,7 @@ int StreamRing::runReadyTracked(bool flush_all)
       if (q.s.max_subframes && q.filled >= q.s.max_subframes) continue;   // run out
       if (!t.entered || q.filled == t.segEnd()) {   // the next segment: the measurement of the segment two in front of it comes back first
         if (t.needsMeasurement()) deliver(q, t.h - 1, false);
+        if (t.searchResultDue()) takeSearch(q);   // (re-acquisition: the search of the segment three in front comes back behind that measurement)
         t.enter();
       }
       const uint64_t end = std::min<uint64_t>(t.segEnd(), q.done + blk);
@@ -425,6 +539,7 @@ int StreamRing::runReadyTracked(bool flush_all)
       }
       for (size_t c = 0; c < cells.size(); c++) cells[c].filled += piece[c];
     }
+    if (reacquiring) launchSearches();
     bool submitted = false;
     for (size_t c = 0; c < cells.size() && failed == LSN_SUCCESS; c++) {
       Cell& q = cells[c];

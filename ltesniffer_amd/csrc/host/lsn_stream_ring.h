@@ -1,6 +1,7 @@
 // lsn_stream_ring.h - the object behind lsn_stream_*: the raw input of a live stream in ONE device ring, the cells' Phys fed out of it by k_resample_ring
 //  - or, when the cells have a channel filter, by k_chan_fir_ring and one k_resample per cell (section 3.1j).  The counting is lsn_stream.h's; this is the part that speaks to the HIP runtime and to the engines.
-// A tracked stream (track(), section 3.1h) counts by the segments of lsn_track.h instead and measures every segment's PSS with k_pss_timing.
+// A tracked stream (track(), section 3.1h) counts by the segments of lsn_track.h instead and measures every segment's PSS with k_pss_timing; with reacquire()
+// (section 3.1k) it searches a cell that has lost its PSS with k_pss_acquire and keeps 8 subframes of input more per such cell.
 #pragma once
 #include "lsn_engine.h"
 #include "lsn_resample_launch.h"
@@ -33,6 +34,9 @@ public:
   // the timing loop (lsn_stream_track): accepted before the first sample only; a refusal leaves the stream as it was
   int track(const lsn_stream_track_cfg_t& cfg, double rate_in /* the stream's sample rate */);
   int trackStatus(lsn_stream_track_status_t* out);
+  // re-acquisition (lsn_stream_reacquire): after track(), before the first sample; a refusal leaves the stream as it was
+  int reacquire(const lsn_stream_reacquire_cfg_t& cfg);
+  int reacquireStatus(lsn_stream_reacquire_status_t* out);
   uint64_t pushedSamples() const { return pushed; }
   uint64_t ringSamples() const { return ring_samples; }
   uint32_t blockSubframes() const { return blk; }
@@ -66,6 +70,11 @@ private:
     float* h_C = nullptr;                // pinned, [TRACK_SLOTS][13]: k_pss_timing writes, the host reads behind the event
     struct Pending { uint64_t h; hipEvent_t ev; uint32_t slot; };   // the measurement of segment h: ev null = none could be taken
     std::deque<Pending> pending;
+    // re-acquisition: the span of the search in flight (TrackCell::search) is resampled into acq_x and k_pss_acquire writes its values into acq_C
+    cf32* acq_x = nullptr;               // [6][antenna][sflen]
+    float* acq_C = nullptr;              // pinned, [75 N / d]
+    hipEvent_t acq_ev = nullptr;         // behind the search that was launched
+    uint64_t acq_keep = 0;               // input samples kept behind what the cell needs anyway (0: no re-acquisition)
   };
   static constexpr uint32_t TRACK_SLOTS = 4;   // at most kTrackDelay measurements of a cell are in flight
   struct Launch { hipEvent_t ev; int64_t lo; };   // recorded behind a launch that read the ring from recording sample lo on (filtered: the widened span's)
@@ -87,6 +96,9 @@ private:
   void submitBlock(Cell& q, uint32_t nsf);
   void deliver(Cell& q, uint64_t upto_h, bool all);   // the measurements of segments <= upto_h (all: every one in flight) go to the loop; waits for their events
   bool inGap(int64_t lo, int64_t hi) const;
+  int64_t trackedBlockInput(double max_ppm) const;   // stream_block_input with every step widened by 1 + max_ppm 1e-6: what track() and reacquire() hold the ring against
+  void launchSearches();                 // the searches that are due and whose span is complete in the ring: one resampling launch into the scratches, one k_pss_acquire
+  void takeSearch(Cell& q);              // the result of the cell's search goes to its TrackCell, if it was launched; waits for its event
   hipEvent_t takeEvent();
   const int device;
   const uint32_t nant, fmt;
@@ -103,7 +115,7 @@ private:
   std::vector<Launch> inflight;
   std::vector<hipEvent_t> ev_free;
   uint64_t pushed = 0;
-  bool tracking = false;
+  bool tracking = false, reacquiring = false;
   std::vector<std::pair<int64_t, int64_t>> gaps;   // tracked: the gaps [lo, hi) a cell may still read
   int failed = LSN_SUCCESS;              // the first engine's failure: nothing more is submitted, every later call returns it
 };

@@ -112,15 +112,71 @@ void TrackCell::enter()
   } else {
     delta = enabled ? track_delta(rate_in, rate_out, seglen, loop.corr) : 0;   // segments 0 and 1: the opened rate times 1 + initial_ppm 1e-6
   }
+  u128 b2 = b;
+  if (searchResultDue()) {   // behind the loop's step: an accepted search moves the position once, by o outputs at the step of the segment that was searched
+    if (!search.done) throw std::runtime_error("track: a segment entered before its search came back");
+    if (search.accepted) {
+      const __int128 jump = (__int128)search.offset * (__int128)search.step;
+      b2 = (u128)((__int128)b + jump);
+      loop.invalid_run = 0;
+      acq_jumps += jump;
+      acq_jump_segment = h + 1;
+    }
+    search = Search();
+  }
   h = entered ? h + 1 : 0;
   entered = true;
   sf0 = s0;
   nsf = h ? kTrackSegSubframes : first_nsf;
   if (max_subframes && sf0 + nsf > max_subframes) nsf = sf0 < max_subframes ? (uint32_t)(max_subframes - sf0) : 0;
-  base = b;
+  base = b2;
   step = (u128)((__int128)rs->step + delta);
   span = (uint32_t)(((u128)512 * step) >> 64) + rs->taps + 2;   // ResamplePlan::init's rule (512 = LSN_RS_RUN, outputs of one run) at this segment's step
   if (span < rs->span) span = rs->span;
+  if (acq && enabled && !search.active && loop.invalid_run >= acq_after) {   // a search of this segment is due
+    search.active = true; search.h = h; search.base = base; search.step = step; search.span = span;
+  }
+}
+
+void TrackCell::searchInputSpan(int64_t& lo, int64_t& hi) const
+{
+  const int64_t half = (int64_t)rs->taps / 2;
+  const u128 last = search.base + (u128)((uint64_t)kAcqSpanSubframes * sflen - 1) * search.step;
+  lo = (int64_t)(uint64_t)(search.base >> 64) - half + 1;
+  hi = (int64_t)(uint64_t)(last >> 64) + half + 1;
+}
+
+void TrackCell::searched(const float* C)
+{
+  if (!search.active || search.done) throw std::runtime_error("track: a search result nobody waits for");
+  search.done = true;
+  if (C) {
+    const uint32_t d = track_lag_spacing(N);
+    search.accepted = track_acquire_decide(C, kTrackSegSubframes * sflen / d, d, N, acq_min_ratio, search.hist_mean, search.offset, acq_peak, acq_ratio);
+    acq_offset = search.offset;
+  }
+  if (search.accepted) acq_accepted++; else acq_rejected++;
+}
+
+bool track_acquire_decide(const float* C, uint32_t n, uint32_t d, uint32_t N, double min_ratio, double history_mean, int64_t& offset, double& peak, double& ratio)
+{
+  uint32_t b = 0;
+  for (uint32_t i = 1; i < n; i++) if (C[i] > C[b]) b = i;
+  double far = 0.0;
+  for (uint32_t i = 0; i < n; i++) {
+    const uint32_t fw = i >= b ? i - b : i + n - b, dist = std::min(fw, n - fw);
+    if (dist > kAcqFar && (double)C[i] > far) far = (double)C[i];
+  }
+  peak = (double)C[b];
+  ratio = far > 0.0 ? peak / far : (peak > 0.0 ? INFINITY : 0.0);
+  const int64_t W5 = 75 * (int64_t)N, p = (int64_t)track_pss_index(N);
+  offset = (((int64_t)b * d - p + W5 / 2) % W5 + W5) % W5 - W5 / 2;
+  return peak > 0.0 && peak >= min_ratio * far && !(history_mean >= 0.0 && !(peak >= 0.25 * history_mean));
+}
+
+uint64_t track_acquire_keep(u128 step, double max_ppm, uint32_t sflen)
+{
+  return (uint64_t)(((u128)((uint64_t)kAcqKeepSubframes * sflen) * track_widened_step(step, max_ppm)) >> 64) + 1;
 }
 
 void TrackCell::measured(const float* C)
@@ -129,6 +185,14 @@ void TrackCell::measured(const float* C)
   if (C && enabled) {
     double e, peak;
     if (track_observe(C, track_lag_spacing(N), e, peak) && peaks.accept(peak)) { m.valid = true; m.e = e; last_e = e; }
+  }
+  if (search.active && nvalid + ninvalid == search.h + 1) {   // this is the measurement of segment h + 1 (every segment has one, in order): the history the decision reads
+    search.hist_mean = -1.0;
+    if (peaks.n) {
+      double sum = 0.0;
+      for (uint32_t i = 0; i < peaks.n; i++) sum = sum + peaks.hist[(peaks.at + 8 - peaks.n + i) % 8];
+      search.hist_mean = sum / (double)peaks.n;
+    }
   }
   if (m.valid) nvalid++; else ninvalid++;
   if (nq >= kTrackDelay) throw std::runtime_error("track: more measurements than the loop's delay");
@@ -192,6 +256,14 @@ int lsn_pss_timing_error(const float* C, uint32_t d, double* e, double* peak)
 {
   if (!C || !d || !e || !peak) return LSN_ERROR_INVALID_INPUTS;
   return lsn::track_observe(C, d, *e, *peak) ? 1 : 0;
+}
+
+int lsn_pss_acquire_decide(const float* C, uint32_t n, uint32_t d, uint32_t N, double min_ratio, double history_mean, int64_t* offset, double* peak, double* ratio)
+{
+  if (!C || !offset || !peak || !ratio || N < 128 || N > 2048 || d != lsn::track_lag_spacing(N) || (uint64_t)n * d != 75ull * N || std::isnan(history_mean)) return LSN_ERROR_INVALID_INPUTS;
+  if (min_ratio == 0.0) min_ratio = lsn::kAcqMinRatio;
+  if (!std::isfinite(min_ratio) || min_ratio < 1.0) return LSN_ERROR_INVALID_INPUTS;
+  return lsn::track_acquire_decide(C, n, d, N, min_ratio, history_mean, *offset, *peak, *ratio) ? 1 : 0;
 }
 
 }  // extern "C"

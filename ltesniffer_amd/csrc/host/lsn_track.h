@@ -10,6 +10,12 @@ namespace lsn {
 static constexpr uint32_t kTrackLags = 13;        // l_j = (j - 6) d
 static constexpr uint32_t kTrackSegSubframes = 5; // one half frame: a PSS in the first subframe of every segment behind the first
 static constexpr uint32_t kTrackDelay = 2;        // the measurement of segment h decides the step of segment h + 2
+// re-acquisition
+static constexpr uint32_t kAcqSpanSubframes = 6;  // a search reads segment h and one subframe more, all at segment h's step
+static constexpr uint32_t kAcqDelay = 3;          // and is taken in on entering segment h + 3
+static constexpr uint32_t kAcqFar = 8;            // lags around the maximum that do not count as another peak
+static constexpr uint32_t kAcqKeepSubframes = 8;  // 6 for the span of the segment behind, 2.5 for a backward jump, rounded up
+static constexpr double kAcqMinRatio = 3.0;       // the geometric mean of the ratio measured on noise (1.86) and with the cell present (5.1)
 
 inline uint32_t track_lag_spacing(uint32_t N) { return N / 128 ? N / 128 : 1; }
 // index, inside a subframe 0 / 5, of the first useful sample of the PSS symbol: symbol 6 of slot 0 with the normal prefix, symbol 5 with the extended one - 13 N / 2
@@ -72,6 +78,30 @@ struct TrackCell {
   uint32_t nq = 0;
   uint64_t nvalid = 0, ninvalid = 0;
   double last_e = 0.0;
+  // re-acquisition (off unless reacquire() was called): at most one search per cell is in flight.  It is due on entering segment h, after the loop's step, when
+  // invalid_run >= after; its span is segment h's base and step; its result - searched() - is taken in by the enter() of segment h + 3
+  struct Search {
+    bool active = false, launched = false, done = false, accepted = false;
+    uint64_t h = 0;
+    u128 base = 0, step = 0;
+    uint32_t span = 0;
+    double hist_mean = -1.0;   // the valid-peak history behind the measurement of segment h + 1 (measured() fills it; < 0: empty)
+    int64_t offset = 0;
+  };
+  bool acq = false;
+  uint32_t acq_after = 0;
+  double acq_min_ratio = kAcqMinRatio;
+  Search search;
+  uint64_t acq_launched = 0, acq_accepted = 0, acq_rejected = 0, acq_jump_segment = 0;
+  double acq_peak = 0.0, acq_ratio = 0.0;
+  int64_t acq_offset = 0;
+  __int128 acq_jumps = 0;    // the sum of all jumps, 2^-64 input samples
+
+  void reacquire(uint32_t after, double min_ratio) { acq = true; acq_after = after ? after : cfg.lost_after; acq_min_ratio = min_ratio != 0.0 ? min_ratio : kAcqMinRatio; }
+  bool searchResultDue() const { return search.active && entered && h + 1 == search.h + kAcqDelay; }   // the next enter() takes the search's result in
+  void searchInputSpan(int64_t& lo, int64_t& hi) const;   // input samples the search in flight reads
+  // the result: C the values of k_pss_acquire (75 N / d of them), null = the search could not be launched (its span reads a gap) - rejected
+  void searched(const float* C);
 
   void init(const ResamplePlan* plan, uint32_t sflen_, uint32_t N_, uint32_t start_tti, uint64_t max_sf, double r_in, const TrackCfg& c, bool enable, double initial_ppm);
   uint64_t segEnd() const { return entered ? sf0 + nsf : 0; }       // first subframe behind the current segment (0 before segment 0 is entered)
@@ -93,5 +123,13 @@ struct TrackCell {
 int track_cfg_resolve(double kp, double ki, double max_ppm, uint32_t lost_after, TrackCfg& out);
 // the plan's step widened by 1 + max_ppm 1e-6, rounded up: the fastest a tracked cell moves through the ring
 u128 track_widened_step(u128 step, double max_ppm);
+
+// ---- re-acquisition (lsn_stream_reacquire) ----
+// the decision over the values of k_pss_acquire, C[n] with n d = 75 N: i* the first maximum, peak = C[i*], far the largest value whose circular distance from i*
+// is above kAcqFar lags; accepted when peak > 0, peak >= min_ratio far and peak >= 0.25 history_mean (history_mean < 0: an empty history accepts);
+// offset = ((i* d - 13 N / 2 + 75 N / 2) mod 75 N) - 75 N / 2 output samples: the nearest PSS; ratio = peak / far (far = 0: infinity, or 0 when peak is 0 too)
+bool track_acquire_decide(const float* C, uint32_t n, uint32_t d, uint32_t N, double min_ratio, double history_mean, int64_t& offset, double& peak, double& ratio);
+// input samples a cell with re-acquisition keeps behind what it keeps anyway: kAcqKeepSubframes output subframes at the widened step
+uint64_t track_acquire_keep(u128 step, double max_ppm, uint32_t sflen);
 
 }  // namespace lsn

@@ -1,4 +1,4 @@
-// lsn_track_launch.h - the launcher of kernels/track.hip (k_pss_timing): the part of the timing loop's host side that speaks the HIP runtime's types (lsn_track.h,
+// lsn_track_launch.h - the launchers of kernels/track.hip (k_pss_timing, k_pss_acquire): the part of the timing loop's host side that speaks the HIP runtime's types (lsn_track.h,
 // the loop and the segments, does not).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -22,3 +22,19 @@ struct LsnTimingCell {
   uint32_t pad;
 };
 void lsn_launch_pss_timing(const LsnTimingCell* cells, uint32_t n_cells, hipStream_t s);
+
+#define LSN_ACQ_TILE 16u          // consecutive lags one workgroup of k_pss_acquire takes
+#define LSN_ACQ_SUBFRAMES 6u      // the span of a search: a half frame of lags and one window more
+
+// what one cell of a k_pss_acquire launch brings: the span x of 6 subframes - 90 N samples per antenna, contiguous in time - and the 75 N / d lags L_i = i d from its
+// first sample on; value i goes to C[i]
+struct LsnAcquireCell {
+  const cf32* x;      // [6][antenna][sflen], sflen = 15 N
+  const cf32* rep;    // [N]
+  float* C;           // [75 N / d]; device memory, or pinned host memory the device writes
+  uint32_t N, d;      // symbol size; lag spacing max(1, N / 128)
+  uint32_t sflen, nant;
+  uint32_t n_lags;    // 75 N / d, a multiple of LSN_ACQ_TILE; 0: the cell takes no part in this launch
+  uint32_t pad;
+};
+void lsn_launch_pss_acquire(const LsnAcquireCell* cells, uint32_t n_cells, hipStream_t s);
