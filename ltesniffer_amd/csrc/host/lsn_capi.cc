@@ -12,7 +12,6 @@
 // lets batches grow towards half the pool; live mode (getAvailImmediate, :439) dispatches whatever is pending at once.
 #include "lsn_engine.h"
 #include "lsn_cells.h"
-#include "lsn_chanfilt_launch.h"
 #include "lsn_stream_ring.h"
 #include <chrono>
 #include <condition_variable>
@@ -811,123 +810,6 @@ int lsn_phy_set_channel_filter(lsn_phy_t* phy, double stopband_hz)
   return phy->engine->setChannelFilter(stopband_hz);
 }
 
-// stage 1 alone (k_chan_fir), no Phy
-int lsn_channel_filter(int device, const void* in, int in_on_device, uint64_t n_in, const lsn_channel_filter_cfg_t* cfg, float* out, int out_on_device, uint64_t n_out)
-{
-  lsn::ChanFilter f;
-  const int r = lsn_channel_filter_plan(cfg, f);
-  if (r != LSN_SUCCESS) return r;
-  if (!n_out) return LSN_SUCCESS;
-  if (!in || !out || n_out >= (1ull << 40) || n_in >= (1ull << 62)) return LSN_ERROR_INVALID_INPUTS;
-  int64_t lo = (int64_t)cfg->out_first, hi = (int64_t)(cfg->out_first + n_out);
-  f.widen(lo, hi);
-  const int64_t need_lo = std::max<int64_t>(lo, 0);   // in front of the recording: zeros
-  if (need_lo < (int64_t)cfg->in_base || hi > (int64_t)(cfg->in_base + n_in)) return LSN_ERROR_INVALID_INPUTS;   // the input does not hold what these outputs read
-  const uint32_t nant = cfg->nof_antennas, fmt = cfg->sample_format;
-  const LsnSampleFormat sfm = lsn_sample_format(fmt, cfg->sample_scale);
-  const size_t smp = (size_t)sfm.bytes * nant;
-  const uint64_t len = (uint64_t)(hi - need_lo);
-  const uint8_t* src = (const uint8_t*)in + ((uint64_t)need_lo - cfg->in_base) * smp;
-  void *d_in = nullptr, *d_out = nullptr;
-  float* d_taps = nullptr;
-  const cf32* d_nco = nullptr;
-  hipStream_t st = nullptr;
-  int rc = LSN_SUCCESS;
-  try {
-    HIP_CHECK(hipSetDevice(device));
-    HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    lsn_chan_fir_upload(f, d_taps, d_nco, st);
-    const void* raw = src;
-    if (!in_on_device) {
-      HIP_CHECK(hipMalloc(&d_in, len * smp));
-      HIP_CHECK(hipMemcpyAsync(d_in, src, len * smp, hipMemcpyHostToDevice, st));
-      raw = d_in;
-    }
-    cf32* dst = (cf32*)out;
-    const size_t out_bytes = (size_t)n_out * nant * sizeof(cf32);
-    if (!out_on_device) {
-      HIP_CHECK(hipMalloc(&d_out, out_bytes));
-      dst = (cf32*)d_out;
-    }
-    LsnChanFirCell k;
-    k.taps = d_taps; k.L = f.L; k.w = f.tune; k.nco = d_nco; k.out = dst; k.out_first = (int64_t)cfg->out_first; k.n_out = n_out;
-    lsn_launch_chan_fir(raw, fmt, sfm.scale, need_lo, len, nant, 0, &k, 1, st);
-    if (!out_on_device) HIP_CHECK(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-  } catch (const std::exception& ex) {
-    fprintf(stderr, "ltesniffer_amd: channel_filter: %s\n", ex.what());
-    rc = LSN_ERROR;
-  }
-  if (st) (void)hipStreamDestroy(st);
-  if (d_in) (void)hipFree(d_in);
-  if (d_taps) (void)hipFree(d_taps);
-  if (d_out) (void)hipFree(d_out);
-  return rc;
-}
-
-// stage 1 out of a ring (k_chan_fir_ring), no Phy: the whole window goes to its slots of a device ring, every cell's filter runs in ONE launch
-int lsn_channel_filter_ring(int device, const void* in, uint64_t n_in, uint64_t ring_samples, const lsn_channel_filter_cfg_t* cfgs, uint32_t n_cells, float* const* outs,
-                            const uint64_t* n_out)
-{
-  if (!in || !cfgs || !outs || !n_out || n_cells < 1 || n_cells > LSN_FILE_MAX_CELLS) return LSN_ERROR_INVALID_INPUTS;
-  if (!ring_samples || (ring_samples & (ring_samples - 1)) || ring_samples > (1ull << 32) || n_in > ring_samples || n_in >= (1ull << 62)) return LSN_ERROR_INVALID_INPUTS;
-  std::vector<lsn::ChanFilter> f(n_cells);
-  const lsn_channel_filter_cfg_t& c0 = cfgs[0];
-  bool any = false;
-  for (uint32_t c = 0; c < n_cells; c++) {
-    const lsn_channel_filter_cfg_t& k = cfgs[c];
-    const int r = lsn_channel_filter_plan(&k, f[c]);
-    if (r != LSN_SUCCESS) return r;
-    if (k.nof_antennas != c0.nof_antennas || k.sample_format != c0.sample_format || !(k.sample_scale == c0.sample_scale) || k.rate_in_hz != c0.rate_in_hz || k.in_base != c0.in_base)
-      return LSN_ERROR_INVALID_INPUTS;
-    if (!n_out[c]) continue;
-    if (!outs[c] || n_out[c] >= (1ull << 40)) return LSN_ERROR_INVALID_INPUTS;
-    int64_t lo = (int64_t)k.out_first, hi = (int64_t)(k.out_first + n_out[c]);
-    f[c].widen(lo, hi);
-    if (std::max<int64_t>(lo, 0) < (int64_t)k.in_base || hi > (int64_t)(k.in_base + n_in)) return LSN_ERROR_INVALID_INPUTS;   // the window does not hold what these outputs read
-    any = true;
-  }
-  if (!any) return LSN_SUCCESS;
-  const uint32_t nant = c0.nof_antennas, fmt = c0.sample_format;
-  const LsnSampleFormat sfm = lsn_sample_format(fmt, c0.sample_scale);
-  const size_t smp = (size_t)sfm.bytes * nant;
-  void* d_ring = nullptr;
-  std::vector<float*> d_taps(n_cells, nullptr);
-  std::vector<void*> d_out(n_cells, nullptr);
-  hipStream_t st = nullptr;
-  int rc = LSN_SUCCESS;
-  try {
-    HIP_CHECK(hipSetDevice(device));
-    HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    // slots no sample of the window goes to keep a pattern (NaN as cf32) that a read outside the window would carry into the outputs
-    HIP_CHECK(hipMalloc(&d_ring, ring_samples * smp));
-    HIP_CHECK(hipMemsetAsync(d_ring, 0xFF, ring_samples * smp, st));
-    const uint64_t slot = c0.in_base & (ring_samples - 1), head = std::min(n_in, ring_samples - slot);
-    if (head) HIP_CHECK(hipMemcpyAsync((uint8_t*)d_ring + slot * smp, in, head * smp, hipMemcpyHostToDevice, st));
-    if (n_in > head) HIP_CHECK(hipMemcpyAsync(d_ring, (const uint8_t*)in + head * smp, (n_in - head) * smp, hipMemcpyHostToDevice, st));   // behind the end of the ring
-    LsnChanFirCell k[LSN_FILE_MAX_CELLS];
-    for (uint32_t c = 0; c < n_cells; c++) {
-      k[c] = LsnChanFirCell();
-      if (!n_out[c]) continue;
-      const cf32* d_nco = nullptr;
-      lsn_chan_fir_upload(f[c], d_taps[c], d_nco, st);
-      HIP_CHECK(hipMalloc(&d_out[c], (size_t)n_out[c] * nant * sizeof(cf32)));
-      k[c].taps = d_taps[c]; k[c].L = f[c].L; k[c].w = f[c].tune; k[c].nco = d_nco; k[c].out = (cf32*)d_out[c]; k[c].out_first = (int64_t)cfgs[c].out_first; k[c].n_out = n_out[c];
-    }
-    lsn_launch_chan_fir(d_ring, fmt, sfm.scale, (int64_t)c0.in_base, n_in, nant, ring_samples, k, n_cells, st);
-    for (uint32_t c = 0; c < n_cells; c++)
-      if (n_out[c]) HIP_CHECK(hipMemcpyAsync(outs[c], d_out[c], (size_t)n_out[c] * nant * sizeof(cf32), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-  } catch (const std::exception& ex) {
-    fprintf(stderr, "ltesniffer_amd: channel_filter_ring: %s\n", ex.what());
-    rc = LSN_ERROR;
-  }
-  if (st) (void)hipStreamDestroy(st);
-  if (d_ring) (void)hipFree(d_ring);
-  for (float* t : d_taps) if (t) (void)hipFree(t);
-  for (void* o : d_out) if (o) (void)hipFree(o);
-  return rc;
-}
 int lsn_phy_prepare_file(lsn_phy_t* phy, uint32_t nof_antennas)
 {
   if (!phy) return LSN_ERROR_INVALID_INPUTS;

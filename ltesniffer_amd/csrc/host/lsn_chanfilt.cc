@@ -58,7 +58,7 @@ static int chan_cfg_filter(const lsn_channel_filter_cfg_t* cfg, lsn::ChanFilter&
   return f.init(cfg->rate_in_hz, cfg->passband_hz, cfg->stopband_hz, cfg->center_offset_hz);
 }
 
-// what lsn_channel_filter (lsn_capi.cc) validates with
+// what lsn_channel_filter (lsn_front_launch.cc) validates with
 int lsn_channel_filter_plan(const lsn_channel_filter_cfg_t* cfg, lsn::ChanFilter& f) { return chan_cfg_filter(cfg, f); }
 
 extern "C" {

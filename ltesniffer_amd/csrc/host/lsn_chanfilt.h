@@ -1,8 +1,9 @@
 // lsn_chanfilt.h - host side of the channel filter, stage 1 in front of the resampler (kernels/chanfilt.hip; launcher: lsn_chanfilt_launch.h): the design of
-// one filter - half length L, cut-off, the 2L + 1 taps, the mixer's tuning word - its refusals, and the input spans it widens.  Definition: DESIGN.md section 3.1f.
+// one filter - half length L, cut-off, the 2L + 1 taps, the mixer's tuning word - its refusals, the input spans it widens, and the span of the intermediate stage 2 reads.  Definition: DESIGN.md section 3.1f.
 // No HIP header, like lsn_resample.h: the design is plain host arithmetic and is tested on a machine with no GPU.
 #pragma once
 #include "../../../include/ltesniffer_amd.h"
+#include <algorithm>
 #include <cstdint>
 #include <vector>
 
@@ -24,6 +25,15 @@ struct ChanFilter {
   // a recording of in_end samples carries y1[n] for n < in_end - L: what stage 2 may read
   uint64_t insideEnd(uint64_t in_end) const { return in_end > L ? in_end - L : 0; }
 };
+
+// Stage 2 behind stage 1 (lsn_front_launch.h): a resampler piece that reads the input span [lo, hi) reads y1[lo2, hi2) of its cell's intermediate - the part at or behind
+// sample 0 (in front of it the zeros are the resampler's own; a piece wholly in front of the recording: the empty span at 0).  True: it fits an intermediate of cap samples
+inline bool chan_mid_span(int64_t lo, int64_t hi, uint64_t cap, int64_t& lo2, int64_t& hi2)
+{
+  lo2 = std::max<int64_t>(lo, 0);
+  hi2 = std::max(hi, lo2);
+  return (uint64_t)(hi2 - lo2) <= cap;
+}
 
 }  // namespace lsn
 

@@ -291,6 +291,7 @@ public:
   // the buffer as an open filtered stream holds it (lsn_stream_ring.cc keeps the pointer for its launches): growing frees and reallocates it, so while a stream
   // holds it a call that would grow it is refused (LSN_ERROR_INVALID_INPUTS) and nothing is freed.  The stream itself grows it only in front of its first launch
   cf32* chanBuffer() const { return d_chan; }
+  uint64_t chanBufferSamples(uint32_t nant) const { return chan_bytes / ((size_t)nant * sizeof(cf32)); }   // samples of nant antennas it holds right now
   void holdChanBuffer(bool held) { chan_held = held; }
   int reserveFileBuffers(uint32_t nof_antennas);   // lsn_phy_prepare_file: pinned read blocks + device blocks of the file source, ahead of the first replay
   // what reserveFileBuffers sizes them by - subframes per block (LSN_FILE_BLOCK) and blocks in flight (LSN_FILE_SLOTS) - and the device block of slot si that a

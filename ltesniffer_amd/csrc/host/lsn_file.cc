@@ -10,8 +10,7 @@
 // and crosses PCIe straight from the page cache; on the boxes measured the lock / unlock per block costs more than the copy it saves.
 // Product code: no CPU fallback, nothing from oracle/ is included or linked.
 #include "lsn_engine.h"
-#include "lsn_resample_launch.h"
-#include "lsn_chanfilt_launch.h"
+#include "lsn_front_launch.h"
 #include "lsn_cells.h"
 #include <deque>
 #include <cmath>
@@ -147,16 +146,15 @@ struct Engine::FileReplay {
   struct Cell {
     Engine* e = nullptr;
     const ResamplePlan* rs = nullptr;
-    const ChanFilter* cf = nullptr;   // stage 1 in front of rs: raw block -> mid (y1 over the span rs reads) -> rs; null: rs reads the raw block
-    cf32* mid = nullptr;              // the cell's engine's intermediate (Engine::reserveChanBuffer)
-    float* d_taps = nullptr;          // the filter's taps ...
-    const cf32* d_mix = nullptr;      // ... and, behind them, its mixer's tables when it has a tuning word
     uint32_t sflen = 0;
     float offset_freq_hz = 0.0f;
     uint32_t start_tti = 0, update_meta_period = 0;
     uint64_t max_subframes = 0;
     uint64_t sf_in_file = 0, first_sf = 0, done = 0;   // complete subframes in the file / in front of the replay (DECODE_MIB state of the reference) / submitted
-    ResampleTables tb;            // the -o rotation and, with rs, the resampler's bank and NCO tables (a few hundred kB, as short-lived as the replay)
+    // the -o rotation and, with rs, the resampler's bank and NCO tables (a few hundred kB, as short-lived as the replay); front.cf: stage 1 in front of rs, raw block
+    // -> the engine's intermediate (y1 over the span rs reads) -> rs, or null: rs reads the raw block.  The tables go with the cell: ~FileReplay clears the cells, whose
+    // engines it has waited for, before it destroys the stream
+    FrontCell front;
     int rc = LSN_SUCCESS;         // what this cell's engine answered (submit, then wait)
   };
   struct Slot { cf32* h_raw = nullptr; cf32* d_raw = nullptr; cf32* d_iq[kFileMaxCells] = {}; uint32_t nsf[kFileMaxCells] = {}; uint64_t mark[kFileMaxCells] = {};
@@ -193,7 +191,7 @@ struct Engine::FileReplay {
     uint32_t widest = 0;
     for (uint32_t c = 0; c < n; c++) {
       Cell k;
-      k.e = jobs[c].e; k.rs = jobs[c].rs; k.cf = jobs[c].cf; k.sflen = k.e->cd.sflen; k.offset_freq_hz = jobs[c].offset_freq_hz; k.start_tti = jobs[c].start_tti;
+      k.e = jobs[c].e; k.rs = jobs[c].rs; k.front.cf = jobs[c].cf; k.sflen = k.e->cd.sflen; k.offset_freq_hz = jobs[c].offset_freq_hz; k.start_tti = jobs[c].start_tti;
       k.update_meta_period = jobs[c].update_meta_period; k.max_subframes = jobs[c].max_subframes;
       if (k.sflen > widest) { widest = k.sflen; big = k.e; }
       cells.push_back(std::move(k));
@@ -208,8 +206,6 @@ struct Engine::FileReplay {
     fcv.notify_all();
     if (reader.joinable()) reader.join();
     for (auto& s : slot) if (s.reg) (void)hipHostUnregister(s.reg);
-    for (auto& c : cells)
-      if (c.d_taps) (void)hipFree(c.d_taps);
     cells.clear();   // the cells' tables go before the stream does
     if (st) (void)hipStreamDestroy(st);
     if (map) munmap(map, file_size);
@@ -217,7 +213,7 @@ struct Engine::FileReplay {
   }
 
   bool resampled() const { return cells[0].rs != nullptr; }   // (several cells: every one has a plan)
-  bool filtered() const { return cells[0].cf != nullptr; }    // (several cells: all or none, lsn_file_process_cells)
+  bool filtered() const { return cells[0].front.cf != nullptr; }    // (several cells: all or none, lsn_file_process_cells)
 
   // the cells as lsn_cells.h wants them, from where each one starts
   void plan()
@@ -225,7 +221,7 @@ struct Engine::FileReplay {
     plans.clear();
     for (auto& c : cells) {
       FileCellPlan p;
-      p.rs = c.rs; p.pre = c.cf ? c.cf->L : 0; p.sflen = c.sflen; p.first_sf = c.first_sf; p.total = file_cell_total(c.sf_in_file, c.first_sf, c.max_subframes);
+      p.rs = c.rs; p.pre = c.front.cf ? c.front.cf->L : 0; p.sflen = c.sflen; p.first_sf = c.first_sf; p.total = file_cell_total(c.sf_in_file, c.first_sf, c.max_subframes);
       plans.push_back(p);
     }
   }
@@ -254,7 +250,7 @@ struct Engine::FileReplay {
     file_size = (size_t)sb.st_size;
     for (auto& c : cells) {
       const uint64_t in_end = (uint64_t)file_size / spb;
-      if (c.rs) c.sf_in_file = c.rs->outputsInside(c.cf ? c.cf->insideEnd(in_end) : in_end) / c.sflen;  // output subframes whose whole input span lies inside the file
+      if (c.rs) c.sf_in_file = c.rs->outputsInside(c.front.cf ? c.front.cf->insideEnd(in_end) : in_end) / c.sflen;  // output subframes whose whole input span lies inside the file
       else c.sf_in_file = (uint64_t)file_size > file_off0 ? ((uint64_t)file_size - file_off0) / sf_bytes : 0;  // complete subframes only
     }
     if (resampled() && !fitBlock()) return LSN_ERROR_INVALID_INPUTS;
@@ -268,63 +264,27 @@ struct Engine::FileReplay {
     return LSN_SUCCESS;
   }
 
-  // the y1 samples [lo2, hi2) stage 2 reads for n subframes from output subframe pos (in front of sample 0: zeros, the resampler's own)
-  void midSpan(const Cell& c, uint64_t pos, uint32_t n, int64_t& lo2, int64_t& hi2) const
+  // the cells [c0, c1) through the chain (lsn_front_launch.h): nsf[c] subframes from output subframe sf0[c], out of the raw samples [lo, lo + len) of the recording
+  // into out[c], queued on st
+  void queueFront(size_t c0, size_t c1, const void* raw, int64_t lo, uint64_t len, const uint64_t* sf0, const uint32_t* nsf, cf32* const* out)
   {
-    c.rs->inputSpan(pos * c.sflen, (uint64_t)n * c.sflen, lo2, hi2);
-    lo2 = std::max<int64_t>(lo2, 0);
-    hi2 = std::max(hi2, lo2);
-  }
-
-  // stage 1 of the cells [c0, c1) in ONE k_chan_fir launch: raw samples [lo, lo + len) of the recording -> every cell's intermediate, for nsf[c] subframes from sf0[c]
-  void queueFilter(size_t c0, size_t c1, const void* raw, int64_t lo, uint64_t len, const uint64_t* sf0, const uint32_t* nsf)
-  {
-    LsnChanFirCell k[kFileMaxCells];
+    const FrontCell* fc[kFileMaxCells];
+    LsnResampleCell k[kFileMaxCells];
+    int64_t in_lo[kFileMaxCells] = {}, in_hi[kFileMaxCells] = {};
     for (size_t c = c0; c < c1; c++) {
       const Cell& q = cells[c];
-      LsnChanFirCell& f = k[c - c0];
-      int64_t lo2 = 0, hi2 = 0;
-      if (nsf[c]) midSpan(q, sf0[c], nsf[c], lo2, hi2);
-      if ((size_t)(hi2 - lo2) * nant * sizeof(cf32) > q.e->chan_bytes) throw std::runtime_error("file source: a block's filtered samples do not fit the intermediate buffer");
-      f.taps = q.d_taps; f.L = q.cf->L; f.w = q.cf->tune; f.nco = q.d_mix; f.out = q.mid; f.out_first = lo2; f.n_out = (uint64_t)(hi2 - lo2);
+      fc[c - c0] = &q.front;
+      k[c - c0] = q.rs->cell(sf0[c] * q.sflen, q.sflen, q.front.tb, out[c], (uint64_t)nsf[c] * q.sflen);
+      if (nsf[c]) q.rs->inputSpan(sf0[c] * q.sflen, (uint64_t)nsf[c] * q.sflen, in_lo[c - c0], in_hi[c - c0]);
     }
-    lsn_launch_chan_fir(raw, fmt, sfm.scale, lo, len, nant, 0, k, (uint32_t)(c1 - c0), st);
-  }
-
-  // k_resample for one cell: n subframes from output subframe pos, out of the raw samples [lo, lo + len) of the recording, queued on st
-  void queueResampleOne(const Cell& c, const void* raw, int64_t lo, uint64_t len, uint64_t pos, uint32_t n, cf32* out)
-  {
-    const LsnResampleCell k = c.rs->cell(pos * c.sflen, c.sflen, c.tb, out, (uint64_t)n * c.sflen);
-    if (c.cf) {   // stage 2 of a filtered cell: the plain cf32 k_resample from the cell's intermediate, which queueFilter has filled for these subframes.  Its plan
-                  // was formed with no centre offset (processFileRate, lsn_file_process_cells): tune = 0, no NCO tables - the mixer ran in stage 1
-      int64_t lo2, hi2;
-      midSpan(c, pos, n, lo2, hi2);
-      lsn_launch_resample({c.mid, 0, 1.0f, lo2, (uint64_t)(hi2 - lo2), nant, 0}, k, st);
-      return;
-    }
-    lsn_launch_resample({raw, fmt, sfm.scale, lo, len, nant, 0}, k, st);
+    lsn_launch_front({raw, fmt, sfm.scale, lo, len, nant, 0}, fc, k, in_lo, in_hi, (uint32_t)(c1 - c0), st, "file source: a block");
   }
 
   // the conversion of a block, raw block -> [subframe][antenna][sample] cf32 of every cell that takes part, queued on st
   void queueConvert(Slot& s, const FileCellsBlock& b)
   {
-    if (!resampled()) { lsn_launch_file_unpack(s.d_raw, fmt, sfm.scale, cells[0].tb.d_rot, cells[0].sflen, nant, s.d_iq[0], b.nsf[0], st); return; }
-    const uint64_t len = (uint64_t)(b.in_hi - b.in_lo);
-    if (filtered()) {
-      // one k_chan_fir launch covers all cells; each cell then has an input of its own, and k_resample_cells takes ONE raw buffer per launch: stage 2 is one
-      // k_resample per cell (the same expressions - both kernels expand LSN_RESAMPLE_RUN)
-      queueFilter(0, cells.size(), s.d_raw, b.in_lo, len, b.sf0, b.nsf);
-      for (size_t c = 0; c < cells.size(); c++)
-        if (b.nsf[c]) queueResampleOne(cells[c], nullptr, 0, 0, b.sf0[c], b.nsf[c], s.d_iq[c]);
-      return;
-    }
-    if (cells.size() == 1) { queueResampleOne(cells[0], s.d_raw, b.in_lo, len, b.sf0[0], b.nsf[0], s.d_iq[0]); return; }
-    LsnResampleCell k[kFileMaxCells];
-    for (size_t c = 0; c < cells.size(); c++) {
-      const Cell& q = cells[c];
-      k[c] = q.rs->cell(b.sf0[c] * q.sflen, q.sflen, q.tb, s.d_iq[c], (uint64_t)b.nsf[c] * q.sflen);
-    }
-    lsn_launch_resample_cells({s.d_raw, fmt, sfm.scale, b.in_lo, len, nant, 0}, k, (uint32_t)cells.size(), st);
+    if (!resampled()) { lsn_launch_file_unpack(s.d_raw, fmt, sfm.scale, cells[0].front.tb.d_rot, cells[0].sflen, nant, s.d_iq[0], b.nsf[0], st); return; }
+    queueFront(0, cells.size(), s.d_raw, b.in_lo, (uint64_t)(b.in_hi - b.in_lo), b.sf0, b.nsf, s.d_iq);
   }
 
   // stream, block buffers (kept by the engines: no-op when lsn_phy_prepare_file or an earlier call made them), rotation tables, resampler banks and NCO tables -
@@ -343,12 +303,13 @@ struct Engine::FileReplay {
       for (size_t c = 0; c < cells.size(); c++) s.d_iq[c] = cells[c].e->file_buf[si].d_iq;
     }
     for (auto& c : cells) {
-      c.tb.rotation(c.offset_freq_hz, c.sflen, 15000.0 * (double)c.e->cd.N);
-      if (c.rs) c.tb.upload(*c.rs, st);
-      if (c.cf) {   // the intermediate: reserved by lsn_phy_prepare_file when the filter was set by then, otherwise here - in front of the first block, never inside the loop
-        lsn_chan_fir_upload(*c.cf, c.d_taps, c.d_mix, st);
-        if (c.e->reserveChanBuffer(chan_buffer_bytes(raw_bytes / spb, nant, c.cf->L)) != LSN_SUCCESS) throw std::runtime_error("file source: channel filter buffer");
-        c.mid = c.e->d_chan;
+      FrontCell& f = c.front;
+      f.tb.rotation(c.offset_freq_hz, c.sflen, 15000.0 * (double)c.e->cd.N);
+      if (c.rs) f.tb.upload(*c.rs, st);
+      if (f.cf) {   // the intermediate: reserved by lsn_phy_prepare_file when the filter was set by then, otherwise here - in front of the first block, never inside the loop
+        f.ft.upload(*f.cf, st);
+        if (c.e->reserveChanBuffer(chan_buffer_bytes(raw_bytes / spb, nant, f.cf->L)) != LSN_SUCCESS) throw std::runtime_error("file source: channel filter buffer");
+        f.mid = c.e->chanBuffer(); f.mid_cap = c.e->chanBufferSamples(nant);
       }
     }
     if (resampled()) HIP_CHECK(hipStreamSynchronize(st));
@@ -360,7 +321,7 @@ struct Engine::FileReplay {
     Cell& c = cells[ci];
     for (uint64_t i = 0; i < c.sf_in_file && i < 10 * 64; i += 10) {  // the file starts at subframe 0 of a radio frame (file mode has no sync)
       int64_t lo = 0, hi = 0;
-      if (c.rs) { c.rs->inputSpan(i * c.sflen, c.sflen, lo, hi); if (c.cf) c.cf->widen(lo, hi); lo = std::max<int64_t>(lo, 0); }
+      if (c.rs) { c.rs->inputSpan(i * c.sflen, c.sflen, lo, hi); if (c.front.cf) c.front.cf->widen(lo, hi); lo = std::max<int64_t>(lo, 0); }
       const uint64_t len = c.rs ? (uint64_t)(hi - lo) : c.sflen;
       const size_t bytes = c.rs ? (size_t)len * spb : sf_bytes;
       if (bytes > raw_bytes) throw std::runtime_error("file source: one subframe's input does not fit the block buffer");
@@ -368,9 +329,8 @@ struct Engine::FileReplay {
       if (pread(fd, one.data(), bytes, (off_t)(c.rs ? (uint64_t)lo * spb : file_off0 + i * sf_bytes)) != (ssize_t)bytes) break;
       HIP_CHECK(hipMemcpyAsync(slot[0].d_raw, one.data(), bytes, hipMemcpyHostToDevice, st));
       HIP_CHECK(hipStreamSynchronize(st));
-      if (c.cf) { uint64_t sf0[kFileMaxCells] = {}; uint32_t one_sf[kFileMaxCells] = {}; sf0[ci] = i; one_sf[ci] = 1; queueFilter(ci, ci + 1, slot[0].d_raw, lo, len, sf0, one_sf); }
-      if (c.rs) queueResampleOne(c, slot[0].d_raw, lo, len, i, 1, slot[0].d_iq[ci]);
-      else lsn_launch_file_unpack(slot[0].d_raw, fmt, sfm.scale, c.tb.d_rot, c.sflen, nant, slot[0].d_iq[ci], 1, st);
+      if (c.rs) { uint64_t sf0[kFileMaxCells] = {}; uint32_t one_sf[kFileMaxCells] = {}; sf0[ci] = i; one_sf[ci] = 1; queueFront(ci, ci + 1, slot[0].d_raw, lo, len, sf0, one_sf, slot[0].d_iq); }   // one cell of several: a one-cell launch
+      else lsn_launch_file_unpack(slot[0].d_raw, fmt, sfm.scale, c.front.tb.d_rot, c.sflen, nant, slot[0].d_iq[ci], 1, st);
       HIP_CHECK(hipStreamSynchronize(st));
       lsn_mib_t mib;
       const int r = c.e->mibDecode(slot[0].d_iq[ci], true, &mib, nullptr);

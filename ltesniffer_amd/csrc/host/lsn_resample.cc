@@ -1,8 +1,8 @@
 // lsn_resample.cc - host side of the polyphase resampler: the plan of a rate pair (step and start in 64.64 fixed point, formed in 128-bit
 // integers; number of taps; the bank of 512 phases; the tuning word and tables of the mixer), ResampleTables, the owner of a cell's device copies of them, and
-// lsn_resample / lsn_resample_cells, the stand-alone entry points (they need no Phy, like lsn_cell_search).
+// lsn_resample_span (the stand-alone calls that launch: lsn_front_launch.cc).
 // The filter is DESIGN.md section 3.1b, restated there as a formula; tests/resample_model.py is written from that formula, not from this file.
-// Product code: no CPU fallback (the samples are computed by k_resample only), nothing from oracle/ is included or linked.
+// Product code: nothing from oracle/ is included or linked.
 #include "lsn_hip.h"
 #include "../kernels/lsn_dev.h"
 #include "lsn_resample_launch.h"
@@ -144,7 +144,7 @@ uint64_t ResamplePlan::outputsInside(uint64_t in_end) const
 
 }  // namespace lsn
 
-static int resample_plan(const lsn_resample_cfg_t* cfg, lsn::ResamplePlan& plan)
+int lsn_resample_plan(const lsn_resample_cfg_t* cfg, lsn::ResamplePlan& plan)
 {
   // two sizes are known: the struct up to passband_hz (center_offset_hz reads as 0) and the whole struct
   if (!cfg || (cfg->struct_size != offsetof(lsn_resample_cfg_t, center_offset_hz) && cfg->struct_size != sizeof(lsn_resample_cfg_t))) return LSN_ERROR_INVALID_INPUTS;
@@ -158,7 +158,7 @@ extern "C" {
 int lsn_resample_span(const lsn_resample_cfg_t* cfg, uint64_t n_out, uint64_t in_end, lsn_resample_span_t* out)
 {
   lsn::ResamplePlan plan;
-  const int r = resample_plan(cfg, plan);
+  const int r = lsn_resample_plan(cfg, plan);
   if (r != LSN_SUCCESS || !out) return r != LSN_SUCCESS ? r : LSN_ERROR_INVALID_INPUTS;
   if (cfg->out_first >= (1ull << 40) || n_out >= (1ull << 40)) return LSN_ERROR_INVALID_INPUTS;
   memset(out, 0, sizeof(*out));
@@ -167,151 +167,6 @@ int lsn_resample_span(const lsn_resample_cfg_t* cfg, uint64_t n_out, uint64_t in
   const uint64_t inside = plan.outputsInside(in_end);
   out->max_out = inside > cfg->out_first ? inside - cfg->out_first : 0;
   return LSN_SUCCESS;
-}
-
-int lsn_resample(int device, const void* in, int in_on_device, uint64_t n_in, const lsn_resample_cfg_t* cfg, float* out, int out_on_device, uint64_t n_out)
-{
-  lsn::ResamplePlan plan;
-  const int r = resample_plan(cfg, plan);
-  if (r != LSN_SUCCESS) return r;
-  if (!n_out) return LSN_SUCCESS;
-  if (!in || !out || n_out >= (1ull << 32) || cfg->out_first >= (1ull << 40) || cfg->in_base >= (1ull << 62) || n_in >= (1ull << 62)) return LSN_ERROR_INVALID_INPUTS;
-  int64_t lo, hi;
-  plan.inputSpan(cfg->out_first, n_out, lo, hi);
-  if (hi >= (int64_t)1 << 62) return LSN_ERROR_INVALID_INPUTS;
-  const int64_t need_lo = std::max<int64_t>(lo, 0);   // in front of the recording: zeros
-  if (need_lo < (int64_t)cfg->in_base || hi > (int64_t)(cfg->in_base + n_in)) return LSN_ERROR_INVALID_INPUTS;   // the input does not hold what these outputs read
-  const uint32_t nant = cfg->nof_antennas, fmt = cfg->sample_format;
-  const LsnSampleFormat sfm = lsn_sample_format(fmt, cfg->sample_scale);
-  const size_t smp = (size_t)sfm.bytes * nant;
-  const float scale = sfm.scale;
-  const uint64_t len = hi > need_lo ? (uint64_t)(hi - need_lo) : 0;
-  const uint8_t* src = (const uint8_t*)in + ((uint64_t)need_lo - cfg->in_base) * smp;
-  void *d_in = nullptr, *d_out = nullptr;
-  lsn::ResampleTables tb;
-  hipStream_t st = nullptr;
-  int rc = LSN_SUCCESS;
-  try {
-    HIP_CHECK(hipSetDevice(device));
-    HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    tb.upload(plan, st);
-    const void* raw = src;
-    if (!in_on_device && len) {
-      HIP_CHECK(hipMalloc(&d_in, len * smp));
-      HIP_CHECK(hipMemcpyAsync(d_in, src, len * smp, hipMemcpyHostToDevice, st));
-      raw = d_in;
-    }
-    cf32* dst = (cf32*)out;
-    const size_t out_bytes = (size_t)n_out * nant * sizeof(cf32);
-    if (!out_on_device) {
-      HIP_CHECK(hipMalloc(&d_out, out_bytes));
-      dst = (cf32*)d_out;
-    }
-    lsn_launch_resample({raw, fmt, scale, need_lo, len, nant, 0}, plan.cell(cfg->out_first, (uint32_t)n_out, tb, dst, n_out), st);
-    if (!out_on_device) HIP_CHECK(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-  } catch (const std::exception& ex) {
-    fprintf(stderr, "ltesniffer_amd: resample: %s\n", ex.what());
-    rc = LSN_ERROR;
-  }
-  if (st) (void)hipStreamDestroy(st);
-  if (d_in) (void)hipFree(d_in);
-  if (d_out) (void)hipFree(d_out);
-  return rc;
-}
-
-// several resamplings of one input: one upload of the union of what the cells read, one launch of k_resample_cells.  ring_samples != 0 (host input): the whole
-// window goes to its slots in a device ring of that many samples instead, and k_resample_ring reads it there
-static int resample_cells(int device, const void* in, int in_on_device, uint64_t n_in, uint64_t ring_samples, const lsn_resample_cfg_t* cfgs, uint32_t n_cells, float* const* outs,
-                          int out_on_device, const uint64_t* n_out)
-{
-  if (!cfgs || !outs || !n_out || n_cells < 1 || n_cells > LSN_FILE_MAX_CELLS) return LSN_ERROR_INVALID_INPUTS;
-  std::vector<lsn::ResamplePlan> plans(n_cells);
-  const lsn_resample_cfg_t& c0 = cfgs[0];
-  int64_t need_lo = 0, need_hi = 0;
-  bool any = false;
-  for (uint32_t c = 0; c < n_cells; c++) {
-    const lsn_resample_cfg_t& k = cfgs[c];
-    const int r = resample_plan(&k, plans[c]);
-    if (r != LSN_SUCCESS) return r;
-    if (k.struct_size != sizeof(lsn_resample_cfg_t) || k.nof_antennas != c0.nof_antennas || k.sample_format != c0.sample_format || !(k.sample_scale == c0.sample_scale) ||
-        k.rate_in_hz != c0.rate_in_hz || k.in_base != c0.in_base)
-      return LSN_ERROR_INVALID_INPUTS;
-    if (!n_out[c]) continue;
-    if (!in || !outs[c] || n_out[c] >= (1ull << 32) || k.out_first >= (1ull << 40) || k.in_base >= (1ull << 62) || n_in >= (1ull << 62)) return LSN_ERROR_INVALID_INPUTS;
-    int64_t lo, hi;
-    plans[c].inputSpan(k.out_first, n_out[c], lo, hi);
-    if (hi >= (int64_t)1 << 62) return LSN_ERROR_INVALID_INPUTS;
-    lo = std::max<int64_t>(lo, 0);   // in front of the recording: zeros
-    if (lo < (int64_t)k.in_base || hi > (int64_t)(k.in_base + n_in)) return LSN_ERROR_INVALID_INPUTS;   // the input does not hold what these outputs read
-    need_lo = any ? std::min(need_lo, lo) : lo;
-    need_hi = any ? std::max(need_hi, hi) : hi;
-    any = true;
-  }
-  if (!any) return LSN_SUCCESS;
-  const uint32_t nant = c0.nof_antennas, fmt = c0.sample_format;
-  const LsnSampleFormat sfm = lsn_sample_format(fmt, c0.sample_scale);
-  const size_t smp = (size_t)sfm.bytes * nant;
-  const uint64_t len = need_hi > need_lo ? (uint64_t)(need_hi - need_lo) : 0;
-  const uint8_t* src = (const uint8_t*)in + ((uint64_t)need_lo - c0.in_base) * smp;
-  void* d_in = nullptr;
-  std::vector<lsn::ResampleTables> tb(n_cells);
-  std::vector<void*> d_out(n_cells, nullptr);
-  hipStream_t st = nullptr;
-  int rc = LSN_SUCCESS;
-  try {
-    HIP_CHECK(hipSetDevice(device));
-    HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    const void* raw = src;
-    if (ring_samples) {
-      // slots no sample of the window goes to keep a pattern (NaN as cf32) that a read outside the window would carry into the outputs
-      HIP_CHECK(hipMalloc(&d_in, ring_samples * smp));
-      HIP_CHECK(hipMemsetAsync(d_in, 0xFF, ring_samples * smp, st));
-      const uint64_t slot = c0.in_base & (ring_samples - 1), head = std::min(n_in, ring_samples - slot);
-      if (head) HIP_CHECK(hipMemcpyAsync((uint8_t*)d_in + slot * smp, in, head * smp, hipMemcpyHostToDevice, st));
-      if (n_in > head) HIP_CHECK(hipMemcpyAsync(d_in, (const uint8_t*)in + head * smp, (n_in - head) * smp, hipMemcpyHostToDevice, st));   // behind the end of the ring
-    } else if (!in_on_device && len) {
-      HIP_CHECK(hipMalloc(&d_in, len * smp));
-      HIP_CHECK(hipMemcpyAsync(d_in, src, len * smp, hipMemcpyHostToDevice, st));
-      raw = d_in;
-    }
-    LsnResampleCell k[LSN_FILE_MAX_CELLS];
-    for (uint32_t c = 0; c < n_cells; c++) {
-      tb[c].upload(plans[c], st);
-      cf32* dst = (cf32*)outs[c];
-      if (!out_on_device && n_out[c]) {
-        HIP_CHECK(hipMalloc(&d_out[c], (size_t)n_out[c] * nant * sizeof(cf32)));
-        dst = (cf32*)d_out[c];
-      }
-      k[c] = plans[c].cell(cfgs[c].out_first, (uint32_t)std::max<uint64_t>(n_out[c], 1), tb[c], dst, n_out[c]);
-    }
-    if (ring_samples) lsn_launch_resample_cells({d_in, fmt, sfm.scale, (int64_t)c0.in_base, n_in, nant, ring_samples}, k, n_cells, st);
-    else lsn_launch_resample_cells({raw, fmt, sfm.scale, need_lo, len, nant, 0}, k, n_cells, st);
-    if (!out_on_device)
-      for (uint32_t c = 0; c < n_cells; c++)
-        if (n_out[c]) HIP_CHECK(hipMemcpyAsync(outs[c], d_out[c], (size_t)n_out[c] * nant * sizeof(cf32), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-  } catch (const std::exception& ex) {
-    fprintf(stderr, "ltesniffer_amd: resample_cells: %s\n", ex.what());
-    rc = LSN_ERROR;
-  }
-  if (st) (void)hipStreamDestroy(st);
-  if (d_in) (void)hipFree(d_in);
-  for (void* o : d_out) if (o) (void)hipFree(o);
-  return rc;
-}
-
-int lsn_resample_cells(int device, const void* in, int in_on_device, uint64_t n_in, const lsn_resample_cfg_t* cfgs, uint32_t n_cells, float* const* outs, int out_on_device,
-                       const uint64_t* n_out)
-{
-  return resample_cells(device, in, in_on_device, n_in, 0, cfgs, n_cells, outs, out_on_device, n_out);
-}
-
-int lsn_resample_cells_ring(int device, const void* in, uint64_t n_in, uint64_t ring_samples, const lsn_resample_cfg_t* cfgs, uint32_t n_cells, float* const* outs,
-                            const uint64_t* n_out)
-{
-  if (!in || !ring_samples || (ring_samples & (ring_samples - 1)) || ring_samples > (1ull << 32) || n_in > ring_samples) return LSN_ERROR_INVALID_INPUTS;
-  return resample_cells(device, in, 0, n_in, ring_samples, cfgs, n_cells, outs, 0, n_out);
 }
 
 }  // extern "C"

@@ -2,6 +2,7 @@
 // owner of a cell's device tables, the description of the buffer a launch reads, and the two launchers of kernels/resample.hip.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "../../../include/ltesniffer_amd.h"
 #include "lsn_resample.h"
 
 namespace lsn {
@@ -28,3 +29,6 @@ struct LsnResampleSource {
 };
 void lsn_launch_resample(const LsnResampleSource& src, const LsnResampleCell& cell, hipStream_t s);                            // k_resample (a linear buffer)
 void lsn_launch_resample_cells(const LsnResampleSource& src, const LsnResampleCell* cells, uint32_t n_cells, hipStream_t s);   // k_resample_cells, or k_resample_ring out of a ring
+
+// the plan of a lsn_resample_cfg_t, validated: what lsn_resample_span and the stand-alone calls (lsn_front_launch.cc) share
+int lsn_resample_plan(const lsn_resample_cfg_t* cfg, lsn::ResamplePlan& plan);

@@ -12,8 +12,9 @@
 // A tracked stream that asked for it too (reacquire()) searches a cell whose loop has lost the PSS over a whole half frame: launchSearches
 // resamples the span into a scratch of the cell's and runs k_pss_acquire on it - launches of their own, which a stream that loses nothing never issues -, and the
 // enter() of three segments later moves the position once.
-// Cells with a channel filter: launchRing runs the file source's two stages instead - one k_chan_fir_ring launch out of the ring into the
-// cells' intermediates, one k_resample per cell out of those - and every span that guards the ring is L samples wider on both sides.  Without one, nothing differs.
+// Cells with a channel filter: the chain launchRing queues (lsn_launch_front, the one the file source queues: section 3.1l) runs both stages -
+// one k_chan_fir_ring launch out of the ring into the cells' intermediates, one k_resample per cell out of those - and every span that guards the ring is L samples
+// wider on both sides.  Without one, nothing differs.
 #include "lsn_stream_ring.h"
 #include "lsn_track_launch.h"
 #include "lsn_clock.h"
@@ -37,6 +38,7 @@ StreamRing::StreamRing(int device_, uint32_t nant_, uint32_t fmt_, float sample_
     StreamCellPlan p;
     p.rs = &c.s.plan; p.sflen = c.sflen; p.max_subframes = c.s.max_subframes; p.pre = c.s.filt.L;
     plans.push_back(p);
+    c.front.cf = &c.s.filt;
   }
 }
 
@@ -51,8 +53,7 @@ StreamRing::~StreamRing()
   if (ev_copy) (void)hipEventDestroy(ev_copy);
   for (auto& c : cells) {
     if (c.d_rep) (void)hipFree(c.d_rep);
-    if (c.d_taps) (void)hipFree(c.d_taps);
-    if (c.mid) c.s.e->holdChanBuffer(false);   // (mid is the Phy's: given back, not freed)
+    if (c.front.mid) c.s.e->holdChanBuffer(false);   // (mid is the Phy's: given back, not freed)
     if (c.h_C) (void)hipHostFree(c.h_C);
     if (c.acq_x) (void)hipFree(c.acq_x);
     if (c.acq_C) (void)hipHostFree(c.acq_C);
@@ -81,10 +82,10 @@ int StreamRing::setup()
       if (r != LSN_SUCCESS) return r;
       for (int si = 0; si < nslot; si++)
         if (c.s.e->fileIqBlockBytes(si) < (size_t)blk * c.sflen * nant * sizeof(cf32)) throw std::runtime_error("stream: block buffer");
-      c.tb.rotation(c.s.offset_freq_hz, c.sflen, 15000.0 * (double)c.s.e->symbolSz());   // the -o rotation of the cell's output samples, the file source's
-      c.tb.upload(c.s.plan, st_run);
+      c.front.tb.rotation(c.s.offset_freq_hz, c.sflen, 15000.0 * (double)c.s.e->symbolSz());   // the -o rotation of the cell's output samples, the file source's
+      c.front.tb.upload(c.s.plan, st_run);
       if (c.s.filt.L) {
-        lsn_chan_fir_upload(c.s.filt, c.d_taps, c.d_mix, st_run);
+        c.front.ft.upload(c.s.filt, st_run);
         const int rm = reserveMid(c, midSamples(c, c.s.plan.step));
         if (rm != LSN_SUCCESS) return rm;
       }
@@ -106,10 +107,9 @@ int StreamRing::reserveMid(Cell& c, uint64_t samples)
   // called from setup() and, in front of the first push, from track(): nothing of this stream's has been launched on the buffer yet, so it may still move
   c.s.e->holdChanBuffer(false);
   const int r = c.s.e->reserveChanBuffer((size_t)samples * nant * sizeof(cf32));
-  c.mid = c.s.e->chanBuffer();
-  if (r == LSN_SUCCESS) c.mid_samples = samples;
-  else if (!c.mid) c.mid_samples = 0;       // the old buffer went and no new one came: every later launch of this cell throws in front of stage 1
-  if (c.mid) c.s.e->holdChanBuffer(true);   // from here on nobody grows - frees - it under this stream
+  c.front.mid = c.s.e->chanBuffer();
+  c.front.mid_cap = c.s.e->chanBufferSamples(nant);   // what the Phy holds now.  0: the old buffer went and no new one came - every later launch of this cell throws in front of stage 1
+  if (c.front.mid) c.s.e->holdChanBuffer(true);       // from here on nobody grows - frees - it under this stream
   return r;
 }
 
@@ -182,9 +182,9 @@ int StreamRing::runReady(bool flush_all)
     for (size_t c = 0; c < cells.size(); c++) {
       Cell& q = cells[c];
       k[c] = LsnResampleCell();
-      if (nsf[c]) k[c] = q.s.plan.cell(q.done * q.sflen, q.sflen, q.tb, bufferFor(q), (uint64_t)nsf[c] * q.sflen);
+      if (nsf[c]) k[c] = q.s.plan.cell(q.done * q.sflen, q.sflen, q.front.tb, bufferFor(q), (uint64_t)nsf[c] * q.sflen);
     }
-    launchRing(k, lo, hi, "block");
+    launchRing(k, lo, hi, "stream: a block");
     for (size_t c = 0; c < cells.size() && failed == LSN_SUCCESS; c++)
       if (nsf[c]) submitBlock(cells[c], nsf[c]);
   }
@@ -204,29 +204,12 @@ void StreamRing::launchRing(const LsnResampleCell* k, const int64_t* lo, const i
   }
   in_lo = std::max<int64_t>(in_lo, 0);   // zeros in front of the stream are the kernel's
   if (in_hi > (int64_t)pushed || (uint64_t)(in_hi - in_lo) > ring_samples || (int64_t)pushed - in_lo > (int64_t)ring_samples)
-    throw std::runtime_error(std::string("stream: a ") + what + "'s input is not in the ring");
+    throw std::runtime_error(std::string(what) + "'s input is not in the ring");
   HIP_CHECK(hipEventRecord(ev_copy, st_copy));
   HIP_CHECK(hipStreamWaitEvent(st_run, ev_copy, 0));   // the samples pushed so far are in their slots
-  if (filtered()) {
-    // stage 1, one launch for all cells: y1 over exactly the span each cell's resampler piece reads (in front of sample 0: zeros, the resampler's own - the file
-    // pass's midSpan); stage 2, per cell: the plain cf32 k_resample out of the cell's intermediate (k_resample_cells takes one source per launch)
-    LsnChanFirCell f[kFileMaxCells];
-    int64_t lo2[kFileMaxCells] = {}, hi2[kFileMaxCells] = {};
-    for (size_t c = 0; c < cells.size(); c++) {
-      const Cell& q = cells[c];
-      f[c] = LsnChanFirCell();
-      if (!k[c].n_out) continue;
-      lo2[c] = std::max<int64_t>(lo[c], 0);
-      hi2[c] = std::max(hi[c], lo2[c]);
-      if ((uint64_t)(hi2[c] - lo2[c]) > q.mid_samples) throw std::runtime_error(std::string("stream: a ") + what + "'s filtered samples do not fit the intermediate buffer");
-      f[c].taps = q.d_taps; f[c].L = q.s.filt.L; f[c].w = q.s.filt.tune; f[c].nco = q.d_mix; f[c].out = q.mid; f[c].out_first = lo2[c]; f[c].n_out = (uint64_t)(hi2[c] - lo2[c]);
-    }
-    lsn_launch_chan_fir(d_ring, fmt, sfm.scale, in_lo, (uint64_t)(in_hi - in_lo), nant, ring_samples, f, (uint32_t)cells.size(), st_run);
-    for (size_t c = 0; c < cells.size(); c++)
-      if (k[c].n_out) lsn_launch_resample({cells[c].mid, 0, 1.0f, lo2[c], (uint64_t)(hi2[c] - lo2[c]), nant, 0}, k[c], st_run);
-  } else {
-    lsn_launch_resample_cells({d_ring, fmt, sfm.scale, in_lo, (uint64_t)(in_hi - in_lo), nant, ring_samples}, k, (uint32_t)cells.size(), st_run);
-  }
+  const FrontCell* fc[kFileMaxCells];
+  for (size_t c = 0; c < cells.size(); c++) fc[c] = &cells[c].front;
+  lsn_launch_front({d_ring, fmt, sfm.scale, in_lo, (uint64_t)(in_hi - in_lo), nant, ring_samples}, fc, k, lo, hi, (uint32_t)cells.size(), st_run, what);
   Launch l;
   l.ev = takeEvent(); l.lo = in_lo;
   HIP_CHECK(hipEventRecord(l.ev, st_run));
@@ -316,7 +299,7 @@ int StreamRing::track(const lsn_stream_track_cfg_t& tc, double rate_in)
   for (auto& q : cells) {
     if (!q.s.filt.L) continue;
     const uint64_t need = midSamples(q, track_widened_step(q.s.plan.step, cfg.max_ppm));
-    if (need <= q.mid_samples) continue;
+    if (need <= q.front.mid_cap) continue;
     const int rm = reserveMid(q, need);
     if (rm != LSN_SUCCESS) return rm;
   }
@@ -408,13 +391,13 @@ void StreamRing::launchSearches()
     if (hi[c] > (int64_t)pushed) continue;   // the span is not complete yet
     t.search.launched = true;
     if (inGap(lo[c], hi[c])) continue;       // not launched: it comes back rejected (acq_ev stays null)
-    k[c] = q.s.plan.cell(t.search.base, t.search.step, t.search.span, q.sflen, 0, q.tb, q.acq_x, (uint64_t)kAcqSpanSubframes * q.sflen);
+    k[c] = q.s.plan.cell(t.search.base, t.search.step, t.search.span, q.sflen, 0, q.front.tb, q.acq_x, (uint64_t)kAcqSpanSubframes * q.sflen);
     a[c].x = q.acq_x; a[c].rep = q.d_rep; a[c].C = q.acq_C; a[c].N = t.N; a[c].d = track_lag_spacing(t.N); a[c].sflen = q.sflen; a[c].nant = nant;
     a[c].n_lags = kTrackSegSubframes * q.sflen / a[c].d;
     any = true;
   }
   if (!any) return;
-  launchRing(k, lo, hi, "search");   // a launch of its own: the scratches are no block buffers, and the decode path's launches stay what they are
+  launchRing(k, lo, hi, "stream: a search");   // a launch of its own: the scratches are no block buffers, and the decode path's launches stay what they are
   lsn_launch_pss_acquire(a, (uint32_t)cells.size(), st_run);
   for (size_t c = 0; c < cells.size(); c++) {
     if (!a[c].n_lags) continue;
@@ -505,13 +488,13 @@ int StreamRing::runReadyTracked(bool flush_all)
       const uint64_t upto = std::min<uint64_t>(t.completeInSegment(insideEnd(q)), end);
       if (upto <= q.filled || (upto < end && !flush_all)) continue;
       piece[c] = (uint32_t)(upto - q.filled);
-      k[c] = q.s.plan.cell(t.position(q.filled), t.step, t.span, q.sflen, (uint32_t)(q.filled - q.done) * q.sflen, q.tb, bufferFor(q, q.filled == q.done),
+      k[c] = q.s.plan.cell(t.position(q.filled), t.step, t.span, q.sflen, (uint32_t)(q.filled - q.done) * q.sflen, q.front.tb, bufferFor(q, q.filled == q.done),
                            (uint64_t)piece[c] * q.sflen);
       t.inputSpan(q.filled, upto, lo[c], hi[c]);
       any = true;
     }
     if (any) {
-      launchRing(k, lo, hi, "segment");
+      launchRing(k, lo, hi, "stream: a segment");
       // the windows of the segments that began in this launch
       LsnTimingCell tm[kFileMaxCells];
       bool timing = false;

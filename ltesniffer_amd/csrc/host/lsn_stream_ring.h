@@ -4,8 +4,7 @@
 // (section 3.1k) it searches a cell that has lost its PSS with k_pss_acquire and keeps 8 subframes of input more per such cell.
 #pragma once
 #include "lsn_engine.h"
-#include "lsn_resample_launch.h"
-#include "lsn_chanfilt_launch.h"
+#include "lsn_front_launch.h"
 #include "lsn_stream.h"
 #include "lsn_track.h"
 #include <deque>
@@ -54,13 +53,10 @@ private:
     uint32_t sflen = 0;
     uint64_t done = 0;
     int rc = LSN_SUCCESS;
-    ResampleTables tb;                   // the plan's bank and NCO tables, the -o rotation
-    // a filtered cell: stage 1 writes y1 over the span one launch's resampler piece reads into mid, element 0 = y1[lo]; one mid serves every block-buffer slot,
-    // the launches being ordered on st_run
-    float* d_taps = nullptr;             // the filter's taps ...
-    const cf32* d_mix = nullptr;         // ... and, behind them, its mixer's tables when it has a tuning word
-    cf32* mid = nullptr;                 // the Phy's intermediate (Engine::reserveChanBuffer), at least mid_samples samples of all antennas
-    uint64_t mid_samples = 0;
+    // what the cell brings to every launch (lsn_front_launch.h): the plan's tables and the -o rotation and, of a filtered cell (front.cf = &s.filt), the filter's
+    // tables and the Phy's intermediate - one serves every block-buffer slot, the launches being ordered on st_run.  The tables go with the cell, behind
+    // ~StreamRing's body, which has waited for every engine and synchronised both streams
+    FrontCell front;
     uint64_t launches = 0;              // block buffer of launch k: slot k mod nslot ...
     uint64_t mark[NSLOT_MAX] = {};       // ... free again when the engine has consumed the chunks up to this mark (0: never used)
     // a tracked stream (runReadyTracked): the block buffer fills segment by segment
@@ -82,9 +78,9 @@ private:
   int runReady(bool flush_all);
   int runReadyTracked(bool flush_all);
   // the steps the two loops share.  launchRing: the cells in k (n_out != 0) resampled out of the ring, cell c reading the recording samples [lo[c], hi[c]), behind
-  // the copies queued so far, and the event behind it into `inflight`; `what` names the input in the refusal.  Unfiltered: ONE k_resample_ring launch over the
-  // union of the spans.  Filtered: ONE k_chan_fir_ring launch over the union of the spans widened by every cell's L writes each cell's y1[lo, hi) into its
-  // intermediate, then one k_resample per cell reads that (the file source's two stages, lsn_file.cc).  bufferFor: the block buffer the cell fills next; empty (nothing of the next
+  // the copies queued so far, and the event behind it into `inflight`; `what` names the input in the refusals ("stream: a block").  The launches are
+  // lsn_launch_front's over the union of the spans, each widened by its cell's L: unfiltered ONE k_resample_ring, filtered ONE k_chan_fir_ring and one k_resample per
+  // cell.  bufferFor: the block buffer the cell fills next; empty (nothing of the next
   // block is in it yet): waits until the block it carried last has been through stage A.  submitBlock: the first nsf subframes of that buffer go to the cell's Phy
   void launchRing(const LsnResampleCell* k, const int64_t* lo, const int64_t* hi, const char* what);
   bool filtered() const { return cells[0].s.filt.L != 0; }

@@ -159,7 +159,7 @@ __global__ __launch_bounds__(256) void k_chan_fir_ring(const LsnChanFirCellsArgs
   chan_fir_tile<FMT, true>(A, A.nco != nullptr, cf_lo, cf_hi);
 }
 
-void lsn_chan_fir_upload(const lsn::ChanFilter& f, float*& d_taps, const cf32*& d_nco, hipStream_t s)
+void lsn::ChanFirTables::upload(const lsn::ChanFilter& f, hipStream_t s)
 {
   const size_t nt = ((f.taps.size() + 7 + 3) / 4) * 4;   // the last quad's scalar load ends at h[4 ((2L + 3) / 4) + 3] <= h[2L + 6]
   std::vector<float> h(nt + (f.tune ? (4096 + 1024) * 2 : 0), 0.0f);
