@@ -610,7 +610,8 @@ int lsn_pss_timing(int device, int blocks_on_device, const lsn_pss_timing_cell_t
  *   ring      a cell with re-acquisition keeps 8 output subframes of input more (at the step widened by 1 + max_ppm 1e-6), behind what it keeps anyway: 6 for the
  *             span of the segment behind, 2.5 for a backward jump, rounded up.  oldest_needed and the ring guards count with it; lsn_stream_span keeps describing
  *             the nominal plan.
- * Limits: a slip beyond +- 2.5 ms is repaired to the nearest PSS and leaves the TTI off by a multiple of 5 subframes (that needs the SSS and the MIB: not built);
+ * Limits: a slip beyond +- 2.5 ms is repaired to the nearest PSS and leaves the TTI off by a multiple of 5 subframes (lsn_stream_frame_sync,
+ * below and DESIGN section 3.1m, sets it right from one PBCH decode; no SSS is needed);
  * one search per cell in flight; streams only - file replays do not track -, and not on a stream with the channel filter.
  * lsn_stream_reacquire refuses with LSN_ERROR_INVALID_INPUTS, the stream unchanged and usable: a struct_size it does not know, an untracked stream, a second call,
  * after a push, min_ratio not finite or below 1 (0 = the default), a stream with the channel filter, a ring shorter than lsn_stream_track's bound plus the 8
@@ -647,6 +648,60 @@ typedef struct {
   float* C;                  /* out */
 } lsn_pss_acquire_cell_t;
 int lsn_pss_acquire(int device, int blocks_on_device, const lsn_pss_acquire_cell_t* cells, uint32_t n_cells);
+
+/* ---- a re-acquiring stream that sets the TTI right again after a slip of any length ----
+ * lsn_stream_reacquire moves the position to the NEAREST PSS: a slip beyond +- 2.5 ms leaves the TTI off by a multiple of 5 subframes, and a slip by whole radio
+ * frames even decodes perfectly - every record then carries the wrong frame number.  The PBCH exists only in subframe 0 and is scrambled with the cell id, so ONE
+ * PBCH decode of a segment's first subframe settles the half frame, the frame number and the cell; no SSS is needed.  Opt-in per stream, accepted only after
+ * lsn_stream_reacquire and before the first push; a stream that does not ask runs exactly the launches it ran before, and one that asks and loses nothing runs no
+ * PBCH launch at all.  Notation of the section above: the search of segment h was accepted and its jump is in force at segment g = h + 3.
+ *   check     a jump of an enabled cell starts a check at segment g.  Attempts run on the segments a = g, g + 1, ..., at most `tries` of them.  A new accepted jump
+ *             restarts the check at its own g; attempts on segments in front of that g are ignored when they come back.
+ *   attempt   the PBCH decode (lsn_phy_mib_decode_side's: the Phy's side scratch) of the first subframe of segment a, read from the block buffer, queued directly
+ *             behind that piece's k_pss_timing window.  Not launched - and counted as "not found" - when that subframe's input span reads a declared gap: the test
+ *             that decides whether the window is launched.  Its result rides with the measurement of segment a and is taken in on entering segment a + 2, behind
+ *             that measurement; status calls and flushes may fetch it early and change nothing, the rule looks at it on entering segment a + 2 only.
+ *   decision  lsn_frame_sync_decide: accepted when the MIB is found and its nof_prb and nof_ports equal the Phy's.  T = 10 sfn; C = the TTI the segment's first
+ *             subframe was counted as; delta = (T - C) mod 10240, reported signed in (-5120, 5120].  C mod 5 != 0 (and with it delta mod 5 != 0) is an internal
+ *             error, not a case.  Chance of accepting garbage: 3 CRC masks x 4 phases / 2^16, times 1/3 for the port mask, times 1/8 for the bandwidth field
+ *             (6 of its 8 values are bandwidths, one of them the Phy's): about 8e-6 per attempt.
+ *   relabel   from the first subframe of segment a + 2 on the cell's TTI is start_tti + sf + shift, shift += delta mod 10240.  delta = 0 counts as confirmed,
+ *             anything else as relabelled.  A partly filled block buffer is submitted, as a flush would submit it, before the first relabelled subframe goes in: no
+ *             block spans two countings, and the records do not depend on block_subframes.  Segment boundaries stay on TTI multiples of 5.  After `tries` attempts
+ *             without an accept given_up is incremented when the last of them is taken in, and nothing else changes.  The attempt of segment a + 1 is always in
+ *             flight when the one of segment a decides; it is launched, counted and ignored.
+ *   hold      (the default) the subframes from segment g up to the relabel (or the giving up) are resampled and measured but NOT submitted to the Phy: a slip by
+ *             whole frames would otherwise be written out with the wrong frame number.  hold = LSN_FRAME_SYNC_NO_HOLD submits them as counted.
+ * Everything is a function of (input samples, configuration): records and statuses do not depend on how the stream was pushed, on the ring or on block_subframes.
+ * Limits: a slip by an exact multiple of 5 ms moves no PSS - nothing is searched and nothing is checked, the TTI stays off silently; LSN_TTI_FROM_MIB at open stays
+ * refused; no channel filter (lsn_stream_reacquire's limit); file replays are not covered.
+ * lsn_stream_frame_sync refuses with LSN_ERROR_INVALID_INPUTS, the stream unchanged and usable: a struct_size it does not know, a stream without
+ * lsn_stream_reacquire, a second call, after a push, tries above 64, a hold it does not know. */
+#define LSN_FRAME_SYNC_NO_HOLD 2u
+typedef struct {
+  uint32_t struct_size;      /* sizeof(lsn_stream_frame_sync_cfg_t); every other size is refused */
+  uint32_t tries;            /* attempts per check; 0 = 8: four radio frames, one PBCH period.  At most 64 */
+  uint32_t hold;             /* 0 = the default = 1: hold; LSN_FRAME_SYNC_NO_HOLD: submit the subframes of a running check as counted */
+  uint32_t enable[LSN_FILE_MAX_CELLS];        /* per cell: 0 = never checked (a cell that is not searched is never checked either) */
+} lsn_stream_frame_sync_cfg_t;
+typedef struct {
+  uint32_t struct_size;      /* in: sizeof(lsn_stream_frame_sync_status_t); every other size is refused */
+  uint32_t nof_cells;
+  uint64_t checks[LSN_FILE_MAX_CELLS], attempts[LSN_FILE_MAX_CELLS];   /* checks started; attempts launched (one a gap kept from being launched is not counted) */
+  uint64_t confirmed[LSN_FILE_MAX_CELLS], relabelled[LSN_FILE_MAX_CELLS], given_up[LSN_FILE_MAX_CELLS];
+  uint64_t accept_segment[LSN_FILE_MAX_CELLS];  /* the segment a of the last accepted attempt (0: none yet) */
+  uint64_t relabel_segment[LSN_FILE_MAX_CELLS]; /* the segment from whose first subframe on the last relabel (delta != 0) is in force (0: none yet) */
+  uint64_t held[LSN_FILE_MAX_CELLS];            /* subframes resampled and not submitted */
+  uint32_t last_sfn[LSN_FILE_MAX_CELLS];        /* of the last accepted attempt */
+  int32_t  last_delta[LSN_FILE_MAX_CELLS];      /* of the last accepted attempt, subframes, signed */
+  uint32_t shift[LSN_FILE_MAX_CELLS];           /* the sum of all deltas mod 10240 */
+} lsn_stream_frame_sync_status_t;
+int lsn_stream_frame_sync(lsn_stream_t* s, const lsn_stream_frame_sync_cfg_t* cfg);
+/* the measurements, searches and attempts in flight are waited for first, so after a flush the answer is a function of the samples pushed */
+int lsn_stream_frame_sync_status(lsn_stream_t* s, lsn_stream_frame_sync_status_t* out);
+/* the decision without a GPU: -> 1 accepted (*delta filled, signed, a multiple of 5), 0 not accepted (*delta = 0), LSN_ERROR_INVALID_INPUTS (a null pointer,
+ * counted_tti >= 10240, a found MIB with sfn >= 1024), LSN_ERROR when the MIB is accepted and counted_tti is no multiple of 5 */
+int lsn_frame_sync_decide(const lsn_mib_t* mib, uint32_t nof_prb, uint32_t nof_ports, uint32_t counted_tti, int32_t* delta);
 
 /* ---- sharp channel filter in front of the resampler: a cell next to a much stronger carrier ----
  * The resampler's filter has the transition band [B, min(rate) - B]: a neighbour carrier inside it reaches the FFT's guard bins undamped and leaks into the
@@ -998,6 +1053,9 @@ long lsn_phy_tap(lsn_phy_t* phy, int what, uint32_t sf_in_batch, void* out, size
 int lsn_phy_set_stage_c_taps(lsn_phy_t* phy, int enable);
 /* lsn_phy_mib_decode + the 480 raw (not descrambled) PBCH soft bits of the subframe */
 int lsn_phy_mib_decode_llr(lsn_phy_t* phy, const void* iq, int iq_on_device, lsn_mib_t* out, float* llr_raw480);
+/* the same decode - the same launches, the same result and soft bits (llr_raw480 may be null) - on a one-subframe scratch of its own (allocated on first use) and
+ * a stream of its own: allowed while submitted blocks are in flight, where lsn_phy_mib_decode, which borrows a slot of the pipeline, refuses */
+int lsn_phy_mib_decode_side(lsn_phy_t* phy, const void* iq, int iq_on_device, lsn_mib_t* out, float* llr_raw480);
 typedef struct {
   double ms_stage_a, ms_search, ms_stage_c, ms_commit, ms_total; /* wall clock of the last process call */
   double kernel_ms[16];                                          /* HIP-event time per kernel class, last call */

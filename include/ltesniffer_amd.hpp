@@ -226,6 +226,8 @@ public:
   void setPrachSink(lsn_prach_sink_t cb, void* user) { lsn_phy_set_prach_sink(h, cb, user); }               // work_prach's report
   // srsran_ue_mib_decode + srsran_pbch_mib_unpack on one subframe 0 (LTESniffer_Core.cc:386-391); true when a MIB was found
   bool mibDecode(const cf_t* subframe_iq /* [nof_rx_antennas][SF_LEN] */, lsn_mib_t& mib) { return lsn_phy_mib_decode(h, subframe_iq, 0, &mib) == 1; }
+  // the same beside the pipeline: allowed while submitted blocks are in flight (lsn_phy_mib_decode_side)
+  bool mibDecodeSide(const cf_t* subframe_iq, lsn_mib_t& mib) { return lsn_phy_mib_decode_side(h, subframe_iq, 0, &mib, nullptr) == 1; }
   lsn_ue_config_t getUeConfig(uint16_t rnti) { lsn_ue_config_t c{}; lsn_phy_get_ue_config(h, rnti, &c); return c; }  // MCSTracking::get_ue_config_rnti
   lsn_phy_t* handle() { return h; }
 private:
@@ -292,6 +294,9 @@ public:
   // re-acquisition after a loss of samples (after track(), before the first push): LSN_ERROR_INVALID_INPUTS when refused, the stream unchanged and usable
   int reacquire(lsn_stream_reacquire_cfg_t cfg) { cfg.struct_size = sizeof(cfg); return lsn_stream_reacquire(h, &cfg); }
   lsn_stream_reacquire_status_t reacquire_status() { lsn_stream_reacquire_status_t s{}; s.struct_size = sizeof(s); lsn_stream_reacquire_status(h, &s); return s; }
+  // lsn_stream_frame_sync: after reacquire(), before the first push
+  int frame_sync(lsn_stream_frame_sync_cfg_t cfg) { cfg.struct_size = sizeof(cfg); return lsn_stream_frame_sync(h, &cfg); }
+  lsn_stream_frame_sync_status_t frame_sync_status() { lsn_stream_frame_sync_status_t s{}; s.struct_size = sizeof(s); lsn_stream_frame_sync_status(h, &s); return s; }
   int close() { const int r = h ? lsn_stream_close(h) : LSN_SUCCESS; h = nullptr; return r; }
   // the plan without a device or a Phy; stopband_hz: empty, or one entry per cell (lsn_stream_span_filtered)
   static int span(lsn_stream_cfg_t cfg, std::vector<lsn_file_cell_t> cells, const std::vector<double>& stopband_hz, uint64_t pushed_samples, lsn_stream_span_t& out)

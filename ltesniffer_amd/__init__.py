@@ -47,7 +47,8 @@ EXPORTS = ["lsn_phy_create", "lsn_phy_destroy", "lsn_phy_set_cell", "lsn_phy_get
            "lsn_resample_cells_ring", "lsn_stream_open", "lsn_stream_push", "lsn_stream_flush", "lsn_stream_status", "lsn_stream_close", "lsn_stream_span",
            "lsn_stream_track", "lsn_stream_track_status", "lsn_stream_track_step", "lsn_pss_timing", "lsn_pss_timing_error",
            "lsn_channel_filter_ring", "lsn_stream_span_filtered",
-           "lsn_stream_reacquire", "lsn_stream_reacquire_status", "lsn_pss_acquire", "lsn_pss_acquire_decide"]
+           "lsn_stream_reacquire", "lsn_stream_reacquire_status", "lsn_pss_acquire", "lsn_pss_acquire_decide",
+           "lsn_phy_mib_decode_side", "lsn_stream_frame_sync", "lsn_stream_frame_sync_status", "lsn_frame_sync_decide"]
 
 RATES_3GPP, RATES_SRSRAN = 0, 1   # LSN_RATES_*: sampling mode of a Phy / of a cell search
 
@@ -182,6 +183,20 @@ class StreamReacquireStatus(C.Structure):   # lsn_stream_reacquire_status_t
     _fields_ = [("struct_size", C.c_uint32), ("nof_cells", C.c_uint32), ("launched", C.c_uint64 * FILE_MAX_CELLS), ("accepted", C.c_uint64 * FILE_MAX_CELLS),
                 ("rejected", C.c_uint64 * FILE_MAX_CELLS), ("last_peak", C.c_double * FILE_MAX_CELLS), ("last_ratio", C.c_double * FILE_MAX_CELLS),
                 ("last_offset", C.c_int64 * FILE_MAX_CELLS), ("jump_segment", C.c_uint64 * FILE_MAX_CELLS), ("jumps_total", C.c_double * FILE_MAX_CELLS)]
+
+
+FRAME_SYNC_NO_HOLD = 2   # LSN_FRAME_SYNC_NO_HOLD
+
+
+class StreamFrameSyncCfg(C.Structure):   # lsn_stream_frame_sync_cfg_t
+    _fields_ = [("struct_size", C.c_uint32), ("tries", C.c_uint32), ("hold", C.c_uint32), ("enable", C.c_uint32 * FILE_MAX_CELLS)]
+
+
+class StreamFrameSyncStatus(C.Structure):   # lsn_stream_frame_sync_status_t
+    _fields_ = [("struct_size", C.c_uint32), ("nof_cells", C.c_uint32), ("checks", C.c_uint64 * FILE_MAX_CELLS), ("attempts", C.c_uint64 * FILE_MAX_CELLS),
+                ("confirmed", C.c_uint64 * FILE_MAX_CELLS), ("relabelled", C.c_uint64 * FILE_MAX_CELLS), ("given_up", C.c_uint64 * FILE_MAX_CELLS),
+                ("accept_segment", C.c_uint64 * FILE_MAX_CELLS), ("relabel_segment", C.c_uint64 * FILE_MAX_CELLS), ("held", C.c_uint64 * FILE_MAX_CELLS),
+                ("last_sfn", C.c_uint32 * FILE_MAX_CELLS), ("last_delta", C.c_int32 * FILE_MAX_CELLS), ("shift", C.c_uint32 * FILE_MAX_CELLS)]
 
 
 class PssAcquireCell(C.Structure):   # lsn_pss_acquire_cell_t
@@ -490,6 +505,10 @@ def lib():
         L.lsn_pss_timing_error.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.lsn_stream_reacquire.argtypes = [C.c_void_p, C.POINTER(StreamReacquireCfg)]
         L.lsn_stream_reacquire_status.argtypes = [C.c_void_p, C.POINTER(StreamReacquireStatus)]
+        L.lsn_phy_mib_decode_side.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(Mib), C.c_void_p]
+        L.lsn_stream_frame_sync.argtypes = [C.c_void_p, C.POINTER(StreamFrameSyncCfg)]
+        L.lsn_stream_frame_sync_status.argtypes = [C.c_void_p, C.POINTER(StreamFrameSyncStatus)]
+        L.lsn_frame_sync_decide.argtypes = [C.POINTER(Mib), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32)]
         L.lsn_pss_acquire.argtypes = [C.c_int, C.c_int, C.POINTER(PssAcquireCell), C.c_uint32]
         L.lsn_pss_acquire_decide.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                              C.POINTER(C.c_double)]
@@ -768,6 +787,18 @@ class Phy:
         r = lib().lsn_phy_mib_decode_llr(self._h, iq.ctypes.data, 0, C.byref(m), llr.ctypes.data)
         if r < 0:
             _check(r, "mib_decode")
+        d = {n: int(getattr(m, n)) for n, _ in Mib._fields_}
+        return (d, llr) if with_llr else d
+
+    def mib_decode_side(self, iq, with_llr=False):
+        """lsn_phy_mib_decode_side: mib_decode on the Phy's side scratch and a stream of its own - the same dict and soft bits -, allowed while submitted blocks
+        are in flight"""
+        iq = np.ascontiguousarray(iq, dtype=np.complex64)
+        m = Mib()
+        llr = np.zeros(480, dtype=np.float32)
+        r = lib().lsn_phy_mib_decode_side(self._h, iq.ctypes.data, 0, C.byref(m), llr.ctypes.data if with_llr else None)
+        if r < 0:
+            _check(r, "mib_decode_side")
         d = {n: int(getattr(m, n)) for n, _ in Mib._fields_}
         return (d, llr) if with_llr else d
 
@@ -1425,6 +1456,33 @@ def pss_acquire_decide(Cv, d, N, min_ratio=0.0, history_mean=None):
     return bool(rc), int(o.value), float(pk.value), float(ra.value)
 
 
+def _frame_sync_cfg(n_cells, tries=0, hold=True, enable=True):
+    cfg = StreamFrameSyncCfg()
+    cfg.struct_size, cfg.tries, cfg.hold = C.sizeof(StreamFrameSyncCfg), int(tries), 1 if hold else FRAME_SYNC_NO_HOLD
+    vals = list(enable) if isinstance(enable, (list, tuple)) else [enable] * n_cells
+    if len(vals) != n_cells:
+        raise ValueError("frame_sync: enable needs one value per cell")
+    for i, v in enumerate(vals):
+        cfg.enable[i] = 1 if v else 0
+    return cfg
+
+
+def frame_sync_decide(mib, nof_prb, nof_ports, counted_tti):
+    """lsn_frame_sync_decide (needs no GPU): the decision over one attempt.  mib: None (not found) or a dict with found, sfn, nof_prb, nof_ports (Phy.mib_decode's)
+    -> (accepted, delta in subframes, signed in (-5120, 5120]).  Raises ValueError when refused, RuntimeError for a counted_tti that is no multiple of 5"""
+    m = Mib()
+    for k, v in (mib or {}).items():
+        setattr(m, k, int(v))
+    if not 0 <= int(counted_tti) < 1 << 32:
+        raise ValueError("frame_sync_decide: refused")
+    delta = C.c_int32()
+    rc = lib().lsn_frame_sync_decide(C.byref(m), int(nof_prb), int(nof_ports), int(counted_tti), C.byref(delta))
+    if rc == LSN_ERROR_INVALID_INPUTS:
+        raise ValueError("frame_sync_decide: refused")
+    _check_n(rc, "lsn_frame_sync_decide")
+    return bool(rc), int(delta.value)
+
+
 def pss_acquire(cells, device=0):
     """lsn_pss_acquire: k_pss_acquire without a Phy.  cells: a list of dict(blocks: complex64 [6][antenna][15 N], replica: complex64 [N], d), all of them in one
     launch -> a list of float32 arrays [75 N / d].  Raises ValueError when refused"""
@@ -1459,9 +1517,10 @@ class Stream:
     (nothing is allocated, every Phy stays usable).  Close the stream before its Phys; a Phy that is closed first closes the stream."""
 
     def __init__(self, sample_rate, cells, nof_antennas=None, sample_format=FILE_CF32, sample_scale=0.0, block_subframes=0, ring_samples=0, device=0, track=None,
-                 reacquire=None):
+                 reacquire=None, frame_sync=None):
         """track: None, or the keyword arguments of track() - the timing loop is set up before the first push.  reacquire: None, or the keyword arguments of
-        reacquire(), called behind track().  A refused track or reacquire closes the stream and raises"""
+        reacquire(), called behind track().  frame_sync: None, or the keyword arguments of frame_sync(), called behind reacquire().  A refused track, reacquire
+        or frame_sync closes the stream and raises"""
         self._h = None
         self._phys = [phy for phy, _ in cells]     # kept alive as long as the stream
         arr = (FileCell * max(len(cells), 1))()
@@ -1489,6 +1548,12 @@ class Stream:
         if reacquire is not None:
             try:
                 self.reacquire(**reacquire)
+            except ValueError:
+                self.close()
+                raise
+        if frame_sync is not None:
+            try:
+                self.frame_sync(**frame_sync)
             except ValueError:
                 self.close()
                 raise
@@ -1526,6 +1591,22 @@ class Stream:
         return dict(launched=[int(v) for v in st.launched[:n]], accepted=[int(v) for v in st.accepted[:n]], rejected=[int(v) for v in st.rejected[:n]],
                     last_peak=[float(v) for v in st.last_peak[:n]], last_ratio=[float(v) for v in st.last_ratio[:n]], last_offset=[int(v) for v in st.last_offset[:n]],
                     jump_segment=[int(v) for v in st.jump_segment[:n]], jumps_total=[float(v) for v in st.jumps_total[:n]])
+
+    def frame_sync(self, tries=0, hold=True, enable=True):
+        """lsn_stream_frame_sync: after a jump of reacquire() the first subframe of the following segments goes through the PBCH decode until one - at most `tries`
+        (0: 8) - says which TTI the cell is at; from two segments behind it on the records carry that TTI.  hold (the default): the subframes between
+        the jump and that point are not submitted to the Phy; False: they are, as counted.  Only after reacquire() and before the first push.  enable: one value
+        for every cell, or a list.  Raises ValueError when the library refuses (the stream is unchanged and usable)"""
+        self._call(lib().lsn_stream_frame_sync(self._h, C.byref(_frame_sync_cfg(self.nof_cells, tries, hold, enable))), "lsn_stream_frame_sync")
+
+    def frame_sync_status(self):
+        """lsn_stream_frame_sync_status -> dict of per-cell lists: checks, attempts, confirmed, relabelled, given_up, accept_segment, relabel_segment, held
+        (subframes), last_sfn, last_delta (subframes, signed), shift (subframes, mod 10240).  Behind a flush it is a function of the samples pushed"""
+        st = StreamFrameSyncStatus()
+        st.struct_size = C.sizeof(StreamFrameSyncStatus)
+        self._call(lib().lsn_stream_frame_sync_status(self._h, C.byref(st)), "lsn_stream_frame_sync_status")
+        n = int(st.nof_cells)
+        return {name: [int(v) for v in getattr(st, name)[:n]] for name, _ in StreamFrameSyncStatus._fields_[2:]}
 
     def _call(self, rc, what):
         if rc == LSN_ERROR_INVALID_INPUTS:

@@ -534,6 +534,11 @@ int lsn_phy_mib_decode_llr(lsn_phy_t* phy, const void* iq, int iq_on_device, lsn
   if (!phy) return LSN_ERROR_INVALID_INPUTS;
   return phy->engine->mibDecode(iq, iq_on_device != 0, out, llr_raw480);
 }
+int lsn_phy_mib_decode_side(lsn_phy_t* phy, const void* iq, int iq_on_device, lsn_mib_t* out, float* llr_raw480)
+{
+  if (!phy) return LSN_ERROR_INVALID_INPUTS;
+  return phy->engine->mibDecodeSide(iq, iq_on_device != 0, out, llr_raw480);
+}
 int lsn_phy_process_file(lsn_phy_t* phy, const char* path, const lsn_file_cfg_t* cfg, uint32_t start_tti, uint64_t max_subframes, uint32_t update_meta_period,
                          uint64_t* subframes_done)
 {
@@ -789,6 +794,20 @@ int lsn_stream_reacquire_status(lsn_stream_t* s, lsn_stream_reacquire_status_t* 
   if (!s || !out) return LSN_ERROR_INVALID_INPUTS;
   std::unique_lock<std::mutex> lk(s->ring->mtx);
   return s->ring->reacquireStatus(out);
+}
+
+int lsn_stream_frame_sync(lsn_stream_t* s, const lsn_stream_frame_sync_cfg_t* cfg)
+{
+  if (!s || !cfg || cfg->struct_size != sizeof(lsn_stream_frame_sync_cfg_t)) return LSN_ERROR_INVALID_INPUTS;
+  std::unique_lock<std::mutex> lk(s->ring->mtx);
+  return s->ring->frameSync(*cfg);
+}
+
+int lsn_stream_frame_sync_status(lsn_stream_t* s, lsn_stream_frame_sync_status_t* out)
+{
+  if (!s || !out) return LSN_ERROR_INVALID_INPUTS;
+  std::unique_lock<std::mutex> lk(s->ring->mtx);
+  return s->ring->frameSyncStatus(out);
 }
 
 int lsn_stream_close(lsn_stream_t* s)

@@ -271,6 +271,14 @@ public:
   void waitIqConsumed(uint64_t mark) { if (cfg.sniffer_mode == 1) waitMark(mark); else waitStageAMark(mark); }
   void waitMark(uint64_t mark) { std::unique_lock<std::mutex> lk(mtx); cv_done.wait(lk, [&] { return seq_written >= mark || stop; }); }
   int mibDecode(const void* iq, bool on_device, lsn_mib_t* out, float* llr_raw480);
+  // the same decode beside the pipeline (lsn_phy_mib_decode_side): on the engine's private one-subframe scratch and a stream of its own, so it does
+  // not refuse while blocks are in flight
+  int mibDecodeSide(const void* iq, bool on_device, lsn_mib_t* out, float* llr_raw480);
+  // what a stream's frame sync uses of it (lsn_stream_ring.cc): the scratch ahead of the first push, and one decode queued on the caller's stream `st` - the
+  // launches and the copy of the four candidates to `h_cand4` (pinned); no wait.  The caller parses them (mib_parse) behind an event of its own
+  int reserveMibSide();
+  void mibLaunchSide(const cf32* d_iq, LsnCand* h_cand4, hipStream_t st);
+  uint32_t nofPorts() const { return cell.nof_ports; }
   int processFile(const char* path, const lsn_file_cfg_t& fc, uint32_t start_tti, uint64_t max_subframes, uint32_t update_meta_period,
                   uint64_t* subframes_done);
   int processFileRate(const char* path, const lsn_file_cfg_t& fc, const lsn_file_rate_t& fr, uint32_t start_tti, uint64_t max_subframes, uint32_t update_meta_period,
@@ -629,6 +637,26 @@ private:
     size_t off_cap = 0, y_cap = 0, corr_cap = 0, out_cap = 0;
   } prach;
   cf32* mib_d_iq = nullptr; float* mib_d_llr = nullptr; LsnCand* mib_d_cand = nullptr;
+  // the buffers one PBCH decode runs in: mibDecode's are chunk slot 0's and mib_d_*, the side decode's are its own (MibSide)
+  struct MibBufs {
+    cf32 *d_grid = nullptr, *d_ce = nullptr;
+    float* d_chest_raw = nullptr; LsnChest* d_chest = nullptr;
+    uint32_t *d_sfidx = nullptr, *h_sfidx = nullptr;
+    float* d_llr = nullptr; LsnCand* d_cand = nullptr;
+  };
+  void mibLaunch(const cf32* d_iq, const MibBufs& b, hipStream_t st);                                 // sfidx up, k_ofdm, k_chest, k_chest_fin, the PBCH kernels
+  void mibFetch(const MibBufs& b, LsnCand* cand4, float* llr_raw480_or_null, hipStream_t st);         // the candidates (and the soft bits) device to host, queued
+  struct MibSide {
+    MibBufs b;
+    cf32* d_iq = nullptr;
+    LsnCand* h_cand = nullptr;          // pinned result slot of mibDecodeSide
+    hipStream_t st = nullptr;
+    hipEvent_t ev = nullptr;            // behind the last decode a stream queued (mibLaunchSide): mibDecodeSide waits for it before it touches the scratch
+    bool queued = false;
+    std::mutex mtx;
+  } mib_side;
+  void ensureMibSide();
+  void freeMibSide();
   lsn_prach_sink_t prach_sink = nullptr; void* prach_sink_user = nullptr;
   std::vector<int> numa_cpus;  // CPUs local to the GPU (empty: unknown, no pinning)
   // LSN_TRACE=<file>: pipeline event log (thread, event, chunk, ms since the first event), written by wait(); tools/trace_gantt.py reads it

@@ -12,6 +12,9 @@
 // A tracked stream that asked for it too (reacquire()) searches a cell whose loop has lost the PSS over a whole half frame: launchSearches
 // resamples the span into a scratch of the cell's and runs k_pss_acquire on it - launches of their own, which a stream that loses nothing never issues -, and the
 // enter() of three segments later moves the position once.
+// With frameSync() on top the first subframe of every segment of a running check goes through the PBCH decode of its Phy's side scratch,
+// queued on st_run directly behind the segment's k_pss_timing window; the result rides with the measurement (Cell::Pending) and the rule in lsn_track.cc decides the
+// TTI from it.  Where the counting or the hold changes, the block buffer is closed first: no block spans two countings.
 // Cells with a channel filter: the chain launchRing queues (lsn_launch_front, the one the file source queues: section 3.1l) runs both stages -
 // one k_chan_fir_ring launch out of the ring into the cells' intermediates, one k_resample per cell out of those - and every span that guards the ring is L samples
 // wider on both sides.  Without one, nothing differs.
@@ -58,6 +61,7 @@ StreamRing::~StreamRing()
     if (c.acq_x) (void)hipFree(c.acq_x);
     if (c.acq_C) (void)hipHostFree(c.acq_C);
     if (c.acq_ev) (void)hipEventDestroy(c.acq_ev);
+    if (c.h_cand) (void)hipHostFree(c.h_cand);
     for (auto& p : c.pending) if (p.ev) (void)hipEventDestroy(p.ev);
   }
   if (d_ring) (void)hipFree(d_ring);
@@ -225,8 +229,18 @@ cf32* StreamRing::bufferFor(Cell& q, bool empty)
 
 void StreamRing::submitBlock(Cell& q, uint32_t nsf)
 {
+  closeBlock(q, nsf, tracking && q.tk.frameHolding(), tracking ? q.tk.tti(q.done) : (uint32_t)((q.s.start_tti + q.done) % 10240u));
+}
+
+void StreamRing::closeBlock(Cell& q, uint32_t nsf, bool held, uint32_t tti)
+{
   const int si = (int)(q.launches % (uint64_t)nslot);
-  q.rc = q.s.e->submit(q.s.e->fileIqBlock(si), nsf, (uint32_t)((q.s.start_tti + q.done) % 10240u), q.s.update_meta_period, st_run);
+  if (held) {   // resampled and measured, not decoded: the same buffer is filled again (everything that touches it is ordered on st_run)
+    q.tk.fs.held += nsf;
+    q.done += nsf;
+    return;
+  }
+  q.rc = q.s.e->submit(q.s.e->fileIqBlock(si), nsf, tti, q.s.update_meta_period, st_run);
   q.mark[si] = q.s.e->submitMark();
   q.launches++;
   q.done += nsf;
@@ -441,6 +455,53 @@ int StreamRing::reacquireStatus(lsn_stream_reacquire_status_t* out)
   });
 }
 
+// ---- frame sync (lsn_track.h) ----
+
+int StreamRing::frameSync(const lsn_stream_frame_sync_cfg_t& fc)
+{
+  if (pushed || !reacquiring || framing || failed != LSN_SUCCESS) return LSN_ERROR_INVALID_INPUTS;
+  if (fc.tries > kFrameMaxTries || fc.hold > LSN_FRAME_SYNC_NO_HOLD) return LSN_ERROR_INVALID_INPUTS;
+  const int r = guarded([&]() -> int {
+    HIP_CHECK(hipSetDevice(device));
+    for (size_t c = 0; c < cells.size(); c++) {
+      Cell& q = cells[c];
+      if (!fc.enable[c] || !q.tk.acq) continue;   // a cell that is never searched never jumps
+      const int rm = q.s.e->reserveMibSide();
+      if (rm != LSN_SUCCESS) return rm;
+      if (!q.h_cand) HIP_CHECK(hipHostMalloc((void**)&q.h_cand, (size_t)TRACK_SLOTS * 4 * sizeof(LsnCand), hipHostMallocCoherent | hipHostMallocMapped));
+    }
+    return LSN_SUCCESS;
+  });
+  if (r != LSN_SUCCESS) return r;
+  for (size_t c = 0; c < cells.size(); c++) {
+    Cell& q = cells[c];
+    if (q.h_cand && fc.enable[c]) q.tk.frameSync(fc.tries, fc.hold != LSN_FRAME_SYNC_NO_HOLD, q.s.e->nofPrb(), q.s.e->nofPorts());
+  }
+  framing = true;
+  return LSN_SUCCESS;
+}
+
+int StreamRing::frameSyncStatus(lsn_stream_frame_sync_status_t* out)
+{
+  if (!out || out->struct_size != sizeof(lsn_stream_frame_sync_status_t) || !framing) return LSN_ERROR_INVALID_INPUTS;
+  return guarded([&]() -> int {
+    HIP_CHECK(hipSetDevice(device));
+    memset(out, 0, sizeof(*out));
+    out->struct_size = sizeof(*out);
+    out->nof_cells = (uint32_t)cells.size();
+    for (size_t c = 0; c < cells.size(); c++) {
+      Cell& q = cells[c];
+      deliver(q, 0, true);   // the attempts in flight come back with their measurements; the rule looks at them when their segment's turn comes
+      takeSearch(q);
+      const TrackCell::Frame& f = q.tk.fs;
+      out->checks[c] = f.checks; out->attempts[c] = f.attempts; out->confirmed[c] = f.confirmed; out->relabelled[c] = f.relabelled; out->given_up[c] = f.given_up;
+      out->accept_segment[c] = f.accept_segment; out->relabel_segment[c] = f.relabel_segment; out->held[c] = f.held;
+      out->last_sfn[c] = f.last_sfn; out->last_delta[c] = f.last_delta; out->shift[c] = f.shift;
+    }
+    return LSN_SUCCESS;
+  });
+}
+
 bool StreamRing::inGap(int64_t lo, int64_t hi) const
 {
   for (const auto& g : gaps) if (g.first < hi && lo < g.second) return true;
@@ -452,13 +513,16 @@ void StreamRing::deliver(Cell& q, uint64_t upto_h, bool all)
   while (!q.pending.empty() && (all || q.pending.front().h <= upto_h)) {
     const Cell::Pending p = q.pending.front();
     q.pending.pop_front();
+    TrackCell::Attempt at;
+    at.due = p.due; at.launched = p.mib;
     if (p.ev) {
       const hipError_t e = hipEventSynchronize(p.ev);
       ev_free.push_back(p.ev);
       HIP_CHECK(e);
-      q.tk.measured(q.h_C + (size_t)p.slot * kTrackLags);
+      if (p.mib) (void)mib_parse(q.h_cand + (size_t)p.slot * 4, at.mib);
+      q.tk.measured(p.timing ? q.h_C + (size_t)p.slot * kTrackLags : nullptr, p.due ? &at : nullptr);
     } else {
-      q.tk.measured(nullptr);
+      q.tk.measured(nullptr, p.due ? &at : nullptr);
     }
   }
 }
@@ -482,7 +546,14 @@ int StreamRing::runReadyTracked(bool flush_all)
       if (!t.entered || q.filled == t.segEnd()) {   // the next segment: the measurement of the segment two in front of it comes back first
         if (t.needsMeasurement()) deliver(q, t.h - 1, false);
         if (t.searchResultDue()) takeSearch(q);   // (re-acquisition: the search of the segment three in front comes back behind that measurement)
+        const bool held = t.frameHolding();
+        const uint32_t shift = t.fs.shift, tti = t.tti(q.done);
         t.enter();
+        // (frame sync) the counting or the hold changes with this segment: what the buffer holds goes first - to the Phy or nowhere -, as what it was counted as
+        if ((t.frameHolding() != held || t.fs.shift != shift) && q.filled > q.done) {
+          closeBlock(q, (uint32_t)(q.filled - q.done), held, tti);
+          if (failed != LSN_SUCCESS) return failed;
+        }
       }
       const uint64_t end = std::min<uint64_t>(t.segEnd(), q.done + blk);
       const uint64_t upto = std::min<uint64_t>(t.completeInSegment(insideEnd(q)), end);
@@ -497,7 +568,8 @@ int StreamRing::runReadyTracked(bool flush_all)
       launchRing(k, lo, hi, "stream: a segment");
       // the windows of the segments that began in this launch
       LsnTimingCell tm[kFileMaxCells];
-      bool timing = false;
+      bool timing = false, mibs = false;
+      const cf32* mib_sf[kFileMaxCells] = {};
       for (size_t c = 0; c < cells.size(); c++) {
         Cell& q = cells[c];
         TrackCell& t = q.tk;
@@ -506,19 +578,36 @@ int StreamRing::runReadyTracked(bool flush_all)
         int64_t g_lo, g_hi;
         t.inputSpan(t.sf0, t.sf0 + 1, g_lo, g_hi);
         q.s.filt.widen(g_lo, g_hi);   // (L = 0: as it is)
-        Cell::Pending p = {t.h, nullptr, (uint32_t)(t.h % TRACK_SLOTS)};
-        if (t.enabled && t.hasPss() && !inGap(g_lo, g_hi)) {
+        const bool gap = inGap(g_lo, g_hi);
+        Cell::Pending p = {t.h, nullptr, (uint32_t)(t.h % TRACK_SLOTS), false, framing && t.frameAttemptDue(), false};
+        if (p.due && !gap) {   // (frame sync) the attempt of this segment: the PBCH decode of the subframe the window looks at
+          p.mib = true;
+          p.ev = takeEvent();
+          mibs = true;
+          t.fs.attempts++;
+        }
+        if (t.enabled && t.hasPss() && !gap) {
+          p.timing = true;
           tm[c].x = k[c].out; tm[c].rep = q.d_rep; tm[c].C = q.h_C + (size_t)p.slot * kTrackLags; tm[c].N = t.N; tm[c].d = track_lag_spacing(t.N); tm[c].sflen = q.sflen; tm[c].nant = nant;
           tm[c].n_occ = 1; tm[c].sf[0] = (uint32_t)(q.filled - q.done); tm[c].p[0] = track_pss_index(t.N);
-          p.ev = takeEvent();
+          if (!p.ev) p.ev = takeEvent();
           timing = true;
         }
+        mib_sf[c] = p.mib ? k[c].out + (size_t)(q.filled - q.done) * nant * q.sflen : nullptr;
         q.pending.push_back(p);
       }
       if (timing) {
         lsn_launch_pss_timing(tm, (uint32_t)cells.size(), st_run);
         for (size_t c = 0; c < cells.size(); c++)
-          if (tm[c].n_occ) HIP_CHECK(hipEventRecord(cells[c].pending.back().ev, st_run));
+          if (tm[c].n_occ && !mib_sf[c]) HIP_CHECK(hipEventRecord(cells[c].pending.back().ev, st_run));
+      }
+      if (mibs) {   // directly behind the windows; a cell's event lies behind its candidates' copy
+        for (size_t c = 0; c < cells.size(); c++) {
+          if (!mib_sf[c]) continue;
+          const Cell::Pending& p = cells[c].pending.back();
+          cells[c].s.e->mibLaunchSide(mib_sf[c], cells[c].h_cand + (size_t)p.slot * 4, st_run);
+          HIP_CHECK(hipEventRecord(p.ev, st_run));
+        }
       }
       for (size_t c = 0; c < cells.size(); c++) cells[c].filled += piece[c];
     }

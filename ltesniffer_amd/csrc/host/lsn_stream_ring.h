@@ -1,7 +1,8 @@
 // lsn_stream_ring.h - the object behind lsn_stream_*: the raw input of a live stream in ONE device ring, the cells' Phys fed out of it by k_resample_ring
 //  - or, when the cells have a channel filter, by k_chan_fir_ring and one k_resample per cell (section 3.1j).  The counting is lsn_stream.h's; this is the part that speaks to the HIP runtime and to the engines.
 // A tracked stream (track(), section 3.1h) counts by the segments of lsn_track.h instead and measures every segment's PSS with k_pss_timing; with reacquire()
-// (section 3.1k) it searches a cell that has lost its PSS with k_pss_acquire and keeps 8 subframes of input more per such cell.
+// (section 3.1k) it searches a cell that has lost its PSS with k_pss_acquire and keeps 8 subframes of input more per such cell; with frameSync() (section 3.1m) a jump
+// is followed by PBCH decodes on the Phy's side scratch until one says which TTI the cell is at.
 #pragma once
 #include "lsn_engine.h"
 #include "lsn_front_launch.h"
@@ -36,6 +37,9 @@ public:
   // re-acquisition (lsn_stream_reacquire): after track(), before the first sample; a refusal leaves the stream as it was
   int reacquire(const lsn_stream_reacquire_cfg_t& cfg);
   int reacquireStatus(lsn_stream_reacquire_status_t* out);
+  // frame sync (lsn_stream_frame_sync): after reacquire(), before the first sample; a refusal leaves the stream as it was
+  int frameSync(const lsn_stream_frame_sync_cfg_t& cfg);
+  int frameSyncStatus(lsn_stream_frame_sync_status_t* out);
   uint64_t pushedSamples() const { return pushed; }
   uint64_t ringSamples() const { return ring_samples; }
   uint32_t blockSubframes() const { return blk; }
@@ -64,13 +68,16 @@ private:
     uint64_t filled = 0;                 // subframes resampled into block buffers, done <= filled <= done + blk
     cf32* d_rep = nullptr;               // the PSS replica, [N]
     float* h_C = nullptr;                // pinned, [TRACK_SLOTS][13]: k_pss_timing writes, the host reads behind the event
-    struct Pending { uint64_t h; hipEvent_t ev; uint32_t slot; };   // the measurement of segment h: ev null = none could be taken
+    // the measurement of segment h: timing false = none could be taken.  due: the segment is one of a running frame check; mib: its attempt was launched, and
+    // its candidates land in h_cand's slot.  ev (null: nothing was launched) lies behind both
+    struct Pending { uint64_t h; hipEvent_t ev; uint32_t slot; bool timing, due, mib; };
     std::deque<Pending> pending;
     // re-acquisition: the span of the search in flight (TrackCell::search) is resampled into acq_x and k_pss_acquire writes its values into acq_C
     cf32* acq_x = nullptr;               // [6][antenna][sflen]
     float* acq_C = nullptr;              // pinned, [75 N / d]
     hipEvent_t acq_ev = nullptr;         // behind the search that was launched
     uint64_t acq_keep = 0;               // input samples kept behind what the cell needs anyway (0: no re-acquisition)
+    LsnCand* h_cand = nullptr;           // frame sync: pinned, [TRACK_SLOTS][4]: the candidates of the attempts in flight
   };
   static constexpr uint32_t TRACK_SLOTS = 4;   // at most kTrackDelay measurements of a cell are in flight
   struct Launch { hipEvent_t ev; int64_t lo; };   // recorded behind a launch that read the ring from recording sample lo on (filtered: the widened span's)
@@ -89,7 +96,8 @@ private:
   int reserveMid(Cell& c, uint64_t samples);
   uint64_t insideEnd(const Cell& c) const { return c.s.filt.insideEnd(pushed); }   // what of y1 the samples pushed so far carry (L = 0: pushed)
   cf32* bufferFor(Cell& q, bool empty = true);
-  void submitBlock(Cell& q, uint32_t nsf);
+  void submitBlock(Cell& q, uint32_t nsf);   // (a tracked cell: at the TTI its TrackCell counts; while a frame check holds the cell the subframes are dropped instead)
+  void closeBlock(Cell& q, uint32_t nsf, bool held, uint32_t tti);   // submitBlock's work, the hold and the TTI given: held = the subframes go nowhere
   void deliver(Cell& q, uint64_t upto_h, bool all);   // the measurements of segments <= upto_h (all: every one in flight) go to the loop; waits for their events
   bool inGap(int64_t lo, int64_t hi) const;
   int64_t trackedBlockInput(double max_ppm) const;   // stream_block_input with every step widened by 1 + max_ppm 1e-6: what track() and reacquire() hold the ring against
@@ -111,7 +119,7 @@ private:
   std::vector<Launch> inflight;
   std::vector<hipEvent_t> ev_free;
   uint64_t pushed = 0;
-  bool tracking = false, reacquiring = false;
+  bool tracking = false, reacquiring = false, framing = false;
   std::vector<std::pair<int64_t, int64_t>> gaps;   // tracked: the gaps [lo, hi) a cell may still read
   int failed = LSN_SUCCESS;              // the first engine's failure: nothing more is submitted, every later call returns it
 };

@@ -83,6 +83,7 @@ void Engine::freeDevice(bool keep_file_buffers)
     df(prach.d_W); df(prach.d_V); df(prach.d_D); df(prach.d_Y); df(prach.d_corr); df(prach.d_out); df(prach.d_off);
     prach = Prach();
     df(mib_d_iq); df(mib_d_llr); df(mib_d_cand);
+    freeMibSide();
     // the file source's block buffers hold raw bytes, not cell tables: a cell that is set (again) keeps them - page-locking 1.5 GB costs more than replaying
     // 10 000 subframes, and a caller that reserved them (lsn_phy_prepare_file) and then sets its cell must not pay for them a second time inside its first replay
     if (!keep_file_buffers)

@@ -85,10 +85,11 @@ u128 track_widened_step(u128 step, double max_ppm)
   return step + (((step >> 32) + 1) * f);
 }
 
-void TrackCell::init(const ResamplePlan* plan, uint32_t sflen_, uint32_t N_, uint32_t start_tti, uint64_t max_sf, double r_in, const TrackCfg& c, bool enable, double initial_ppm)
+void TrackCell::init(const ResamplePlan* plan, uint32_t sflen_, uint32_t N_, uint32_t tti0, uint64_t max_sf, double r_in, const TrackCfg& c, bool enable, double initial_ppm)
 {
   rs = plan; sflen = sflen_; N = N_; max_subframes = max_sf; rate_in = r_in; rate_out = 15000.0 * (double)N_; cfg = c; enabled = enable;
-  const uint32_t ph = start_tti % kTrackSegSubframes;
+  start_tti = tti0;
+  const uint32_t ph = tti0 % kTrackSegSubframes;
   first_nsf = ph ? kTrackSegSubframes - ph : kTrackSegSubframes;
   first_has_pss = ph == 0;
   loop = TrackLoop();
@@ -106,8 +107,11 @@ void TrackCell::enter()
   if (needsMeasurement()) {
     if (!nq) throw std::runtime_error("track: a segment entered before its measurement came back");
     const Meas m = q[0];
+    const Attempt at = fq[0];
     q[0] = q[1];
+    fq[0] = fq[1];
     nq--;
+    if (at.due) frameTakeIn(h - 1, at);   // (frame sync) the attempt of segment h - 1, two in front of the one that begins here: in front of a jump's restart
     delta = enabled ? track_step(cfg, rate_in, rate_out, seglen, loop, m.e, m.valid) : 0;
   } else {
     delta = enabled ? track_delta(rate_in, rate_out, seglen, loop.corr) : 0;   // segments 0 and 1: the opened rate times 1 + initial_ppm 1e-6
@@ -121,6 +125,7 @@ void TrackCell::enter()
       loop.invalid_run = 0;
       acq_jumps += jump;
       acq_jump_segment = h + 1;
+      if (fs.on) { fs.active = true; fs.g = h + 1; fs.checks++; }   // (frame sync) the check of this jump, a running one restarted
     }
     search = Search();
   }
@@ -135,6 +140,29 @@ void TrackCell::enter()
   if (span < rs->span) span = rs->span;
   if (acq && enabled && !search.active && loop.invalid_run >= acq_after) {   // a search of this segment is due
     search.active = true; search.h = h; search.base = base; search.step = step; search.span = span;
+  }
+}
+
+// the attempt of segment a, looked at on entering segment a + 2 (enter(): h is still a + 1): a result nobody waits for - no check runs, or the segment lies in
+// front of the running check's first - is dropped
+void TrackCell::frameTakeIn(uint64_t a, const Attempt& at)
+{
+  if (!fs.active || a < fs.g) return;
+  int32_t delta = 0;
+  const uint32_t counted = (uint32_t)((start_tti + segmentStart(a) + fs.shift) % kTtiWrap);
+  if (at.launched && track_frame_decide(at.mib, fs.nof_prb, fs.nof_ports, counted, delta)) {
+    fs.last_sfn = at.mib.sfn; fs.last_delta = delta; fs.accept_segment = a;
+    if (delta) {
+      fs.shift = (uint32_t)(((int64_t)fs.shift + kTtiWrap + delta) % kTtiWrap);
+      fs.relabelled++;
+      fs.relabel_segment = a + kTrackDelay;
+    } else {
+      fs.confirmed++;
+    }
+    fs.active = false;
+  } else if (a - fs.g + 1 >= fs.tries) {
+    fs.given_up++;
+    fs.active = false;
   }
 }
 
@@ -174,12 +202,43 @@ bool track_acquire_decide(const float* C, uint32_t n, uint32_t d, uint32_t N, do
   return peak > 0.0 && peak >= min_ratio * far && !(history_mean >= 0.0 && !(peak >= 0.25 * history_mean));
 }
 
+bool mib_parse(const LsnCand cand[4], lsn_mib_t& out)
+{
+  static const uint32_t bw[6] = {6, 15, 25, 50, 75, 100};
+  static const uint32_t ng6[4] = {1, 3, 6, 12};
+  std::memset(&out, 0, sizeof(out));
+  for (uint32_t q = 0; q < 4; q++) {
+    const uint32_t mask = cand[q].rnti & 0xFFFFu;
+    const uint32_t ports = mask == 0x0000u ? 1u : (mask == 0xFFFFu ? 2u : (mask == 0x5555u ? 4u : 0u));
+    const uint32_t mib = (uint32_t)(cand[q].bits >> 40);  // 24 bits, first bit = MSB
+    if (!ports || !mib) continue;  // an all-zero block passes the CRC trivially
+    const uint32_t bwi = mib >> 21;
+    if (bwi > 5) continue;
+    out.found = 1; out.sfn_offset = q; out.nof_ports = ports; out.mib_bits = mib;
+    out.nof_prb = bw[bwi]; out.phich_length = (mib >> 20) & 1u; out.phich_resources_x6 = ng6[(mib >> 18) & 3u];
+    out.sfn = ((((mib >> 10) & 0xFFu) << 2) + q) % 1024u;
+    return true;
+  }
+  return false;
+}
+
+bool track_frame_decide(const lsn_mib_t& mib, uint32_t nof_prb, uint32_t nof_ports, uint32_t counted_tti, int32_t& delta)
+{
+  delta = 0;
+  if (!mib.found || mib.nof_prb != nof_prb || mib.nof_ports != nof_ports) return false;
+  if (counted_tti % kTrackSegSubframes) throw std::runtime_error("frame sync: a segment that does not begin on a TTI multiple of 5");
+  const uint32_t t = 10u * (mib.sfn % 1024u);
+  const uint32_t m = (t + kTtiWrap - counted_tti % kTtiWrap) % kTtiWrap;
+  delta = m > kTtiWrap / 2 ? (int32_t)m - (int32_t)kTtiWrap : (int32_t)m;
+  return true;
+}
+
 uint64_t track_acquire_keep(u128 step, double max_ppm, uint32_t sflen)
 {
   return (uint64_t)(((u128)((uint64_t)kAcqKeepSubframes * sflen) * track_widened_step(step, max_ppm)) >> 64) + 1;
 }
 
-void TrackCell::measured(const float* C)
+void TrackCell::measured(const float* C, const Attempt* at)
 {
   Meas m = {false, 0.0};
   if (C && enabled) {
@@ -196,6 +255,7 @@ void TrackCell::measured(const float* C)
   }
   if (m.valid) nvalid++; else ninvalid++;
   if (nq >= kTrackDelay) throw std::runtime_error("track: more measurements than the loop's delay");
+  fq[nq] = at ? *at : Attempt();
   q[nq++] = m;
 }
 
@@ -256,6 +316,16 @@ int lsn_pss_timing_error(const float* C, uint32_t d, double* e, double* peak)
 {
   if (!C || !d || !e || !peak) return LSN_ERROR_INVALID_INPUTS;
   return lsn::track_observe(C, d, *e, *peak) ? 1 : 0;
+}
+
+int lsn_frame_sync_decide(const lsn_mib_t* mib, uint32_t nof_prb, uint32_t nof_ports, uint32_t counted_tti, int32_t* delta)
+{
+  if (!mib || !delta || counted_tti >= lsn::kTtiWrap || (mib->found && mib->sfn >= 1024u)) return LSN_ERROR_INVALID_INPUTS;
+  try {
+    return lsn::track_frame_decide(*mib, nof_prb, nof_ports, counted_tti, *delta) ? 1 : 0;
+  } catch (const std::exception&) {
+    return LSN_ERROR;
+  }
 }
 
 int lsn_pss_acquire_decide(const float* C, uint32_t n, uint32_t d, uint32_t N, double min_ratio, double history_mean, int64_t* offset, double* peak, double* ratio)

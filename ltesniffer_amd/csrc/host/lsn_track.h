@@ -3,7 +3,9 @@
 // Plain host arithmetic in doubles and 128-bit integers, no HIP header (like lsn_stream.h): it runs - and is tested (tests/test_track_model.py) - on a machine with
 // no GPU.  Every decision here is a function of (input samples, configuration) only; nothing depends on when a push arrived.
 #pragma once
+#include "../../../include/ltesniffer_amd.h"
 #include "lsn_resample.h"
+#include "lsn_types.h"
 
 namespace lsn {
 
@@ -16,6 +18,10 @@ static constexpr uint32_t kAcqDelay = 3;          // and is taken in on entering
 static constexpr uint32_t kAcqFar = 8;            // lags around the maximum that do not count as another peak
 static constexpr uint32_t kAcqKeepSubframes = 8;  // 6 for the span of the segment behind, 2.5 for a backward jump, rounded up
 static constexpr double kAcqMinRatio = 3.0;       // the geometric mean of the ratio measured on noise (1.86) and with the cell present (5.1)
+// frame sync
+static constexpr uint32_t kFrameTries = 8;        // attempts of one check: four radio frames, one PBCH period
+static constexpr uint32_t kFrameMaxTries = 64;
+static constexpr uint32_t kTtiWrap = 10240;
 
 inline uint32_t track_lag_spacing(uint32_t N) { return N / 128 ? N / 128 : 1; }
 // index, inside a subframe 0 / 5, of the first useful sample of the PSS symbol: symbol 6 of slot 0 with the normal prefix, symbol 5 with the extended one - 13 N / 2
@@ -97,6 +103,30 @@ struct TrackCell {
   int64_t acq_offset = 0;
   __int128 acq_jumps = 0;    // the sum of all jumps, 2^-64 input samples
 
+  // frame sync (off unless frameSync() was called): an accepted jump starts a check at the segment it takes force at, g.  Every segment
+  // a = g .. g + tries - 1 of a running check is due an attempt - a PBCH decode of its first subframe -, whose result comes in with the segment's measurement
+  // (measured()) and waits with it: enter() looks at the result of segment a when it enters segment a + 2 and at no other time, so nothing depends on when a
+  // status call fetched it.  Accepted: the shift changes, from this segment on; `tries` results without one: given up.  Either ends the check
+  struct Attempt { bool due = false, launched = false; lsn_mib_t mib = {}; };   // due: the segment was one of a running check when its first piece was launched
+  struct Frame {
+    bool on = false, hold = true;
+    uint32_t tries = kFrameTries, nof_prb = 0, nof_ports = 0;
+    bool active = false;
+    uint64_t g = 0;
+    uint32_t shift = 0;        // subframes, mod 10240: the TTI of subframe sf is start_tti + sf + shift
+    uint64_t checks = 0, attempts = 0, confirmed = 0, relabelled = 0, given_up = 0, accept_segment = 0, relabel_segment = 0, held = 0;
+    uint32_t last_sfn = 0;
+    int32_t last_delta = 0;
+  };
+  Frame fs;
+  Attempt fq[kTrackDelay] = {};   // in step with q[]
+  uint32_t start_tti = 0;
+  void frameSync(uint32_t tries, bool hold, uint32_t nof_prb, uint32_t nof_ports) { fs.on = true; fs.tries = tries ? tries : kFrameTries; fs.hold = hold; fs.nof_prb = nof_prb; fs.nof_ports = nof_ports; }
+  bool frameAttemptDue() const { return fs.active && entered && h >= fs.g && h - fs.g < fs.tries; }   // of the current segment
+  bool frameHolding() const { return fs.active && fs.hold; }                                           // the current segment's subframes are not submitted
+  uint32_t tti(uint64_t sf) const { return (uint32_t)((start_tti + sf + fs.shift) % kTtiWrap); }     // of a subframe of the current segment
+  uint64_t segmentStart(uint64_t a) const { return a ? first_nsf + (a - 1) * kTrackSegSubframes : 0; }  // the first subframe of segment a
+
   void reacquire(uint32_t after, double min_ratio) { acq = true; acq_after = after ? after : cfg.lost_after; acq_min_ratio = min_ratio != 0.0 ? min_ratio : kAcqMinRatio; }
   bool searchResultDue() const { return search.active && entered && h + 1 == search.h + kAcqDelay; }   // the next enter() takes the search's result in
   void searchInputSpan(int64_t& lo, int64_t& hi) const;   // input samples the search in flight reads
@@ -111,8 +141,10 @@ struct TrackCell {
   // the next segment begins at subframe segEnd().  needs(): it takes a measurement out of q first (segments 2 ...)
   bool needsMeasurement() const { return entered && h + 1 >= kTrackDelay; }
   void enter();
+  void frameTakeIn(uint64_t a, const Attempt& at);
   // the measurement of the current segment, taken from its first subframe: C null = none could be taken (no PSS, a gap, the cell not enabled)
-  void measured(const float* C);
+  // at: the attempt of that segment, if it was due one (frame sync; null: none)
+  void measured(const float* C, const Attempt* at = nullptr);
   // subframes [.., n) of the cell that are complete once `pushed` samples have arrived, counted up to the end of the current segment
   uint64_t completeInSegment(uint64_t pushed) const;
   void inputSpan(uint64_t sf_lo, uint64_t sf_hi, int64_t& lo, int64_t& hi) const;   // subframes [sf_lo, sf_hi) of the current segment
@@ -131,5 +163,15 @@ u128 track_widened_step(u128 step, double max_ppm);
 bool track_acquire_decide(const float* C, uint32_t n, uint32_t d, uint32_t N, double min_ratio, double history_mean, int64_t& offset, double& peak, double& ratio);
 // input samples a cell with re-acquisition keeps behind what it keeps anyway: kAcqKeepSubframes output subframes at the widened step
 uint64_t track_acquire_keep(u128 step, double max_ppm, uint32_t sflen);
+
+// ---- frame sync (lsn_stream_frame_sync) ----
+// the four candidates of k_pbch_viterbi (radio-frame phases 0 .. 3: bits, CRC mask) -> the MIB of the first one that passes; true when one did.  lsn_phy_mib_decode's
+// host part: out is zeroed first
+bool mib_parse(const LsnCand cand[4], lsn_mib_t& out);
+// the decision over one attempt.  Accepted (true) when the MIB is found and its nof_prb and nof_ports are the Phy's; T = 10 sfn, C = counted_tti (below 10240: the
+// TTI the attempt's subframe was counted as), delta = (T - C) mod 10240, signed in (-5120, 5120].  An accepted MIB with C mod 5 != 0 - and with it delta mod 5
+// != 0 - is an internal error (throws): segments begin on TTI multiples of 5 and stay there, delta being one.
+// Chance of accepting garbage: 3 CRC masks x 4 phases / 2^16, times 1/3 for the port mask, times 1/8 for the bandwidth field: about 8e-6 per attempt
+bool track_frame_decide(const lsn_mib_t& mib, uint32_t nof_prb, uint32_t nof_ports, uint32_t counted_tti, int32_t& delta);
 
 }  // namespace lsn
