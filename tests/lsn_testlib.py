@@ -62,6 +62,10 @@ class TxgPdu(C.Structure):
                 ("table256", C.c_uint8), ("is_ul", C.c_uint8), ("nof_prb", C.c_uint32), ("mcs", C.c_uint32), ("cqi_req", C.c_uint32), ("hop_bits_plus1", C.c_uint32)]
 
 
+class OCbSegm(C.Structure):  # o_cbsegm_t
+    _fields_ = [(n, C.c_int) for n in ("C", "Cp", "Cm", "Kp", "Km", "F", "tbs")]
+
+
 _oracle = None
 _txgen = None
 
@@ -91,6 +95,10 @@ def oracle():
         lib.o_pdsch_decode_tb.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                           C.POINTER(C.c_int)]
         lib.o_tbs_from_idx.argtypes = [C.c_int, C.c_uint32]
+        lib.o_tbs_from_idx.restype = C.c_int
+        lib.o_cbsegm.argtypes = [C.POINTER(OCbSegm), C.c_int]
+        lib.o_ra_nof_re.restype = C.c_uint32
+        lib.o_ra_nof_re.argtypes = [C.POINTER(OCell), C.c_uint32, C.c_uint32, C.POINTER(OGrant)]
         lib.o_worker_new.restype = C.c_void_p
         lib.o_worker_new.argtypes = [C.POINTER(OWorkerCfg)]
         lib.o_worker_free.argtypes = [C.c_void_p]

@@ -219,8 +219,10 @@ def pbch_res(nof_prb, cell_id, cp):
 
 # ---------------------------------------------------------------------------------------------------------------------------- one subframe
 def control_subframe(nof_prb, nof_ports, cell_id, cp=0, sf_idx=0, sfn=0, cfi=1, ng_x6=1, nof_rx=1, dcis=(), gains=None, snr_db=None, scale=1.0,
-                     seed=0):
+                     seed=0, pdsch=()):
     """dcis: (L, ncce, rnti, payload bits).  gains[nof_ports, nof_rx]: flat channel (default: random, |h| in [0.5, 1.5]).
+    pdsch: the shared channels of tests/spec_pdsch.py (dicts with res: the (l, k) of their resource elements in mapping order, y[nof_ports, len(res)]),
+    placed into the same grid; every other element of the data region stays empty.
     -> (iq[nof_rx, 15 N] complex64, truth dict)"""
     rng = np.random.default_rng(seed)
     nre, nfft, nsym = 12 * nof_prb, FFT[nof_prb], 12 if cp else 14
@@ -267,6 +269,12 @@ def control_subframe(nof_prb, nof_ports, cell_id, cp=0, sf_idx=0, sfn=0, cfi=1, 
         for i, (l, k) in enumerate(pbch_res(nof_prb, cell_id, cp)):
             tx[:, l, k] = y[:, i]
         truth.update(mib=mib, pbch_bits=quarter)
+    # PDSCH (6.3.5): nothing may land on an element that is in use
+    for ch in pdsch:
+        ll, kk = np.array([l for l, _ in ch["res"]]), np.array([k for _, k in ch["res"]])
+        assert ll.min() >= reg.nof_symbols(cfi) and not np.any(tx[:, ll, kk]), "PDSCH on an occupied resource element"
+        tx[:, ll, kk] = ch["y"]
+    truth["pdsch"] = list(pdsch)
     # channel: a flat complex gain per (port, rx), AWGN of variance 10^(-snr/10) per RE, an overall amplitude
     if gains is None:
         gains = rng.uniform(0.5, 1.5, (nof_ports, nof_rx)) * np.exp(2j * np.pi * rng.uniform(0, 1, (nof_ports, nof_rx)))

@@ -7,7 +7,7 @@ import os
 import numpy as np
 import pytest
 
-from lsn_testlib import (LsnCand, OCell, OGrant, OracleWorker, TxGen, candidate_table, hosttest, oracle, scenario, ROOT,
+from lsn_testlib import (LsnCand, OCbSegm, OCell, OGrant, OracleWorker, TxGen, candidate_table, hosttest, oracle, scenario, ROOT,
                          MAX_LOC, MAX_SIZES, CCE_STRIDE)
 
 
@@ -153,11 +153,7 @@ def test_ul_grants_with_frequency_hopping_offsets():
 
 def test_cbsegm_all_tbs():
     h, o = hosttest(), oracle()
-
-    class Seg(C.Structure):
-        _fields_ = [(n, C.c_int) for n in ("C", "Cp", "Cm", "Kp", "Km", "F", "tbs")]
-    o.o_cbsegm.argtypes = [C.POINTER(Seg), C.c_int]
-    o.o_tbs_from_idx.restype = C.c_int
+    Seg = OCbSegm
     seen = set()
     for itbs in range(0, 34):
         for nprb in range(1, 111):
