@@ -2,7 +2,10 @@
 // grant, DMRS channel estimation, 1-tap MMSE equalisation, transform de-precoding, soft demodulation, descrambling and
 // channel de-interleaving.  They replace srsran_enb_ul_fft (/root/reference/src/src/UL_Sniffer_PUSCH.cc:392),
 // srsran_chest_ul_estimate_pusch (:256) and the front half of srsran_pusch_decode (:262); the back half (rate
-// de-matching + turbo + CRC) is k_turbo of stage_c.hip.  Scope: one antenna, no hopping, no SRS, no UCI, L_prb >= 3.
+// de-matching + turbo + CRC) is k_rm / k_turbo of stage_c.hip.  Scope: one antenna; every allocation of 2^a 3^b 5^c PRB up to
+// M_sc = 1200 (one and two PRB on the tabulated base sequences); both cyclic prefixes; group and sequence hopping of the
+// reference signal (host tables); type-1 frequency hopping (slot 1 at n_prb2); HARQ-ACK / RI / CQI cells located by the
+// closed form of the 36.212 5.2.2.8 interleaver (RI and CQI skipped, HARQ-ACK erased), never decoded.  No SRS, no type-2 hopping.
 // Float arithmetic: one rounding per operation, fixed summation orders (bit-identical to the tests' CPU oracle).
 #include "lsn_dsp.h"
 

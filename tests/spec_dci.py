@@ -1,9 +1,10 @@
-"""DCI payloads of formats 1A, 1, 2A and 2 for FDD, packed from TS 36.212 5.3.3.1 and TS 36.213 7.1.6 alone (test infrastructure only; no line shared
-with tools/txgen, oracle/ or the product).
+"""DCI payloads of formats 0, 1A, 1, 2A and 2 for FDD, packed from TS 36.212 5.3.3.1 and TS 36.213 7.1.6 / 8.4 alone (test infrastructure only; no line
+shared with tools/txgen, oracle/ or the product).
 
 Covered: the field order of each format, resource allocation type 0 (RBG size P of 36.213 Table 7.1.6.1-1, the short last RBG), type 2 with
 localised VRBs (the RIV of 7.1.6.3), the type-0 / type-1 header bit above 10 PRB, the transport-block-to-codeword swap flag, the precoding information
-field for two ports (36.212 Table 5.3.3.1.5-4; format 2A has none on two ports, Table 5.3.3.1.5A-1) and the size rules of 5.3.3.1.
+field for two ports (36.212 Table 5.3.3.1.5-4; format 2A has none on two ports, Table 5.3.3.1.5A-1), the hopping bits of format 0 (36.213 Table 8.4-1)
+and the size rules of 5.3.3.1.
 Left out: resource allocation type 1 and distributed VRBs (nothing here packs them)."""
 AMBIGUOUS = (12, 14, 16, 20, 24, 26, 32, 40, 44, 56)     # 36.212 Table 5.3.3.1.2-1
 
@@ -95,6 +96,25 @@ def pack_1a(nof_prb, start, length, mcs, rv, harq=0, ndi=0, tpc=0):
     """format 1A with a C-RNTI, localised VRBs -> (bits, PRBs)"""
     b = [1, 0] + _bits(riv(nof_prb, start, length), riv_bits(nof_prb)) + _bits(mcs, 5) + _bits(harq, 3) + [ndi] + _bits(rv, 2) + _bits(tpc, 2)
     return _pad(b, size_format1a(nof_prb)), list(range(start, start + length))
+
+
+def hop_bits_format0(nof_prb):
+    """36.213 Table 8.4-1: N_UL_hop = 1 for 6..49 PRB, 2 for 50..110"""
+    return 1 if nof_prb < 50 else 2
+
+
+def pack_0(nof_prb, start, length, mcs, ndi=0, tpc=0, cyclic_shift=0, cqi_request=0, hop=None):
+    """format 0 (5.3.3.1.1, FDD, one uplink carrier): flag 0, hopping flag, resource block assignment and hopping allocation of
+    ceil(log2(N (N + 1) / 2)) bits - with the hopping flag set its N_UL_hop most significant bits are the hopping bits `hop` and the rest carries the
+    RIV (36.213 8.4) -, MCS and redundancy version 5, NDI, TPC 2, cyclic shift for DM RS 3, CQI request; zeros up to the size of format 1A -> bits"""
+    nb = riv_bits(nof_prb)
+    if hop is None:
+        alloc = _bits(riv(nof_prb, start, length), nb)
+    else:
+        nh = hop_bits_format0(nof_prb)
+        alloc = _bits(hop, nh) + _bits(riv(nof_prb, start, length), nb - nh)
+    b = [0, 0 if hop is None else 1] + alloc + _bits(mcs, 5) + [ndi] + _bits(tpc, 2) + _bits(cyclic_shift, 3) + [cqi_request]
+    return _pad(b, size_format0(nof_prb))
 
 
 def pack_1a_si(nof_prb, start, length, itbs, rv, nprb1a):
