@@ -278,6 +278,75 @@ int lsn_cell_search(int device, const void* iq, int iq_on_device, uint64_t nof_s
 int lsn_cell_search_rates(int device, const void* iq, int iq_on_device, uint64_t nof_samples, uint32_t nof_prb, int rates, const lsn_cell_search_cfg_t* cfg,
                           lsn_cell_search_t* out, float* corr_out);
 
+/* ---- every cell of a carrier: successive cell search ----
+ * lsn_cell_search reports the strongest cell.  A network reuses one frequency in all its cells, so a receiver hears several on each carrier: the sectors of
+ * a site share their timing and differ in N_id_2, other sites arrive at other timings.  lsn_cell_search_all finds them one after the other on a device copy
+ * of the samples (the caller's buffer is never written):
+ *   round 0      lsn_cell_search's decision on the untouched samples - every field of cell 0 is what lsn_cell_search returns for the same input and
+ *                configuration; no cell at all when its found is 0.
+ *   every round  the SSS decision is repeated robustly at the round's peak: the 336 hypothesis powers are added over ALL occurrences whose SSS symbol lies
+ *                in the buffer (subframe 0 / 5 swapped on odd occurrences), with the channel from the PSS averaged over +-2 carriers inside each half of
+ *                the band.  sss_ratio = best / second accumulated power of the winning cyclic-prefix hypothesis.
+ *   rounds >= 1  accept the peak when peak / mean(root) >= threshold_next AND sss_ratio >= sss_ratio_min AND the cell is not one already reported; cell id, CP,
+ *                sf_start, sf_idx and the carrier offsets come from the accumulated decision by lsn_cell_search's formulas.  The search stops at the first
+ *                round that accepts nothing, or at max_cells.
+ *   shared PSS   two cells with the same root at the same timing are one PSS peak: the runner-up hypothesis of a round (another N_id_1 than the best) is
+ *                reported as a cell of its own, shared_pss = 1 and the round's timing, when its accumulated power is >= shared_pss_ratio x the best.
+ *   cancellation after an accepted round the cell's PSS is taken out of the working copy, one complex gain per occurrence (lsn_pss_cancel), and the
+ *                correlation is recomputed only where samples changed: the lags |n - pss_pos| < N (mod 75 N), lsn_cell_search_all_plan.
+ * threshold_next = 8 was measured for 8 periods (the floor after a cancellation stays below 4.7); with fewer periods noise alone reaches
+ * higher (10.2 at 2 periods) and the threshold must be raised.  Cells more than about 6 dB below the strongest are not reported reliably.  FDD, one antenna.
+ * Same input as lsn_cell_search_rates.  Returns the number of cells found (0..max_cells), < 0 on error. */
+typedef struct {
+  uint32_t nof_periods;    /* 1..16, 0 = 8 */
+  int32_t  force_n_id_2;   /* -1: the three roots */
+  float threshold;         /* round 0, as lsn_cell_search_cfg_t.threshold */
+  float threshold_next;    /* rounds >= 1 on peak / mean; 0 = 8 */
+  float sss_ratio_min;     /* rounds >= 1 on best / second accumulated SSS power; 0 = 1.5 */
+  float shared_pss_ratio;  /* 0 = 0.6; < 0: no second cell from one PSS peak */
+  uint32_t max_cells;      /* 1..8, 0 = 8 */
+} lsn_cell_search_all_cfg_t;
+#define LSN_SEARCH_MAX_CELLS 8
+typedef struct {
+  lsn_cell_search_t cell;
+  uint32_t round;          /* the round that found it */
+  uint32_t shared_pss;     /* 1: the runner-up of its round (same root, same timing as the cell before it) */
+  float sss_ratio;         /* best / second accumulated SSS power of its round */
+  float rel_power_db;      /* mean |a_j|^2 of its cancellation against cell 0's (a shared-PSS cell: its round's, scaled by runner-up / best power) */
+} lsn_cell_found_t;
+int lsn_cell_search_all(int device, const void* iq, int iq_on_device, uint64_t nof_samples, uint32_t nof_prb, int rates, const lsn_cell_search_all_cfg_t* cfg,
+                        lsn_cell_found_t* out /* [max_cells] */, uint32_t* nof_found, float* corr_out /* optional, host: [rounds run][3][75 N] */);
+/* corr_out: room for max_cells + 1 rounds.  Rounds run: 1 when nothing was found; else the last found cell's round + 2 when the search ended on a round that
+ * accepted nothing, + 1 when max_cells ended it (the correlation after the last cancellation is then not formed). */
+/* the cancellation alone: iq (host, (nof_periods + 1) 75 N + N samples at least) -> residual (host, as many samples as iq) and a [nof_periods + 1][2]:
+ * a_j = sum_k conj(p[k]) iq[pss_pos + j 75 N + k], residual = iq - a_j p at each occurrence; p: lsn_clock_replica's (unit energy, rotated by cfo_hz) */
+int lsn_pss_cancel(int device, const void* iq, uint64_t nof_samples, uint32_t nof_prb, int rates, uint32_t nof_periods, uint32_t n_id_2, uint32_t pss_pos,
+                   float cfo_hz, void* residual, float* a_out);
+/* the accumulated SSS decision's raw numbers at a lag (no search): sums [2 CP][nof_periods + 1][336][2] coherent sums (0 where the SSS symbol is outside
+ * the buffer), valid [2][nof_periods + 1], halves [nof_periods + 1][2][3] (re, im, energy of the PSS matched-filter halves), acc [2][336] powers */
+int lsn_sss_accumulate(int device, const void* iq, uint64_t nof_samples, uint32_t nof_prb, int rates, uint32_t nof_periods, uint32_t n_id_2, uint32_t pss_pos,
+                       float* sums, uint32_t* valid, float* halves, float* acc);
+/* No GPU.  The lags a cancellation at pss_pos changes: n_lag = 2 N - 1 lags from n_lo on, modulo W5 = 75 N; as runs of consecutive lags: one, or two when
+ * the window wraps at W5 (the run that starts at 0 comes second). */
+typedef struct {
+  uint32_t n_lo, n_lag;
+  uint32_t nof_runs;
+  uint32_t run_lo[2], run_len[2];
+} lsn_cell_search_all_plan_t;
+int lsn_cell_search_all_plan(uint32_t pss_pos, uint32_t N, uint32_t W5, lsn_cell_search_all_plan_t* out);
+/* No GPU.  The rule of one round on its statistics: peak and sum of the winning root's correlation over W5 lags, acc [2 CP][336] accumulated powers. */
+typedef struct {
+  uint32_t accept;         /* round 0: p2avg >= threshold; rounds >= 1: both tests above */
+  uint32_t cp;             /* winning cyclic-prefix hypothesis: the larger best power, normal on a tie */
+  uint32_t best, second;   /* hypotheses h = 2 N_id_1 + (subframe 5 at occurrence 0): first maximum and second largest power */
+  uint32_t shared;         /* 1: runner_up is a cell of its own when the round is accepted */
+  uint32_t runner_up;      /* largest power among the hypotheses of another N_id_1 than best's */
+  float p2avg, sss_ratio;
+  float best_power, second_power, runner_up_power;
+} lsn_cell_search_all_decision_t;
+int lsn_cell_search_all_decide(const lsn_cell_search_all_cfg_t* cfg, uint32_t round, float peak, double sum, uint32_t W5, const float* acc,
+                               lsn_cell_search_all_decision_t* out);
+
 /* ---- IQ capture file replay ----
  * Replaces the file source of the reference's file mode: srsran_ue_sync_init_file_multi(&ue_sync, nof_prb, file, offset_time,
  * offset_freq, nof_rx_antennas) + one srsran_ue_sync_zerocopy per subframe (LTESniffer_Core.cc:252-258,365; options -O / -o,

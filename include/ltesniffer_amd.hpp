@@ -265,6 +265,16 @@ inline int cellSearchRates(const cf_t* iq, uint64_t nof_samples, uint32_t nof_pr
   lsn_cell_search_cfg_t c{nof_periods, force_N_id_2, threshold};
   return lsn_cell_search_rates(device, iq, 0, nof_samples, nof_prb, rates, &c, &out, nullptr);
 }
+// lsn_cell_search_all: every cell of the carrier, strongest first (cell 0 is cellSearch's answer); cfg fields left 0 take their defaults.  < 0 error
+inline int cellSearchAll(const cf_t* iq, uint64_t nof_samples, uint32_t nof_prb, std::vector<lsn_cell_found_t>& out, lsn_cell_search_all_cfg_t cfg = {0, -1, 20.0f, 0, 0, 0, 0},
+                         int rates = LSN_RATES_3GPP, int device = 0)
+{
+  lsn_cell_found_t f[LSN_SEARCH_MAX_CELLS];
+  uint32_t n = 0;
+  const int r = lsn_cell_search_all(device, iq, 0, nof_samples, nof_prb, rates, &cfg, f, &n, nullptr);
+  out.assign(f, f + (r < 0 ? 0 : n));
+  return r;
+}
 
 // A live wideband stream pushed in host buffers (lsn_stream_*): the place of the reference's receive loop (srsran_ue_sync_zerocopy per subframe,
 // LTESniffer_Core.cc:365) for a radio that delivers more than one cell's worth of bandwidth.  cells: lsn_file_cell_t, each with phy = Phy::handle().

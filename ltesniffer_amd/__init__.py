@@ -48,7 +48,8 @@ EXPORTS = ["lsn_phy_create", "lsn_phy_destroy", "lsn_phy_set_cell", "lsn_phy_get
            "lsn_stream_track", "lsn_stream_track_status", "lsn_stream_track_step", "lsn_pss_timing", "lsn_pss_timing_error",
            "lsn_channel_filter_ring", "lsn_stream_span_filtered",
            "lsn_stream_reacquire", "lsn_stream_reacquire_status", "lsn_pss_acquire", "lsn_pss_acquire_decide",
-           "lsn_phy_mib_decode_side", "lsn_stream_frame_sync", "lsn_stream_frame_sync_status", "lsn_frame_sync_decide"]
+           "lsn_phy_mib_decode_side", "lsn_stream_frame_sync", "lsn_stream_frame_sync_status", "lsn_frame_sync_decide",
+           "lsn_cell_search_all", "lsn_pss_cancel", "lsn_sss_accumulate", "lsn_cell_search_all_plan", "lsn_cell_search_all_decide"]
 
 RATES_3GPP, RATES_SRSRAN = 0, 1   # LSN_RATES_*: sampling mode of a Phy / of a cell search
 
@@ -116,6 +117,24 @@ class CellSearch(C.Structure):
     _fields_ = [("found", C.c_uint32), ("cell_id", C.c_uint32), ("n_id_2", C.c_uint32), ("n_id_1", C.c_uint32), ("sf_idx", C.c_uint32),
                 ("pss_pos", C.c_uint32), ("sf_start", C.c_uint32), ("pss_peak", C.c_float), ("pss_p2avg", C.c_float),
                 ("sss_metric", C.c_float), ("sss_second", C.c_float), ("cfo_hz", C.c_float), ("cfo_coarse_hz", C.c_float), ("cp", C.c_uint32)]
+
+
+class CellSearchAllCfg(C.Structure):   # lsn_cell_search_all_cfg_t
+    _fields_ = [("nof_periods", C.c_uint32), ("force_n_id_2", C.c_int32), ("threshold", C.c_float), ("threshold_next", C.c_float), ("sss_ratio_min", C.c_float),
+                ("shared_pss_ratio", C.c_float), ("max_cells", C.c_uint32)]
+
+
+class CellFound(C.Structure):   # lsn_cell_found_t
+    _fields_ = [("cell", CellSearch), ("round", C.c_uint32), ("shared_pss", C.c_uint32), ("sss_ratio", C.c_float), ("rel_power_db", C.c_float)]
+
+
+class CellSearchAllPlan(C.Structure):   # lsn_cell_search_all_plan_t
+    _fields_ = [("n_lo", C.c_uint32), ("n_lag", C.c_uint32), ("nof_runs", C.c_uint32), ("run_lo", C.c_uint32 * 2), ("run_len", C.c_uint32 * 2)]
+
+
+class CellSearchAllDecision(C.Structure):   # lsn_cell_search_all_decision_t
+    _fields_ = [("accept", C.c_uint32), ("cp", C.c_uint32), ("best", C.c_uint32), ("second", C.c_uint32), ("shared", C.c_uint32), ("runner_up", C.c_uint32),
+                ("p2avg", C.c_float), ("sss_ratio", C.c_float), ("best_power", C.c_float), ("second_power", C.c_float), ("runner_up_power", C.c_float)]
 
 
 class FileCfg(C.Structure):
@@ -538,6 +557,13 @@ def lib():
         L.lsn_clock_plan.argtypes = [C.POINTER(ClockCfg), C.c_uint64, C.c_uint32, C.POINTER(Clock), C.POINTER(ClockObs), C.c_uint32]
         L.lsn_clock_fit.argtypes = [C.POINTER(ClockObs), C.c_uint32, C.c_uint32, C.POINTER(Clock)]
         L.lsn_clock_replica.argtypes = [C.POINTER(ClockCfg), C.c_void_p]
+        L.lsn_cell_search_all.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(CellSearchAllCfg), C.POINTER(CellFound),
+                                          C.POINTER(C.c_uint32), C.c_void_p]
+        L.lsn_pss_cancel.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p]
+        L.lsn_sss_accumulate.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]
+        L.lsn_cell_search_all_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(CellSearchAllPlan)]
+        L.lsn_cell_search_all_decide.argtypes = [C.POINTER(CellSearchAllCfg), C.c_uint32, C.c_float, C.c_double, C.c_uint32, C.c_void_p, C.POINTER(CellSearchAllDecision)]
         L.lsn_clock_track.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.POINTER(ClockCfg), C.POINTER(ClockObs), C.c_uint32, C.c_void_p]
         L.lsn_clock_estimate.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.POINTER(ClockCfg), C.POINTER(Clock), C.POINTER(ClockObs), C.c_uint32]
         L.lsn_file_clock_estimate.argtypes = [C.c_int, C.c_char_p, C.POINTER(FileCfg), C.POINTER(FileRate), C.c_uint32, C.POINTER(ClockCfg), C.POINTER(Clock)]
@@ -1055,6 +1081,82 @@ def cell_search(iq, nof_prb, nof_periods=2, force_n_id_2=-1, threshold=20.0, dev
         ptr, n, on_dev = iq.ctypes.data, iq.size, 0
     rc = _check_n(lib().lsn_cell_search_rates(device, ptr, on_dev, n, nof_prb, int(rates), C.byref(cfg), C.byref(out), corr.ctypes.data if with_corr else None), "lsn_cell_search")
     return (rc, out, corr) if with_corr else (rc, out)
+
+
+def cell_search_all(iq, nof_prb, nof_periods=8, force_n_id_2=-1, threshold=20.0, threshold_next=0.0, sss_ratio_min=0.0, shared_pss_ratio=0.0, max_cells=0,
+                    device=0, with_corr=False, rates=RATES_3GPP):
+    """lsn_cell_search_all: every cell of the carrier in iq (as cell_search: numpy complex64 or a torch cuda tensor, one antenna), strongest first -> list of
+    CellFound (cell: what cell_search reports, round, shared_pss, sss_ratio, rel_power_db)[, corr[rounds run, 3, 75 N]: the correlation each round decided on].
+    Arguments left 0 take the library's defaults (threshold_next 8, sss_ratio_min 1.5, shared_pss_ratio 0.6, max_cells 8); threshold_next is measured for 8
+    periods and must be raised for fewer."""
+    import numpy as np
+    N = symbol_sz(nof_prb, rates) or 128
+    cfg = CellSearchAllCfg(int(nof_periods), int(force_n_id_2), float(threshold), float(threshold_next), float(sss_ratio_min), float(shared_pss_ratio), int(max_cells))
+    cap = int(max_cells) if 0 < int(max_cells) <= 8 else 8
+    out = (CellFound * 8)()
+    nf = C.c_uint32(0)
+    corr = np.zeros((cap + 1, 3, 75 * N), dtype=np.float32) if with_corr else None
+    if hasattr(iq, "data_ptr"):
+        ptr, n, on_dev = iq.data_ptr(), iq.numel(), 1
+    else:
+        iq = np.ascontiguousarray(iq, dtype=np.complex64)
+        ptr, n, on_dev = iq.ctypes.data, iq.size, 0
+    _check_n(lib().lsn_cell_search_all(device, ptr, on_dev, n, nof_prb, int(rates), C.byref(cfg), out, C.byref(nf), corr.ctypes.data if with_corr else None),
+             "lsn_cell_search_all")
+    cells = [CellFound.from_buffer_copy(out[i]) for i in range(nf.value)]
+    if not with_corr:
+        return cells
+    rounds = 1 if not cells else cells[-1].round + (2 if len(cells) < cap else 1)
+    return cells, corr[:rounds]
+
+
+def pss_cancel(iq, nof_prb, n_id_2, pss_pos, cfo_hz=0.0, nof_periods=8, device=0, rates=RATES_3GPP):
+    """lsn_pss_cancel: the cancellation step of cell_search_all alone, on host samples -> (residual complex64 like iq, a complex64 [nof_periods + 1])"""
+    import numpy as np
+    iq = np.ascontiguousarray(iq, dtype=np.complex64)
+    res = np.zeros_like(iq)
+    a = np.zeros(int(nof_periods) + 1, dtype=np.complex64)
+    _check(lib().lsn_pss_cancel(device, iq.ctypes.data, iq.size, int(nof_prb), int(rates), int(nof_periods), int(n_id_2), int(pss_pos), float(cfo_hz),
+                                res.ctypes.data, a.ctypes.data), "lsn_pss_cancel")
+    return res, a
+
+
+def sss_accumulate(iq, nof_prb, n_id_2, pss_pos, nof_periods=8, device=0, rates=RATES_3GPP):
+    """lsn_sss_accumulate: the accumulated SSS decision's numbers at lag pss_pos of root n_id_2 -> dict(sums complex64 [2 CP, occurrence, 336], valid [2, occurrence],
+    halves float32 [occurrence, 2, 3], acc float32 [2, 336])"""
+    import numpy as np
+    iq = np.ascontiguousarray(iq, dtype=np.complex64)
+    nocc = int(nof_periods) + 1
+    sums = np.zeros((2, nocc, 336), dtype=np.complex64)
+    valid = np.zeros((2, nocc), dtype=np.uint32)
+    halves = np.zeros((nocc, 2, 3), dtype=np.float32)
+    acc = np.zeros((2, 336), dtype=np.float32)
+    _check(lib().lsn_sss_accumulate(device, iq.ctypes.data, iq.size, int(nof_prb), int(rates), int(nof_periods), int(n_id_2), int(pss_pos), sums.ctypes.data,
+                                    valid.ctypes.data, halves.ctypes.data, acc.ctypes.data), "lsn_sss_accumulate")
+    return dict(sums=sums, valid=valid, halves=halves, acc=acc)
+
+
+def cell_search_all_plan(pss_pos, N, W5=None):
+    """lsn_cell_search_all_plan (needs no GPU): the lags a cancellation at pss_pos changes -> dict(n_lo, n_lag, runs=[(lo, len), ...])"""
+    pl = CellSearchAllPlan()
+    rc = lib().lsn_cell_search_all_plan(int(pss_pos), int(N), int(75 * N if W5 is None else W5), C.byref(pl))
+    if rc != LSN_SUCCESS:
+        raise ValueError("lsn_cell_search_all_plan refused (pss_pos %d, N %d)" % (pss_pos, N))
+    return dict(n_lo=int(pl.n_lo), n_lag=int(pl.n_lag), runs=[(int(pl.run_lo[i]), int(pl.run_len[i])) for i in range(pl.nof_runs)])
+
+
+def cell_search_all_decide(round, peak, sum, W5, acc, nof_periods=8, threshold=20.0, threshold_next=0.0, sss_ratio_min=0.0, shared_pss_ratio=0.0, max_cells=0):
+    """lsn_cell_search_all_decide (needs no GPU): the rule of one round on its statistics; acc: [2, 336] accumulated powers -> CellSearchAllDecision"""
+    import numpy as np
+    acc = np.ascontiguousarray(acc, dtype=np.float32)
+    if acc.shape != (2, 336):
+        raise ValueError("acc: [2, 336]")
+    cfg = CellSearchAllCfg(int(nof_periods), -1, float(threshold), float(threshold_next), float(sss_ratio_min), float(shared_pss_ratio), int(max_cells))
+    out = CellSearchAllDecision()
+    rc = lib().lsn_cell_search_all_decide(C.byref(cfg), int(round), float(peak), float(sum), int(W5), acc.ctypes.data, C.byref(out))
+    if rc != LSN_SUCCESS:
+        raise ValueError("lsn_cell_search_all_decide refused: %d" % rc)
+    return out
 
 
 def clock_cfg(nof_prb, search, max_ppm=200.0, rates=RATES_3GPP, max_periods=0):
@@ -1784,6 +1886,14 @@ def carrier_channel(iq, rate_in, center_offset_hz, n_out=None, first_sample=0, f
     out = np.zeros((nant, n_out), dtype=np.complex64)
     _check(lib().lsn_carrier_channel(device, iq.ctypes.data, 0, n_in, C.byref(cfg), out.ctypes.data, 0, n_out), "lsn_carrier_channel")
     return out
+
+
+def carrier_cells(head, sample_rate, carrier_hz, antenna=0, sample_format=FILE_CF32, sample_scale=0.0, device=0, **kw):
+    """every cell of one carrier of a wideband recording's head: carrier_channel (the 1.92 MS/s channel of the carrier carrier_hz off the centre) followed by
+    cell_search_all at 6 resource blocks on one antenna of it; kw: cell_search_all's.  pss_pos and sf_start count samples of the 1.92 MS/s channel, as
+    CarrierResult.search's do.  carrier_scan itself reports one cell per carrier."""
+    ch = carrier_channel(head, sample_rate, carrier_hz, sample_format=sample_format, sample_scale=sample_scale, device=device)
+    return cell_search_all(ch[int(antenna)], 6, device=device, **kw)
 
 
 def carrier_mib(channel, search, max_batch=1, device=0):

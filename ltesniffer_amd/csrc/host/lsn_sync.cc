@@ -27,7 +27,7 @@ struct SyncFin {  // LsnSyncFin of stage_sync.hip
 };
 
 // 36.211 6.11.1.1: d_u(n), the length-63 Zadoff-Chu sequence of root 25 / 29 / 34 without its middle element
-static void pss_sequence(uint32_t n_id_2, cf32* d)
+void pss_sequence(uint32_t n_id_2, cf32* d)  // also lsn_sync_all.cc
 {
   static const int kRoot[3] = {25, 29, 34};
   for (int n = 0; n < 62; n++) {
@@ -74,7 +74,7 @@ static void pss_replica(uint32_t n_id_2, uint32_t N, cf32* p)
 }
 
 // 36.211 6.11.2.1: all 168 x 2 SSS sequences of one N_id_2, row h = 2 N_id_1 + (subframe 5)
-static void sss_table(uint32_t n_id_2, int8_t* out /* [336][62] */)
+void sss_table(uint32_t n_id_2, int8_t* out /* [336][62] */)  // also lsn_sync_all.cc
 {
   int s[31], c[31], z[31];
   for (int i = 0; i < 5; i++) s[i] = c[i] = z[i] = (i == 4);
@@ -100,8 +100,9 @@ static void sss_table(uint32_t n_id_2, int8_t* out /* [336][62] */)
   }
 }
 
-int cell_search(int device, const cf32* iq, bool on_device, uint64_t nsamples, uint32_t nof_prb, int rates, const lsn_cell_search_cfg_t& cfg,
-                lsn_cell_search_t& out, float* corr_out)
+// d_corr_keep: optional device buffer [nroots][75 N] that receives the correlation instead of a buffer of this call's own (lsn_sync_all.cc goes on from it)
+int cell_search_keep(int device, const cf32* iq, bool on_device, uint64_t nsamples, uint32_t nof_prb, int rates, const lsn_cell_search_cfg_t& cfg,
+                     lsn_cell_search_t& out, float* corr_out, float* d_corr_keep)
 {
   std::memset(&out, 0, sizeof out);
   const uint32_t N = symbol_size(nof_prb, rates);  // 0 for an unknown bandwidth or sampling mode: refused below
@@ -126,7 +127,7 @@ int cell_search(int device, const cf32* iq, bool on_device, uint64_t nsamples, u
     d_x = dx;
   }
   cf32* d_p = bp.alloc<cf32>(rep.size());
-  float* d_c = bc.alloc<float>((size_t)nroots * W5);
+  float* d_c = d_corr_keep ? d_corr_keep : bc.alloc<float>((size_t)nroots * W5);
   HIP_CHECK(hipMemcpyAsync(d_p, rep.data(), rep.size() * sizeof(cf32), hipMemcpyHostToDevice, st));
   lsn_launch_pss_corr(d_x, d_p, N, W5, P, nroots, d_c, st);
   std::vector<float> C((size_t)nroots * W5);
@@ -217,6 +218,12 @@ int cell_search(int device, const cf32* iq, bool on_device, uint64_t nsamples, u
     }
   }
   return out.found ? 1 : 0;
+}
+
+int cell_search(int device, const cf32* iq, bool on_device, uint64_t nsamples, uint32_t nof_prb, int rates, const lsn_cell_search_cfg_t& cfg,
+                lsn_cell_search_t& out, float* corr_out)
+{
+  return cell_search_keep(device, iq, on_device, nsamples, nof_prb, rates, cfg, out, corr_out, nullptr);
 }
 
 }  // namespace lsn
