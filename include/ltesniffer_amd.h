@@ -387,9 +387,11 @@ int lsn_phy_prepare_file(lsn_phy_t* phy, uint32_t nof_antennas);
  * doubles, so a recording whose clock is off by a KNOWN amount replays correctly when the true rate is given (open loop: nothing tracks;
  * lsn_clock_estimate / lsn_file_clock_estimate below MEASURE that amount ahead of the replay).
  * Filter: Kaiser-windowed sinc, cut-off min(rate_in, rate_out) / 2, 80 dB design attenuation, pass band |f| <= passband_hz, stop band from
- * min(rate_in, rate_out) - passband_hz; the number of taps follows from the width between the two.  Refused (LSN_ERROR_INVALID_INPUTS): rate_in >
- * 4 rate_out, a pass band the lower rate cannot carry with at most 192 taps (min(rate_in, rate_out) below about 2.06 passband_hz when up-sampling),
- * a struct_size the library does not know, rates that are zero, negative or not finite.
+ * min(rate_in, rate_out) - passband_hz; the number of taps follows from the width between the two.  Accepted: rate_in <= 4 rate_out with at most 192
+ * taps (a pass band the lower rate cannot carry with them - min(rate_in, rate_out) below about 2.06 passband_hz when up-sampling - is refused), and 4 rate_out <
+ * rate_in <= 32 rate_out with rate_in <= 122.88e6, rate_out >= 3.84e6 and at most 768 taps: every cell of 15 resource blocks or more out of a recording of up
+ * to 122.88 MS/s (a 1.92 MS/s output - the 6-PRB cell - stays refused above ratio 4).  Refused (LSN_ERROR_INVALID_INPUTS): everything
+ * else, a struct_size the library does not know, rates that are zero, negative or not finite.
  *
  * A cell that is not at the centre of the recording (offset-tuned capture, one carrier of a wideband capture): center_offset_hz is its carrier relative
  * to the recording's centre.  Input sample n (its index in the RECORDING) is multiplied by exp(-2 pi j Phi(n) / 2^64) before the filter sees it, Phi(n) =

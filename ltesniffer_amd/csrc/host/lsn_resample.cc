@@ -18,7 +18,7 @@ namespace lsn {
 
 static constexpr double kAtten = 80.0;                          // design attenuation A of the Kaiser window, dB
 static constexpr double kBeta = 0.1102 * (kAtten - 8.7);        // Kaiser's beta for A > 50
-static constexpr uint32_t kPhases = 512, kRun = 512;  // kRun = LSN_RS_RUN of the kernel
+static constexpr uint32_t kPhases = 512;
 
 static double bessel_i0(double x)
 {
@@ -52,7 +52,11 @@ int ResamplePlan::init(double rate_in, double rate_out, double passband_hz, uint
   if (!(rate_in > 0.0 && rate_in < 1e12) || !(rate_out > 0.0 && rate_out < 1e12)) return LSN_ERROR_INVALID_INPUTS;
   if (!(first_frac >= 0.0 && first_frac < 1.0) || first_sample >= (1ull << 62)) return LSN_ERROR_INVALID_INPUTS;
   const double ratio = rate_in / rate_out;
-  if (!(ratio <= max_ratio && ratio >= 1.0 / 65536.0)) return LSN_ERROR_INVALID_INPUTS;
+  if (!(ratio >= 1.0 / 65536.0)) return LSN_ERROR_INVALID_INPUTS;
+  if (!(ratio <= max_ratio)) {   // the wide-ratio run (accepted range)
+    if (!(ratio <= kWideMaxRatio && rate_in <= kWideMaxRateIn && rate_out >= kWideMinRateOut)) return LSN_ERROR_INVALID_INPUTS;
+    max_taps = kWideMaxTaps;
+  }
   const double lo_rate = std::min(rate_in, rate_out), rho = std::max(1.0, ratio);
   if (passband_hz == 0.0) passband_hz = 0.44 * lo_rate;
   if (!(passband_hz > 0.0)) return LSN_ERROR_INVALID_INPUTS;
@@ -76,7 +80,9 @@ int ResamplePlan::init(double rate_in, double rate_out, double passband_hz, uint
     nco.resize((4096 + 1024) * 2);
     lsn_nco_tables((cf32*)nco.data(), (cf32*)nco.data() + 4096);
   }
-  span = (uint32_t)(((u128)kRun * step) >> 64) + taps + 2;
+  grp = groupOf(step);
+  run = runOf(grp);
+  span = spanAt(step);
   // bank: H[p][j] = h(j - T/2 + 1 - p / 512), h(t) = sinc(t / rho) / rho * I0(beta sqrt(1 - (2 t / T)^2)) / I0(beta)
   const double i0b = bessel_i0(kBeta), half = 0.5 * (double)taps;
   auto h = [&](double t) {

@@ -136,7 +136,7 @@ void TrackCell::enter()
   if (max_subframes && sf0 + nsf > max_subframes) nsf = sf0 < max_subframes ? (uint32_t)(max_subframes - sf0) : 0;
   base = b2;
   step = (u128)((__int128)rs->step + delta);
-  span = (uint32_t)(((u128)512 * step) >> 64) + rs->taps + 2;   // ResamplePlan::init's rule (512 = LSN_RS_RUN, outputs of one run) at this segment's step
+  span = rs->spanAt(step);   // ResamplePlan::init's rule at this segment's step; the run length and the lanes per output stay the plan's
   if (span < rs->span) span = rs->span;
   if (acq && enabled && !search.active && loop.invalid_run >= acq_after) {   // a search of this segment is due
     search.active = true; search.h = h; search.base = base; search.step = step; search.span = span;

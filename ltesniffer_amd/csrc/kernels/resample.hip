@@ -150,15 +150,145 @@ __global__ __launch_bounds__(256) void k_resample_ring(const LsnResampleCellsArg
   LSN_RESAMPLE_RUN(A.nco != nullptr, n & (int64_t)A.ring_mask)
 }
 
+// ---- ratios above 4: the wide-ratio run ----
+//
+// Above ratio 4 one lane per output strides the lanes' LDS reads by the ratio (a 32-way conflict at ratio 32) and a run of 512 outputs no longer fits LDS.  Here
+// GRP lanes (8, 16 or 32: the smallest power of two >= the plan's NOMINAL ratio, which is at most 32 - fixed when the plan is made, never the launch's or a
+// tracked segment's choice) share one output: lane q of a group sums taps j = q, q + GRP, q + 2 GRP, ... (j < T; T is no multiple of GRP in general) in ascending j
+// into its own accumulator, and the GRP partial sums are added by an xor butterfly in the fixed order GRP/2 .. 1, after which every lane of the group holds the
+// same bits.  An output is therefore still a function of (input samples, configuration, m) alone: which taps meet in which accumulator, and in what order the
+// accumulators are added, depends on j, T and GRP and on nothing else.  In one step of the tap loop the lanes of a group read GRP consecutive float2 of LDS
+// (one ds_read_b64 each) and GRP consecutive float2 (H, dH) of the bank row; neighbouring groups start floor-of-ratio float2 apart, and because GRP >= ratio
+// the 32 lanes of a half wavefront stay inside 32 consecutive float2 = the 64 banks of ds_read_b64 once (overlapping groups read the SAME addresses:
+// broadcast).  A workgroup runs W.run / (256 / GRP) = 16 rounds of 256 / GRP outputs over one staged span of floor(run * D) + T + 2 <= 4096 + 770 samples.
+// The staging loop is LSN_RESAMPLE_RUN's, to the expression; so are the position arithmetic, c_j = fma(f, dH, H) and the one fma per product.
+struct LsnResampleWideArgs {
+  LsnResampleArgs a;
+  uint32_t grp, run;     // lanes per output (8, 16, 32) and outputs per workgroup (4096 / grp)
+};
+static_assert(sizeof(LsnResampleWideArgs) == 136, "eight of them are one kernel argument block");
+
+#define LSN_RESAMPLE_WIDE_RUN(MIXCOND, SRCSAMPLE) \
+  const uint32_t a = blockIdx.y, half = A.taps / 2;                                                                                                                     \
+  const uint64_t i0 = (uint64_t)blockIdx.x * W.run;                                                                                                                     \
+  /* position of the run's first output: base + i0 * D */                                                                                                               \
+  uint64_t lo = i0 * A.d_lo, hi = __umul64hi(i0, A.d_lo) + i0 * (uint64_t)A.d_hi;                                                                                       \
+  lo += A.base_lo;                                                                                                                                                      \
+  hi += A.base_hi + (lo < A.base_lo ? 1u : 0u);                                                                                                                         \
+  const int64_t n_lo = (int64_t)hi - (int64_t)half + 1;  /* input sample staged at rs_x[0] */                                                                           \
+  for (uint32_t s = threadIdx.x; s < A.span; s += 256) {                                                                                                                \
+    const int64_t n = n_lo + (int64_t)s, k = n - A.buf_base;                                                                                                            \
+    float2 x = make_float2(0.0f, 0.0f);                                                                                                                                 \
+    if (n >= 0 && k >= 0 && (uint64_t)k < A.buf_len) {                                                                                                                  \
+      const size_t src = (size_t)(SRCSAMPLE) * A.nant + a;                                                                                                              \
+      if (FMT == 1) {                                                                                                                                                   \
+        const short2 q = ((const short2*)A.raw)[src];                                                                                                                   \
+        x.x = (float)q.x * A.scale; x.y = (float)q.y * A.scale;                                                                                                         \
+      } else if (FMT == 2) {                                                                                                                                            \
+        const char2 q = ((const char2*)A.raw)[src];                                                                                                                     \
+        x.x = (float)q.x * A.scale; x.y = (float)q.y * A.scale;                                                                                                         \
+      } else {                                                                                                                                                          \
+        x = ((const float2*)A.raw)[src];                                                                                                                                \
+      }                                                                                                                                                                 \
+      if (MIXCOND) {                                                                                                                                                    \
+        const uint64_t ph = (uint64_t)n * A.w;  /* low 64 bits of n W */                                                                                                \
+        const cf32 e = cmul(A.nco[ph >> 52], A.nco[4096u + (uint32_t)((ph >> 42) & 1023u)]);                                                                            \
+        cf32 v; v.r = x.x; v.i = x.y;                                                                                                                                   \
+        v = cmulconj(v, e);                                                                                                                                             \
+        x.x = v.r; x.y = v.i;                                                                                                                                           \
+      }                                                                                                                                                                 \
+    }                                                                                                                                                                   \
+    rs_x[s] = x;                                                                                                                                                        \
+  }                                                                                                                                                                     \
+  __syncthreads();                                                                                                                                                      \
+  const uint32_t per = 256u / W.grp, gi = threadIdx.x / W.grp, gq = threadIdx.x & (W.grp - 1u);  /* outputs per round; this lane's output in it and lane in its group */ \
+  for (uint32_t r = 0; r * per < W.run; r++) {                                                                                                                          \
+    if (i0 + r * per >= A.n_out) break;  /* uniform over the workgroup: no output of this or a later round exists */                                                    \
+    const uint64_t i = i0 + r * per + gi;                                                                                                                               \
+    uint64_t plo = i * A.d_lo, phi = __umul64hi(i, A.d_lo) + i * (uint64_t)A.d_hi;                                                                                      \
+    plo += A.base_lo;                                                                                                                                                   \
+    phi += A.base_hi + (plo < A.base_lo ? 1u : 0u);                                                                                                                     \
+    const uint32_t s0 = (uint32_t)((int64_t)phi - (int64_t)half + 1 - n_lo);  /* first of the T staged samples of this output */                                        \
+    const uint32_t p = (uint32_t)(plo >> 55);  /* 9 bits of phase */                                                                                                    \
+    const float f = (float)(uint32_t)((plo >> 31) & 0xFFFFFFu) * 0x1p-24f;  /* 24 bits inside the phase, exact */                                                       \
+    /* s0 + T > span cannot happen for an output that exists (the host sizes span); the test keeps the LDS reads inside.  Every lane of a group agrees on it */         \
+    const bool live = i < A.n_out && s0 <= A.span && s0 + A.taps <= A.span;                                                                                             \
+    float yr = 0.0f, yi = 0.0f;                                                                                                                                         \
+    if (live) {                                                                                                                                                         \
+      const float2* row = A.bank + (size_t)p * A.taps;                                                                                                                  \
+      const float2* x = rs_x + s0;                                                                                                                                      \
+      uint32_t j = gq;                                                                                                                                                  \
+      /* four taps of this lane at a time while all four exist: eight loads in flight, the same fmas in the same (ascending j) order as the loop behind it */           \
+      for (; j + 3u * W.grp < A.taps; j += 4u * W.grp) {                                                                                                                \
+        const float2 ca = row[j], cb = row[j + W.grp], cc = row[j + 2u * W.grp], cd = row[j + 3u * W.grp];                                                              \
+        const float2 xa = x[j], xb = x[j + W.grp], xc = x[j + 2u * W.grp], xd = x[j + 3u * W.grp];                                                                      \
+        const float ja = __builtin_fmaf(f, ca.y, ca.x), jb = __builtin_fmaf(f, cb.y, cb.x), jc = __builtin_fmaf(f, cc.y, cc.x), jd = __builtin_fmaf(f, cd.y, cd.x);     \
+        yr = __builtin_fmaf(ja, xa.x, yr); yi = __builtin_fmaf(ja, xa.y, yi);                                                                                           \
+        yr = __builtin_fmaf(jb, xb.x, yr); yi = __builtin_fmaf(jb, xb.y, yi);                                                                                           \
+        yr = __builtin_fmaf(jc, xc.x, yr); yi = __builtin_fmaf(jc, xc.y, yi);                                                                                           \
+        yr = __builtin_fmaf(jd, xd.x, yr); yi = __builtin_fmaf(jd, xd.y, yi);                                                                                           \
+      }                                                                                                                                                                 \
+      for (; j < A.taps; j += W.grp) {                                                                                                                                  \
+        const float2 c = row[j], xj = x[j];                                                                                                                             \
+        const float cj = __builtin_fmaf(f, c.y, c.x);                                                                                                                   \
+        yr = __builtin_fmaf(cj, xj.x, yr); yi = __builtin_fmaf(cj, xj.y, yi);                                                                                           \
+      }                                                                                                                                                                 \
+    }                                                                                                                                                                   \
+    /* every lane takes part: a lane's partners are the lanes of its own group (m < grp), live or not together */                                                       \
+    for (uint32_t m = W.grp >> 1; m; m >>= 1) {                                                                                                                         \
+      yr += __shfl_xor(yr, (int)m); yi += __shfl_xor(yi, (int)m);                                                                                                       \
+    }                                                                                                                                                                   \
+    if (live && gq == 0) {                                                                                                                                              \
+      const uint32_t q = (uint32_t)i + A.sf_off, sf = q / A.sflen, n = q - sf * A.sflen;  /* the launcher keeps n_out + sf_off below 2^32 */                            \
+      cf32 y; y.r = yr; y.i = yi;                                                                                                                                       \
+      if (A.rot) y = cmul(y, A.rot[n]);                                                                                                                                 \
+      A.out[((size_t)sf * A.nant + a) * A.sflen + n] = y;                                                                                                               \
+    }                                                                                                                                                                   \
+  }
+
+template <int FMT, bool MIX>
+__global__ __launch_bounds__(256) void k_resample_wide(const LsnResampleWideArgs W)
+{
+  extern __shared__ float2 rs_x[];
+  const LsnResampleArgs& A = W.a;
+  LSN_RESAMPLE_WIDE_RUN(MIX, k)
+}
+
+struct LsnResampleWideCellsArgs { LsnResampleWideArgs c[LSN_RS_MAX_CELLS]; };
+
+// the wide-ratio cells of a launch of lsn_launch_resample_cells: grid, early exit and "a cell mixes when it has NCO tables" as k_resample_cells
+template <int FMT>
+__global__ __launch_bounds__(256) void k_resample_cells_wide(const LsnResampleWideCellsArgs P)
+{
+  extern __shared__ float2 rs_x[];
+  const LsnResampleWideArgs& W = P.c[blockIdx.z];
+  const LsnResampleArgs& A = W.a;
+  if ((uint64_t)blockIdx.x * W.run >= A.n_out) return;
+  LSN_RESAMPLE_WIDE_RUN(A.nco != nullptr, k)
+}
+
+// ... and out of a ring, as k_resample_ring
+template <int FMT>
+__global__ __launch_bounds__(256) void k_resample_ring_wide(const LsnResampleWideCellsArgs P)
+{
+  extern __shared__ float2 rs_x[];
+  const LsnResampleWideArgs& W = P.c[blockIdx.z];
+  const LsnResampleArgs& A = W.a;
+  if ((uint64_t)blockIdx.x * W.run >= A.n_out) return;
+  LSN_RESAMPLE_WIDE_RUN(A.nco != nullptr, n & (int64_t)A.ring_mask)
+}
+
 // ---- host side: one function forms a run's arguments, two launchers (lsn_resample_launch.h) ----
 
-// the arguments of cell k's runs out of src, checked: span = samples a run of LSN_RS_RUN outputs needs (host: lsn_resample.cc), n_out + sf_off below 2^32 (the
-// kernel's row arithmetic).  -> the cell's number of runs.  `kernel` names the launch in a refusal
+// the arguments of cell k's runs out of src, checked: span = samples a run needs (host: lsn_resample.cc), n_out + sf_off below 2^32 (the kernel's row arithmetic); a
+// run is LSN_RS_RUN outputs, or k.run of the wide-ratio geometry (k.grp = 8, 16 or 32 lanes per output, k.run a whole number of rounds of 256 / k.grp).
+// -> the cell's number of runs.  `kernel` names the launch in a refusal
 static uint64_t resample_args(const char* kernel, const LsnResampleSource& src, const LsnResampleCell& k, LsnResampleArgs& A)
 {
   if (k.taps < 2 || (k.taps & 1) || k.span < k.taps || (size_t)k.span * sizeof(float2) > 64 * 1024 || src.buf_base < 0 || !k.sflen)
     throw std::runtime_error(std::string(kernel) + ": bad geometry");
-  const uint64_t runs = (k.n_out + LSN_RS_RUN - 1) / LSN_RS_RUN;
+  if (k.grp && ((k.grp != 8 && k.grp != 16 && k.grp != 32) || !k.run || k.run % (256u / k.grp))) throw std::runtime_error(std::string(kernel) + ": bad geometry");
+  const uint64_t run = k.grp ? k.run : LSN_RS_RUN, runs = (k.n_out + run - 1) / run;
   if (runs > 0x7FFFFFFFull || k.n_out + k.sf_off > 0xFFFFFFFFull) throw std::runtime_error(std::string(kernel) + ": launch too long");
   A.raw = src.raw; A.buf_base = src.buf_base; A.buf_len = src.buf_len; A.base_hi = k.base_hi; A.base_lo = k.base_lo; A.d_lo = k.d_lo; A.d_hi = k.d_hi; A.taps = k.taps; A.span = k.span;
   A.nant = src.nant; A.sflen = k.sflen; A.sf_off = k.sf_off; A.n_out = k.n_out; A.scale = src.scale; A.bank = (const float2*)k.bank; A.rot = k.rot; A.out = k.out;
@@ -175,20 +305,31 @@ static uint64_t resample_args(const char* kernel, const LsnResampleSource& src, 
   } while (0)
 #define LSN_RS_COMMA ,
 
-// one cell out of a linear buffer.  cell.nco != null: the mixing instantiations with tuning word w; null: the plain ones, as before the mixer existed
+// one cell out of a linear buffer.  cell.nco != null: the mixing instantiations with tuning word w; null: the plain ones, as before the mixer existed.  cell.grp != 0:
+// the wide-ratio kernel
 void lsn_launch_resample(const LsnResampleSource& src, const LsnResampleCell& cell, hipStream_t s)
 {
   if (!cell.n_out) return;
   if (src.ring_samples) throw std::runtime_error("k_resample: reads a linear buffer");
+  const size_t lds = (size_t)cell.span * sizeof(float2);
+  if (cell.grp) {
+    LsnResampleWideArgs W;
+    memset(&W, 0, sizeof(W));
+    const dim3 g((uint32_t)resample_args("k_resample_wide", src, cell, W.a), src.nant);
+    W.grp = cell.grp; W.run = cell.run;
+    if (cell.nco) LSN_RS_LAUNCH_FMT(k_resample_wide, LSN_RS_COMMA true, src.fmt, g, lds, s, W);
+    else LSN_RS_LAUNCH_FMT(k_resample_wide, LSN_RS_COMMA false, src.fmt, g, lds, s, W);
+    return;
+  }
   LsnResampleArgs A;
   const dim3 g((uint32_t)resample_args("k_resample", src, cell, A), src.nant);
-  const size_t lds = (size_t)cell.span * sizeof(float2);
   if (cell.nco) LSN_RS_LAUNCH_FMT(k_resample, LSN_RS_COMMA true, src.fmt, g, lds, s, A);
   else LSN_RS_LAUNCH_FMT(k_resample, LSN_RS_COMMA false, src.fmt, g, lds, s, A);
 }
 
 // the cells of one launch: the source is the recording's and shared, everything else is the cell's own.  A cell with n_out = 0 takes no part; no launch when
-// none does.  Out of a ring: ring_samples a power of two (at most 2^32) that holds the window
+// none does.  Out of a ring: ring_samples a power of two (at most 2^32) that holds the window.  Cells of the two run geometries go to two launches on the same
+// stream - the cells of ratio up to 4 to the kernel they always went to, with the arguments they always had; the wide-ratio cells to its _wide twin
 void lsn_launch_resample_cells(const LsnResampleSource& src, const LsnResampleCell* cells, uint32_t n_cells, hipStream_t s)
 {
   const uint64_t rn = src.ring_samples;
@@ -196,18 +337,33 @@ void lsn_launch_resample_cells(const LsnResampleSource& src, const LsnResampleCe
   if (rn && ((rn & (rn - 1)) || rn > (1ull << 32) || src.buf_len > rn)) throw std::runtime_error("k_resample_ring: bad ring");
   if (n_cells > LSN_RS_MAX_CELLS || src.buf_base < 0) throw std::runtime_error(std::string(kernel) + ": bad geometry");
   LsnResampleCellsArgs P;
+  LsnResampleWideCellsArgs Q;
   memset(&P, 0, sizeof(P));
-  uint32_t n = 0, span = 0;
-  uint64_t runs = 0;
+  memset(&Q, 0, sizeof(Q));
+  uint32_t n = 0, span = 0, nw = 0, span_w = 0;
+  uint64_t runs = 0, runs_w = 0;
   for (uint32_t c = 0; c < n_cells; c++) {
     if (!cells[c].n_out) continue;
-    runs = std::max(runs, resample_args(kernel, src, cells[c], P.c[n++]));
-    span = std::max(span, cells[c].span);
+    if (cells[c].grp) {
+      LsnResampleWideArgs& W = Q.c[nw++];
+      runs_w = std::max(runs_w, resample_args(kernel, src, cells[c], W.a));
+      W.grp = cells[c].grp; W.run = cells[c].run;
+      span_w = std::max(span_w, cells[c].span);
+    } else {
+      runs = std::max(runs, resample_args(kernel, src, cells[c], P.c[n++]));
+      span = std::max(span, cells[c].span);
+    }
   }
-  if (!n) return;
-  const dim3 g((uint32_t)runs, src.nant, n);
-  const size_t lds = (size_t)span * sizeof(float2);
-  if (!rn) LSN_RS_LAUNCH_FMT(k_resample_cells, , src.fmt, g, lds, s, P);
-  else LSN_RS_LAUNCH_FMT(k_resample_ring, , src.fmt, g, lds, s, P);
+  if (n) {
+    const dim3 g((uint32_t)runs, src.nant, n);
+    const size_t lds = (size_t)span * sizeof(float2);
+    if (!rn) LSN_RS_LAUNCH_FMT(k_resample_cells, , src.fmt, g, lds, s, P);
+    else LSN_RS_LAUNCH_FMT(k_resample_ring, , src.fmt, g, lds, s, P);
+  }
+  if (nw) {
+    const dim3 g((uint32_t)runs_w, src.nant, nw);
+    const size_t lds = (size_t)span_w * sizeof(float2);
+    if (!rn) LSN_RS_LAUNCH_FMT(k_resample_cells_wide, , src.fmt, g, lds, s, Q);
+    else LSN_RS_LAUNCH_FMT(k_resample_ring_wide, , src.fmt, g, lds, s, Q);
+  }
 }
-
