@@ -1065,8 +1065,55 @@ int lsn_phy_pusch_decode(lsn_phy_t* phy, const void* ul_iq, int iq_on_device, ui
                          const lsn_pusch_grant_t* grants, uint32_t n_grants, lsn_pusch_result_t* results, uint8_t* payloads, size_t payload_cap);
 /* Read-only taps of the last lsn_phy_pusch_decode / lsn_phy_prach_detect call; returns the bytes written.  what = 0: uplink grid of subframe `index`,
  * 1: rate-matched LLRs of grant `index`, 2: PRACH correlation power of occasion `index`, 3: the code blocks of grant `index` in transport-block order, six
- * uint32 each (K, F, E, rv, ok, iters), 4: for the same blocks in the same order the K + 12 words the rate de-matcher handed to the turbo decoder. */
+ * uint32 each (K, F, E, rv, ok, iters), 4: for the same blocks in the same order the K + 12 words the rate de-matcher handed to the turbo decoder,
+ * 5: the private grid rows of grant `index` ([14 or 12 symbols][12 nof_prb] cf32) when the last lsn_phy_pusch_decode ran with lsn_phy_set_ul_timing mode 2:
+ * the grant's symbols cut again `shift` samples earlier, or a copy of the common rows when its shift is 0; LSN_ERROR_INVALID_INPUTS in the other modes. */
 long lsn_phy_tap_ul(lsn_phy_t* phy, int what, uint32_t index, void* out, size_t cap);
+
+/* ---- uplink arrival time ----
+ * A UE transmits its timing advance ahead of its own downlink, so at a sniffer that does not stand at the eNB its subframe arrives EARLY by
+ * (d_eNB-UE + d_eNB-sniffer - d_UE-sniffer) / c: between 0 and the UE's full timing advance, never late.  The cyclic prefix protects against late arrival
+ * only; an arrival a samples ahead of the common SC-FDMA window puts a samples of the next symbol into it (ISI floor about N / 2a) and a phase ramp of
+ * 2 pi a / N per carrier under the three-tap smoother of the channel estimate.  This is the reference's chest_res.ta_us ("DL-UL_delay" of its uplink table).
+ * mode 0 (the default): off - lsn_phy_pusch_decode and UL_MODE issue exactly the launches they issue without this call.
+ * mode 1: measure.  One more launch per decode call; per grant tau = arg(sum_n ls[n+1] conj(ls[n])) N / 2 pi over the least-squares estimates of both
+ *         reference-signal symbols, in samples at the cell's rate, positive = early.  Every other result is bit for bit that of mode 0.
+ * mode 2: measure and re-window.  shift = round(tau), clamped to [-late_max, +max_advance], 0 when |shift| < min_shift; a grant with a shift is demodulated
+ *         again with every symbol cut `shift` samples earlier, into grid rows of its own, and estimated, equalised and decoded from those; a grant with
+ *         shift 0 comes out bit for bit as in mode 0.  snr_db of lsn_pusch_result_t is that of the re-cut symbols.  Decided per grant on the device,
+ *         nothing is remembered between subframes.  In UL_MODE the uplink antenna of the chunk is the source.
+ * min_shift: 0 = N / 128 (at least 1).  max_advance: 0 = N / 4; at most N / 2.  late_max is the normal cyclic prefix, 144 N / 2048.
+ * The zero rule: a sample in front of the grant's own subframe, or behind its end, reads as zero in the second window, in every subframe - a result never
+ * depends on where a call or a chunk begins.  A shift above the first cyclic prefix (160 N / 2048) therefore costs the start of symbol 0.
+ * Limits: one arrival per grant, measured on that grant alone; a UE whose neighbours in frequency arrive at other times sees their leakage (the
+ * orthogonality is lost), which is not cancelled; PRACH and the downlink are untouched.
+ * Returns LSN_ERROR_INVALID_INPUTS for a null pointer, mode > 2, max_advance > N / 2 or min_shift > N / 2; LSN_ERROR before a cell is set and while
+ * submitted blocks are in flight (call lsn_phy_wait first).  Nothing changes on a refusal. */
+typedef struct { uint32_t mode, min_shift, max_advance; } lsn_ul_timing_cfg_t;
+#define LSN_TOA_FLAG_CLAMPED 1u   /* round(tau) lay outside [-late_max, +max_advance] */
+#define LSN_TOA_FLAG_BELOW 2u     /* |shift| < min_shift: shift = 0 */
+typedef struct {
+  uint32_t measured;  /* 1: the fields below are filled (a grant that was decoded in mode 1 / 2), 0: all zero */
+  float tau;          /* samples, positive = early */
+  int32_t shift;      /* the decision (also reported in mode 1, where nothing is moved) */
+  uint32_t flags;     /* LSN_TOA_FLAG_* */
+  float residual;     /* mode 2 with a sample source: tau measured again on the re-cut symbols; else 0 */
+  float toa_us;       /* the arrival in microseconds: (shift + residual) after a re-cut, else tau, times 1 / (15000 N) */
+  float confidence;   /* |z| / sum |ls|^2 */
+} lsn_pusch_timing_t;
+int lsn_phy_set_ul_timing(lsn_phy_t* phy, const lsn_ul_timing_cfg_t* cfg);
+/* per grant of the last lsn_phy_pusch_decode, in the caller's grant order: min(cap, n_grants) records are written, n_grants is returned */
+long lsn_phy_get_pusch_timing(lsn_phy_t* phy, lsn_pusch_timing_t* out, uint32_t cap);
+/* The decision without a GPU (what k_pusch_toa computes from tau): N = symbol length of the cell (128 .. 2048), cfg as for lsn_phy_set_ul_timing (mode
+ * is not read).  Ties of round() go to the even integer.  Returns LSN_SUCCESS, or LSN_ERROR_INVALID_INPUTS (null pointer, N out of range, max_advance or
+ * min_shift above N / 2). */
+int lsn_pusch_toa_decide(float tau, uint32_t N, const lsn_ul_timing_cfg_t* cfg, int32_t* shift, uint32_t* flags);
+/* UL_MODE only (else LSN_ERROR_INVALID_INPUTS): the row of the reference's uplink table for one RNTI (MCSTracking.cc:441-472) - modulation class, counted
+ * (active) and successful decodes, mean SNR and mean arrival ("DL-UL_delay") over the counted decodes.  Updated where update_statistic_ul is, behind the
+ * same SNR gate, with the values of the last attempt that ran; dropped with the RNTI's database entry.  In mode 0 the arrival fields are 0 and
+ * measured = 0.  Returns 1 when the RNTI has an entry (out filled), 0 when not.  Call between lsn_phy_wait and the next submit. */
+typedef struct { uint32_t mod, active, success; float mean_snr_db; uint32_t measured; float mean_toa_us, mean_toa_samples; } lsn_ul_ue_stats_t;
+int lsn_phy_get_ul_ue_stats(lsn_phy_t* phy, uint16_t rnti, lsn_ul_ue_stats_t* out);
 
 /* ---- uplink (PRACH) ----
  * lsn_phy_set_prach_config replaces PUSCH_Decoder::set_rach_config (UL_Sniffer_PUSCH.cc:640-653: srsran_prach_init,

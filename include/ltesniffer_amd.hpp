@@ -222,6 +222,16 @@ public:
     if (fromSib2) *fromSib2 = f != 0;
     return ok;
   }
+  // per-grant uplink arrival time (the reference's meas_ta_en / chest_res.ta_us, UL_Sniffer_PUSCH.cc:424): 0 off (default), 1 measure, 2 measure and
+  // demodulate a grant again in a window moved to where its signal is; thresholds in samples, 0 = N / 128 and N / 4 (lsn_phy_set_ul_timing)
+  bool setUlTiming(uint32_t mode, uint32_t minShift = 0, uint32_t maxAdvance = 0)
+  {
+    lsn_ul_timing_cfg_t t{mode, minShift, maxAdvance};
+    return lsn_phy_set_ul_timing(h, &t) == LSN_SUCCESS;
+  }
+  long getPuschTiming(lsn_pusch_timing_t* out, uint32_t cap) { return lsn_phy_get_pusch_timing(h, out, cap); }   // per grant of the last lsn_phy_pusch_decode
+  // the row of the reference's uplink table for one RNTI, "DL-UL_delay" included (MCSTracking.cc:441-472); UL_MODE only
+  bool getUlUeStats(uint16_t rnti, lsn_ul_ue_stats_t& s) { return lsn_phy_get_ul_ue_stats(h, rnti, &s) == 1; }
   bool setRachConfig(const lsn_prach_cfg_t& p) { return lsn_phy_set_prach_config(h, &p) == LSN_SUCCESS; }    // PUSCH_Decoder::set_rach_config
   void setPrachSink(lsn_prach_sink_t cb, void* user) { lsn_phy_set_prach_sink(h, cb, user); }               // work_prach's report
   // srsran_ue_mib_decode + srsran_pbch_mib_unpack on one subframe 0 (LTESniffer_Core.cc:386-391); true when a MIB was found

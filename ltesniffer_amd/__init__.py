@@ -35,7 +35,7 @@ EXPORTS = ["lsn_phy_create", "lsn_phy_destroy", "lsn_phy_set_cell", "lsn_phy_get
            "lsn_phy_get_perf", "lsn_kernel_name", "lsn_version", "lsn_pcap_open", "lsn_pcap_open_mem",
            "lsn_pcap_set_wall_clock", "lsn_pcap_write", "lsn_pcap_sink", "lsn_pcap_mem", "lsn_pcap_nof_records",
            "lsn_pcap_reset", "lsn_pcap_close", "lsn_phy_set_pcap_writer", "lsn_phy_set_api_mode", "lsn_phy_tracked_ul_modulation", "lsn_phy_set_ul_config", "lsn_phy_get_ul_config", "lsn_sib2_decode", "lsn_phy_pusch_decode",
-           "lsn_phy_tap_ul", "lsn_phy_set_prach_config", "lsn_phy_prach_detect", "lsn_phy_set_prach_sink", "lsn_prach_tti_opportunity", "lsn_phy_process_file", "lsn_phy_mib_decode", "lsn_phy_mib_decode_llr", "lsn_phy_submit_device", "lsn_phy_wait", "lsn_cell_search",
+           "lsn_phy_tap_ul", "lsn_phy_set_ul_timing", "lsn_phy_get_pusch_timing", "lsn_pusch_toa_decide", "lsn_phy_get_ul_ue_stats", "lsn_phy_set_prach_config", "lsn_phy_prach_detect", "lsn_phy_set_prach_sink", "lsn_prach_tti_opportunity", "lsn_phy_process_file", "lsn_phy_mib_decode", "lsn_phy_mib_decode_llr", "lsn_phy_submit_device", "lsn_phy_wait", "lsn_cell_search",
            "lsn_phy_set_shortcut_discovery", "lsn_phy_get_shortcut_discovery", "lsn_phy_set_histogram_threshold", "lsn_phy_print_stats",
            "lsn_phy_set_mcs_update_interval", "lsn_phy_update_mcs_database", "lsn_phy_nof_tracked_rnti", "lsn_worker_buffers_offset", "lsn_pcap_digest", "lsn_pcap_set_store", "lsn_pcap_set_digest_blocks", "lsn_pcap_block_digests", "lsn_phy_create_multi", "lsn_phy_nof_devices",
            "lsn_phy_set_cfo_correction", "lsn_phy_get_cfo_correction", "lsn_phy_set_candidate_pruning", "lsn_phy_set_stage_c_taps", "lsn_phy_prepare_file", "lsn_phy_get_meta_formats", "lsn_phy_nof_workers", "lsn_phy_worker",
@@ -380,6 +380,31 @@ class PuschResult(C.Structure):
     _fields_ = [("crc_ok", C.c_uint32), ("iterations", C.c_uint32), ("snr_db", C.c_float), ("payload_off", C.c_uint32)]
 
 
+class UlTimingCfg(C.Structure):
+    _fields_ = [("mode", C.c_uint32), ("min_shift", C.c_uint32), ("max_advance", C.c_uint32)]
+
+
+class PuschTiming(C.Structure):
+    _fields_ = [("measured", C.c_uint32), ("tau", C.c_float), ("shift", C.c_int32), ("flags", C.c_uint32), ("residual", C.c_float), ("toa_us", C.c_float),
+                ("confidence", C.c_float)]
+
+
+class UlUeStats(C.Structure):
+    _fields_ = [("mod", C.c_uint32), ("active", C.c_uint32), ("success", C.c_uint32), ("mean_snr_db", C.c_float), ("measured", C.c_uint32),
+                ("mean_toa_us", C.c_float), ("mean_toa_samples", C.c_float)]
+
+
+TOA_FLAG_CLAMPED, TOA_FLAG_BELOW = 1, 2
+
+
+def pusch_toa_decide(tau, N, min_shift=0, max_advance=0):
+    """the window decision of k_pusch_toa without a GPU -> (shift, flags); ValueError for what lsn_pusch_toa_decide refuses"""
+    cfg, shift, flags = UlTimingCfg(0, min_shift, max_advance), C.c_int32(0), C.c_uint32(0)
+    if lib().lsn_pusch_toa_decide(C.c_float(tau), N, C.byref(cfg), C.byref(shift), C.byref(flags)) != LSN_SUCCESS:
+        raise ValueError("lsn_pusch_toa_decide refused N = %r, min_shift = %r, max_advance = %r" % (N, min_shift, max_advance))
+    return shift.value, flags.value
+
+
 SINK_T = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(PduCtx), C.POINTER(C.c_uint8), C.c_uint32)
 
 _lib = None
@@ -497,6 +522,11 @@ def lib():
                                            C.c_void_p, C.c_size_t]
         L.lsn_phy_tap_ul.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_size_t]
         L.lsn_phy_tap_ul.restype = C.c_long
+        L.lsn_phy_set_ul_timing.argtypes = [C.c_void_p, C.POINTER(UlTimingCfg)]
+        L.lsn_phy_get_pusch_timing.argtypes = [C.c_void_p, C.POINTER(PuschTiming), C.c_uint32]
+        L.lsn_phy_get_pusch_timing.restype = C.c_long
+        L.lsn_pusch_toa_decide.argtypes = [C.c_float, C.c_uint32, C.POINTER(UlTimingCfg), C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]
+        L.lsn_phy_get_ul_ue_stats.argtypes = [C.c_void_p, C.c_uint16, C.POINTER(UlUeStats)]
         L.lsn_phy_submit_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
         L.lsn_phy_wait.argtypes = [C.c_void_p]
         L.lsn_phy_mib_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(Mib)]
@@ -903,6 +933,40 @@ class Phy:
         return [dict(crc_ok=int(res[i].crc_ok), iterations=int(res[i].iterations), snr_db=float(res[i].snr_db),
                      payload=bytes(pay[res[i].payload_off:res[i].payload_off + grants[i]["tbs"] // 8]) if res[i].crc_ok else b"")
                 for i in range(n)]
+
+    def setUlTiming(self, mode, min_shift=0, max_advance=0):
+        """per-grant uplink arrival time: 0 off (default), 1 measure, 2 measure and re-window; the thresholds in samples (0: N / 128 and N / 4).
+        -> the C return code (LSN_SUCCESS when accepted)"""
+        t = UlTimingCfg(mode, min_shift, max_advance)
+        return lib().lsn_phy_set_ul_timing(self._h, C.byref(t))
+
+    def pusch_timing(self):
+        """per grant of the last pusch_decode: list of dict(measured, tau, shift, flags, residual, toa_us, confidence)"""
+        n = lib().lsn_phy_get_pusch_timing(self._h, None, 0)
+        if n < 0:
+            raise RuntimeError("get_pusch_timing failed: %d" % n)
+        arr = (PuschTiming * max(1, n))()
+        lib().lsn_phy_get_pusch_timing(self._h, arr, n)
+        return [dict(measured=int(a.measured), tau=float(a.tau), shift=int(a.shift), flags=int(a.flags), residual=float(a.residual), toa_us=float(a.toa_us),
+                     confidence=float(a.confidence)) for a in arr[:n]]
+
+    def ul_ue_stats(self, rnti):
+        """UL_MODE: the reference's uplink table row of one RNTI -> dict, or None without an entry; RuntimeError outside UL_MODE"""
+        s = UlUeStats()
+        r = lib().lsn_phy_get_ul_ue_stats(self._h, rnti, C.byref(s))
+        if r < 0:
+            raise RuntimeError("get_ul_ue_stats failed: %d" % r)
+        return dict(mod=int(s.mod), active=int(s.active), success=int(s.success), mean_snr_db=float(s.mean_snr_db), measured=int(s.measured),
+                    mean_toa_us=float(s.mean_toa_us), mean_toa_samples=float(s.mean_toa_samples)) if r == 1 else None
+
+    def tap_ul_priv_grid(self, grant_index):
+        """mode 2 of setUlTiming: the private grid rows of grant `grant_index` of the last pusch_decode -> complex64 [14 or 12, 12 nof_prb]"""
+        nre = 12 * self.cell.nof_prb
+        buf = np.zeros(14 * nre, dtype=np.complex64)
+        nb = lib().lsn_phy_tap_ul(self._h, 5, grant_index, buf.ctypes.data, buf.nbytes)
+        if nb < 0:
+            raise RuntimeError("tap_ul failed: %d" % nb)
+        return buf[: nb // 8].reshape(-1, nre)
 
     def tap_ul_grid(self, sf):
         nre = 12 * self.cell.nof_prb

@@ -876,6 +876,31 @@ long lsn_phy_tap_ul(lsn_phy_t* phy, int what, uint32_t index, void* out, size_t 
   if (what == 2) return phy->engine->tapPrach(index, out, cap);
   return phy->engine->tapUl(what, index, out, cap);
 }
+int lsn_phy_set_ul_timing(lsn_phy_t* phy, const lsn_ul_timing_cfg_t* cfg)
+{
+  if (!phy || !cfg) return LSN_ERROR_INVALID_INPUTS;
+  return phy->engine->setUlTiming(*cfg);
+}
+long lsn_phy_get_pusch_timing(lsn_phy_t* phy, lsn_pusch_timing_t* out, uint32_t cap)
+{
+  if (!phy || (!out && cap)) return LSN_ERROR_INVALID_INPUTS;
+  return phy->engine->getPuschTiming(out, cap);
+}
+int lsn_pusch_toa_decide(float tau, uint32_t N, const lsn_ul_timing_cfg_t* cfg, int32_t* shift, uint32_t* flags)
+{
+  if (!cfg || !shift || !flags || N < 128 || N > 2048 || cfg->max_advance > N / 2 || cfg->min_shift > N / 2) return LSN_ERROR_INVALID_INPUTS;
+  LsnUlToaCfg c;   // the defaults as Engine::ulToaCfg resolves them
+  c.min_shift = cfg->min_shift ? (int32_t)cfg->min_shift : (N / 128 ? (int32_t)(N / 128) : 1);
+  c.max_advance = cfg->max_advance ? (int32_t)cfg->max_advance : (int32_t)(N / 4);
+  c.late_max = (int32_t)(144 * N / 2048);
+  *shift = lsn_toa_decide(tau, c, flags);
+  return LSN_SUCCESS;
+}
+int lsn_phy_get_ul_ue_stats(lsn_phy_t* phy, uint16_t rnti, lsn_ul_ue_stats_t* out)
+{
+  if (!phy || !out) return LSN_ERROR_INVALID_INPUTS;
+  return phy->engine->getUlUeStats(rnti, out);
+}
 int lsn_phy_set_prach_config(lsn_phy_t* phy, const lsn_prach_cfg_t* cfg)
 {
   if (!phy || !cfg) return LSN_ERROR_INVALID_INPUTS;

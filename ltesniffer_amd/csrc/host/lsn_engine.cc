@@ -230,6 +230,7 @@ int Engine::setCell(const lsn_cell_t& c)
       uploadUlStatic();
       std::lock_guard<std::mutex> lk(mcs_mtx);  // uplink tracking database (shared by the engines of a capture): sized here, never lazily on the commit thread
       ulmod.assign(65536, 0); ul_uecfg.assign(65536, UeSpecConfig()); ul_time.assign(65536, 0); ul_active.assign(65536, 0); ul_success.assign(65536, 0);
+      ul_snr_sum.assign(65536, 0.0f); ul_toa_sum.assign(65536, 0.0f); ul_toa_n.assign(65536, 0);
       ulmod_count = 0;
     }
     // hipMemset on device memory (dalloc) is asynchronous to the host and runs on the null stream, which the engine's non-blocking streams do not

@@ -11,6 +11,7 @@
 #pragma once
 #include "../../../include/ltesniffer_amd.h"
 #include "../kernels/lsn_dev.h"
+#include "../kernels/lsn_ul_toa.h"
 #include "lsn_commit.h"
 #include "lsn_hip.h"
 #include "lsn_rates.h"
@@ -213,6 +214,8 @@ struct SharedSeq {
   std::vector<uint8_t> ulmod; uint32_t ulmod_count = 0;
   std::vector<UeSpecConfig> ul_uecfg;
   std::vector<uint32_t> ul_time, ul_active, ul_success;
+  std::vector<float> ul_snr_sum, ul_toa_sum; std::vector<uint32_t> ul_toa_n;  // lsn_phy_get_ul_ue_stats: sums over the counted decodes (dB; samples) and how many carried an arrival
+  float last_ul_toa = 0.0f; bool last_ul_toa_ok = false;                      // arrival of the last attempt that ran, as last_ul_snr
   float last_ul_snr = 0.0f;
   lsn_ul_cfg_t ul_cfg{}; bool ul_set = false;
   bool sib2_learned = false; Sib2Config sib2;
@@ -337,6 +340,9 @@ public:
   int puschDecode(const void* ul_iq, bool on_device, uint32_t nsf, uint32_t start_tti, const lsn_pusch_grant_t* grants, uint32_t ngrants,
                   lsn_pusch_result_t* results, uint8_t* payloads, size_t payload_cap);
   long tapUl(int what, uint32_t index, void* out, size_t cap);
+  int setUlTiming(const lsn_ul_timing_cfg_t& t);
+  long getPuschTiming(lsn_pusch_timing_t* out, uint32_t cap) const;
+  int getUlUeStats(uint16_t rnti, lsn_ul_ue_stats_t* out);
   int setPrachConfig(const lsn_prach_cfg_t& p);
   int prachDetect(const void* ul_iq, bool on_device, uint32_t nsf, uint32_t start_tti, lsn_prach_det_t* out, uint32_t cap);
   long tapPrach(uint32_t index, void* out, size_t cap);
@@ -384,8 +390,11 @@ private:
   struct CommitHost;   // lsn_engine.cc: what the commit walk (lsn_commit.h) asks of (engine, chunk, runner, subframe)
   void commitChunkUl(Chunk& ch, JobRunner& r);
   void prachDetectDev(const cf32* d_iq, uint32_t nant, uint32_t ant, uint32_t nsf, uint32_t start_tti, std::vector<lsn_prach_det_t>& out, uint32_t first_sf = 0);
+  // d_src (optional): the samples the grid was cut from, [sf][src_nant][sflen] on the device, uplink antenna src_ant - what mode 2 of lsn_phy_set_ul_timing
+  // re-cuts a grant's symbols from; without it mode 2 measures only
   void puschDecodeGrid(const cf32* d_grid, uint32_t nsf, uint32_t start_tti, const lsn_pusch_grant_t* grants, uint32_t ngrants,
-                       lsn_pusch_result_t* results, std::vector<uint8_t>& payload_out);
+                       lsn_pusch_result_t* results, std::vector<uint8_t>& payload_out, const cf32* d_src = nullptr, uint32_t src_nant = 1, uint32_t src_ant = 0,
+                       lsn_pusch_timing_t* timing = nullptr);
   // RA-RNTI grants whose content feeds the RNTI manager: DL mode 2..9 (rnti_name == RA_RNTI, DL_Sniffer_PDSCH.cc:1409), UL mode 1..10 (:373)
   bool isRarFeedbackRnti(uint16_t r) const { return cfg.sniffer_mode == 1 ? (r >= RARNTI_START && r <= RARNTI_END) : (r > RARNTI_START && r < RARNTI_END); }
   bool ulModeDecodesDl(const DlEntry& e) const
@@ -612,6 +621,8 @@ private:
   std::vector<UeSpecConfig>& ul_uecfg = sh->ul_uecfg;
   std::vector<uint32_t>& ul_time = sh->ul_time; std::vector<uint32_t>& ul_active = sh->ul_active; std::vector<uint32_t>& ul_success = sh->ul_success;
   float& last_ul_snr = sh->last_ul_snr;
+  std::vector<float>& ul_snr_sum = sh->ul_snr_sum; std::vector<float>& ul_toa_sum = sh->ul_toa_sum; std::vector<uint32_t>& ul_toa_n = sh->ul_toa_n;
+  float& last_ul_toa = sh->last_ul_toa; bool& last_ul_toa_ok = sh->last_ul_toa_ok;
   void ulTrackAdd(uint16_t rnti, int mod = 1);                        // add_RNTI_ul, MCSTracking.cc:57-69
   void ulAgeDatabase();                                               // update_database_ul, MCSTracking.cc:86-176
 
@@ -625,6 +636,14 @@ private:
   size_t ul_iq_cap = 0, ul_grid_cap = 0, ul_hs_cap = 0, ul_stat_cap = 0, ul_grants_cap = 0;
   LsnUlGrantDev* ul_h_grants = nullptr; size_t ul_h_grants_cap = 0;
   float* ul_h_stat = nullptr; size_t ul_h_stat_cap = 0;  // pinned mirror of the grant descriptors
+  // per-grant arrival time (lsn_phy_set_ul_timing; ul_timing.hip): mode 0 off, 1 measure, 2 measure and re-window.  The arenas are runner_u's, like the ones above
+  lsn_ul_timing_cfg_t ul_timing{};           // as set (0 = the defaults); ulToaCfg resolves it at the cell's N
+  LsnUlToaCfg ulToaCfg() const;
+  LsnUlToaDev* ul_d_toa = nullptr; LsnUlGrantDev* ul_d_grants2 = nullptr; cf32* ul_d_priv = nullptr;  // records; grants that name their private row set; [grant][14][nre]
+  size_t ul_toa_cap = 0, ul_grants2_cap = 0, ul_priv_cap = 0;
+  LsnUlToaDev* ul_h_toa = nullptr; size_t ul_h_toa_cap = 0;   // pinned mirror of the records
+  std::vector<lsn_pusch_timing_t> ul_last_timing;             // per grant of the last puschDecodeGrid call (index: the caller's grant)
+  bool ul_last_priv = false;                                  // that call re-windowed: ul_d_priv holds its private rows (tap 5)
   struct Prach {
     bool set = false;
     lsn_prach_cfg_t cfg{};

@@ -79,6 +79,11 @@ void Engine::freeDevice(bool keep_file_buffers)
     ul_iq_cap = ul_grid_cap = ul_hs_cap = ul_stat_cap = ul_grants_cap = 0;
     if (ul_h_grants) { (void)hipHostFree(ul_h_grants); ul_h_grants = nullptr; ul_h_grants_cap = 0; }
     if (ul_h_stat) { (void)hipHostFree(ul_h_stat); ul_h_stat = nullptr; ul_h_stat_cap = 0; }
+    df(ul_d_toa); df(ul_d_grants2); df(ul_d_priv);
+    ul_toa_cap = ul_grants2_cap = ul_priv_cap = 0;
+    if (ul_h_toa) { (void)hipHostFree(ul_h_toa); ul_h_toa = nullptr; ul_h_toa_cap = 0; }
+    ul_last_timing.clear(); ul_last_priv = false;
+    ul_timing = lsn_ul_timing_cfg_t{};   // its thresholds are in samples of the cell that goes
     ul_set = false;
     df(prach.d_W); df(prach.d_V); df(prach.d_D); df(prach.d_Y); df(prach.d_corr); df(prach.d_out); df(prach.d_off);
     prach = Prach();

@@ -175,7 +175,7 @@ int Engine::puschDecode(const void* ul_iq, bool on_device, uint32_t nsf, uint32_
     grow_dev(ul_d_grid, ul_grid_cap, (size_t)nsf * 14 * cd.nre, st);
     lsn_launch_ul_fft(cd, d_iq, 1, 0, ul_d_grid, nsf, st);
     std::vector<uint8_t> pay;
-    puschDecodeGrid(ul_d_grid, nsf, start_tti, grants, ngrants, results, pay);
+    puschDecodeGrid(ul_d_grid, nsf, start_tti, grants, ngrants, results, pay, d_iq, 1, 0);
     if (payloads && pay.size() > payload_cap) return LSN_ERROR_INVALID_INPUTS;  // results[].payload_off would point past the caller's buffer
     if (payloads) std::memcpy(payloads, pay.data(), pay.size());
     return LSN_SUCCESS;
@@ -184,8 +184,12 @@ int Engine::puschDecode(const void* ul_iq, bool on_device, uint32_t nsf, uint32_
 
 // srsran_chest_ul_estimate_pusch + srsran_pusch_decode for a list of grants on an uplink grid that is already on the device
 // (stream runner_u).  payload_out: tbs/8 bytes per valid grant at results[i].payload_off.  Throws on HIP errors.
+// With lsn_phy_set_ul_timing (mode 1 / 2) k_pusch_toa measures every grant's arrival on d_grid and decides its window shift; in mode 2, given the samples
+// (d_src), k_ul_fft_win cuts the grants again into private rows, the estimate and the demodulator run on those, and k_pusch_toa once more for the
+// residual.  No host wait between the passes.  timing (optional): one record per caller's grant.
 void Engine::puschDecodeGrid(const cf32* d_grid, uint32_t nsf, uint32_t start_tti, const lsn_pusch_grant_t* grants, uint32_t ngrants,
-                             lsn_pusch_result_t* results, std::vector<uint8_t>& payload_out)
+                             lsn_pusch_result_t* results, std::vector<uint8_t>& payload_out, const cf32* d_src, uint32_t src_nant, uint32_t src_ant,
+                             lsn_pusch_timing_t* timing)
 {
   static const uint32_t n_dmrs1[8] = {0, 2, 3, 4, 6, 8, 9, 10};  // 36.211 Table 5.5.2.1.1-2
   static const uint32_t n_dmrs2[8] = {0, 6, 3, 4, 2, 8, 10, 9};  // Table 5.5.2.1.1-1
@@ -251,6 +255,10 @@ void Engine::puschDecodeGrid(const cf32* d_grid, uint32_t nsf, uint32_t start_tt
   }
   ul_last_gd = gd; ul_last_idx = gidx;
   ul_last_cbs.clear(); ul_last_tbs.clear();
+  const uint32_t tmode = ul_timing.mode;
+  const bool rewin = tmode == 2 && d_src;
+  ul_last_timing.assign(ngrants, lsn_pusch_timing_t{}); ul_last_priv = false;
+  if (timing) std::fill(timing, timing + ngrants, lsn_pusch_timing_t{});
   const uint32_t ng = (uint32_t)gd.size(), ncb = (uint32_t)r.h_cbs.size();
   if (!ng) { HIP_CHECK(hipStreamSynchronize(st)); return; }
   // (these arenas are runner_u's, written and read on its stream only - also when the UL_MODE commit calls in with a chunk's grid, which stage A finished long ago)
@@ -261,6 +269,8 @@ void Engine::puschDecodeGrid(const cf32* d_grid, uint32_t nsf, uint32_t start_tt
   grow_dev(r.d_cbs, r.cbs_cap, ncb, st);
   grow_dev(r.d_cbres, r.cbres_cap, ncb, st);
   grow_dev(r.d_payload, r.payload_cap, pay_n + 16, st);
+  if (tmode) { grow_dev(ul_d_toa, ul_toa_cap, ng, st); grow_host(ul_h_toa, ul_h_toa_cap, ng, st); }
+  if (rewin) { grow_dev(ul_d_grants2, ul_grants2_cap, ng, st); grow_dev(ul_d_priv, ul_priv_cap, (size_t)ng * 14 * cd.nre, st); }
   const TurboOrder to = turbo_classic_order(r.h_cbs);
   // descriptors go through pinned mirrors and the upload kernel, not through the host -> device copy engine (its FIFO may hold IQ blocks, lsn_dev.h)
   grow_host(ul_h_grants, ul_h_grants_cap, ng, st);
@@ -271,8 +281,18 @@ void Engine::puschDecodeGrid(const cf32* d_grid, uint32_t nsf, uint32_t start_tt
   lsn_launch_upload(ul_d_grants, ul_h_grants, ng * sizeof(LsnUlGrantDev), st);
   lsn_launch_upload(r.d_cbs, r.h_cbs_pinned, ncb * sizeof(LsnCbDev), st);
   HIP_CHECK(hipMemsetAsync(r.d_llr16, 0, llr_n * sizeof(int16_t), st));
-  lsn_launch_pusch_chest(cd, ul_d_grants, d_grid, ul_d_hs, ul_d_stat, ng, st);
-  lsn_launch_pusch_demod(cd, ul_d_grants, d_grid, ul_d_hs, ul_d_stat, r.d_llr16, ng, st);
+  const LsnUlGrantDev* d_g = ul_d_grants;   // what the estimate and the demodulator read: the common grid, or in mode 2 every grant's private rows
+  const cf32* d_rows = d_grid;
+  const LsnUlToaCfg tc = ulToaCfg();
+  if (tmode) lsn_launch_pusch_toa(cd, ul_d_grants, d_grid, tc, ul_d_toa, ul_h_toa, rewin ? ul_d_grants2 : nullptr, false, ng, st);
+  if (rewin) {
+    lsn_launch_ul_fft_win(cd, d_src, src_nant, src_ant, ul_d_grants, ul_d_toa, d_grid, ul_d_priv, ng, st);
+    d_g = ul_d_grants2; d_rows = ul_d_priv;
+    ul_last_priv = true;
+  }
+  lsn_launch_pusch_chest(cd, d_g, d_rows, ul_d_hs, ul_d_stat, ng, st);
+  lsn_launch_pusch_demod(cd, d_g, d_rows, ul_d_hs, ul_d_stat, r.d_llr16, ng, st);
+  if (rewin) lsn_launch_pusch_toa(cd, d_g, d_rows, tc, ul_d_toa, ul_h_toa, nullptr, true, ng, st);
   lsn_launch_rm(r.d_cbs, r.d_llr16, r.d_spp, ncb, place.emax, st);
   lsn_launch_turbo(cd, r.d_cbs, r.d_spp, r.d_payload, r.d_cbres, to.n128, to.kmax128, ncb - to.n128, to.kmax64, st);
   // results come back through pinned mirrors written by the copy kernel (lsn_dev.h), not through the copy engine
@@ -296,6 +316,13 @@ void Engine::puschDecodeGrid(const cf32* d_grid, uint32_t nsf, uint32_t start_tt
     res.snr_db = 10.0f * log10f(stat[2 * t + 1] / stat[2 * t]);
     res.payload_off = (uint32_t)payload_out.size();
     payload_out.insert(payload_out.end(), pl, pl + ref.tbs / 8);
+    if (tmode) {  // (k_pusch_toa wrote the pinned mirror; tbs[t] belongs to gd[t])
+      const LsnUlToaDev& q = ul_h_toa[t];
+      lsn_pusch_timing_t& o = ul_last_timing[ref.grant];
+      o.measured = 1; o.tau = q.tau; o.shift = q.shift; o.flags = q.flags; o.residual = q.residual; o.confidence = q.conf;
+      o.toa_us = (rewin ? (float)q.shift + q.residual : q.tau) * (1.0e6f / (15000.0f * (float)cd.N));
+      if (timing) timing[ref.grant] = o;
+    }
   }
   // taps 3 / 4: the blocks of every grant in transport-block order with their verdicts and where turbo_place put their de-rate-matched words (tbs[t] belongs to gd[t])
   ul_last_cbs.reserve(ncb);
@@ -307,6 +334,48 @@ void Engine::puschDecodeGrid(const cf32* d_grid, uint32_t nsf, uint32_t start_tt
       ul_last_cbs.push_back({cb.K, cb.F, cb.E, cb.rv, cr.ok, cr.iters, place.spp_of[q]});
     }
   }
+}
+
+LsnUlToaCfg Engine::ulToaCfg() const
+{
+  const int32_t N = (int32_t)cd.N;
+  LsnUlToaCfg c;
+  c.min_shift = ul_timing.min_shift ? (int32_t)ul_timing.min_shift : std::max(1, N / 128);
+  c.max_advance = ul_timing.max_advance ? (int32_t)ul_timing.max_advance : N / 4;
+  c.late_max = 144 * N / 2048;
+  return c;
+}
+
+int Engine::setUlTiming(const lsn_ul_timing_cfg_t& t)
+{
+  if (!cell_set || batch_open) return LSN_ERROR;  // the thresholds are in samples of the cell; not while submitted blocks are in flight (call lsn_phy_wait first)
+  if (t.mode > 2 || t.max_advance > cd.N / 2 || t.min_shift > cd.N / 2) return LSN_ERROR_INVALID_INPUTS;
+  ul_timing = t;
+  return LSN_SUCCESS;
+}
+
+// the row of the reference's uplink table (MCSTracking.cc:441-472) for one RNTI; the sums are kept where update_statistic_ul is restated (lsn_ulmode.cc)
+int Engine::getUlUeStats(uint16_t rnti, lsn_ul_ue_stats_t* out)
+{
+  if (cfg.sniffer_mode != 1) return LSN_ERROR_INVALID_INPUTS;
+  std::lock_guard<std::mutex> lk(mcs_mtx);
+  *out = lsn_ul_ue_stats_t{};
+  if (ulmod.empty() || !ulmod[rnti]) return 0;
+  out->mod = ulmod[rnti]; out->active = ul_active[rnti]; out->success = ul_success[rnti];
+  if (out->active) out->mean_snr_db = ul_snr_sum[rnti] / (float)out->active;
+  out->measured = ul_toa_n[rnti];
+  if (out->measured) {
+    out->mean_toa_samples = ul_toa_sum[rnti] / (float)out->measured;
+    out->mean_toa_us = out->mean_toa_samples * (1.0e6f / (15000.0f * (float)cd.N));
+  }
+  return 1;
+}
+
+long Engine::getPuschTiming(lsn_pusch_timing_t* out, uint32_t cap) const
+{
+  const size_t n = std::min<size_t>(cap, ul_last_timing.size());
+  if (out && n) std::memcpy(out, ul_last_timing.data(), n * sizeof(lsn_pusch_timing_t));
+  return (long)ul_last_timing.size();
 }
 
 long Engine::tapUl(int what, uint32_t index, void* out, size_t cap)
@@ -337,6 +406,13 @@ long Engine::tapUl(int what, uint32_t index, void* out, size_t cap)
       o += c.K + 12;
     }
     return (long)n;
+  } else if (what == 5) {  // private grid rows of grant `index` of the last call (mode 2 of lsn_phy_set_ul_timing)
+    if (!ul_last_priv) return LSN_ERROR_INVALID_INPUTS;
+    long row = -1;
+    for (size_t i = 0; i < ul_last_idx.size(); i++)
+      if ((uint32_t)ul_last_idx[i] == index) row = (long)i;
+    if (row < 0) return LSN_ERROR_INVALID_INPUTS;
+    n = (size_t)cd.nsym * cd.nre * sizeof(cf32); src = ul_d_priv + (size_t)row * 14 * cd.nre;
   } else return LSN_ERROR_INVALID_INPUTS;
   if (n > cap) return LSN_ERROR_INVALID_INPUTS;
   if (hipMemcpy(out, src, n, hipMemcpyDeviceToHost) != hipSuccess) return LSN_ERROR;

@@ -20,7 +20,7 @@ namespace {
 // (uci: CQI report size | 1 + betaOffset indices << 8 / 13 / 18 - they move the UL-SCH resource elements, UL_Sniffer_PUSCH.cc:429-450)
 struct Attempt { uint32_t sf; uint32_t idx; bool use256; int qm; uint32_t uci; };
 inline bool operator<(const Attempt& a, const Attempt& b) { return std::tie(a.sf, a.idx, a.use256, a.qm, a.uci) < std::tie(b.sf, b.idx, b.use256, b.qm, b.uci); }
-struct AttemptResult { bool crc = false; bool ran = false; float snr = 0.0f; std::vector<uint8_t> payload; };  // ran: the channel estimate of the attempt was computed
+struct AttemptResult { bool crc = false; bool ran = false; float snr = 0.0f; bool toa_ok = false; float toa = 0.0f; std::vector<uint8_t> payload; };  // ran: the channel estimate of the attempt was computed
 // downlink records keep the OFFSET of their payload in ch.h_payload: a later on-demand decode of the same loop may grow (reallocate) that
 // arena, so the pointer is only formed when the record is emitted
 struct PendingPdu { bool ul; char name; uint16_t rnti; uint8_t tb; size_t off; std::vector<uint8_t> own; uint32_t len; bool msg3 = false; };
@@ -53,6 +53,7 @@ void Engine::ulTrackAdd(uint16_t rnti, int mod)
   if (ulmod[rnti]) return;  // std::map::insert keeps an existing entry
   ulmod[rnti] = (uint8_t)mod; ulmod_count++;
   ul_time[rnti] = commit_sf_cnt; ul_active[rnti] = ul_success[rnti] = 0;
+  ul_snr_sum[rnti] = ul_toa_sum[rnti] = 0.0f; ul_toa_n[rnti] = 0;
   ul_uecfg[rnti] = mcs_tracking.default_config();
 }
 
@@ -225,11 +226,14 @@ void Engine::commitChunkUl(Chunk& ch, JobRunner& r)
     if (gl.empty()) return;
     std::vector<lsn_pusch_result_t> res(gl.size());
     std::vector<uint8_t> pay;
-    puschDecodeGrid(ch.d_ul_grid, ch.nsf, ch.start_tti, gl.data(), (uint32_t)gl.size(), res.data(), pay);
+    std::vector<lsn_pusch_timing_t> tim(gl.size());
+    // mode 2 of lsn_phy_set_ul_timing re-cuts from the chunk's own IQ block, uplink antenna 1 (kept until the chunk is written): no copy of the capture
+    puschDecodeGrid(ch.d_ul_grid, ch.nsf, ch.start_tti, gl.data(), (uint32_t)gl.size(), res.data(), pay, ul_timing.mode == 2 ? ch.d_iq_src : nullptr, cd.iq_nant, 1, tim.data());
     for (size_t i = 0; i < gl.size(); i++) {
       AttemptResult& ar = results[keys[i]];
       ar.crc = res[i].crc_ok != 0;
       ar.ran = res[i].iterations > 0; ar.snr = res[i].snr_db;
+      ar.toa_ok = tim[i].measured != 0; ar.toa = (ul_timing.mode == 2 && ch.d_iq_src) ? (float)tim[i].shift + tim[i].residual : tim[i].tau;  // samples, as lsn_pusch_timing_t::toa_us
       if (ar.crc) ar.payload.assign(pay.begin() + res[i].payload_off, pay.begin() + res[i].payload_off + gl[i].tbs / 8);
       r.perf.nof_tb_decodes++;
       r.perf.nof_turbo_iterations += res[i].iterations;
@@ -280,7 +284,7 @@ void Engine::commitChunkUl(Chunk& ch, JobRunner& r)
         a[k].sf = sf; a[k].idx = i; a[k].uci = uci;
         if (!results.count(a[k])) { run_batch({a[k]}); r.perf.nof_ondemand_decodes++; }
         const AttemptResult& ar = results[a[k]];
-        if (ar.ran) last_ul_snr = ar.snr;
+        if (ar.ran) { last_ul_snr = ar.snr; last_ul_toa = ar.toa; last_ul_toa_ok = ar.toa_ok; }
         if (!ar.crc) continue;
         crc = true;
         PendingPdu p{true, 'C', m.rnti, 0, 0, ar.payload, (uint32_t)ar.payload.size(), m.is_rar};
@@ -295,6 +299,8 @@ void Engine::commitChunkUl(Chunk& ch, JobRunner& r)
         ulTrackAdd(m.rnti, mem_mod);
         ul_active[m.rnti]++;
         if (crc) ul_success[m.rnti]++;
+        ul_snr_sum[m.rnti] += last_ul_snr;   // lsn_phy_get_ul_ue_stats: the table row's mean SNR and mean arrival ("DL-UL_delay", MCSTracking.cc:441-472)
+        if (last_ul_toa_ok) { ul_toa_sum[m.rnti] += last_ul_toa; ul_toa_n[m.rnti]++; }
       }
     }
     for (auto& p : out[sf]) {

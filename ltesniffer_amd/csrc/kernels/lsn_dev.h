@@ -166,6 +166,12 @@ void lsn_launch_prach(const cf32* iq, const uint64_t* occ_off, uint32_t nocc, co
 void lsn_launch_pusch_chest(const LsnCellDev& c, const LsnUlGrantDev* g, const cf32* grid, cf32* hs, float* stat, uint32_t ngrants, hipStream_t s);
 void lsn_launch_pusch_demod(const LsnCellDev& c, const LsnUlGrantDev* g, const cf32* grid, const cf32* hs, const float* stat, int16_t* llr,
                             uint32_t ngrants, hipStream_t s);
+// ul_timing.hip (LsnUlToaCfg / LsnUlToaDev: lsn_ul_toa.h)
+struct LsnUlToaCfg; struct LsnUlToaDev;
+void lsn_launch_pusch_toa(const LsnCellDev& c, const LsnUlGrantDev* g, const cf32* grid, const LsnUlToaCfg& cfg, LsnUlToaDev* rec, LsnUlToaDev* mirror,
+                          LsnUlGrantDev* g_out, bool residual_pass, uint32_t ngrants, hipStream_t s);
+void lsn_launch_ul_fft_win(const LsnCellDev& c, const cf32* iq, uint32_t nant, uint32_t ant, const LsnUlGrantDev* g, const LsnUlToaDev* rec, const cf32* grid,
+                           cf32* priv, uint32_t ngrants, hipStream_t s);
 void lsn_launch_pdsch_demod(const LsnCellDev& c, const LsnGrantDev* g, const uint32_t* items, uint32_t nitems, const uint16_t* prefix, const cf32* grid, const cf32* ce,
                             const LsnChest* ch, int16_t* llr, hipStream_t s);
 void lsn_launch_rm(const LsnCbDev* cb, const int16_t* llr, uint32_t* spp, uint32_t ncb, uint32_t emax, hipStream_t s);
