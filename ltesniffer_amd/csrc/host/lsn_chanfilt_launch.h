@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "lsn_chanfilt.h"
+#include "lsn_front_source.h"
 
 struct cf32;
 
@@ -40,8 +41,5 @@ private:
 
 }  // namespace lsn
 
-// raw holds the samples [buf_base, buf_base + buf_len) of the recording; what a cell reads outside of it (and in front of sample 0) reads as zeros.
-// ring_samples 0: raw is a linear buffer whose element 0 is sample buf_base.  Otherwise (as LsnResampleSource's): raw is a ring of ring_samples samples per antenna,
-// a power of two of at most 2^32 that holds the window (buf_len <= ring_samples), sample n at slot n & (ring_samples - 1); such a launch is k_chan_fir_ring's
-void lsn_launch_chan_fir(const void* raw, uint32_t fmt, float scale, int64_t buf_base, uint64_t buf_len, uint32_t nant, uint64_t ring_samples, const LsnChanFirCell* cells,
-                         uint32_t n_cells, hipStream_t s);
+// src (lsn_front_source.h): what a cell reads outside of its window (and in front of sample 0) reads as zeros; a launch out of a ring is k_chan_fir_ring's
+void lsn_launch_chan_fir(const LsnFrontSource& src, const LsnChanFirCell* cells, uint32_t n_cells, hipStream_t s);

@@ -9,7 +9,7 @@
 #include <cstdio>
 #include <vector>
 
-void lsn::lsn_launch_front(const LsnResampleSource& src, const FrontCell* const* cells, const LsnResampleCell* k, const int64_t* lo, const int64_t* hi, uint32_t n, hipStream_t s,
+void lsn::lsn_launch_front(const LsnFrontSource& src, const FrontCell* const* cells, const LsnResampleCell* k, const int64_t* lo, const int64_t* hi, uint32_t n, hipStream_t s,
                            const char* what)
 {
   if (!n || n > LSN_FILE_MAX_CELLS) throw std::runtime_error("front end: bad number of cells");
@@ -27,7 +27,7 @@ void lsn::lsn_launch_front(const LsnResampleSource& src, const FrontCell* const*
     if (!chan_mid_span(lo[c], hi[c], q.mid_cap, lo2[c], hi2[c])) throw std::runtime_error(std::string(what) + "'s filtered samples do not fit the intermediate buffer");
     f[c] = q.ft.cell(*q.cf, q.mid, lo2[c], (uint64_t)(hi2[c] - lo2[c]));
   }
-  lsn_launch_chan_fir(src.raw, src.fmt, src.scale, src.buf_base, src.buf_len, src.nant, src.ring_samples, f, n, s);
+  lsn_launch_chan_fir(src, f, n, s);
   // stage 2 reads cf32 that the mixer has been through: the piece's plan was formed with no centre offset (tune = 0, no NCO tables)
   for (uint32_t c = 0; c < n; c++)
     if (k[c].n_out) lsn_launch_resample({cells[c]->mid, 0, 1.0f, lo2[c], (uint64_t)(hi2[c] - lo2[c]), src.nant, 0}, k[c], s);
@@ -109,18 +109,17 @@ int lsn_resample(int device, const void* in, int in_on_device, uint64_t n_in, co
   int64_t lo, hi;
   plan.inputSpan(cfg->out_first, n_out, lo, hi);
   if (hi >= (int64_t)1 << 62) return LSN_ERROR_INVALID_INPUTS;
-  const int64_t need_lo = std::max<int64_t>(lo, 0);   // in front of the recording: zeros
-  if (need_lo < (int64_t)cfg->in_base || hi > (int64_t)(cfg->in_base + n_in)) return LSN_ERROR_INVALID_INPUTS;   // the input does not hold what these outputs read
+  const LsnWindowNeed need = lsn_window_holds(cfg->in_base, n_in, lo, hi);
+  if (!need.ok) return LSN_ERROR_INVALID_INPUTS;
   const uint32_t nant = cfg->nof_antennas, fmt = cfg->sample_format;
   const LsnSampleFormat sfm = lsn_sample_format(fmt, cfg->sample_scale);
   const size_t smp = (size_t)sfm.bytes * nant;
-  const uint64_t len = hi > need_lo ? (uint64_t)(hi - need_lo) : 0;
-  const uint8_t* src = (const uint8_t*)in + ((uint64_t)need_lo - cfg->in_base) * smp;
+  const uint8_t* src = (const uint8_t*)in + ((uint64_t)need.lo - cfg->in_base) * smp;
   lsn::ResampleTables tb;
   return staged("resample", device, [&](Staging& g) {
     tb.upload(plan, g.st);
-    const void* raw = g.input(src, in_on_device, len * smp);
-    lsn_launch_resample({raw, fmt, sfm.scale, need_lo, len, nant, 0}, plan.cell(cfg->out_first, (uint32_t)n_out, tb, g.output(0, out, out_on_device, n_out, nant), n_out), g.st);
+    const void* raw = g.input(src, in_on_device, need.len * smp);
+    lsn_launch_resample({raw, fmt, sfm.scale, need.lo, need.len, nant, 0}, plan.cell(cfg->out_first, (uint32_t)n_out, tb, g.output(0, out, out_on_device, n_out, nant), n_out), g.st);
   });
 }
 
@@ -146,8 +145,9 @@ static int resample_cells(int device, const void* in, int in_on_device, uint64_t
     int64_t lo, hi;
     plans[c].inputSpan(k.out_first, n_out[c], lo, hi);
     if (hi >= (int64_t)1 << 62) return LSN_ERROR_INVALID_INPUTS;
-    lo = std::max<int64_t>(lo, 0);   // in front of the recording: zeros
-    if (lo < (int64_t)k.in_base || hi > (int64_t)(k.in_base + n_in)) return LSN_ERROR_INVALID_INPUTS;   // the input does not hold what these outputs read
+    const LsnWindowNeed need = lsn_window_holds(k.in_base, n_in, lo, hi);
+    if (!need.ok) return LSN_ERROR_INVALID_INPUTS;
+    lo = need.lo;
     need_lo = any ? std::min(need_lo, lo) : lo;
     need_hi = any ? std::max(need_hi, hi) : hi;
     any = true;
@@ -160,8 +160,8 @@ static int resample_cells(int device, const void* in, int in_on_device, uint64_t
   const uint8_t* src = (const uint8_t*)in + ((uint64_t)need_lo - c0.in_base) * smp;
   std::vector<lsn::ResampleTables> tb(n_cells);
   return staged("resample_cells", device, [&](Staging& g) {
-    const LsnResampleSource from = ring_samples ? LsnResampleSource{g.ring(in, c0.in_base, n_in, ring_samples, smp), fmt, sfm.scale, (int64_t)c0.in_base, n_in, nant, ring_samples}
-                                                : LsnResampleSource{g.input(src, in_on_device, len * smp), fmt, sfm.scale, need_lo, len, nant, 0};
+    const LsnFrontSource from = ring_samples ? LsnFrontSource{g.ring(in, c0.in_base, n_in, ring_samples, smp), fmt, sfm.scale, (int64_t)c0.in_base, n_in, nant, ring_samples}
+                                                : LsnFrontSource{g.input(src, in_on_device, len * smp), fmt, sfm.scale, need_lo, len, nant, 0};
     LsnResampleCell k[LSN_FILE_MAX_CELLS];
     for (uint32_t c = 0; c < n_cells; c++) {
       tb[c].upload(plans[c], g.st);
@@ -180,7 +180,7 @@ int lsn_resample_cells(int device, const void* in, int in_on_device, uint64_t n_
 int lsn_resample_cells_ring(int device, const void* in, uint64_t n_in, uint64_t ring_samples, const lsn_resample_cfg_t* cfgs, uint32_t n_cells, float* const* outs,
                             const uint64_t* n_out)
 {
-  if (!in || !ring_samples || (ring_samples & (ring_samples - 1)) || ring_samples > (1ull << 32) || n_in > ring_samples) return LSN_ERROR_INVALID_INPUTS;
+  if (!in || !lsn_ring_holds(ring_samples, n_in)) return LSN_ERROR_INVALID_INPUTS;
   return resample_cells(device, in, 0, n_in, ring_samples, cfgs, n_cells, outs, 0, n_out);
 }
 
@@ -194,19 +194,18 @@ int lsn_channel_filter(int device, const void* in, int in_on_device, uint64_t n_
   if (!in || !out || n_out >= (1ull << 40) || n_in >= (1ull << 62)) return LSN_ERROR_INVALID_INPUTS;
   int64_t lo = (int64_t)cfg->out_first, hi = (int64_t)(cfg->out_first + n_out);
   f.widen(lo, hi);
-  const int64_t need_lo = std::max<int64_t>(lo, 0);   // in front of the recording: zeros
-  if (need_lo < (int64_t)cfg->in_base || hi > (int64_t)(cfg->in_base + n_in)) return LSN_ERROR_INVALID_INPUTS;   // the input does not hold what these outputs read
+  const LsnWindowNeed need = lsn_window_holds(cfg->in_base, n_in, lo, hi);
+  if (!need.ok) return LSN_ERROR_INVALID_INPUTS;
   const uint32_t nant = cfg->nof_antennas, fmt = cfg->sample_format;
   const LsnSampleFormat sfm = lsn_sample_format(fmt, cfg->sample_scale);
   const size_t smp = (size_t)sfm.bytes * nant;
-  const uint64_t len = (uint64_t)(hi - need_lo);
-  const uint8_t* src = (const uint8_t*)in + ((uint64_t)need_lo - cfg->in_base) * smp;
+  const uint8_t* src = (const uint8_t*)in + ((uint64_t)need.lo - cfg->in_base) * smp;
   lsn::ChanFirTables ft;
   return staged("channel_filter", device, [&](Staging& g) {
     ft.upload(f, g.st);
-    const void* raw = g.input(src, in_on_device, len * smp);
+    const void* raw = g.input(src, in_on_device, need.len * smp);
     const LsnChanFirCell k = ft.cell(f, g.output(0, out, out_on_device, n_out, nant), (int64_t)cfg->out_first, n_out);
-    lsn_launch_chan_fir(raw, fmt, sfm.scale, need_lo, len, nant, 0, &k, 1, g.st);
+    lsn_launch_chan_fir({raw, fmt, sfm.scale, need.lo, need.len, nant, 0}, &k, 1, g.st);
   });
 }
 
@@ -215,7 +214,7 @@ int lsn_channel_filter_ring(int device, const void* in, uint64_t n_in, uint64_t 
                             const uint64_t* n_out)
 {
   if (!in || !cfgs || !outs || !n_out || n_cells < 1 || n_cells > LSN_FILE_MAX_CELLS) return LSN_ERROR_INVALID_INPUTS;
-  if (!ring_samples || (ring_samples & (ring_samples - 1)) || ring_samples > (1ull << 32) || n_in > ring_samples || n_in >= (1ull << 62)) return LSN_ERROR_INVALID_INPUTS;
+  if (!lsn_ring_holds(ring_samples, n_in)) return LSN_ERROR_INVALID_INPUTS;
   std::vector<lsn::ChanFilter> f(n_cells);
   const lsn_channel_filter_cfg_t& c0 = cfgs[0];
   bool any = false;
@@ -229,7 +228,7 @@ int lsn_channel_filter_ring(int device, const void* in, uint64_t n_in, uint64_t 
     if (!outs[c] || n_out[c] >= (1ull << 40)) return LSN_ERROR_INVALID_INPUTS;
     int64_t lo = (int64_t)k.out_first, hi = (int64_t)(k.out_first + n_out[c]);
     f[c].widen(lo, hi);
-    if (std::max<int64_t>(lo, 0) < (int64_t)k.in_base || hi > (int64_t)(k.in_base + n_in)) return LSN_ERROR_INVALID_INPUTS;   // the window does not hold what these outputs read
+    if (!lsn_window_holds(k.in_base, n_in, lo, hi).ok) return LSN_ERROR_INVALID_INPUTS;
     any = true;
   }
   if (!any) return LSN_SUCCESS;
@@ -245,7 +244,7 @@ int lsn_channel_filter_ring(int device, const void* in, uint64_t n_in, uint64_t 
       ft[c].upload(f[c], g.st);
       k[c] = ft[c].cell(f[c], g.output(c, outs[c], 0, n_out[c], nant), (int64_t)cfgs[c].out_first, n_out[c]);
     }
-    lsn_launch_chan_fir(d_ring, fmt, sfm.scale, (int64_t)c0.in_base, n_in, nant, ring_samples, k, n_cells, g.st);
+    lsn_launch_chan_fir({d_ring, fmt, sfm.scale, (int64_t)c0.in_base, n_in, nant, ring_samples}, k, n_cells, g.st);
   });
 }
 

@@ -22,7 +22,7 @@ struct FrontCell {
 // y1 over exactly chan_mid_span of each piece into its cell's intermediate, then one k_resample per cell reads that (k_resample_cells takes one source per launch);
 // a span that does not fit throws "<what>'s filtered samples do not fit the intermediate buffer" in front of every launch.  Unfiltered: k_resample for one cell
 // out of a linear buffer, else one k_resample_cells (k_resample_ring out of a ring) for all.
-void lsn_launch_front(const LsnResampleSource& src, const FrontCell* const* cells, const LsnResampleCell* k, const int64_t* lo, const int64_t* hi, uint32_t n, hipStream_t s,
+void lsn_launch_front(const LsnFrontSource& src, const FrontCell* const* cells, const LsnResampleCell* k, const int64_t* lo, const int64_t* hi, uint32_t n, hipStream_t s,
                       const char* what);
 
 }  // namespace lsn

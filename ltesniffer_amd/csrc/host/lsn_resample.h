@@ -9,7 +9,7 @@
 // the owner of a cell's device tables - is declared in lsn_resample_launch.h.
 struct cf32;
 
-// what one cell brings to a launch of its own (the launch's other arguments - raw buffer, format, scale, antennas - are the recording's: LsnResampleSource)
+// what one cell brings to a launch of its own (the launch's other arguments - raw buffer, format, scale, antennas - are the recording's: LsnFrontSource)
 struct LsnResampleCell {
   uint64_t base_hi, base_lo;   // position of the cell's output 0 in this launch
   uint64_t d_lo; uint32_t d_hi;

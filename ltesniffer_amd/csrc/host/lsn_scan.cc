@@ -14,9 +14,6 @@
 #include <unistd.h>
 #include <vector>
 
-void lsn_launch_chan_bank(const void* raw, uint32_t fmt, float scale, int64_t buf_base, uint64_t buf_len, uint64_t base_hi, uint64_t base_lo, uint32_t d_hi, uint64_t d_lo,
-                          uint32_t taps, uint32_t span, uint32_t run, const float* bank, const uint64_t* tunes, uint32_t tune_step, const cf32* nco, uint32_t nant,
-                          uint32_t ant0, uint32_t ant_step, uint32_t nch, cf32* out, size_t out_stride, uint64_t n_out, hipStream_t s);
 void lsn_launch_scan_peaks(const float* C, size_t c_stride, uint32_t W5, uint32_t nroots, uint32_t nch, void* out, hipStream_t s);
 void lsn_launch_pss_corr_bank(const cf32* x, size_t x_stride, const cf32* p, uint32_t N, uint32_t W5, uint32_t P, uint32_t nroots, float* C, size_t c_stride, uint32_t nch,
                               hipStream_t s);
@@ -161,9 +158,10 @@ static int carrier_scan(int device, const void* in, bool in_on_device, uint64_t 
   ScanPeak* d_peak = bpeak.alloc<ScanPeak>((size_t)batch * 3);
   std::vector<ScanPeak> peaks((size_t)batch * 3);
   std::vector<lsn_carrier_metric_t> metric = sp.hyp;
+  // hypotheses h0 .. h0 + n - 1, one channel each, all on the scan's antenna; output 0 at input 0
   auto channels = [&](uint32_t h0, uint32_t n) {
-    lsn_launch_chan_bank(d_in, cfg.sample_format, sfm.scale, 0, sp.n_in, 0, 0, (uint32_t)(rs.step >> 64), (uint64_t)rs.step, rs.taps, span, run, tb.d_bank, d_tune + h0, 1, tb.d_nco,
-                         cfg.nof_antennas, cfg.antenna, 0, n, d_chan, nch, nch, st.s);
+    lsn_launch_chan_bank({d_in, cfg.sample_format, sfm.scale, 0, sp.n_in, cfg.nof_antennas, 0},
+                         {0, 0, (uint32_t)(rs.step >> 64), (uint64_t)rs.step, rs.taps, span, run, tb.d_bank, d_tune + h0, 1, tb.d_nco, cfg.antenna, 0, n, d_chan, nch, nch}, st.s);
   };
   for (uint32_t h0 = 0; h0 < H; h0 += batch) {
     const uint32_t n = std::min(batch, H - h0);
@@ -232,14 +230,13 @@ static int carrier_channel(int device, const void* in, bool in_on_device, uint64
   int64_t lo, hi;
   plan.inputSpan(cfg->out_first, n_out, lo, hi);
   if (hi >= (int64_t)1 << 62) return LSN_ERROR_INVALID_INPUTS;
-  const int64_t need_lo = std::max<int64_t>(lo, 0);   // in front of the recording: zeros
-  if (need_lo < (int64_t)cfg->in_base || hi > (int64_t)(cfg->in_base + n_in)) return LSN_ERROR_INVALID_INPUTS;   // the input does not hold what these outputs read
+  const LsnWindowNeed need = lsn_window_holds(cfg->in_base, n_in, lo, hi);
+  if (!need.ok) return LSN_ERROR_INVALID_INPUTS;
   if (!have_device(device)) return LSN_ERROR_NO_DEVICE;
   const uint32_t nant = cfg->nof_antennas;
   const LsnSampleFormat sfm = lsn_sample_format(cfg->sample_format, cfg->sample_scale);
   const size_t smp = (size_t)sfm.bytes * nant;
-  const uint64_t len = hi > need_lo ? (uint64_t)(hi - need_lo) : 0;
-  const uint8_t* src = (const uint8_t*)in + ((uint64_t)need_lo - cfg->in_base) * smp;
+  const uint8_t* src = (const uint8_t*)in + ((uint64_t)need.lo - cfg->in_base) * smp;
   HIP_CHECK(hipSetDevice(device));
   OwnedStream st;
   DevBuf bin, btune, bout;
@@ -249,8 +246,8 @@ static int carrier_channel(int device, const void* in, bool in_on_device, uint64
   HIP_CHECK(hipMemcpyAsync(d_tune, &plan.tune, sizeof(uint64_t), hipMemcpyHostToDevice, st.s));
   const void* raw = src;
   if (!in_on_device) {
-    raw = bin.alloc<uint8_t>(len * smp);
-    if (len) HIP_CHECK(hipMemcpyAsync((void*)raw, src, len * smp, hipMemcpyHostToDevice, st.s));
+    raw = bin.alloc<uint8_t>(need.len * smp);
+    if (need.len) HIP_CHECK(hipMemcpyAsync((void*)raw, src, need.len * smp, hipMemcpyHostToDevice, st.s));
   }
   cf32* dst = (cf32*)out;
   const size_t out_bytes = (size_t)n_out * nant * sizeof(cf32);
@@ -258,8 +255,11 @@ static int carrier_channel(int device, const void* in, bool in_on_device, uint64
   uint32_t run, span;
   chan_geometry(plan, run, span);
   const u128 base = plan.position(cfg->out_first);
-  lsn_launch_chan_bank(raw, cfg->sample_format, sfm.scale, need_lo, len, (uint64_t)(base >> 64), (uint64_t)base, (uint32_t)(plan.step >> 64), (uint64_t)plan.step, plan.taps, span,
-                       run, tb.d_bank, d_tune, 0, tb.d_nco, nant, 0, 1, nant, dst, n_out, n_out, st.s);
+  // one tuning word, a channel per antenna
+  lsn_launch_chan_bank({raw, cfg->sample_format, sfm.scale, need.lo, need.len, nant, 0},
+                       {(uint64_t)(base >> 64), (uint64_t)base, (uint32_t)(plan.step >> 64), (uint64_t)plan.step, plan.taps, span, run, tb.d_bank, d_tune, 0, tb.d_nco, 0, 1, nant, dst,
+                        n_out, n_out},
+                       st.s);
   if (!out_on_device) HIP_CHECK(hipMemcpyAsync(out, dst, out_bytes, hipMemcpyDeviceToHost, st.s));
   HIP_CHECK(hipStreamSynchronize(st.s));
   return LSN_SUCCESS;

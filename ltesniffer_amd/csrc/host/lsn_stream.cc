@@ -2,6 +2,7 @@
 // (tests/test_stream_plan.py) - on a machine with no GPU.
 #include "../../../include/ltesniffer_amd.h"
 #include "lsn_stream.h"
+#include "lsn_front_source.h"
 #include <algorithm>
 
 namespace lsn {
@@ -59,9 +60,8 @@ int stream_ring_check(const StreamCellPlan* cells, uint32_t n, uint32_t blk, uin
 {
   if (!n || !blk) return LSN_ERROR_INVALID_INPUTS;
   if (!ring_samples) ring_samples = stream_default_ring(cells, n, blk);
-  if (!ring_samples || (ring_samples & (ring_samples - 1)) || ring_samples > (1ull << 32)) return LSN_ERROR_INVALID_INPUTS;
   // a block of every cell between the oldest start and the newest data: a ring shorter than that is too small for the block, or the starts lie too far apart
-  if (stream_block_input(cells, n, blk) > ring_samples) return LSN_ERROR_INVALID_INPUTS;
+  if (!lsn_ring_holds(ring_samples, stream_block_input(cells, n, blk))) return LSN_ERROR_INVALID_INPUTS;
   return LSN_SUCCESS;
 }
 

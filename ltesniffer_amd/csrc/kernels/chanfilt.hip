@@ -2,7 +2,7 @@
 // Definition: DESIGN.md section 3.1f; host side (design, refusals, spans): host/lsn_chanfilt.cc.
 //
 //   y1[n] = sum over k = n - L .. n + L, in that order, of g[n - k] xm[k]     one fma per product into ONE float32 accumulator per component, from 0
-//   xm[n] = the recording's sample n, converted and mixed exactly as k_resample stages it (resample.hip); 0 for n < 0
+//   xm[n] = the recording's sample n, converted and mixed by the text k_resample stages it with (LSN_FRONT_SAMPLE, lsn_front_dev.h); 0 for n < 0
 //
 // One workgroup produces a tile of LSN_CF_TILE = 1024 consecutive outputs of one antenna: 256 lanes x 4 neighbouring outputs.  It stages the tile's 1024 + 2L input
 // samples in LDS (converted and mixed once, zeros in front of sample 0 and outside the buffer), then every lane walks its window four staged samples - one "quad" -
@@ -20,7 +20,7 @@
 // The products of one output run in ascending k whichever lane, tile or launch computes it, and nothing else enters it: the bits do not depend on the tiling.
 // The first and the last quads of a window hold products that do not belong to every output (k outside n - L .. n + L): those quads take the guarded path - the
 // guards are wave-uniform - so that no product is formed that the definition does not have (a zero tap times an infinite sample would be a NaN).
-#include "lsn_dsp.h"
+#include "lsn_front_dev.h"
 #include "../host/lsn_hip.h"
 #include "../host/lsn_chanfilt_launch.h"
 #include <algorithm>
@@ -61,27 +61,7 @@ __device__ __forceinline__ void chan_fir_tile(const LsnChanFirArgs& A, const boo
   const uint32_t need = nt + L2;                                            // staged samples this tile's outputs read
   const int64_t n_lo = A.out_first + (int64_t)i0 - (int64_t)A.L;            // input sample staged as s = 0
   for (uint32_t s = t; s < nstage; s += 256) {
-    const int64_t n = n_lo + (int64_t)s, k = n - A.buf_base;
-    float2 x = make_float2(0.0f, 0.0f);
-    if (s < need && n >= 0 && k >= 0 && (uint64_t)k < A.buf_len) {
-      const size_t src = (size_t)(RING ? n & (int64_t)A.ring_mask : k) * A.nant + a;
-      if (FMT == 1) {
-        const short2 q = ((const short2*)A.raw)[src];
-        x.x = (float)q.x * A.scale; x.y = (float)q.y * A.scale;
-      } else if (FMT == 2) {
-        const char2 q = ((const char2*)A.raw)[src];
-        x.x = (float)q.x * A.scale; x.y = (float)q.y * A.scale;
-      } else {
-        x = ((const float2*)A.raw)[src];
-      }
-      if (mix) {
-        const uint64_t ph = (uint64_t)n * A.w;  // low 64 bits of n W
-        const cf32 e = cmul(A.nco[ph >> 52], A.nco[4096u + (uint32_t)((ph >> 42) & 1023u)]);
-        cf32 v; v.r = x.x; v.i = x.y;
-        v = cmulconj(v, e);
-        x.x = v.r; x.y = v.i;
-      }
-    }
+    LSN_FRONT_SAMPLE(s < need, RING ? LSN_FRONT_RING : LSN_FRONT_LINEAR, mix, A.w)
     float2* half = (float2*)((s & 2u) ? cf_hi : cf_lo);
     half[2 * (s >> 2) + (s & 1u)] = x;
   }
@@ -171,14 +151,13 @@ void lsn::ChanFirTables::upload(const lsn::ChanFilter& f, hipStream_t s)
   d_nco = f.tune ? (const cf32*)(d_taps + nt) : nullptr;
 }
 
-// A cell with n_out = 0 takes no part.  One cell: k_chan_fir, the mixer a template flag; several: k_chan_fir_cells.  Out of a ring (ring_samples != 0: a power
-// of two, at most 2^32, that holds the window): k_chan_fir_ring, also for one cell
-void lsn_launch_chan_fir(const void* raw, uint32_t fmt, float scale, int64_t buf_base, uint64_t buf_len, uint32_t nant, uint64_t ring_samples, const LsnChanFirCell* cells,
-                         uint32_t n_cells, hipStream_t s)
+// A cell with n_out = 0 takes no part.  One cell: k_chan_fir, the mixer a template flag; several: k_chan_fir_cells.  Out of a ring (src.ring_samples != 0, which
+// lsn_ring_holds the window): k_chan_fir_ring, also for one cell
+void lsn_launch_chan_fir(const LsnFrontSource& src, const LsnChanFirCell* cells, uint32_t n_cells, hipStream_t s)
 {
-  const uint64_t rn = ring_samples;
-  if (n_cells > LSN_CF_MAX_CELLS || buf_base < 0 || !nant) throw std::runtime_error("k_chan_fir: bad geometry");
-  if (rn && ((rn & (rn - 1)) || rn > (1ull << 32) || buf_len > rn)) throw std::runtime_error("k_chan_fir_ring: bad ring");
+  const uint64_t rn = src.ring_samples;
+  if (n_cells > LSN_CF_MAX_CELLS || src.buf_base < 0 || !src.nant) throw std::runtime_error("k_chan_fir: bad geometry");
+  if (rn && !lsn_ring_holds(rn, src.buf_len)) throw std::runtime_error("k_chan_fir_ring: bad ring");
   LsnChanFirCellsArgs P;
   memset(&P, 0, sizeof(P));
   uint32_t n = 0;
@@ -190,33 +169,19 @@ void lsn_launch_chan_fir(const void* raw, uint32_t fmt, float scale, int64_t buf
     const uint64_t r = (k.n_out + LSN_CF_TILE - 1) / LSN_CF_TILE;
     if (r > 0x7FFFFFFFull) throw std::runtime_error("k_chan_fir: launch too long");
     LsnChanFirArgs& A = P.c[n++];
-    A.raw = raw; A.buf_base = buf_base; A.buf_len = buf_len; A.out_first = k.out_first; A.n_out = k.n_out; A.taps = k.taps; A.w = k.w; A.nco = k.nco; A.out = k.out;
-    A.L = k.L; A.nant = nant; A.scale = scale; A.ring_mask = rn ? (uint32_t)(rn - 1) : 0;
+    A.raw = src.raw; A.buf_base = src.buf_base; A.buf_len = src.buf_len; A.out_first = k.out_first; A.n_out = k.n_out; A.taps = k.taps; A.w = k.w; A.nco = k.nco;
+    A.out = k.out; A.L = k.L; A.nant = src.nant; A.scale = src.scale; A.ring_mask = rn ? (uint32_t)(rn - 1) : 0;
     tiles = std::max(tiles, r);
   }
   if (!n) return;
   if (n == 1 && !rn) {
     const LsnChanFirArgs& A = P.c[0];
-    const dim3 g((uint32_t)tiles, nant);
-    if (A.nco) {
-      if (fmt == 1) LSN_LAUNCH((k_chan_fir<1, true>), g, dim3(256), 0, s, A);
-      else if (fmt == 2) LSN_LAUNCH((k_chan_fir<2, true>), g, dim3(256), 0, s, A);
-      else LSN_LAUNCH((k_chan_fir<0, true>), g, dim3(256), 0, s, A);
-    } else {
-      if (fmt == 1) LSN_LAUNCH((k_chan_fir<1, false>), g, dim3(256), 0, s, A);
-      else if (fmt == 2) LSN_LAUNCH((k_chan_fir<2, false>), g, dim3(256), 0, s, A);
-      else LSN_LAUNCH((k_chan_fir<0, false>), g, dim3(256), 0, s, A);
-    }
+    const dim3 g((uint32_t)tiles, src.nant);
+    if (A.nco) LSN_LAUNCH_FMT(k_chan_fir, LSN_COMMA true, src.fmt, g, dim3(256), 0, s, A);
+    else LSN_LAUNCH_FMT(k_chan_fir, LSN_COMMA false, src.fmt, g, dim3(256), 0, s, A);
     return;
   }
-  const dim3 g((uint32_t)tiles, nant, n);
-  if (!rn) {
-    if (fmt == 1) LSN_LAUNCH((k_chan_fir_cells<1>), g, dim3(256), 0, s, P);
-    else if (fmt == 2) LSN_LAUNCH((k_chan_fir_cells<2>), g, dim3(256), 0, s, P);
-    else LSN_LAUNCH((k_chan_fir_cells<0>), g, dim3(256), 0, s, P);
-    return;
-  }
-  if (fmt == 1) LSN_LAUNCH((k_chan_fir_ring<1>), g, dim3(256), 0, s, P);
-  else if (fmt == 2) LSN_LAUNCH((k_chan_fir_ring<2>), g, dim3(256), 0, s, P);
-  else LSN_LAUNCH((k_chan_fir_ring<0>), g, dim3(256), 0, s, P);
+  const dim3 g((uint32_t)tiles, src.nant, n);
+  if (!rn) LSN_LAUNCH_FMT(k_chan_fir_cells, , src.fmt, g, dim3(256), 0, s, P);
+  else LSN_LAUNCH_FMT(k_chan_fir_ring, , src.fmt, g, dim3(256), 0, s, P);
 }

@@ -22,6 +22,14 @@
     const hipError_t _le = hipGetLastError();                                                                                  \
     if (_le != hipSuccess) throw std::runtime_error(std::string("launch of " #kernel " failed: ") + hipGetErrorString(_le));   \
   } while (0)
+// the instantiation of kernel template K for sample format fmt (LSN_FMT_*): K<FMT REST>, REST = the template's further arguments behind LSN_COMMA, or nothing
+#define LSN_LAUNCH_FMT(K, REST, fmt, grid, block, lds, stream, args)                 \
+  do {                                                                               \
+    if ((fmt) == 1) LSN_LAUNCH((K<1 REST>), grid, block, lds, stream, args);         \
+    else if ((fmt) == 2) LSN_LAUNCH((K<2 REST>), grid, block, lds, stream, args);    \
+    else LSN_LAUNCH((K<0 REST>), grid, block, lds, stream, args);                    \
+  } while (0)
+#define LSN_COMMA ,
 // hipFuncAttributeMaxDynamicSharedMemorySize belongs to the function ON ONE DEVICE: an engine on a second GPU of the process needs its own call
 // (rounds 1-4 set it once per process).  `done` = one bit per device ordinal.
 inline void lsn_func_max_lds(const void* fn, int bytes, std::atomic<uint64_t>& done, const char* name)

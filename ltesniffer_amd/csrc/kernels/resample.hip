@@ -19,7 +19,7 @@
 //
 // Three kernels expand the one copy of that text: k_resample (one cell, a linear buffer), k_resample_cells (several cells, one linear buffer) and
 // k_resample_ring (several cells out of the device ring a pushed stream keeps its raw samples in).
-#include "lsn_dsp.h"
+#include "lsn_front_dev.h"
 #include "../host/lsn_resample_launch.h"
 #include <algorithm>
 #include <cstring>
@@ -49,55 +49,30 @@ struct LsnResampleArgs {
 };
 static_assert(sizeof(LsnResampleArgs) == 128, "eight of them are one kernel argument block; ring_mask sits in what was padding behind scale");
 
-// One run of one antenna: the staging loop and the tap loop.  They exist ONCE in this file, as text: the body is a macro that the three kernels
-// expand, over the names A (the run's LsnResampleArgs), rs_x (the dynamic LDS) and FMT, with MIXCOND the one thing that differs - k_resample's template flag, or
-// the cell's own "has NCO tables", uniform over the workgroup.  A macro and not an inlined __device__ function: the compiler simplifies a function on its own
-// before it inlines it, which reorders k_resample's instructions; expanded as text, all six k_resample instantiations are the instruction streams
-// they were when this was k_resample's body.  SRCSAMPLE is the second thing that differs: the index, in A.raw, of the sample the staging loop loads, over the
-// loop's names n (index in the recording) and k (n - buf_base).  k_resample and k_resample_cells read a linear buffer and pass k; k_resample_ring passes the slot
-// of n in its ring.  [buf_base, buf_base + buf_len) is the window of recording indices that hold samples either way.
-#define LSN_RESAMPLE_RUN(MIXCOND, SRCSAMPLE) \
+// One run of one antenna: the staging loop and the tap loop.  They exist ONCE in this file, as text: the body is a macro that the kernels expand, over the names A
+// (the run's LsnResampleArgs), rs_x (the dynamic LDS) and FMT (why a macro and not a function: lsn_front_dev.h, whose staged sample and position arithmetic these
+// are).  Two things differ between the kernels: MIXCOND - k_resample's template flag, or the cell's own "has NCO tables", uniform over the workgroup - and SRCSAMPLE,
+// where the sample sits in A.raw: k_resample and k_resample_cells read a linear buffer (LSN_FRONT_LINEAR), k_resample_ring the slot of n in its ring (LSN_FRONT_RING).
+// The staging loop, from the position of the run's first output to the barrier, is the one text of both run geometries; RUNLEN is the outputs of a run.
+#define LSN_RESAMPLE_STAGE(RUNLEN, MIXCOND, SRCSAMPLE) \
   const uint32_t a = blockIdx.y, half = A.taps / 2;                                                                                                                     \
-  const uint64_t i0 = (uint64_t)blockIdx.x * LSN_RS_RUN;                                                                                                                \
-  /* position of the run's first output: base + i0 * D */                                                                                                               \
-  uint64_t lo = i0 * A.d_lo, hi = __umul64hi(i0, A.d_lo) + i0 * (uint64_t)A.d_hi;                                                                                       \
-  lo += A.base_lo;                                                                                                                                                      \
-  hi += A.base_hi + (lo < A.base_lo ? 1u : 0u);                                                                                                                         \
+  const uint64_t i0 = (uint64_t)blockIdx.x * (RUNLEN);                                                                                                                  \
+  LSN_FRONT_POSITION(i0, hi, lo)  /* of the run's first output */                                                                                                       \
   const int64_t n_lo = (int64_t)hi - (int64_t)half + 1;  /* input sample staged at rs_x[0] */                                                                           \
   for (uint32_t s = threadIdx.x; s < A.span; s += 256) {                                                                                                                \
-    const int64_t n = n_lo + (int64_t)s, k = n - A.buf_base;                                                                                                            \
-    float2 x = make_float2(0.0f, 0.0f);                                                                                                                                 \
-    if (n >= 0 && k >= 0 && (uint64_t)k < A.buf_len) {                                                                                                                  \
-      const size_t src = (size_t)(SRCSAMPLE) * A.nant + a;                                                                                                              \
-      if (FMT == 1) {                                                                                                                                                   \
-        const short2 q = ((const short2*)A.raw)[src];                                                                                                                   \
-        x.x = (float)q.x * A.scale; x.y = (float)q.y * A.scale;                                                                                                         \
-      } else if (FMT == 2) {                                                                                                                                            \
-        const char2 q = ((const char2*)A.raw)[src];                                                                                                                     \
-        x.x = (float)q.x * A.scale; x.y = (float)q.y * A.scale;                                                                                                         \
-      } else {                                                                                                                                                          \
-        x = ((const float2*)A.raw)[src];                                                                                                                                \
-      }                                                                                                                                                                 \
-      if (MIXCOND) {                                                                                                                                                    \
-        const uint64_t ph = (uint64_t)n * A.w;  /* low 64 bits of n W */                                                                                                \
-        const cf32 e = cmul(A.nco[ph >> 52], A.nco[4096u + (uint32_t)((ph >> 42) & 1023u)]);                                                                            \
-        cf32 v; v.r = x.x; v.i = x.y;                                                                                                                                   \
-        v = cmulconj(v, e);                                                                                                                                             \
-        x.x = v.r; x.y = v.i;                                                                                                                                           \
-      }                                                                                                                                                                 \
-    }                                                                                                                                                                   \
+    LSN_FRONT_SAMPLE(true, SRCSAMPLE, MIXCOND, A.w)                                                                                                                     \
     rs_x[s] = x;                                                                                                                                                        \
   }                                                                                                                                                                     \
-  __syncthreads();                                                                                                                                                      \
+  __syncthreads();
+
+#define LSN_RESAMPLE_RUN(MIXCOND, SRCSAMPLE) \
+  LSN_RESAMPLE_STAGE(LSN_RS_RUN, MIXCOND, SRCSAMPLE)                                                                                                                    \
   for (uint32_t r = 0; r < LSN_RS_RUN / 256; r++) {                                                                                                                     \
     const uint64_t i = i0 + r * 256 + threadIdx.x;                                                                                                                      \
     if (i >= A.n_out) break;                                                                                                                                            \
-    uint64_t plo = i * A.d_lo, phi = __umul64hi(i, A.d_lo) + i * (uint64_t)A.d_hi;                                                                                      \
-    plo += A.base_lo;                                                                                                                                                   \
-    phi += A.base_hi + (plo < A.base_lo ? 1u : 0u);                                                                                                                     \
+    LSN_FRONT_POSITION(i, phi, plo)                                                                                                                                     \
     const uint32_t s0 = (uint32_t)((int64_t)phi - (int64_t)half + 1 - n_lo);  /* first of the T staged samples of this output */                                        \
-    const uint32_t p = (uint32_t)(plo >> 55);  /* 9 bits of phase */                                                                                                    \
-    const float f = (float)(uint32_t)((plo >> 31) & 0xFFFFFFu) * 0x1p-24f;  /* 24 bits inside the phase, exact */                                                       \
+    LSN_FRONT_PHASE(plo, p, f)                                                                                                                                          \
     if (s0 + A.taps > A.span) continue;  /* cannot happen (the host sizes span); keeps the LDS reads inside */                                                          \
     const float4* row = (const float4*)(A.bank + (size_t)p * A.taps);                                                                                                   \
     const float2* x = rs_x + s0;                                                                                                                                        \
@@ -119,7 +94,7 @@ template <int FMT, bool MIX>
 __global__ __launch_bounds__(256) void k_resample(const LsnResampleArgs A)
 {
   extern __shared__ float2 rs_x[];
-  LSN_RESAMPLE_RUN(MIX, k)
+  LSN_RESAMPLE_RUN(MIX, LSN_FRONT_LINEAR)
 }
 
 // Several cells of one recording from ONE raw buffer in one launch (lsn_file_process_cells, lsn_resample_cells): grid (largest number of runs
@@ -135,7 +110,7 @@ __global__ __launch_bounds__(256) void k_resample_cells(const LsnResampleCellsAr
   extern __shared__ float2 rs_x[];
   const LsnResampleArgs& A = P.c[blockIdx.z];
   if ((uint64_t)blockIdx.x * LSN_RS_RUN >= A.n_out) return;
-  LSN_RESAMPLE_RUN(A.nco != nullptr, k)
+  LSN_RESAMPLE_RUN(A.nco != nullptr, LSN_FRONT_LINEAR)
 }
 
 // The same launch out of a RING (lsn_stream, lsn_resample_cells_ring): raw holds ring_mask + 1 samples per antenna and sample n of the recording sits
@@ -147,7 +122,7 @@ __global__ __launch_bounds__(256) void k_resample_ring(const LsnResampleCellsArg
   extern __shared__ float2 rs_x[];
   const LsnResampleArgs& A = P.c[blockIdx.z];
   if ((uint64_t)blockIdx.x * LSN_RS_RUN >= A.n_out) return;
-  LSN_RESAMPLE_RUN(A.nco != nullptr, n & (int64_t)A.ring_mask)
+  LSN_RESAMPLE_RUN(A.nco != nullptr, LSN_FRONT_RING)
 }
 
 // ---- ratios above 4: the wide-ratio run ----
@@ -161,7 +136,8 @@ __global__ __launch_bounds__(256) void k_resample_ring(const LsnResampleCellsArg
 // (one ds_read_b64 each) and GRP consecutive float2 (H, dH) of the bank row; neighbouring groups start floor-of-ratio float2 apart, and because GRP >= ratio
 // the 32 lanes of a half wavefront stay inside 32 consecutive float2 = the 64 banks of ds_read_b64 once (overlapping groups read the SAME addresses:
 // broadcast).  A workgroup runs W.run / (256 / GRP) = 16 rounds of 256 / GRP outputs over one staged span of floor(run * D) + T + 2 <= 4096 + 770 samples.
-// The staging loop is LSN_RESAMPLE_RUN's, to the expression; so are the position arithmetic, c_j = fma(f, dH, H) and the one fma per product.
+// The staging loop is LSN_RESAMPLE_RUN's - the same LSN_RESAMPLE_STAGE - and the position arithmetic the same lsn_front_dev.h; c_j = fma(f, dH, H) and the one
+// fma per product are as there.
 struct LsnResampleWideArgs {
   LsnResampleArgs a;
   uint32_t grp, run;     // lanes per output (8, 16, 32) and outputs per workgroup (4096 / grp)
@@ -169,48 +145,14 @@ struct LsnResampleWideArgs {
 static_assert(sizeof(LsnResampleWideArgs) == 136, "eight of them are one kernel argument block");
 
 #define LSN_RESAMPLE_WIDE_RUN(MIXCOND, SRCSAMPLE) \
-  const uint32_t a = blockIdx.y, half = A.taps / 2;                                                                                                                     \
-  const uint64_t i0 = (uint64_t)blockIdx.x * W.run;                                                                                                                     \
-  /* position of the run's first output: base + i0 * D */                                                                                                               \
-  uint64_t lo = i0 * A.d_lo, hi = __umul64hi(i0, A.d_lo) + i0 * (uint64_t)A.d_hi;                                                                                       \
-  lo += A.base_lo;                                                                                                                                                      \
-  hi += A.base_hi + (lo < A.base_lo ? 1u : 0u);                                                                                                                         \
-  const int64_t n_lo = (int64_t)hi - (int64_t)half + 1;  /* input sample staged at rs_x[0] */                                                                           \
-  for (uint32_t s = threadIdx.x; s < A.span; s += 256) {                                                                                                                \
-    const int64_t n = n_lo + (int64_t)s, k = n - A.buf_base;                                                                                                            \
-    float2 x = make_float2(0.0f, 0.0f);                                                                                                                                 \
-    if (n >= 0 && k >= 0 && (uint64_t)k < A.buf_len) {                                                                                                                  \
-      const size_t src = (size_t)(SRCSAMPLE) * A.nant + a;                                                                                                              \
-      if (FMT == 1) {                                                                                                                                                   \
-        const short2 q = ((const short2*)A.raw)[src];                                                                                                                   \
-        x.x = (float)q.x * A.scale; x.y = (float)q.y * A.scale;                                                                                                         \
-      } else if (FMT == 2) {                                                                                                                                            \
-        const char2 q = ((const char2*)A.raw)[src];                                                                                                                     \
-        x.x = (float)q.x * A.scale; x.y = (float)q.y * A.scale;                                                                                                         \
-      } else {                                                                                                                                                          \
-        x = ((const float2*)A.raw)[src];                                                                                                                                \
-      }                                                                                                                                                                 \
-      if (MIXCOND) {                                                                                                                                                    \
-        const uint64_t ph = (uint64_t)n * A.w;  /* low 64 bits of n W */                                                                                                \
-        const cf32 e = cmul(A.nco[ph >> 52], A.nco[4096u + (uint32_t)((ph >> 42) & 1023u)]);                                                                            \
-        cf32 v; v.r = x.x; v.i = x.y;                                                                                                                                   \
-        v = cmulconj(v, e);                                                                                                                                             \
-        x.x = v.r; x.y = v.i;                                                                                                                                           \
-      }                                                                                                                                                                 \
-    }                                                                                                                                                                   \
-    rs_x[s] = x;                                                                                                                                                        \
-  }                                                                                                                                                                     \
-  __syncthreads();                                                                                                                                                      \
+  LSN_RESAMPLE_STAGE(W.run, MIXCOND, SRCSAMPLE)                                                                                                                         \
   const uint32_t per = 256u / W.grp, gi = threadIdx.x / W.grp, gq = threadIdx.x & (W.grp - 1u);  /* outputs per round; this lane's output in it and lane in its group */ \
   for (uint32_t r = 0; r * per < W.run; r++) {                                                                                                                          \
     if (i0 + r * per >= A.n_out) break;  /* uniform over the workgroup: no output of this or a later round exists */                                                    \
     const uint64_t i = i0 + r * per + gi;                                                                                                                               \
-    uint64_t plo = i * A.d_lo, phi = __umul64hi(i, A.d_lo) + i * (uint64_t)A.d_hi;                                                                                      \
-    plo += A.base_lo;                                                                                                                                                   \
-    phi += A.base_hi + (plo < A.base_lo ? 1u : 0u);                                                                                                                     \
+    LSN_FRONT_POSITION(i, phi, plo)                                                                                                                                     \
     const uint32_t s0 = (uint32_t)((int64_t)phi - (int64_t)half + 1 - n_lo);  /* first of the T staged samples of this output */                                        \
-    const uint32_t p = (uint32_t)(plo >> 55);  /* 9 bits of phase */                                                                                                    \
-    const float f = (float)(uint32_t)((plo >> 31) & 0xFFFFFFu) * 0x1p-24f;  /* 24 bits inside the phase, exact */                                                       \
+    LSN_FRONT_PHASE(plo, p, f)                                                                                                                                          \
     /* s0 + T > span cannot happen for an output that exists (the host sizes span); the test keeps the LDS reads inside.  Every lane of a group agrees on it */         \
     const bool live = i < A.n_out && s0 <= A.span && s0 + A.taps <= A.span;                                                                                             \
     float yr = 0.0f, yi = 0.0f;                                                                                                                                         \
@@ -251,7 +193,7 @@ __global__ __launch_bounds__(256) void k_resample_wide(const LsnResampleWideArgs
 {
   extern __shared__ float2 rs_x[];
   const LsnResampleArgs& A = W.a;
-  LSN_RESAMPLE_WIDE_RUN(MIX, k)
+  LSN_RESAMPLE_WIDE_RUN(MIX, LSN_FRONT_LINEAR)
 }
 
 struct LsnResampleWideCellsArgs { LsnResampleWideArgs c[LSN_RS_MAX_CELLS]; };
@@ -264,7 +206,7 @@ __global__ __launch_bounds__(256) void k_resample_cells_wide(const LsnResampleWi
   const LsnResampleWideArgs& W = P.c[blockIdx.z];
   const LsnResampleArgs& A = W.a;
   if ((uint64_t)blockIdx.x * W.run >= A.n_out) return;
-  LSN_RESAMPLE_WIDE_RUN(A.nco != nullptr, k)
+  LSN_RESAMPLE_WIDE_RUN(A.nco != nullptr, LSN_FRONT_LINEAR)
 }
 
 // ... and out of a ring, as k_resample_ring
@@ -275,7 +217,7 @@ __global__ __launch_bounds__(256) void k_resample_ring_wide(const LsnResampleWid
   const LsnResampleWideArgs& W = P.c[blockIdx.z];
   const LsnResampleArgs& A = W.a;
   if ((uint64_t)blockIdx.x * W.run >= A.n_out) return;
-  LSN_RESAMPLE_WIDE_RUN(A.nco != nullptr, n & (int64_t)A.ring_mask)
+  LSN_RESAMPLE_WIDE_RUN(A.nco != nullptr, LSN_FRONT_RING)
 }
 
 // ---- host side: one function forms a run's arguments, two launchers (lsn_resample_launch.h) ----
@@ -283,7 +225,7 @@ __global__ __launch_bounds__(256) void k_resample_ring_wide(const LsnResampleWid
 // the arguments of cell k's runs out of src, checked: span = samples a run needs (host: lsn_resample.cc), n_out + sf_off below 2^32 (the kernel's row arithmetic); a
 // run is LSN_RS_RUN outputs, or k.run of the wide-ratio geometry (k.grp = 8, 16 or 32 lanes per output, k.run a whole number of rounds of 256 / k.grp).
 // -> the cell's number of runs.  `kernel` names the launch in a refusal
-static uint64_t resample_args(const char* kernel, const LsnResampleSource& src, const LsnResampleCell& k, LsnResampleArgs& A)
+static uint64_t resample_args(const char* kernel, const LsnFrontSource& src, const LsnResampleCell& k, LsnResampleArgs& A)
 {
   if (k.taps < 2 || (k.taps & 1) || k.span < k.taps || (size_t)k.span * sizeof(float2) > 64 * 1024 || src.buf_base < 0 || !k.sflen)
     throw std::runtime_error(std::string(kernel) + ": bad geometry");
@@ -296,18 +238,9 @@ static uint64_t resample_args(const char* kernel, const LsnResampleSource& src, 
   return runs;
 }
 
-// the instantiation of kernel template K for sample format fmt (K<FMT, REST...>)
-#define LSN_RS_LAUNCH_FMT(K, REST, fmt, g, lds, s, args)                    \
-  do {                                                                      \
-    if ((fmt) == 1) LSN_LAUNCH((K<1 REST>), g, dim3(256), lds, s, args);    \
-    else if ((fmt) == 2) LSN_LAUNCH((K<2 REST>), g, dim3(256), lds, s, args); \
-    else LSN_LAUNCH((K<0 REST>), g, dim3(256), lds, s, args);               \
-  } while (0)
-#define LSN_RS_COMMA ,
-
 // one cell out of a linear buffer.  cell.nco != null: the mixing instantiations with tuning word w; null: the plain ones, as before the mixer existed.  cell.grp != 0:
 // the wide-ratio kernel
-void lsn_launch_resample(const LsnResampleSource& src, const LsnResampleCell& cell, hipStream_t s)
+void lsn_launch_resample(const LsnFrontSource& src, const LsnResampleCell& cell, hipStream_t s)
 {
   if (!cell.n_out) return;
   if (src.ring_samples) throw std::runtime_error("k_resample: reads a linear buffer");
@@ -317,24 +250,24 @@ void lsn_launch_resample(const LsnResampleSource& src, const LsnResampleCell& ce
     memset(&W, 0, sizeof(W));
     const dim3 g((uint32_t)resample_args("k_resample_wide", src, cell, W.a), src.nant);
     W.grp = cell.grp; W.run = cell.run;
-    if (cell.nco) LSN_RS_LAUNCH_FMT(k_resample_wide, LSN_RS_COMMA true, src.fmt, g, lds, s, W);
-    else LSN_RS_LAUNCH_FMT(k_resample_wide, LSN_RS_COMMA false, src.fmt, g, lds, s, W);
+    if (cell.nco) LSN_LAUNCH_FMT(k_resample_wide, LSN_COMMA true, src.fmt, g, dim3(256), lds, s, W);
+    else LSN_LAUNCH_FMT(k_resample_wide, LSN_COMMA false, src.fmt, g, dim3(256), lds, s, W);
     return;
   }
   LsnResampleArgs A;
   const dim3 g((uint32_t)resample_args("k_resample", src, cell, A), src.nant);
-  if (cell.nco) LSN_RS_LAUNCH_FMT(k_resample, LSN_RS_COMMA true, src.fmt, g, lds, s, A);
-  else LSN_RS_LAUNCH_FMT(k_resample, LSN_RS_COMMA false, src.fmt, g, lds, s, A);
+  if (cell.nco) LSN_LAUNCH_FMT(k_resample, LSN_COMMA true, src.fmt, g, dim3(256), lds, s, A);
+  else LSN_LAUNCH_FMT(k_resample, LSN_COMMA false, src.fmt, g, dim3(256), lds, s, A);
 }
 
 // the cells of one launch: the source is the recording's and shared, everything else is the cell's own.  A cell with n_out = 0 takes no part; no launch when
-// none does.  Out of a ring: ring_samples a power of two (at most 2^32) that holds the window.  Cells of the two run geometries go to two launches on the same
+// none does.  Out of a ring: lsn_ring_holds(ring_samples, buf_len).  Cells of the two run geometries go to two launches on the same
 // stream - the cells of ratio up to 4 to the kernel they always went to, with the arguments they always had; the wide-ratio cells to its _wide twin
-void lsn_launch_resample_cells(const LsnResampleSource& src, const LsnResampleCell* cells, uint32_t n_cells, hipStream_t s)
+void lsn_launch_resample_cells(const LsnFrontSource& src, const LsnResampleCell* cells, uint32_t n_cells, hipStream_t s)
 {
   const uint64_t rn = src.ring_samples;
   const char* kernel = rn ? "k_resample_ring" : "k_resample_cells";
-  if (rn && ((rn & (rn - 1)) || rn > (1ull << 32) || src.buf_len > rn)) throw std::runtime_error("k_resample_ring: bad ring");
+  if (rn && !lsn_ring_holds(rn, src.buf_len)) throw std::runtime_error("k_resample_ring: bad ring");
   if (n_cells > LSN_RS_MAX_CELLS || src.buf_base < 0) throw std::runtime_error(std::string(kernel) + ": bad geometry");
   LsnResampleCellsArgs P;
   LsnResampleWideCellsArgs Q;
@@ -357,13 +290,13 @@ void lsn_launch_resample_cells(const LsnResampleSource& src, const LsnResampleCe
   if (n) {
     const dim3 g((uint32_t)runs, src.nant, n);
     const size_t lds = (size_t)span * sizeof(float2);
-    if (!rn) LSN_RS_LAUNCH_FMT(k_resample_cells, , src.fmt, g, lds, s, P);
-    else LSN_RS_LAUNCH_FMT(k_resample_ring, , src.fmt, g, lds, s, P);
+    if (!rn) LSN_LAUNCH_FMT(k_resample_cells, , src.fmt, g, dim3(256), lds, s, P);
+    else LSN_LAUNCH_FMT(k_resample_ring, , src.fmt, g, dim3(256), lds, s, P);
   }
   if (nw) {
     const dim3 g((uint32_t)runs_w, src.nant, nw);
     const size_t lds = (size_t)span_w * sizeof(float2);
-    if (!rn) LSN_RS_LAUNCH_FMT(k_resample_cells_wide, , src.fmt, g, lds, s, Q);
-    else LSN_RS_LAUNCH_FMT(k_resample_ring_wide, , src.fmt, g, lds, s, Q);
+    if (!rn) LSN_LAUNCH_FMT(k_resample_cells_wide, , src.fmt, g, dim3(256), lds, s, Q);
+    else LSN_LAUNCH_FMT(k_resample_ring_wide, , src.fmt, g, dim3(256), lds, s, Q);
   }
 }
