@@ -259,7 +259,7 @@ int lsn_phy_mib_decode(lsn_phy_t* phy, const void* iq, int iq_on_device, lsn_mib
 typedef struct {
   uint32_t nof_periods;  /* 5 ms periods whose PSS correlation powers are added (1..16; 0 = 1) */
   int32_t force_n_id_2;  /* -1: search the three PSS roots (args.force_N_id_2 of the reference) */
-  float threshold;       /* on peak / mean of the PSS correlation power; 20 is a safe floor (noise alone stays below 15) */
+  float threshold;       /* on peak / mean of the PSS correlation power; 20 is a safe floor (noise alone stays below 15; lower still over two antennas) */
 } lsn_cell_search_cfg_t;
 typedef struct {
   uint32_t found, cell_id, n_id_2, n_id_1;
@@ -277,6 +277,31 @@ int lsn_cell_search(int device, const void* iq, int iq_on_device, uint64_t nof_s
 /* the same on samples at the rate of sampling mode `rates` (LSN_RATES_*): N = lsn_symbol_sz(nof_prb, rates); pss_pos and sf_start count samples of that rate */
 int lsn_cell_search_rates(int device, const void* iq, int iq_on_device, uint64_t nof_samples, uint32_t nof_prb, int rates, const lsn_cell_search_cfg_t* cfg,
                           lsn_cell_search_t* out, float* corr_out);
+
+/* ---- the cell search over all receive antennas ----
+ * lsn_cell_search_rates on nof_antennas antennas of one recording, antenna a at iq + a * ant_stride samples (cf32; [antenna][sample] with ant_stride >= nof_samples,
+ * nof_samples per antenna).  The antennas are combined without their phases, per antenna and per 5 ms period - their channels are independent, and samples added
+ * before the matched filter cancel a cell whose channels are opposite:
+ *   timing   C[r][n] = sum over periods q and antennas a of |<p_r, x_a[q 75 N + n ...]>|^2 / E_a(q, n) (k_pss_corr_ant); peak, mean and pss_p2avg from C by
+ *            lsn_cell_search's rule, the threshold is the caller's (noise alone reaches lower with two antennas than with one).
+ *   SSS      per antenna and cyclic-prefix hypothesis at the common lag (k_sync_fin); M[h] = sum_a |hyp_a[h_a]|^2, h_a = h with the subframe 0 / 5 bit swapped when
+ *            that antenna's occurrence is odd, so every antenna votes in the parity of the first occurrence; the CP with the larger best M (normal on a tie);
+ *            sss_metric / sss_second from M; cfo_hz from the angle of sum_a hyp_a[best], cfo_coarse_hz from that of sum_a conj(y0_a) y1_a; sf_start and sf_idx by
+ *            lsn_cell_search's formulas.
+ * per_ant (optional, [nof_antennas]): what each antenna alone holds at the common lag, under the winning CP hypothesis - which antenna carried the decision.
+ * With nof_antennas = 1 every field of out and corr_out are lsn_cell_search_rates' (==).  nof_antennas 0 or > LSN_SEARCH_MAX_ANTENNAS, ant_stride < nof_samples,
+ * too few samples, an unknown bandwidth or mode, nof_periods > 16: LSN_ERROR_INVALID_INPUTS, before the device is looked at.  Return value as lsn_cell_search. */
+#define LSN_SEARCH_MAX_ANTENNAS 2 /* the Phy's antenna limit */
+typedef struct {
+  float pss_peak;                /* this antenna's own sum over the periods at (n_id_2, pss_pos): the antennas' values add up to lsn_cell_search_t.pss_peak */
+  float sss_metric, sss_second;  /* best and second best of its own 336 hypothesis powers */
+  float cfo_hz;                  /* from its own best hypothesis */
+  uint32_t n_id_1;               /* of its own best hypothesis */
+  uint32_t occurrence;           /* the PSS occurrence its SSS was taken from (sample pss_pos + occurrence * 75 N) */
+} lsn_cell_search_ant_t;
+int lsn_cell_search_ant(int device, const void* iq, int iq_on_device, uint64_t nof_samples /* per antenna */, uint64_t ant_stride /* samples */, uint32_t nof_antennas,
+                        uint32_t nof_prb, int rates, const lsn_cell_search_cfg_t* cfg, lsn_cell_search_t* out, lsn_cell_search_ant_t* per_ant /* optional */,
+                        float* corr_out /* optional, host: [3][75 N] */);
 
 /* ---- every cell of a carrier: successive cell search ----
  * lsn_cell_search reports the strongest cell.  A network reuses one frequency in all its cells, so a receiver hears several on each carrier: the sectors of
@@ -915,12 +940,16 @@ int lsn_file_clock_estimate(int device, const char* path, const lsn_file_cfg_t* 
  *               min_spacing_hz to an accepted one is dropped (a hypothesis a whole number of sub-carriers off a real carrier sees a time-shifted PSS).
  *   verification  lsn_cell_search's algorithm on the channel of every accepted carrier (6 resource blocks, same nof_periods, root free); found is the search's.
  * The head must hold lsn_carrier_scan_plan_t.nof_input_samples samples.  Device scratch for channels and correlations is bounded by 256 MB whatever the number
- * of hypotheses (they are processed in batches).  One antenna is scanned.  lsn_carrier_scan_plan and lsn_carrier_scan_decide need no GPU. */
+ * of hypotheses (they are processed in batches).  One antenna is scanned, or all of them: with antenna = LSN_SCAN_ALL_ANTENNAS the bank forms a channel per
+ * (hypothesis, antenna), the metric is k_pss_corr_ant's correlation added over the antennas, the decision is unchanged, and the verification is
+ * lsn_cell_search_ant on the carrier's nof_antennas channels (a batch holds nof_antennas times the channel memory per hypothesis).  With nof_antennas = 1 that is
+ * the scan of antenna 0, bit for bit.  lsn_carrier_scan_plan and lsn_carrier_scan_decide need no GPU. */
 #define LSN_SCAN_MAX_HYPOTHESES 8192u
+#define LSN_SCAN_ALL_ANTENNAS 0xFFFFFFFFu /* lsn_carrier_scan_cfg_t.antenna: every antenna of the input, combined without their phases */
 typedef struct {
   uint32_t struct_size;      /* sizeof(lsn_carrier_scan_cfg_t); every other size is refused */
   uint32_t nof_antennas;     /* interleaved in the input (lsn_file_carrier_scan: taken from lsn_file_cfg_t) */
-  uint32_t antenna;          /* the one that is scanned */
+  uint32_t antenna;          /* the one that is scanned, 0 .. nof_antennas - 1, or LSN_SCAN_ALL_ANTENNAS */
   uint32_t sample_format;    /* LSN_FILE_* (lsn_file_carrier_scan: from lsn_file_cfg_t, as sample_scale) */
   float    sample_scale;
   uint32_t nof_periods;      /* 5 ms periods added, 1..16; 0 = 2.  With the threshold of 20 one period leaves a false alarm in a few percent of the scans of a

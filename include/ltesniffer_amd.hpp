@@ -275,6 +275,15 @@ inline int cellSearchRates(const cf_t* iq, uint64_t nof_samples, uint32_t nof_pr
   lsn_cell_search_cfg_t c{nof_periods, force_N_id_2, threshold};
   return lsn_cell_search_rates(device, iq, 0, nof_samples, nof_prb, rates, &c, &out, nullptr);
 }
+// lsn_cell_search_ant: the search over all receive antennas, combined without their phases; iq [nof_antennas][ant_stride >= nof_samples].  per_ant: optional
+// [nof_antennas]
+inline int cellSearchAnt(const cf_t* iq, uint64_t nof_samples, uint64_t ant_stride, uint32_t nof_antennas, uint32_t nof_prb, lsn_cell_search_t& out,
+                         lsn_cell_search_ant_t* per_ant = nullptr, int force_N_id_2 = -1, uint32_t nof_periods = 2, float threshold = 20.0f, int device = 0,
+                         int rates = LSN_RATES_3GPP)
+{
+  lsn_cell_search_cfg_t c{nof_periods, force_N_id_2, threshold};
+  return lsn_cell_search_ant(device, iq, 0, nof_samples, ant_stride, nof_antennas, nof_prb, rates, &c, &out, per_ant, nullptr);
+}
 // lsn_cell_search_all: every cell of the carrier, strongest first (cell 0 is cellSearch's answer); cfg fields left 0 take their defaults.  < 0 error
 inline int cellSearchAll(const cf_t* iq, uint64_t nof_samples, uint32_t nof_prb, std::vector<lsn_cell_found_t>& out, lsn_cell_search_all_cfg_t cfg = {0, -1, 20.0f, 0, 0, 0, 0},
                          int rates = LSN_RATES_3GPP, int device = 0)

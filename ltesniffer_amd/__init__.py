@@ -49,7 +49,8 @@ EXPORTS = ["lsn_phy_create", "lsn_phy_destroy", "lsn_phy_set_cell", "lsn_phy_get
            "lsn_channel_filter_ring", "lsn_stream_span_filtered",
            "lsn_stream_reacquire", "lsn_stream_reacquire_status", "lsn_pss_acquire", "lsn_pss_acquire_decide",
            "lsn_phy_mib_decode_side", "lsn_stream_frame_sync", "lsn_stream_frame_sync_status", "lsn_frame_sync_decide",
-           "lsn_cell_search_all", "lsn_pss_cancel", "lsn_sss_accumulate", "lsn_cell_search_all_plan", "lsn_cell_search_all_decide"]
+           "lsn_cell_search_all", "lsn_pss_cancel", "lsn_sss_accumulate", "lsn_cell_search_all_plan", "lsn_cell_search_all_decide",
+           "lsn_cell_search_ant"]
 
 RATES_3GPP, RATES_SRSRAN = 0, 1   # LSN_RATES_*: sampling mode of a Phy / of a cell search
 
@@ -117,6 +118,10 @@ class CellSearch(C.Structure):
     _fields_ = [("found", C.c_uint32), ("cell_id", C.c_uint32), ("n_id_2", C.c_uint32), ("n_id_1", C.c_uint32), ("sf_idx", C.c_uint32),
                 ("pss_pos", C.c_uint32), ("sf_start", C.c_uint32), ("pss_peak", C.c_float), ("pss_p2avg", C.c_float),
                 ("sss_metric", C.c_float), ("sss_second", C.c_float), ("cfo_hz", C.c_float), ("cfo_coarse_hz", C.c_float), ("cp", C.c_uint32)]
+
+
+class CellSearchAnt(C.Structure):   # lsn_cell_search_ant_t
+    _fields_ = [("pss_peak", C.c_float), ("sss_metric", C.c_float), ("sss_second", C.c_float), ("cfo_hz", C.c_float), ("n_id_1", C.c_uint32), ("occurrence", C.c_uint32)]
 
 
 class CellSearchAllCfg(C.Structure):   # lsn_cell_search_all_cfg_t
@@ -578,6 +583,8 @@ def lib():
         L.lsn_worker_buffers_offset.restype = C.POINTER(C.POINTER(C.c_float))
         L.lsn_cell_search.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, C.POINTER(CellSearchCfg), C.POINTER(CellSearch), C.c_void_p]
         L.lsn_cell_search_rates.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(CellSearchCfg), C.POINTER(CellSearch), C.c_void_p]
+        L.lsn_cell_search_ant.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(CellSearchCfg), C.POINTER(CellSearch),
+                                          C.POINTER(CellSearchAnt), C.c_void_p]
         L.lsn_phy_set_sampling.argtypes = [C.c_void_p, C.c_int]
         L.lsn_phy_get_sampling.argtypes = [C.c_void_p]
         L.lsn_symbol_sz.argtypes = [C.c_uint32, C.c_int]
@@ -1145,6 +1152,36 @@ def cell_search(iq, nof_prb, nof_periods=2, force_n_id_2=-1, threshold=20.0, dev
         ptr, n, on_dev = iq.ctypes.data, iq.size, 0
     rc = _check_n(lib().lsn_cell_search_rates(device, ptr, on_dev, n, nof_prb, int(rates), C.byref(cfg), C.byref(out), corr.ctypes.data if with_corr else None), "lsn_cell_search")
     return (rc, out, corr) if with_corr else (rc, out)
+
+
+SEARCH_MAX_ANTENNAS = 2
+
+
+def cell_search_ant(iq, nof_prb, nof_periods=2, force_n_id_2=-1, threshold=20.0, device=0, with_corr=False, rates=RATES_3GPP):
+    """lsn_cell_search_ant: cell_search over all receive antennas of a recording, combined without their phases.  iq: [antenna][sample] numpy
+    complex64 or a torch cuda tensor; a view whose rows lie further apart than their length (a window into a wider buffer) is read in place
+    -> (rc, CellSearch, [CellSearchAnt per antenna: pss_peak, sss_metric, sss_second, cfo_hz, n_id_1, occurrence][, corr[3, 75 N]])"""
+    import numpy as np
+    N = symbol_sz(nof_prb, rates) or 128
+    cfg = CellSearchCfg(nof_periods, force_n_id_2, threshold)
+    out = CellSearch()
+    corr = np.zeros((3, 75 * N), dtype=np.float32) if with_corr else None
+    if hasattr(iq, "data_ptr"):
+        if iq.dim() != 2 or iq.stride(1) != 1:
+            raise ValueError("cell_search_ant: a [antenna][sample] tensor with contiguous rows")
+        ptr, nant, n, stride, on_dev = iq.data_ptr(), iq.shape[0], iq.shape[1], (iq.stride(0) if iq.shape[0] > 1 else iq.shape[1]), 1
+    else:
+        iq = np.asarray(iq)
+        if iq.ndim != 2:
+            raise ValueError("cell_search_ant: iq is [antenna][sample]")
+        if iq.dtype != np.complex64 or iq.shape[1] == 0 or iq.strides[1] != 8 or iq.strides[0] % 8 or iq.strides[0] < 8 * iq.shape[1]:
+            iq = np.ascontiguousarray(iq, dtype=np.complex64)
+        ptr, nant, n, stride, on_dev = iq.ctypes.data, iq.shape[0], iq.shape[1], (iq.strides[0] // 8 if iq.shape[0] > 1 else iq.shape[1]), 0
+    per = (CellSearchAnt * max(nant, 1))()
+    rc = _check_n(lib().lsn_cell_search_ant(device, ptr, on_dev, n, stride, nant, nof_prb, int(rates), C.byref(cfg), C.byref(out), per,
+                                            corr.ctypes.data if with_corr else None), "lsn_cell_search_ant")
+    per = [CellSearchAnt.from_buffer_copy(p) for p in per[:nant]]
+    return (rc, out, per, corr) if with_corr else (rc, out, per)
 
 
 def cell_search_all(iq, nof_prb, nof_periods=8, force_n_id_2=-1, threshold=20.0, threshold_next=0.0, sss_ratio_min=0.0, shared_pss_ratio=0.0, max_cells=0,
@@ -1837,10 +1874,12 @@ class Stream:
 
 SCAN_MAX_HYPOTHESES = 8192
 SCAN_RATE_HZ = 1.92e6   # rate of a carrier's channel: six resource blocks, 128 samples per symbol
+SCAN_ALL_ANTENNAS = 0xFFFFFFFF   # carrier_scan_cfg(antenna="all"): every antenna of the input, combined without their phases
 
 
 def carrier_scan_cfg(rate_in, nof_antennas=1, antenna=0, sample_format=FILE_CF32, sample_scale=0.0, nof_periods=2, raster_hz=100e3, raster_offset_hz=0.0,
                      f_lo_hz=0.0, f_hi_hz=0.0, min_spacing_hz=1.4e6, threshold=20.0):
+    antenna = SCAN_ALL_ANTENNAS if isinstance(antenna, str) and antenna == "all" else antenna
     return CarrierScanCfg(C.sizeof(CarrierScanCfg), int(nof_antennas), int(antenna), int(sample_format), float(sample_scale), int(nof_periods), float(rate_in),
                           float(raster_hz), float(raster_offset_hz), float(f_lo_hz), float(f_hi_hz), float(min_spacing_hz), float(threshold), 0)
 
@@ -1893,7 +1932,7 @@ def carrier_scan(iq, rate_in, with_metric=False, cap=64, device=0, sample_format
     """lsn_carrier_scan: every LTE carrier in the head of a recording made at rate_in, given nothing else.  iq: [sample][antenna] (or [sample]) numpy complex64, or
     int16 / int8 with a last axis of 2 for FILE_SC16 / FILE_SC8; iq[0] is sample 0 of the recording; it must hold carrier_scan_plan(...)["nof_input_samples"].
     -> [Carrier (center_offset_hz, k, scan_p2avg, scan_root, scan_lag, search: CellSearch on the carrier's 1.92 MS/s channel)] in the order of acceptance
-    [, the CarrierMetric of every hypothesis].  kw: carrier_scan_cfg (antenna, nof_periods, raster_hz, raster_offset_hz, f_lo_hz, f_hi_hz, min_spacing_hz, threshold)"""
+    [, the CarrierMetric of every hypothesis].  kw: carrier_scan_cfg (antenna: an index or "all", nof_periods, raster_hz, raster_offset_hz, f_lo_hz, f_hi_hz, min_spacing_hz, threshold)"""
     iq = _scan_input(iq, sample_format)
     cfg = carrier_scan_cfg(rate_in, nof_antennas=iq.shape[1], sample_format=sample_format, **kw)
     carriers = (Carrier * cap)()

@@ -1,11 +1,13 @@
 // lsn_scan.cc - carrier scan: which LTE carriers does a wideband recording hold, and where.  Host side: the plan (hypotheses on the
 // raster, their tuning words, the 1.92 MS/s channel filter = the resampler's plan with its two caps lifted), the batches over k_chan_bank -> k_pss_corr ->
 // k_scan_peaks (kernels/scan.hip, stage_sync.hip), the decision, and the cell search on every accepted carrier's channel.  lsn_carrier_channel hands out the
-// channel of one offset through the same kernel.  Product code: no CPU fallback, nothing from oracle/ is included or linked.
+// channel of one offset through the same kernel.  antenna = LSN_SCAN_ALL_ANTENNAS: a channel per (hypothesis, antenna), k_pss_corr_ant adds the antennas'
+// correlations (kernels/sync_ant.hip), the accepted carriers go through the cell search over all antennas.  Product code: no CPU fallback, nothing from oracle/ is included or linked.
 #include "lsn_hip.h"
 #include "../kernels/lsn_dev.h"
 #include "lsn_scan.h"
 #include "lsn_resample_launch.h"
+#include "lsn_sync_ant.h"
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
@@ -116,7 +118,8 @@ static int carrier_scan(int device, const void* in, bool in_on_device, uint64_t 
   if (r != LSN_SUCCESS) return r;
   const lsn_carrier_scan_cfg_t& cfg = sp.cfg;
   const LsnSampleFormat sfm = lsn_sample_format(cfg.sample_format, cfg.sample_scale);
-  if (!in || !sfm.valid || cfg.nof_antennas < 1 || cfg.nof_antennas > 8 || cfg.antenna >= cfg.nof_antennas || n_in < sp.n_in || (cap && !carriers_out))
+  const bool all = cfg.antenna == LSN_SCAN_ALL_ANTENNAS;
+  if (!in || !sfm.valid || cfg.nof_antennas < 1 || cfg.nof_antennas > 8 || (!all && cfg.antenna >= cfg.nof_antennas) || n_in < sp.n_in || (cap && !carriers_out))
     return LSN_ERROR_INVALID_INPUTS;
   if (!have_device(device)) return LSN_ERROR_NO_DEVICE;
   HIP_CHECK(hipSetDevice(device));
@@ -150,23 +153,29 @@ static int carrier_scan(int device, const void* in, bool in_on_device, uint64_t 
   cf32* d_rep = brep.alloc<cf32>(rep.size());
   HIP_CHECK(hipMemcpyAsync(d_rep, rep.data(), rep.size() * sizeof(cf32), hipMemcpyHostToDevice, st.s));
 
-  // batches: the scratch of one batch stays under kScanScratch whatever H is
-  const size_t per = nch * sizeof(cf32) + (size_t)3 * W5 * sizeof(float) + 3 * sizeof(ScanPeak);
+  // batches: the scratch of one batch stays under kScanScratch whatever H is; a hypothesis has A channels (one per scanned antenna) and one correlation
+  const uint32_t A = all ? cfg.nof_antennas : 1;
+  const size_t per = A * nch * sizeof(cf32) + (size_t)3 * W5 * sizeof(float) + 3 * sizeof(ScanPeak);
   const uint32_t batch = (uint32_t)std::min<size_t>(std::min<size_t>(H, 65535), std::max<size_t>(1, kScanScratch / per));
-  cf32* d_chan = bchan.alloc<cf32>((size_t)batch * nch);
+  const size_t ant_stride = (size_t)batch * nch;   // the bank is [antenna][hypothesis of the batch][sample]
+  cf32* d_chan = bchan.alloc<cf32>(A * ant_stride);
   float* d_corr = bcorr.alloc<float>((size_t)batch * 3 * W5);
   ScanPeak* d_peak = bpeak.alloc<ScanPeak>((size_t)batch * 3);
   std::vector<ScanPeak> peaks((size_t)batch * 3);
   std::vector<lsn_carrier_metric_t> metric = sp.hyp;
-  // hypotheses h0 .. h0 + n - 1, one channel each, all on the scan's antenna; output 0 at input 0
+  // hypotheses h0 .. h0 + n - 1, one channel each per scanned antenna (a launch per antenna: all its channels read one antenna); output 0 at input 0
   auto channels = [&](uint32_t h0, uint32_t n) {
-    lsn_launch_chan_bank({d_in, cfg.sample_format, sfm.scale, 0, sp.n_in, cfg.nof_antennas, 0},
-                         {0, 0, (uint32_t)(rs.step >> 64), (uint64_t)rs.step, rs.taps, span, run, tb.d_bank, d_tune + h0, 1, tb.d_nco, cfg.antenna, 0, n, d_chan, nch, nch}, st.s);
+    for (uint32_t a = 0; a < A; a++)
+      lsn_launch_chan_bank({d_in, cfg.sample_format, sfm.scale, 0, sp.n_in, cfg.nof_antennas, 0},
+                           {0, 0, (uint32_t)(rs.step >> 64), (uint64_t)rs.step, rs.taps, span, run, tb.d_bank, d_tune + h0, 1, tb.d_nco, all ? a : cfg.antenna, 0, n,
+                            d_chan + a * ant_stride, nch, nch},
+                           st.s);
   };
   for (uint32_t h0 = 0; h0 < H; h0 += batch) {
     const uint32_t n = std::min(batch, H - h0);
     channels(h0, n);
-    lsn_launch_pss_corr_bank(d_chan, nch, d_rep, N, W5, P, 3, d_corr, (size_t)3 * W5, n, st.s);
+    if (all) lsn_launch_pss_corr_ant(d_chan, nch, ant_stride, A, d_rep, N, W5, P, 3, 0, W5, d_corr, (size_t)3 * W5, n, st.s);
+    else lsn_launch_pss_corr_bank(d_chan, nch, d_rep, N, W5, P, 3, d_corr, (size_t)3 * W5, n, st.s);
     lsn_launch_scan_peaks(d_corr, (size_t)3 * W5, W5, 3, n, d_peak, st.s);
     HIP_CHECK(hipMemcpyAsync(peaks.data(), d_peak, (size_t)n * 3 * sizeof(ScanPeak), hipMemcpyDeviceToHost, st.s));
     HIP_CHECK(hipStreamSynchronize(st.s));
@@ -201,7 +210,8 @@ static int carrier_scan(int device, const void* in, bool in_on_device, uint64_t 
     c.scan_lag = m.lag;
     channels(acc[i], 1);
     HIP_CHECK(hipStreamSynchronize(st.s));
-    const int rc = cell_search(device, d_chan, true, sp.n_chan, 6, LSN_RATES_3GPP, cs, c.search, nullptr);
+    const int rc = all ? cell_search_ant(device, d_chan, true, sp.n_chan, ant_stride, A, kSearchAntCap, 6, LSN_RATES_3GPP, cs, c.search, nullptr, nullptr)
+                       : cell_search(device, d_chan, true, sp.n_chan, 6, LSN_RATES_3GPP, cs, c.search, nullptr);
     if (rc < 0) return rc;
   }
   return (int)acc.size();
@@ -320,7 +330,8 @@ int lsn_file_carrier_scan(int device, const char* path, const lsn_file_cfg_t* fc
     const int r = sp.init(&cfg);
     if (r != LSN_SUCCESS) return r;
     const LsnSampleFormat sfm = lsn_sample_format(cfg.sample_format, cfg.sample_scale);
-    if (!sfm.valid || cfg.nof_antennas < 1 || cfg.nof_antennas > 8 || cfg.antenna >= cfg.nof_antennas || (cap && !carriers_out)) return LSN_ERROR_INVALID_INPUTS;
+    if (!sfm.valid || cfg.nof_antennas < 1 || cfg.nof_antennas > 8 || (cfg.antenna != LSN_SCAN_ALL_ANTENNAS && cfg.antenna >= cfg.nof_antennas) || (cap && !carriers_out))
+      return LSN_ERROR_INVALID_INPUTS;
     const size_t smp = (size_t)sfm.bytes * cfg.nof_antennas, total = (size_t)sp.n_in * smp;
     const int fd = open(path, O_RDONLY);
     if (fd < 0) return LSN_ERROR_INVALID_INPUTS;
