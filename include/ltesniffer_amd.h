@@ -532,6 +532,43 @@ int lsn_resample_cells(int device, const void* in, int in_on_device, uint64_t n_
 int lsn_resample_cells_ring(int device, const void* in, uint64_t n_in, uint64_t ring_samples, const lsn_resample_cfg_t* cfgs, uint32_t n_cells, float* const* outs,
                             const uint64_t* n_out);
 
+/* ---- the antenna map ----
+ * Everything above moves ALL antennas of a recording by one center_offset_hz and wants a Phy with as many antennas as the recording has.  With a map, output
+ * antenna a of a Phy is cut from input antenna src_antenna[a] of the recording at carrier center_offset_hz + offset_hz[a]; positions, filter, pass band and sample
+ * clock are the cell's own and shared by its outputs.  Two uses: UL_MODE (antenna 0 = downlink, antenna 1 = uplink) from ONE wideband channel that holds both
+ * directions - src_antenna = {0, 0}, offset_hz = {0, -duplex spacing} -, and the replay of any one or two antennas of a recording of up to eight.
+ * While a map is set, in that Phy's lsn_phy_process_file_rate and lsn_file_process_cells replays and in streams opened on it, nof_antennas of the file or stream
+ * is the RECORDING's, 1 .. 8, and need not equal the Phy's; every src_antenna must be below it.  Each output must satisfy
+ * |center_offset_hz + offset_hz[a]| + passband <= rate_in / 2, finite (the rule of lsn_file_rate_t, per output); otherwise the replay returns
+ * LSN_ERROR_INVALID_INPUTS, nothing is decoded and the Phy stays usable.  A mapped replay always goes through the resampler, equal rates included, and
+ * LSN_TTI_FROM_MIB reads the mapped samples.  A pass or a stream may mix mapped and unmapped Phys; an unmapped Phy still needs the recording's antenna count.
+ * The setter refuses (LSN_ERROR_INVALID_INPUTS, the map as it was): a struct_size other than sizeof, nof_out other than the Phy's nof_rx_antennas (so 0 and 3),
+ * src_antenna above 7, an offset that is not finite, a lsn_phy_create_multi handle.  Limits of a mapped Phy, refused when the replay or stream starts: the channel
+ * filter (lsn_phy_set_channel_filter) together with a map, lsn_phy_process_file (it has no rate) - and on a stream that has a mapped cell lsn_stream_track,
+ * lsn_stream_reacquire and lsn_stream_frame_sync.  The worker pool and lsn_phy_process_host* take no map.  The duplex spacing is an input. */
+#define LSN_MAP_MAX_OUT 2u
+typedef struct {
+  uint32_t struct_size;                  /* sizeof(lsn_antenna_map_t); every other size is refused */
+  uint32_t nof_out;                      /* = the Phy's nof_rx_antennas */
+  uint32_t src_antenna[LSN_MAP_MAX_OUT]; /* input antenna each output antenna is cut from; may repeat */
+  double   offset_hz[LSN_MAP_MAX_OUT];   /* added to the cell's center_offset_hz for this output */
+} lsn_antenna_map_t;
+int lsn_phy_set_antenna_map(lsn_phy_t* phy, const lsn_antenna_map_t* map /* NULL = off, the default */);
+/* lsn_resample_cells / lsn_resample_cells_ring with a map per cell (k_resample_map, k_resample_map_ring and their wide-ratio twins).  maps[c].nof_out = 0: the
+ * identity - the cell as lsn_resample_cells resamples it; else outs[c] is [nof_out][n_out[c]] cf32 and row a equals row src_antenna[a] of lsn_resample with
+ * center_offset_hz + offset_hz[a], bit for bit.  cfgs are validated as there (cfgs[c].center_offset_hz itself only through the outputs of a mapped cell), maps as
+ * lsn_phy_set_antenna_map validates them with nof_out 1 or 2, src_antenna below cfgs' nof_antennas, and the rule above per output.  maps NULL: refused. */
+int lsn_resample_cells_map(int device, const void* in, int in_on_device, uint64_t n_in, const lsn_resample_cfg_t* cfgs, const lsn_antenna_map_t* maps, uint32_t n_cells,
+                           float* const* outs, int out_on_device, const uint64_t* n_out);
+int lsn_resample_cells_ring_map(int device, const void* in, uint64_t n_in, uint64_t ring_samples, const lsn_resample_cfg_t* cfgs, const lsn_antenna_map_t* maps,
+                                uint32_t n_cells, float* const* outs, const uint64_t* n_out);
+/* lsn_file_cells_span with the antennas of every cell's Phy given: nof_out[c] = 1 or 2, or 0 = cfg->nof_antennas (an unmapped cell); NULL = all 0.  cfg->nof_antennas
+ * is the recording's.  The raw block buffer is the one of the Phy with the largest blocks - blk_subframes subframes of nof_out antennas of cf32 - and holds samples
+ * of ALL the recording's antennas, so blk_used follows the recording's antenna count; in_lo and in_hi of a block of a given size do not.  A cell with a Phy
+ * takes its Phy's map and antenna count, and a non-zero nof_out[c] must agree with it. */
+int lsn_file_cells_span_map(const lsn_file_cfg_t* cfg, double sample_rate_hz, const lsn_file_cell_t* cells, uint32_t n_cells, const uint32_t* nof_out, uint64_t in_end,
+                            uint32_t block, uint32_t blk_subframes, lsn_file_cells_span_t* out);
+
 /* ---- a live wideband stream pushed in host buffers ----
  * The file replays above take a path.  A stream takes the same samples as they arrive, in host buffers of any length, and feeds the same cells: per cell exactly
  * the subframes a file of the samples pushed so far replays, and - an output sample being a function of (input, configuration, m) only - bit for bit the samples
@@ -611,6 +648,9 @@ int lsn_stream_span(const lsn_stream_cfg_t* cfg, const lsn_file_cell_t* cells, u
  * or none; a stop band the design refuses is refused. */
 int lsn_stream_span_filtered(const lsn_stream_cfg_t* cfg, const lsn_file_cell_t* cells, uint32_t n_cells, const double* stopband_hz, uint64_t pushed_samples,
                              lsn_stream_span_t* out);
+/* lsn_stream_span with the antennas of every cell's Phy given, as lsn_file_cells_span_map takes them (the antenna map, above): cfg->nof_antennas is the stream's.  A
+ * stream's ring and block input count samples per antenna and do not depend on either number; the call refuses what a mapped open refuses. */
+int lsn_stream_span_map(const lsn_stream_cfg_t* cfg, const lsn_file_cell_t* cells, uint32_t n_cells, const uint32_t* nof_out, uint64_t pushed_samples, lsn_stream_span_t* out);
 /* lsn_stream_span describes the NOMINAL plan: a tracked stream (below) counts a cell's subframes by the positions its loop has decided, which leave the plan's by
  * lsn_stream_track_status_t.position_drift. */
 

@@ -173,6 +173,17 @@ public:
   // sampling mode of the buffers the caller fills (LSN_RATES_3GPP default; LSN_RATES_SRSRAN: SRSRAN_SF_LEN_PRB of the reference's srsRAN); in front of setCell
   bool setSampling(int rates) { return lsn_phy_set_sampling(h, rates) == LSN_SUCCESS; }
   int getSampling() const { return lsn_phy_get_sampling(h); }
+  // lsn_phy_set_antenna_map (this library's own): antenna a of this Phy is cut from antenna src[a] of a recording at the cell's centre offset + offset_hz[a], in
+  // its file-rate replays and streams; src empty: off.  UL_MODE from one wideband channel: setAntennaMap({0, 0}, {0.0, -duplexSpacingHz})
+  bool setAntennaMap(const std::vector<uint32_t>& src, const std::vector<double>& offset_hz = {})
+  {
+    if (src.empty()) return lsn_phy_set_antenna_map(h, nullptr) == LSN_SUCCESS;
+    if (src.size() > LSN_MAP_MAX_OUT || (!offset_hz.empty() && offset_hz.size() != src.size())) return false;
+    lsn_antenna_map_t m{};
+    m.struct_size = sizeof(m); m.nof_out = (uint32_t)src.size();
+    for (size_t a = 0; a < src.size(); a++) { m.src_antenna[a] = src[a]; m.offset_hz[a] = offset_hz.empty() ? 0.0 : offset_hz[a]; }
+    return lsn_phy_set_antenna_map(h, &m) == LSN_SUCCESS;
+  }
   static uint32_t symbolSz(uint32_t nof_prb, int rates) { return lsn_symbol_sz(nof_prb, rates); }
   static uint32_t samplingFreqHz(uint32_t nof_prb, int rates) { return lsn_sampling_freq_hz(nof_prb, rates); }
   bool setCell(const lsn_cell_t& cell) { return lsn_phy_set_cell(h, &cell) == LSN_SUCCESS; }               // Phy.cc:111

@@ -50,7 +50,8 @@ EXPORTS = ["lsn_phy_create", "lsn_phy_destroy", "lsn_phy_set_cell", "lsn_phy_get
            "lsn_stream_reacquire", "lsn_stream_reacquire_status", "lsn_pss_acquire", "lsn_pss_acquire_decide",
            "lsn_phy_mib_decode_side", "lsn_stream_frame_sync", "lsn_stream_frame_sync_status", "lsn_frame_sync_decide",
            "lsn_cell_search_all", "lsn_pss_cancel", "lsn_sss_accumulate", "lsn_cell_search_all_plan", "lsn_cell_search_all_decide",
-           "lsn_cell_search_ant"]
+           "lsn_cell_search_ant",
+           "lsn_phy_set_antenna_map", "lsn_resample_cells_map", "lsn_resample_cells_ring_map", "lsn_file_cells_span_map", "lsn_stream_span_map"]
 
 RATES_3GPP, RATES_SRSRAN = 0, 1   # LSN_RATES_*: sampling mode of a Phy / of a cell search
 
@@ -238,6 +239,29 @@ class ResampleCfg(C.Structure):   # lsn_resample_cfg_t
     _fields_ = [("struct_size", C.c_uint32), ("nof_antennas", C.c_uint32), ("sample_format", C.c_uint32), ("sample_scale", C.c_float),
                 ("rate_in_hz", C.c_double), ("rate_out_hz", C.c_double), ("first_sample", C.c_uint64), ("first_frac", C.c_double),
                 ("in_base", C.c_uint64), ("out_first", C.c_uint64), ("passband_hz", C.c_double), ("center_offset_hz", C.c_double)]
+
+
+MAP_MAX_OUT = 2   # LSN_MAP_MAX_OUT
+
+
+class AntennaMap(C.Structure):   # lsn_antenna_map_t
+    _fields_ = [("struct_size", C.c_uint32), ("nof_out", C.c_uint32), ("src_antenna", C.c_uint32 * MAP_MAX_OUT), ("offset_hz", C.c_double * MAP_MAX_OUT)]
+
+
+def antenna_map(src=None, offset_hz=None):
+    """-> AntennaMap: output antenna a is cut from input antenna src[a] at the cell's carrier + offset_hz[a] (None: all 0.0).  src None: the identity (nof_out 0)"""
+    m = AntennaMap()
+    m.struct_size = C.sizeof(AntennaMap)
+    if src is None:
+        return m
+    src = list(src)
+    off = [0.0] * len(src) if offset_hz is None else list(offset_hz)
+    if len(off) != len(src):
+        raise ValueError("antenna map: one offset per source antenna")
+    m.nof_out = len(src)
+    for a in range(min(len(src), MAP_MAX_OUT)):   # (more than MAP_MAX_OUT: nof_out says so and the library refuses)
+        m.src_antenna[a], m.offset_hz[a] = int(src[a]), float(off[a])
+    return m
 
 
 class ResampleSpan(C.Structure):   # lsn_resample_span_t
@@ -545,6 +569,14 @@ def lib():
         L.lsn_file_cells_span.argtypes = [C.POINTER(FileCfg), C.c_double, C.POINTER(FileCell), C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(FileCellsSpan)]
         L.lsn_file_process_cells.argtypes = [C.c_char_p, C.POINTER(FileCfg), C.c_double, C.POINTER(FileCell), C.c_uint32]
         L.lsn_resample_cells_ring.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(ResampleCfg), C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        L.lsn_phy_set_antenna_map.argtypes = [C.c_void_p, C.POINTER(AntennaMap)]
+        L.lsn_resample_cells_map.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.POINTER(ResampleCfg), C.POINTER(AntennaMap), C.c_uint32, C.POINTER(C.c_void_p), C.c_int,
+                                             C.POINTER(C.c_uint64)]
+        L.lsn_resample_cells_ring_map.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(ResampleCfg), C.POINTER(AntennaMap), C.c_uint32, C.POINTER(C.c_void_p),
+                                                  C.POINTER(C.c_uint64)]
+        L.lsn_file_cells_span_map.argtypes = [C.POINTER(FileCfg), C.c_double, C.POINTER(FileCell), C.c_uint32, C.POINTER(C.c_uint32), C.c_uint64, C.c_uint32, C.c_uint32,
+                                              C.POINTER(FileCellsSpan)]
+        L.lsn_stream_span_map.argtypes = [C.POINTER(StreamCfg), C.POINTER(FileCell), C.c_uint32, C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(StreamSpan)]
         L.lsn_stream_open.argtypes = [C.POINTER(StreamCfg), C.POINTER(FileCell), C.c_uint32, C.POINTER(C.c_void_p)]
         L.lsn_stream_push.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
         L.lsn_stream_flush.argtypes = [C.c_void_p]
@@ -766,6 +798,16 @@ class Phy:
         replay starts or a Stream opens; an open Stream stays as it was opened.  False: refused (negative or not finite)"""
         return lib().lsn_phy_set_channel_filter(self._h, float(stopband_hz)) == LSN_SUCCESS
 
+    def set_antenna_map(self, src=None, offset_hz=None):
+        """lsn_phy_set_antenna_map: in this Phy's process_file_rate / process_file_cells replays and in Streams opened on it from then on, antenna a of
+        the Phy is cut from antenna src[a] of the recording at the cell's center_offset_hz + offset_hz[a]; the recording may then have any 1 .. 8 antennas
+        (nof_antennas of the call).  UL_MODE from one wideband channel: set_antenna_map(src=(0, 0), offset_hz=(0.0, -duplex_spacing)).  set_antenna_map(None): off (the
+        default).  Sticky, like set_channel_filter - and refused together with it when a replay starts.  False: refused (len(src) is not the Phy's antenna count, a
+        source above 7, an offset that is not finite)"""
+        if src is None:
+            return lib().lsn_phy_set_antenna_map(self._h, None) == LSN_SUCCESS
+        return lib().lsn_phy_set_antenna_map(self._h, C.byref(antenna_map(src, offset_hz))) == LSN_SUCCESS
+
     def setCell(self, nof_prb, nof_ports, cell_id, phich_resources=0, cp=0):
         """cp: srsran_cell_t.cp - 0 normal, 1 extended cyclic prefix (downlink path)"""
         self.cell = Cell(nof_prb, nof_ports, cell_id, cp, 0, phich_resources, 0)
@@ -870,14 +912,15 @@ class Phy:
         _check(lib().lsn_phy_prepare_file(self._h, self.nof_rx_antennas), "prepare_file")
 
     def process_file(self, path, start_tti=0, offset_time=0, offset_freq=0.0, max_subframes=0, update_meta_period=0, sample_format=FILE_CF32, sample_scale=0.0,
-                     sample_rate=None, offset_time_frac=0.0, center_offset_hz=0.0):
+                     sample_rate=None, offset_time_frac=0.0, center_offset_hz=0.0, nof_antennas=None):
         """file mode of the reference (-i file -O offset_time -o offset_freq): replay a cf32 capture (antennas interleaved per sample);
         sample_format FILE_SC16 / FILE_SC8: integer I/Q pairs, one LSB = sample_scale (0: full scale +-1); returns the number of subframes processed.
         sample_rate (Hz): the file was recorded at this rate and goes through the GPU resampler (lsn_phy_process_file_rate); offset_time and
-        offset_time_frac then count samples of the FILE's rate.  center_offset_hz: see process_file_rate"""
+        offset_time_frac then count samples of the FILE's rate.  center_offset_hz: see process_file_rate.  nof_antennas: the recording's, when an antenna map
+        (set_antenna_map) is set; None: the Phy's"""
         if center_offset_hz != 0.0 and sample_rate is None:
             raise ValueError("center_offset_hz needs sample_rate (the rate of the recording): the translation is part of the resampler")
-        fc = FileCfg(self.nof_rx_antennas, int(offset_time), float(offset_freq), int(sample_format), float(sample_scale))
+        fc = FileCfg(self.nof_rx_antennas if nof_antennas is None else int(nof_antennas), int(offset_time), float(offset_freq), int(sample_format), float(sample_scale))
         done = C.c_uint64(0)
         if sample_rate is not None:
             fr = FileRate(C.sizeof(FileRate), 0, float(sample_rate), float(offset_time_frac), float(center_offset_hz))
@@ -1365,6 +1408,50 @@ def resample_cells(iq, rate_in, cells, n_out=None, in_base=0, sample_format=FILE
     return outs
 
 
+def _resample_cells_map(name, iq, rate_in, cells, ring_samples, n_out, in_base, sample_format, sample_scale, device):
+    iq = _scan_input(iq, sample_format)
+    n_in, nant = iq.shape[0], iq.shape[1]
+    n = len(cells)
+    cfgs = (ResampleCfg * max(n, 1))()
+    maps = (AntennaMap * max(n, 1))()
+    counts = (C.c_uint64 * max(n, 1))()
+    outs = []
+    for i, c in enumerate(cells):
+        cfgs[i] = _resample_cfg(nant, rate_in, c["rate_out"], c.get("first_sample", 0), c.get("first_frac", 0.0), in_base, c.get("out_first", 0), c.get("passband_hz", 0.0),
+                                sample_format, sample_scale, c.get("center_offset_hz", 0.0))
+        maps[i] = antenna_map(c.get("src"), c.get("offset_hz"))
+        k = c.get("n_out", n_out)
+        if k is None:   # (the span does not depend on the offsets)
+            sp = ResampleSpan()
+            plain = _resample_cfg(nant, rate_in, c["rate_out"], c.get("first_sample", 0), c.get("first_frac", 0.0), in_base, c.get("out_first", 0), c.get("passband_hz", 0.0),
+                                  sample_format, sample_scale, 0.0)
+            _check(lib().lsn_resample_span(C.byref(plain), 0, int(in_base) + n_in, C.byref(sp)), "lsn_resample_span")
+            k = int(sp.max_out)
+        counts[i] = int(k)
+        outs.append(np.zeros((int(maps[i].nof_out) if maps[i].nof_out else nant, int(k)), dtype=np.complex64))
+    ptrs = (C.c_void_p * max(n, 1))(*[o.ctypes.data for o in outs])
+    if ring_samples is None:
+        rc = lib().lsn_resample_cells_map(device, iq.ctypes.data, 0, n_in, cfgs, maps, n, ptrs, 0, counts)
+    else:
+        rc = lib().lsn_resample_cells_ring_map(device, iq.ctypes.data, n_in, int(ring_samples), cfgs, maps, n, ptrs, counts)
+    if rc == LSN_ERROR_INVALID_INPUTS:
+        raise ValueError("%s: refused" % name)
+    _check(rc, name)
+    return outs
+
+
+def resample_cells_map(iq, rate_in, cells, n_out=None, in_base=0, sample_format=FILE_CF32, sample_scale=0.0, device=0):
+    """lsn_resample_cells_map: resample_cells with an antenna map per cell (k_resample_map).  cells: resample_cells' dicts, and src=(...) [, offset_hz=(...)]:
+    output row a is cut from antenna src[a] of iq at center_offset_hz + offset_hz[a] and equals row src[a] of resample with that offset, bit for bit; no src: the
+    identity, the cell as resample_cells makes it.  -> a list of complex64 [len(src) or antennas][n_out] arrays.  Raises ValueError when the library refuses"""
+    return _resample_cells_map("lsn_resample_cells_map", iq, rate_in, cells, None, n_out, in_base, sample_format, sample_scale, device)
+
+
+def resample_cells_ring_map(iq, rate_in, cells, ring_samples, n_out=None, in_base=0, sample_format=FILE_CF32, sample_scale=0.0, device=0):
+    """lsn_resample_cells_ring_map: resample_cells_map through the kernel a Stream runs (k_resample_map_ring), the window placed in a ring as resample_cells_ring does"""
+    return _resample_cells_map("lsn_resample_cells_ring_map", iq, rate_in, cells, ring_samples, n_out, in_base, sample_format, sample_scale, device)
+
+
 def resample_cells_ring(iq, rate_in, cells, ring_samples, n_out=None, in_base=0, sample_format=FILE_CF32, sample_scale=0.0, device=0):
     """lsn_resample_cells_ring: resample_cells through the kernel a Stream runs (k_resample_ring).  The window iq = samples in_base .. in_base + len(iq) of the
     recording is placed into a device ring of ring_samples samples (a power of two), sample n at slot n mod ring_samples, and the cells are resampled out of
@@ -1496,16 +1583,23 @@ def _file_cell(phy, kw):
     return cell
 
 
-def file_cells_span(sample_rate, cells, in_end, block=0, blk_subframes=800, nof_antennas=1, sample_format=FILE_CF32, sample_scale=0.0):
+def file_cells_span(sample_rate, cells, in_end, block=0, blk_subframes=800, nof_antennas=1, sample_format=FILE_CF32, sample_scale=0.0, nof_out=None):
     """lsn_file_cells_span (needs no GPU): the plan of block `block` of process_file_cells.  cells: a list of dicts (nof_prb, rates, center_offset_hz, offset_time,
     offset_time_frac, max_subframes, ...) or of (phy, dict) pairs.  -> dict(in_lo, in_hi: the union of input samples the block reads; blk_used; nof_active;
-    first_subframe, nof_subframes, taps: one entry per cell).  Raises ValueError when the library refuses the cells"""
+    first_subframe, nof_subframes, taps: one entry per cell).  nof_out (lsn_file_cells_span_map, the antenna map): per cell the antennas of its Phy, 1 or 2, or 0 =
+    nof_antennas, which is then the RECORDING's - blk_used follows it.  Raises ValueError when the library refuses the cells"""
     arr = (FileCell * max(len(cells), 1))()
     for i, c in enumerate(cells):
         arr[i] = _file_cell(*c) if isinstance(c, tuple) else _file_cell(None, c)
     fc = FileCfg(int(nof_antennas), 0, 0.0, int(sample_format), float(sample_scale))
     sp = FileCellsSpan()
-    rc = lib().lsn_file_cells_span(C.byref(fc), float(sample_rate), arr, len(cells), int(in_end), int(block), int(blk_subframes), C.byref(sp))
+    if nof_out is None:
+        rc = lib().lsn_file_cells_span(C.byref(fc), float(sample_rate), arr, len(cells), int(in_end), int(block), int(blk_subframes), C.byref(sp))
+    else:
+        if len(nof_out) != len(cells):
+            raise ValueError("file_cells_span: nof_out needs one value per cell")
+        rows = (C.c_uint32 * max(len(cells), 1))(*[int(v) for v in nof_out])
+        rc = lib().lsn_file_cells_span_map(C.byref(fc), float(sample_rate), arr, len(cells), rows, int(in_end), int(block), int(blk_subframes), C.byref(sp))
     if rc == LSN_ERROR_INVALID_INPUTS:
         raise ValueError("file cells: refused")
     _check(rc, "lsn_file_cells_span")
@@ -1539,19 +1633,25 @@ def _stream_cfg(sample_rate, nof_antennas, sample_format, sample_scale, block_su
     return StreamCfg(C.sizeof(StreamCfg), int(device), float(sample_rate), int(nof_antennas), int(sample_format), float(sample_scale), int(block_subframes), int(ring_samples))
 
 
-def stream_span(sample_rate, cells, pushed, nof_antennas=1, sample_format=FILE_CF32, sample_scale=0.0, block_subframes=0, ring_samples=0, stopbands=None):
+def stream_span(sample_rate, cells, pushed, nof_antennas=1, sample_format=FILE_CF32, sample_scale=0.0, block_subframes=0, ring_samples=0, stopbands=None, nof_out=None):
     """lsn_stream_span (needs no GPU): the plan of a Stream after `pushed` samples in all.  cells as file_cells_span.  stopbands (lsn_stream_span_filtered): None,
     or one stopband_hz per cell - the plan of the stream with the channel filter on, without a Phy: every span L samples wider on both sides, a cell's subframes
     counted in front of pushed - L; every cell or none (0.0: none), and all 0.0 is None.  With (phy, dict) cells the Phys' own setting counts, as in file_cells_span.  -> dict(ring_samples: the given one or the
     default; block_input: input samples of one block of every cell, which the ring must hold; block_subframes; per cell subframes_complete - what a flush at that
     point has submitted in all -, subframes_submitted - what a stream that was never flushed has - and taps; oldest_needed / oldest_needed_flushed: the oldest
-    sample a cell still needs in the two cases).  Raises ValueError when the library refuses cells or ring"""
+    sample a cell still needs in the two cases).  nof_out (lsn_stream_span_map): as file_cells_span's; not together with stopbands.  Raises ValueError when the
+    library refuses cells or ring"""
     arr = (FileCell * max(len(cells), 1))()
     for i, c in enumerate(cells):
         arr[i] = _file_cell(*c) if isinstance(c, tuple) else _file_cell(None, c)
     cfg = _stream_cfg(sample_rate, nof_antennas, sample_format, sample_scale, block_subframes, ring_samples, 0)
     sp = StreamSpan()
-    if stopbands is None:
+    if nof_out is not None:
+        if stopbands is not None or len(nof_out) != len(cells):
+            raise ValueError("stream_span: nof_out needs one value per cell and no stopbands")
+        rows = (C.c_uint32 * max(len(cells), 1))(*[int(v) for v in nof_out])
+        rc = lib().lsn_stream_span_map(C.byref(cfg), arr, len(cells), rows, int(pushed), C.byref(sp))
+    elif stopbands is None:
         rc = lib().lsn_stream_span(C.byref(cfg), arr, len(cells), int(pushed), C.byref(sp))
     else:
         if len(stopbands) != len(cells):

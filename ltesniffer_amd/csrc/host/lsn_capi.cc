@@ -556,8 +556,12 @@ int lsn_phy_process_file_rate(lsn_phy_t* phy, const char* path, const lsn_file_c
 // need_phy: every cell has a Phy (one engine, its cell set, fcfg's antennas, all on one device, none twice); otherwise a null phy takes nof_prb / rates.
 // filt[c].L != 0: the cell's Phy has a channel filter set - stage 1 carries the offset and plans[c] is the plan without it; all cells or none.
 // stopband_hz (lsn_stream_span_filtered; null: none): a non-zero entry is the cell's stop band in place of its Phy's setting, so that a plan needs no Phy.
+// The antenna map: a Phy that has one set reads a recording of any 1 .. 8 antennas through file_rate_plan_map and never together with a filter; every
+// other Phy has the recording's antennas.  nof_out (the _span_map calls; null: all 0): the antennas of cell c's Phy, 0 = the recording's - without a Phy that is all
+// that is known of a map; with one it must agree.  rows[c]: the antennas of the cell's block buffers.
 static int file_cells_plans(const lsn_file_cfg_t* fc, double sample_rate_hz, const lsn_file_cell_t* cells, uint32_t n, bool need_phy, std::vector<lsn::ResamplePlan>& plans,
-                            std::vector<uint32_t>& sflen, std::vector<lsn::ChanFilter>& filt, const double* stopband_hz = nullptr)
+                            std::vector<uint32_t>& sflen, std::vector<lsn::ChanFilter>& filt, const double* stopband_hz = nullptr, const uint32_t* nof_out = nullptr,
+                            std::vector<uint32_t>* rows = nullptr)
 {
   if (!fc || !cells || n < 1 || n > LSN_FILE_MAX_CELLS) return LSN_ERROR_INVALID_INPUTS;
   if (fc->nof_antennas < 1 || fc->nof_antennas > 8 || fc->offset_time_samples != 0 || fc->offset_freq_hz != 0.0f || !lsn_sample_format(fc->sample_format, fc->sample_scale).valid)
@@ -565,28 +569,38 @@ static int file_cells_plans(const lsn_file_cfg_t* fc, double sample_rate_hz, con
   plans.resize(n);
   sflen.resize(n);
   filt.assign(n, lsn::ChanFilter());
+  if (rows) rows->assign(n, fc->nof_antennas);
   for (uint32_t c = 0; c < n; c++) {
     const lsn_file_cell_t& k = cells[c];
+    const lsn_antenna_map_t* map = k.phy ? k.phy->engine->antennaMap() : nullptr;
+    const uint32_t want = nof_out ? nof_out[c] : 0;
+    if (want > LSN_MAP_MAX_OUT) return LSN_ERROR_INVALID_INPUTS;
     if (k.struct_size != sizeof(lsn_file_cell_t)) return LSN_ERROR_INVALID_INPUTS;
     uint32_t N = 0, nof_prb = 0;
     if (c && !k.phy != !cells[0].phy) return LSN_ERROR_INVALID_INPUTS;   // all with a Phy or none
     if (k.phy) {
       lsn::Engine* e = k.phy->engine.get();
-      if (!k.phy->more.empty() || !e->hasCell() || e->iqAntennas() != fc->nof_antennas || e->device() != cells[0].phy->engine->device()) return LSN_ERROR_INVALID_INPUTS;
+      if (!k.phy->more.empty() || !e->hasCell() || (!map && e->iqAntennas() != fc->nof_antennas) || e->device() != cells[0].phy->engine->device()) return LSN_ERROR_INVALID_INPUTS;
+      if (want && want != e->iqAntennas()) return LSN_ERROR_INVALID_INPUTS;
+      if (rows) (*rows)[c] = e->iqAntennas();
       for (uint32_t d = 0; d < c; d++) if (cells[d].phy == k.phy) return LSN_ERROR_INVALID_INPUTS;
       N = e->symbolSz(); nof_prb = e->nofPrb();
     } else {
       if (need_phy) return LSN_ERROR_INVALID_INPUTS;
       N = lsn::symbol_size(k.nof_prb, k.rates); nof_prb = k.nof_prb;
       if (!N) return LSN_ERROR_INVALID_INPUTS;
+      if (rows && want) (*rows)[c] = want;
     }
     if (!std::isfinite(k.offset_freq_hz)) return LSN_ERROR_INVALID_INPUTS;
     const double stop = stopband_hz && stopband_hz[c] != 0.0 ? stopband_hz[c] : k.phy ? k.phy->engine->channelFilter() : 0.0;
+    if (stop != 0.0 && map) return LSN_ERROR_INVALID_INPUTS;   // (limit: no channel filter with a map)
     if (stop != 0.0) {
       const int rf = filt[c].init(sample_rate_hz, 15000.0 * (6.0 * (double)nof_prb + 1.0), stop, k.center_offset_hz);
       if (rf != LSN_SUCCESS) return rf;
     }
-    const int r = lsn::file_rate_plan(sample_rate_hz, N, nof_prb, k.offset_time_samples, k.offset_time_frac, stop != 0.0 ? 0.0 : k.center_offset_hz, plans[c]);
+    const int r = map ? lsn::file_rate_plan_map(sample_rate_hz, N, nof_prb, k.offset_time_samples, k.offset_time_frac, k.center_offset_hz, fc->nof_antennas, map->nof_out,
+                                                map->src_antenna, map->offset_hz, plans[c])
+                      : lsn::file_rate_plan(sample_rate_hz, N, nof_prb, k.offset_time_samples, k.offset_time_frac, stop != 0.0 ? 0.0 : k.center_offset_hz, plans[c]);
     if (r != LSN_SUCCESS) return r;
     sflen[c] = 15u * N;
   }
@@ -597,22 +611,29 @@ static int file_cells_plans(const lsn_file_cfg_t* fc, double sample_rate_hz, con
 int lsn_file_cells_span(const lsn_file_cfg_t* cfg, double sample_rate_hz, const lsn_file_cell_t* cells, uint32_t n_cells, uint64_t in_end, uint32_t block, uint32_t blk_subframes,
                         lsn_file_cells_span_t* out)
 {
+  return lsn_file_cells_span_map(cfg, sample_rate_hz, cells, n_cells, nullptr, in_end, block, blk_subframes, out);
+}
+
+int lsn_file_cells_span_map(const lsn_file_cfg_t* cfg, double sample_rate_hz, const lsn_file_cell_t* cells, uint32_t n_cells, const uint32_t* nof_out, uint64_t in_end,
+                            uint32_t block, uint32_t blk_subframes, lsn_file_cells_span_t* out)
+{
   return lsn::guarded([&]() -> int {
     std::vector<lsn::ResamplePlan> plans;
-    std::vector<uint32_t> sflen;
+    std::vector<uint32_t> sflen, rows;
     std::vector<lsn::ChanFilter> filt;
-    const int r = file_cells_plans(cfg, sample_rate_hz, cells, n_cells, false, plans, sflen, filt);
+    const int r = file_cells_plans(cfg, sample_rate_hz, cells, n_cells, false, plans, sflen, filt, nullptr, nof_out, &rows);
     if (r != LSN_SUCCESS) return r;
     if (!out || !blk_subframes || in_end >= (1ull << 62)) return LSN_ERROR_INVALID_INPUTS;
     lsn::FileCellPlan cp[LSN_FILE_MAX_CELLS];
-    uint32_t widest = 0;
+    uint64_t widest = 0;   // samples of all antennas of one subframe of the Phy with the largest blocks
     for (uint32_t c = 0; c < n_cells; c++) {
       cp[c].rs = &plans[c]; cp[c].sflen = sflen[c]; cp[c].first_sf = 0; cp[c].pre = filt[c].L;
       cp[c].total = lsn::file_cell_total(plans[c].outputsInside(filt[c].insideEnd(in_end)) / sflen[c], 0, cells[c].max_subframes);
-      widest = std::max(widest, sflen[c]);
+      widest = std::max<uint64_t>(widest, (uint64_t)sflen[c] * rows[c]);
     }
-    // the raw block buffer: blk_subframes subframes of cf32 of the widest cell, in samples of the file's format (Engine::reserveFileBuffers)
-    const uint64_t cap = (uint64_t)((lsn::u128)blk_subframes * widest * sizeof(cf32) / lsn_sample_format(cfg->sample_format, cfg->sample_scale).bytes);
+    // the raw block buffer: blk_subframes subframes of cf32 of that Phy (Engine::reserveFileBuffers), in samples of the file's format and of ALL the recording's
+    // antennas (FileReplay: raw_bytes / spb).  Unmapped, the Phy's antennas are the recording's and cancel
+    const uint64_t cap = (uint64_t)((lsn::u128)blk_subframes * widest * sizeof(cf32) / ((uint64_t)lsn_sample_format(cfg->sample_format, cfg->sample_scale).bytes * cfg->nof_antennas));
     const uint32_t blk = lsn::file_cells_fit(cp, n_cells, blk_subframes, cap);
     if (!blk) return LSN_ERROR_INVALID_INPUTS;
     lsn::FileCellsBlock b;
@@ -651,12 +672,12 @@ int lsn_file_process_cells(const char* path, const lsn_file_cfg_t* cfg, double s
 // What lsn_stream_open and lsn_stream_span check alike, through file_cells_plans - the file pass's own checks and plans - and the stream's refusals on top.
 // filt: the cells' channel filters (L = 0: none; all cells or none, and a stop band ChanFilter::init refuses is refused here), DESIGN 3.1j.
 static int stream_plans(const lsn_stream_cfg_t* cfg, const lsn_file_cell_t* cells, uint32_t n, bool need_phy, const double* stopband_hz, std::vector<lsn::ResamplePlan>& plans,
-                        std::vector<uint32_t>& sflen, std::vector<lsn::ChanFilter>& filt, uint32_t& blk, uint64_t& ring_samples)
+                        std::vector<uint32_t>& sflen, std::vector<lsn::ChanFilter>& filt, uint32_t& blk, uint64_t& ring_samples, const uint32_t* nof_out = nullptr)
 {
   if (!cfg || cfg->struct_size != sizeof(lsn_stream_cfg_t)) return LSN_ERROR_INVALID_INPUTS;
   lsn_file_cfg_t fc{};
   fc.nof_antennas = cfg->nof_antennas; fc.offset_time_samples = 0; fc.offset_freq_hz = 0.0f; fc.sample_format = cfg->sample_format; fc.sample_scale = cfg->sample_scale;
-  const int r = file_cells_plans(&fc, cfg->sample_rate_hz, cells, n, need_phy, plans, sflen, filt, stopband_hz);
+  const int r = file_cells_plans(&fc, cfg->sample_rate_hz, cells, n, need_phy, plans, sflen, filt, stopband_hz, nof_out);
   if (r != LSN_SUCCESS) return r;
   for (uint32_t c = 0; c < n; c++) {
     if (cells[c].start_tti == LSN_TTI_FROM_MIB) return LSN_ERROR_INVALID_INPUTS;
@@ -684,7 +705,21 @@ int lsn_stream_span(const lsn_stream_cfg_t* cfg, const lsn_file_cell_t* cells, u
   return lsn_stream_span_filtered(cfg, cells, n_cells, nullptr, pushed, out);
 }
 
+static int stream_span(const lsn_stream_cfg_t* cfg, const lsn_file_cell_t* cells, uint32_t n_cells, const double* stopband_hz, const uint32_t* nof_out, uint64_t pushed,
+                       lsn_stream_span_t* out);
+
 int lsn_stream_span_filtered(const lsn_stream_cfg_t* cfg, const lsn_file_cell_t* cells, uint32_t n_cells, const double* stopband_hz, uint64_t pushed, lsn_stream_span_t* out)
+{
+  return stream_span(cfg, cells, n_cells, stopband_hz, nullptr, pushed, out);
+}
+
+int lsn_stream_span_map(const lsn_stream_cfg_t* cfg, const lsn_file_cell_t* cells, uint32_t n_cells, const uint32_t* nof_out, uint64_t pushed, lsn_stream_span_t* out)
+{
+  return stream_span(cfg, cells, n_cells, nullptr, nof_out, pushed, out);
+}
+
+static int stream_span(const lsn_stream_cfg_t* cfg, const lsn_file_cell_t* cells, uint32_t n_cells, const double* stopband_hz, const uint32_t* nof_out, uint64_t pushed,
+                       lsn_stream_span_t* out)
 {
   return lsn::guarded([&]() -> int {
     std::vector<lsn::ResamplePlan> plans;
@@ -692,7 +727,7 @@ int lsn_stream_span_filtered(const lsn_stream_cfg_t* cfg, const lsn_file_cell_t*
     std::vector<lsn::ChanFilter> filt;
     uint32_t blk = 0;
     uint64_t ring = 0;
-    const int r = stream_plans(cfg, cells, n_cells, false, stopband_hz, plans, sflen, filt, blk, ring);
+    const int r = stream_plans(cfg, cells, n_cells, false, stopband_hz, plans, sflen, filt, blk, ring, nof_out);
     if (r != LSN_SUCCESS) return r;
     if (!out || pushed >= (1ull << 62)) return LSN_ERROR_INVALID_INPUTS;
     lsn::StreamCellPlan sp[LSN_FILE_MAX_CELLS];
@@ -827,6 +862,12 @@ int lsn_phy_set_channel_filter(lsn_phy_t* phy, double stopband_hz)
 {
   if (!phy) return LSN_ERROR_INVALID_INPUTS;
   return phy->engine->setChannelFilter(stopband_hz);
+}
+
+int lsn_phy_set_antenna_map(lsn_phy_t* phy, const lsn_antenna_map_t* map)
+{
+  if (!phy || !phy->more.empty()) return LSN_ERROR_INVALID_INPUTS;   // (limit: not on a lsn_phy_create_multi handle)
+  return phy->engine->setAntennaMap(map);
 }
 
 int lsn_phy_prepare_file(lsn_phy_t* phy, uint32_t nof_antennas)

@@ -17,6 +17,16 @@ int file_rate_plan(double sample_rate_hz, uint32_t N, uint32_t nof_prb, int64_t 
   return plan.init(sample_rate_hz, 15000.0 * (double)N, 15000.0 * (6.0 * (double)nof_prb + 1.0), first, offset_time_frac - whole, center_offset_hz);
 }
 
+int file_rate_plan_map(double sample_rate_hz, uint32_t N, uint32_t nof_prb, int64_t offset_time_samples, double offset_time_frac, double center_offset_hz, uint32_t nof_in,
+                       uint32_t nof_out, const uint32_t* src, const double* offset_hz, ResamplePlan& plan)
+{
+  if (offset_time_samples < 0 || !(offset_time_frac >= 0.0 && offset_time_frac < 4.0e18)) return LSN_ERROR_INVALID_INPUTS;
+  const double whole = std::floor(offset_time_frac);
+  const uint64_t first = (uint64_t)offset_time_samples + (uint64_t)whole;
+  return plan.initMapped(sample_rate_hz, 15000.0 * (double)N, 15000.0 * (6.0 * (double)nof_prb + 1.0), first, offset_time_frac - whole, center_offset_hz, nof_in, nof_out, src,
+                         offset_hz);
+}
+
 uint64_t file_cell_total(uint64_t sf_in_file, uint64_t first_sf, uint64_t max_subframes)
 {
   const uint64_t avail = sf_in_file > first_sf ? sf_in_file - first_sf : 0;

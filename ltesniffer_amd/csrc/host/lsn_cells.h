@@ -12,6 +12,10 @@ constexpr uint32_t kFileMaxCells = 8;   // LSN_FILE_MAX_CELLS: the cells' kernel
 // position offset_time_samples + offset_time_frac (the whole part of the fraction goes to the integer), tuning word of center_offset_hz.
 // LSN_ERROR_INVALID_INPUTS: a negative or non-finite start, or what ResamplePlan::init refuses.
 int file_rate_plan(double sample_rate_hz, uint32_t N, uint32_t nof_prb, int64_t offset_time_samples, double offset_time_frac, double center_offset_hz, ResamplePlan& plan);
+// The same through an antenna map: nof_out outputs, output a cut from antenna src[a] of the recording's nof_in at center_offset_hz +
+// offset_hz[a].  LSN_ERROR_INVALID_INPUTS also for a source outside the recording and an output that does not lie inside it (ResamplePlan::initMapped).
+int file_rate_plan_map(double sample_rate_hz, uint32_t N, uint32_t nof_prb, int64_t offset_time_samples, double offset_time_frac, double center_offset_hz, uint32_t nof_in,
+                       uint32_t nof_out, const uint32_t* src, const double* offset_hz, ResamplePlan& plan);
 
 struct FileCellPlan {
   const ResamplePlan* rs = nullptr;   // null: the file is at the engine's rate (single-cell replay through k_file_unpack) - such a cell has counts but no span

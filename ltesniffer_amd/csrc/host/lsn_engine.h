@@ -261,6 +261,18 @@ public:
     return LSN_SUCCESS;
   }
   double channelFilter() const { return chan_stopband_hz; }
+  // the antenna map of this engine's file replays and streams (lsn_phy_set_antenna_map): output antenna a from input antenna src_antenna[a] of the
+  // recording at the cell's centre offset + offset_hz[a].  null: off.  Checked against the recording (antennas, rate) when a replay or a stream starts
+  int setAntennaMap(const lsn_antenna_map_t* m)
+  {
+    if (!m) { ant_map.nof_out = 0; return LSN_SUCCESS; }
+    if (m->struct_size != sizeof(lsn_antenna_map_t) || m->nof_out < 1 || m->nof_out > LSN_MAP_MAX_OUT || m->nof_out != cfg.nof_rx_antennas) return LSN_ERROR_INVALID_INPUTS;
+    for (uint32_t a = 0; a < m->nof_out; a++)
+      if (m->src_antenna[a] > 7 || !(m->offset_hz[a] > -1e12 && m->offset_hz[a] < 1e12)) return LSN_ERROR_INVALID_INPUTS;
+    ant_map = *m;
+    return LSN_SUCCESS;
+  }
+  const lsn_antenna_map_t* antennaMap() const { return ant_map.nof_out ? &ant_map : nullptr; }
   int process(const void* d_iq, uint32_t nsf, uint32_t start_tti, uint32_t update_meta_period, hipStream_t stream);
   int submit(const void* d_iq, uint32_t nsf, uint32_t start_tti, uint32_t update_meta_period, hipStream_t stream, bool force_meta_first = false);
   // `nrows` = nsf x antennas rows of one subframe each (sflen samples), `row_pitch` bytes apart in PINNED host memory (the worker pool's slab:
@@ -606,6 +618,7 @@ private:
   struct FileBuf { cf32* h_raw = nullptr; cf32* d_raw = nullptr; cf32* d_iq = nullptr; size_t bytes = 0; };
   FileBuf file_buf[8];
   double chan_stopband_hz = 0.0;   // lsn_phy_set_channel_filter
+  lsn_antenna_map_t ant_map = {};  // lsn_phy_set_antenna_map; nof_out = 0: off
   cf32* d_chan = nullptr; size_t chan_bytes = 0;   // reserveChanBuffer
   bool chan_held = false;                          // holdChanBuffer
   std::atomic<uint32_t>& ul_cfg_epoch = sh->ul_cfg_epoch;  // bumped by every (re)configuration: chunks whose DCI 0 grants were converted earlier are converted again at commit

@@ -100,6 +100,7 @@ static size_t chan_buffer_bytes(uint64_t raw_samples, uint32_t nant, uint32_t L)
 int Engine::processFile(const char* path, const lsn_file_cfg_t& fc, uint32_t start_tti, uint64_t max_subframes, uint32_t update_meta_period,
                         uint64_t* subframes_done)
 {
+  if (antennaMap()) { if (subframes_done) *subframes_done = 0; return LSN_ERROR_INVALID_INPUTS; }   // a map is the resampler's: lsn_phy_process_file_rate
   if (chan_stopband_hz != 0.0) {   // the channel filter is set: the file is at the engine's rate and goes through both stages
     lsn_file_rate_t fr;
     fr.struct_size = sizeof(fr); fr.reserved = 0; fr.sample_rate_hz = 15000.0 * (double)cd.N; fr.offset_time_frac = 0.0; fr.center_offset_hz = 0.0;
@@ -120,6 +121,14 @@ int Engine::processFileRate(const char* path, const lsn_file_cfg_t& fc, const ls
   if (fr.struct_size != offsetof(lsn_file_rate_t, center_offset_hz) && fr.struct_size != sizeof(lsn_file_rate_t)) return LSN_ERROR_INVALID_INPUTS;
   const double center = fr.struct_size == sizeof(lsn_file_rate_t) ? fr.center_offset_hz : 0.0;
   if (fc.offset_time_samples < 0 || !(fr.offset_time_frac >= 0.0 && fr.offset_time_frac < 4.0e18)) return LSN_ERROR_INVALID_INPUTS;
+  if (const lsn_antenna_map_t* m = antennaMap()) {   // always through the resampler, equal rates too; fc.nof_antennas is the recording's
+    if (chan_stopband_hz != 0.0) return LSN_ERROR_INVALID_INPUTS;   // (limit: no channel filter with a map)
+    ResamplePlan plan;
+    const int r = file_rate_plan_map(fr.sample_rate_hz, cd.N, cd.nof_prb, fc.offset_time_samples, fr.offset_time_frac, center, fc.nof_antennas, m->nof_out, m->src_antenna,
+                                     m->offset_hz, plan);
+    if (r != LSN_SUCCESS) return r;
+    return processFileImpl(path, fc, &plan, nullptr, start_tti, max_subframes, update_meta_period, subframes_done);
+  }
   if (fr.sample_rate_hz == 15000.0 * (double)cd.N && fr.offset_time_frac == 0.0 && center == 0.0 && chan_stopband_hz == 0.0)
     return processFileImpl(path, fc, nullptr, nullptr, start_tti, max_subframes, update_meta_period, subframes_done);
   // with the channel filter set the mixer runs in stage 1 and the resampler, stage 2, is the plan of the same pair and start with no offset
@@ -162,14 +171,14 @@ struct Engine::FileReplay {
   std::vector<Cell> cells;
   Engine& e;                   // the first cell's: device, reader-thread pinning
   Engine* big = nullptr;       // the engine whose block buffers are largest: the raw block (pinned and device) of a slot is its
-  const uint32_t nant, fmt;
+  const uint32_t nant, fmt;    // nant: the RECORDING's antennas - what is read and what the raw block holds; a cell's block buffers have its Phy's
   const LsnSampleFormat sfm;   // bytes of one complex sample in the file (the block buffers are sized for cf32, the widest) and the conversion's scale
   const size_t spb;            // bytes of one sample of all antennas
   size_t sf_bytes = 0;         // single cell at the engine's rate: bytes of one subframe ...
   const uint64_t file_off0;    // ... and where subframe 0 starts
   uint32_t blk, nrd;           // subframes per block, page-touch / pread threads per block
   uint32_t blk_geom = 0;       // blk as file_geometry gave it: what the block buffers are sized for
-  size_t raw_bytes = 0;        // bytes a raw block buffer holds: blk_geom subframes of cf32 of the widest cell
+  size_t raw_bytes = 0;        // bytes a raw block buffer holds: blk_geom subframes of cf32 of the cell whose Phy has the largest blocks (subframe length x ITS antennas)
   int NSLOT;                   // blocks in flight (round 2 held eight until their chunks were written - and paid 8 x 393 MB of pinned allocation on the first call)
   int fd = -1; size_t file_size = 0;
   bool use_mmap = false;  // measured on MI355X boxes (page-cache file): pread into pinned blocks 60 k subframes/s, in-place locking 26 k (lock / unlock per block)
@@ -188,16 +197,16 @@ struct Engine::FileReplay {
   {
     file_geometry(blk, nrd, NSLOT);
     blk_geom = blk;
-    uint32_t widest = 0;
+    size_t widest = 0;   // samples of all antennas of one subframe of a Phy
     for (uint32_t c = 0; c < n; c++) {
       Cell k;
       k.e = jobs[c].e; k.rs = jobs[c].rs; k.front.cf = jobs[c].cf; k.sflen = k.e->cd.sflen; k.offset_freq_hz = jobs[c].offset_freq_hz; k.start_tti = jobs[c].start_tti;
       k.update_meta_period = jobs[c].update_meta_period; k.max_subframes = jobs[c].max_subframes;
-      if (k.sflen > widest) { widest = k.sflen; big = k.e; }
+      if ((size_t)k.sflen * k.e->cd.iq_nant > widest) { widest = (size_t)k.sflen * k.e->cd.iq_nant; big = k.e; }
       cells.push_back(std::move(k));
     }
     sf_bytes = (size_t)cells[0].sflen * nant * sfm.bytes;
-    raw_bytes = (size_t)blk_geom * widest * nant * sizeof(cf32);
+    raw_bytes = (size_t)blk_geom * widest * sizeof(cf32);
   }
 
   ~FileReplay()
@@ -294,7 +303,7 @@ struct Engine::FileReplay {
     HIP_CHECK(hipSetDevice(e.cfg.device));
     HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     for (auto& c : cells)
-      if (c.e->reserveFileBuffers(nant) != LSN_SUCCESS) throw std::runtime_error("file source: block buffers");
+      if (c.e->reserveFileBuffers(c.e->cd.iq_nant) != LSN_SUCCESS) throw std::runtime_error("file source: block buffers");
     for (int si = 0; si < NSLOT; si++) {
       Slot& s = slot[si];
       FileBuf& fb = big->file_buf[si];
@@ -513,7 +522,10 @@ int Engine::processFileImpl(const char* path, const lsn_file_cfg_t& fc, const Re
 {
   if (subframes_done) *subframes_done = 0;
   if (!cell_set) return LSN_ERROR;
-  if (!path || fc.nof_antennas != cd.iq_nant || fc.offset_time_samples < 0 || !lsn_sample_format(fc.sample_format, fc.sample_scale).valid) return LSN_ERROR_INVALID_INPUTS;
+  // a mapped plan reads a recording of any 1 .. 8 antennas (its sources were checked against fc.nof_antennas when it was formed); every other replay the Phy's own
+  const bool mapped = rs && rs->map_nout;
+  if (mapped ? (fc.nof_antennas < 1 || fc.nof_antennas > 8 || rs->map_nout != cd.iq_nant) : fc.nof_antennas != cd.iq_nant) return LSN_ERROR_INVALID_INPUTS;
+  if (!path || fc.offset_time_samples < 0 || !lsn_sample_format(fc.sample_format, fc.sample_scale).valid) return LSN_ERROR_INVALID_INPUTS;
   FileCellJob job;
   job.e = this; job.rs = rs; job.cf = cf; job.offset_freq_hz = fc.offset_freq_hz; job.start_tti = start_tti; job.update_meta_period = update_meta_period; job.max_subframes = max_subframes;
   const int rc = replayFile(path, fc, &job, 1);

@@ -125,8 +125,11 @@ int lsn_resample(int device, const void* in, int in_on_device, uint64_t n_in, co
 
 // several resamplings of one input: one upload of the union of what the cells read, one launch of k_resample_cells.  ring_samples != 0 (host input): the whole
 // window goes to its slots in a device ring of that many samples instead, and k_resample_ring reads it there
-static int resample_cells(int device, const void* in, int in_on_device, uint64_t n_in, uint64_t ring_samples, const lsn_resample_cfg_t* cfgs, uint32_t n_cells, float* const* outs,
-                          int out_on_device, const uint64_t* n_out)
+static_assert(LSN_RS_MAP_MAX_OUT == LSN_MAP_MAX_OUT, "lsn_resample.h speaks the public header's limit");
+
+// maps (lsn_resample_cells[_ring]_map; null: none): cell c with maps[c].nof_out != 0 is cut through its antenna map and writes nof_out rows
+static int resample_cells(int device, const void* in, int in_on_device, uint64_t n_in, uint64_t ring_samples, const lsn_resample_cfg_t* cfgs, const lsn_antenna_map_t* maps,
+                          uint32_t n_cells, float* const* outs, int out_on_device, const uint64_t* n_out)
 {
   if (!cfgs || !outs || !n_out || n_cells < 1 || n_cells > LSN_FILE_MAX_CELLS) return LSN_ERROR_INVALID_INPUTS;
   std::vector<lsn::ResamplePlan> plans(n_cells);
@@ -135,7 +138,7 @@ static int resample_cells(int device, const void* in, int in_on_device, uint64_t
   bool any = false;
   for (uint32_t c = 0; c < n_cells; c++) {
     const lsn_resample_cfg_t& k = cfgs[c];
-    const int r = lsn_resample_plan(&k, plans[c]);
+    const int r = lsn_resample_plan_map(&k, maps ? &maps[c] : nullptr, plans[c]);
     if (r != LSN_SUCCESS) return r;
     if (k.struct_size != sizeof(lsn_resample_cfg_t) || k.nof_antennas != c0.nof_antennas || k.sample_format != c0.sample_format || !(k.sample_scale == c0.sample_scale) ||
         k.rate_in_hz != c0.rate_in_hz || k.in_base != c0.in_base)
@@ -165,7 +168,8 @@ static int resample_cells(int device, const void* in, int in_on_device, uint64_t
     LsnResampleCell k[LSN_FILE_MAX_CELLS];
     for (uint32_t c = 0; c < n_cells; c++) {
       tb[c].upload(plans[c], g.st);
-      k[c] = plans[c].cell(cfgs[c].out_first, (uint32_t)std::max<uint64_t>(n_out[c], 1), tb[c], g.output(c, outs[c], out_on_device, n_out[c], nant), n_out[c]);
+      k[c] = plans[c].cell(cfgs[c].out_first, (uint32_t)std::max<uint64_t>(n_out[c], 1), tb[c],
+                           g.output(c, outs[c], out_on_device, n_out[c], plans[c].map_nout ? plans[c].map_nout : nant), n_out[c]);
     }
     lsn_launch_resample_cells(from, k, n_cells, g.st);
   });
@@ -174,14 +178,28 @@ static int resample_cells(int device, const void* in, int in_on_device, uint64_t
 int lsn_resample_cells(int device, const void* in, int in_on_device, uint64_t n_in, const lsn_resample_cfg_t* cfgs, uint32_t n_cells, float* const* outs, int out_on_device,
                        const uint64_t* n_out)
 {
-  return resample_cells(device, in, in_on_device, n_in, 0, cfgs, n_cells, outs, out_on_device, n_out);
+  return resample_cells(device, in, in_on_device, n_in, 0, cfgs, nullptr, n_cells, outs, out_on_device, n_out);
+}
+
+int lsn_resample_cells_map(int device, const void* in, int in_on_device, uint64_t n_in, const lsn_resample_cfg_t* cfgs, const lsn_antenna_map_t* maps, uint32_t n_cells,
+                           float* const* outs, int out_on_device, const uint64_t* n_out)
+{
+  if (!maps) return LSN_ERROR_INVALID_INPUTS;
+  return resample_cells(device, in, in_on_device, n_in, 0, cfgs, maps, n_cells, outs, out_on_device, n_out);
 }
 
 int lsn_resample_cells_ring(int device, const void* in, uint64_t n_in, uint64_t ring_samples, const lsn_resample_cfg_t* cfgs, uint32_t n_cells, float* const* outs,
                             const uint64_t* n_out)
 {
   if (!in || !lsn_ring_holds(ring_samples, n_in)) return LSN_ERROR_INVALID_INPUTS;
-  return resample_cells(device, in, 0, n_in, ring_samples, cfgs, n_cells, outs, 0, n_out);
+  return resample_cells(device, in, 0, n_in, ring_samples, cfgs, nullptr, n_cells, outs, 0, n_out);
+}
+
+int lsn_resample_cells_ring_map(int device, const void* in, uint64_t n_in, uint64_t ring_samples, const lsn_resample_cfg_t* cfgs, const lsn_antenna_map_t* maps,
+                                uint32_t n_cells, float* const* outs, const uint64_t* n_out)
+{
+  if (!in || !maps || !lsn_ring_holds(ring_samples, n_in)) return LSN_ERROR_INVALID_INPUTS;
+  return resample_cells(device, in, 0, n_in, ring_samples, cfgs, maps, n_cells, outs, 0, n_out);
 }
 
 // stage 1 alone (k_chan_fir)

@@ -21,7 +21,8 @@ struct FrontCell {
 // part); [lo[c], hi[c]): the input span that piece reads.  All cells are filtered or none.  Filtered: ONE k_chan_fir launch (k_chan_fir_ring out of a ring) writes
 // y1 over exactly chan_mid_span of each piece into its cell's intermediate, then one k_resample per cell reads that (k_resample_cells takes one source per launch);
 // a span that does not fit throws "<what>'s filtered samples do not fit the intermediate buffer" in front of every launch.  Unfiltered: k_resample for one cell
-// out of a linear buffer, else one k_resample_cells (k_resample_ring out of a ring) for all.
+// out of a linear buffer, else one k_resample_cells (k_resample_ring out of a ring) for all - the _map kernels when a cell of the launch has an antenna map
+// (unfiltered cells only; src.nant is the recording's, a mapped cell's output rows are its Phy's).
 void lsn_launch_front(const LsnFrontSource& src, const FrontCell* const* cells, const LsnResampleCell* k, const int64_t* lo, const int64_t* hi, uint32_t n, hipStream_t s,
                       const char* what);
 

@@ -75,6 +75,7 @@ int ResamplePlan::init(double rate_in, double rate_out, double passband_hz, uint
   if (step == 0) return LSN_ERROR_INVALID_INPUTS;
   start = ((u128)first_sample << 64) + (u128)(uint64_t)std::ldexp(first_frac, 64);
   tune = tuning(center_offset_hz, rate_in);
+  map_nout = 0;
   nco.clear();
   if (tune) {
     nco.resize((4096 + 1024) * 2);
@@ -99,6 +100,30 @@ int ResamplePlan::init(double rate_in, double rate_out, double passband_hz, uint
       bank[((size_t)p * taps + j) * 2] = (float)h0;
       bank[((size_t)p * taps + j) * 2 + 1] = (float)(h1 - h0);
     }
+  return LSN_SUCCESS;
+}
+
+int ResamplePlan::initMapped(double rate_in, double rate_out, double passband_hz, uint64_t first_sample, double first_frac, double center_offset_hz, uint32_t nof_in,
+                             uint32_t nof_out, const uint32_t* src, const double* offset_hz)
+{
+  if (nof_out < 1 || nof_out > LSN_RS_MAP_MAX_OUT || !src || !offset_hz) return LSN_ERROR_INVALID_INPUTS;
+  for (uint32_t a = 0; a < nof_out; a++) if (src[a] >= nof_in) return LSN_ERROR_INVALID_INPUTS;
+  const int r = init(rate_in, rate_out, passband_hz, first_sample, first_frac, 0.0);
+  if (r != LSN_SUCCESS) return r;
+  if (passband_hz == 0.0) passband_hz = 0.44 * std::min(rate_in, rate_out);   // init's default
+  bool mixes = false;
+  for (uint32_t a = 0; a < nof_out; a++) {
+    const double f = center_offset_hz + offset_hz[a];
+    if (!(std::fabs(f) + passband_hz <= 0.5 * rate_in)) return LSN_ERROR_INVALID_INPUTS;   // the output lies inside the recording (NaN and infinity fail here)
+    map_src[a] = src[a];
+    map_w[a] = tuning(f, rate_in);
+    mixes = mixes || map_w[a] != 0;
+  }
+  map_nout = nof_out;
+  if (mixes) {
+    nco.resize((4096 + 1024) * 2);
+    lsn_nco_tables((cf32*)nco.data(), (cf32*)nco.data() + 4096);
+  }
   return LSN_SUCCESS;
 }
 
@@ -157,6 +182,15 @@ int lsn_resample_plan(const lsn_resample_cfg_t* cfg, lsn::ResamplePlan& plan)
   const double center = cfg->struct_size == sizeof(lsn_resample_cfg_t) ? cfg->center_offset_hz : 0.0;
   if (cfg->nof_antennas < 1 || cfg->nof_antennas > 8 || !lsn_sample_format(cfg->sample_format, cfg->sample_scale).valid) return LSN_ERROR_INVALID_INPUTS;
   return plan.init(cfg->rate_in_hz, cfg->rate_out_hz, cfg->passband_hz, cfg->first_sample, cfg->first_frac, center);
+}
+
+int lsn_resample_plan_map(const lsn_resample_cfg_t* cfg, const lsn_antenna_map_t* map, lsn::ResamplePlan& plan)
+{
+  if (!map || !map->nof_out) return lsn_resample_plan(cfg, plan);
+  if (!cfg || cfg->struct_size != sizeof(lsn_resample_cfg_t) || map->struct_size != sizeof(lsn_antenna_map_t)) return LSN_ERROR_INVALID_INPUTS;
+  if (cfg->nof_antennas < 1 || cfg->nof_antennas > 8 || !lsn_sample_format(cfg->sample_format, cfg->sample_scale).valid) return LSN_ERROR_INVALID_INPUTS;
+  return plan.initMapped(cfg->rate_in_hz, cfg->rate_out_hz, cfg->passband_hz, cfg->first_sample, cfg->first_frac, cfg->center_offset_hz, cfg->nof_antennas, map->nof_out,
+                         map->src_antenna, map->offset_hz);
 }
 
 extern "C" {

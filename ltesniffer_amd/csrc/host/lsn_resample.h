@@ -9,6 +9,8 @@
 // the owner of a cell's device tables - is declared in lsn_resample_launch.h.
 struct cf32;
 
+#define LSN_RS_MAP_MAX_OUT 2u   // LSN_MAP_MAX_OUT of the public header (lsn_front_launch.cc asserts it)
+
 // what one cell brings to a launch of its own (the launch's other arguments - raw buffer, format, scale, antennas - are the recording's: LsnFrontSource)
 struct LsnResampleCell {
   uint64_t base_hi, base_lo;   // position of the cell's output 0 in this launch
@@ -22,6 +24,11 @@ struct LsnResampleCell {
   uint64_t n_out;              // 0: the cell takes no part in this launch
   uint32_t grp, run;           // grp = 0: the run of 512 outputs, one lane per output (ratios up to 4); else the wide-ratio run: grp lanes share an output,
                                // a workgroup makes `run` outputs
+  // the antenna map.  map_nout = 0: none - every antenna of the source to the row of its own number, tuned by w.  Else the cell writes map_nout rows,
+  // row a cut from antenna map_src[a] of the source with tuning word map_w[a] (0: not mixed); w is unread, nco is set when a word is non-zero
+  uint32_t map_nout;
+  uint32_t map_src[LSN_RS_MAP_MAX_OUT];
+  uint64_t map_w[LSN_RS_MAP_MAX_OUT];
 };
 
 namespace lsn {
@@ -46,6 +53,11 @@ struct ResamplePlan {
   std::vector<float> bank;  // [512][T][2]: H[p][j] and H[p + 1][j] - H[p][j], float32 (row 511 reaches phase 512 through its difference)
   uint64_t tune = 0;        // W = floor(center_offset_hz / rate_in * 2^64 + 1/2) mod 2^64: input sample n is rotated by exp(-2 pi j (n W mod 2^64) / 2^64)
   std::vector<float> nco;   // tune != 0: the mixer's tables, [4096] coarse then [1024] fine (re, im), lsn_nco_tables; else empty
+  // the antenna map, set by initMapped: map_nout outputs, output a from input antenna map_src[a] with tuning word map_w[a]; tune is 0 then and ONE set
+  // of tables serves both words (the tables do not depend on the word).  map_nout = 0: none
+  uint32_t map_nout = 0;
+  uint32_t map_src[LSN_RS_MAP_MAX_OUT] = {};
+  uint64_t map_w[LSN_RS_MAP_MAX_OUT] = {};
 
   // LSN_SUCCESS, or LSN_ERROR_INVALID_INPUTS when the pair is outside what the filter meets, or the cell at center_offset_hz does not lie inside
   // the recording (accepted range)
@@ -56,6 +68,10 @@ struct ResamplePlan {
   static constexpr uint32_t kWideMaxTaps = 768, kWideRounds = 16, kWideLanes = 256;
   int init(double rate_in, double rate_out, double passband_hz, uint64_t first_sample, double first_frac, double center_offset_hz, double max_ratio = 4.0,
            uint32_t max_taps = 192);
+  // init with an antenna map: the plan of the pair with no offset, then per output a the acceptance rule |center_offset_hz + offset_hz[a]| + pass band <=
+  // rate_in / 2 (NaN and infinity fail it) and the word of that sum.  nof_out 1 .. LSN_RS_MAP_MAX_OUT and src[a] < nof_in, or LSN_ERROR_INVALID_INPUTS
+  int initMapped(double rate_in, double rate_out, double passband_hz, uint64_t first_sample, double first_frac, double center_offset_hz, uint32_t nof_in, uint32_t nof_out,
+                 const uint32_t* src, const double* offset_hz);
   static uint64_t tuning(double center_offset_hz, double rate_in);   // W of one offset
   u128 position(uint64_t m) const { return start + (u128)m * step; }
   // lanes per output of the wide-ratio run at nominal step D: 0 up to ratio 4, else the smallest power of two >= D, 8 .. 32
@@ -77,6 +93,8 @@ struct ResamplePlan {
     k.base_hi = (uint64_t)(base >> 64); k.base_lo = (uint64_t)base; k.d_lo = (uint64_t)step_; k.d_hi = (uint32_t)(step_ >> 64);
     k.taps = taps; k.span = span_; k.sflen = sflen; k.sf_off = sf_off; k.bank = t.d_bank; k.w = tune; k.nco = t.d_nco; k.rot = t.d_rot; k.out = out; k.n_out = n_out;
     k.grp = grp; k.run = run;
+    k.map_nout = map_nout;
+    for (uint32_t a = 0; a < LSN_RS_MAP_MAX_OUT; a++) { k.map_src[a] = map_src[a]; k.map_w[a] = map_w[a]; }
     return k;
   }
   // outputs [m0, m0 + n_out) of this plan, output m0 at the start of a row

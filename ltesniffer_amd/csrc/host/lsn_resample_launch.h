@@ -20,8 +20,12 @@ struct ResampleTables : ResampleTablePtrs {
 }  // namespace lsn
 
 // src: the buffer the launch reads (lsn_front_source.h)
+// src: the recording's, its nant included; a cell with an antenna map (LsnResampleCell::map_nout) writes map_nout rows, every other cell src.nant.  When a cell of
+// the launch is mapped the _map kernels run it; when none is, the kernels named here, as before the map existed
 void lsn_launch_resample(const LsnFrontSource& src, const LsnResampleCell& cell, hipStream_t s);                            // k_resample (a linear buffer)
 void lsn_launch_resample_cells(const LsnFrontSource& src, const LsnResampleCell* cells, uint32_t n_cells, hipStream_t s);   // k_resample_cells, or k_resample_ring out of a ring
 
 // the plan of a lsn_resample_cfg_t, validated: what lsn_resample_span and the stand-alone calls (lsn_front_launch.cc) share
 int lsn_resample_plan(const lsn_resample_cfg_t* cfg, lsn::ResamplePlan& plan);
+// the same with an antenna map: map null or nof_out = 0 is lsn_resample_plan; else the full cfg, the map's size and ResamplePlan::initMapped's verdict
+int lsn_resample_plan_map(const lsn_resample_cfg_t* cfg, const lsn_antenna_map_t* map, lsn::ResamplePlan& plan);

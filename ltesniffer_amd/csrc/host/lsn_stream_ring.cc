@@ -82,10 +82,12 @@ int StreamRing::setup()
     HIP_CHECK(hipEventCreateWithFlags(&ev_copy, hipEventDisableTiming));
     HIP_CHECK(hipMalloc((void**)&d_ring, (size_t)ring_samples * spb));
     for (auto& c : cells) {
-      const int r = c.s.e->reserveFileBuffers(nant);
+      // the ring holds the STREAM's antennas (nant); a cell's block buffers hold its Phy's - the same number unless the cell has an antenna map
+      const uint32_t rows = c.s.e->iqAntennas();
+      const int r = c.s.e->reserveFileBuffers(rows);
       if (r != LSN_SUCCESS) return r;
       for (int si = 0; si < nslot; si++)
-        if (c.s.e->fileIqBlockBytes(si) < (size_t)blk * c.sflen * nant * sizeof(cf32)) throw std::runtime_error("stream: block buffer");
+        if (c.s.e->fileIqBlockBytes(si) < (size_t)blk * c.sflen * rows * sizeof(cf32)) throw std::runtime_error("stream: block buffer");
       c.front.tb.rotation(c.s.offset_freq_hz, c.sflen, 15000.0 * (double)c.s.e->symbolSz());   // the -o rotation of the cell's output samples, the file source's
       c.front.tb.upload(c.s.plan, st_run);
       if (c.s.filt.L) {
@@ -301,6 +303,7 @@ int StreamRing::flush()
 int StreamRing::track(const lsn_stream_track_cfg_t& tc, double rate_in)
 {
   if (pushed || tracking || failed != LSN_SUCCESS) return LSN_ERROR_INVALID_INPUTS;
+  for (const auto& c : cells) if (c.s.plan.map_nout) return LSN_ERROR_INVALID_INPUTS;   // (limit: no timing loop - and so no re-acquisition or frame sync - with an antenna map)
   TrackCfg cfg;
   const int r = track_cfg_resolve(tc.kp, tc.ki, tc.max_ppm, tc.lost_after, cfg);
   if (r != LSN_SUCCESS) return r;

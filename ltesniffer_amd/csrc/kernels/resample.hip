@@ -54,19 +54,22 @@ static_assert(sizeof(LsnResampleArgs) == 128, "eight of them are one kernel argu
 // are).  Two things differ between the kernels: MIXCOND - k_resample's template flag, or the cell's own "has NCO tables", uniform over the workgroup - and SRCSAMPLE,
 // where the sample sits in A.raw: k_resample and k_resample_cells read a linear buffer (LSN_FRONT_LINEAR), k_resample_ring the slot of n in its ring (LSN_FRONT_RING).
 // The staging loop, from the position of the run's first output to the barrier, is the one text of both run geometries; RUNLEN is the outputs of a run.
-#define LSN_RESAMPLE_STAGE(RUNLEN, MIXCOND, SRCSAMPLE) \
-  const uint32_t a = blockIdx.y, half = A.taps / 2;                                                                                                                     \
+// Three more things are one number, blockIdx.y, in these kernels and three numbers in the antenna-map kernels further down: SRCANT, the antenna of the
+// recording's A.nant a workgroup reads; OUTROW of OUTROWS, the row it writes; TUNE, its tuning word.  The kernels here pass blockIdx.y, a of A.nant and A.w - the text
+// they had before the parameters existed, and the instruction streams.
+#define LSN_RESAMPLE_STAGE(RUNLEN, MIXCOND, SRCSAMPLE, SRCANT, TUNE) \
+  const uint32_t a = SRCANT, half = A.taps / 2;                                                                                                                         \
   const uint64_t i0 = (uint64_t)blockIdx.x * (RUNLEN);                                                                                                                  \
   LSN_FRONT_POSITION(i0, hi, lo)  /* of the run's first output */                                                                                                       \
   const int64_t n_lo = (int64_t)hi - (int64_t)half + 1;  /* input sample staged at rs_x[0] */                                                                           \
   for (uint32_t s = threadIdx.x; s < A.span; s += 256) {                                                                                                                \
-    LSN_FRONT_SAMPLE(true, SRCSAMPLE, MIXCOND, A.w)                                                                                                                     \
+    LSN_FRONT_SAMPLE(true, SRCSAMPLE, MIXCOND, TUNE)                                                                                                                    \
     rs_x[s] = x;                                                                                                                                                        \
   }                                                                                                                                                                     \
   __syncthreads();
 
-#define LSN_RESAMPLE_RUN(MIXCOND, SRCSAMPLE) \
-  LSN_RESAMPLE_STAGE(LSN_RS_RUN, MIXCOND, SRCSAMPLE)                                                                                                                    \
+#define LSN_RESAMPLE_RUN(MIXCOND, SRCSAMPLE, SRCANT, TUNE, OUTROW, OUTROWS) \
+  LSN_RESAMPLE_STAGE(LSN_RS_RUN, MIXCOND, SRCSAMPLE, SRCANT, TUNE)                                                                                                      \
   for (uint32_t r = 0; r < LSN_RS_RUN / 256; r++) {                                                                                                                     \
     const uint64_t i = i0 + r * 256 + threadIdx.x;                                                                                                                      \
     if (i >= A.n_out) break;                                                                                                                                            \
@@ -87,14 +90,14 @@ static_assert(sizeof(LsnResampleArgs) == 128, "eight of them are one kernel argu
     const uint32_t q = (uint32_t)i + A.sf_off, sf = q / A.sflen, n = q - sf * A.sflen;  /* the launcher keeps n_out + sf_off below 2^32 */                              \
     cf32 y; y.r = yr; y.i = yi;                                                                                                                                         \
     if (A.rot) y = cmul(y, A.rot[n]);                                                                                                                                   \
-    A.out[((size_t)sf * A.nant + a) * A.sflen + n] = y;                                                                                                                 \
+    A.out[((size_t)sf * (OUTROWS) + (OUTROW)) * A.sflen + n] = y;                                                                                                             \
   }
 
 template <int FMT, bool MIX>
 __global__ __launch_bounds__(256) void k_resample(const LsnResampleArgs A)
 {
   extern __shared__ float2 rs_x[];
-  LSN_RESAMPLE_RUN(MIX, LSN_FRONT_LINEAR)
+  LSN_RESAMPLE_RUN(MIX, LSN_FRONT_LINEAR, blockIdx.y, A.w, a, A.nant)
 }
 
 // Several cells of one recording from ONE raw buffer in one launch (lsn_file_process_cells, lsn_resample_cells): grid (largest number of runs
@@ -110,7 +113,7 @@ __global__ __launch_bounds__(256) void k_resample_cells(const LsnResampleCellsAr
   extern __shared__ float2 rs_x[];
   const LsnResampleArgs& A = P.c[blockIdx.z];
   if ((uint64_t)blockIdx.x * LSN_RS_RUN >= A.n_out) return;
-  LSN_RESAMPLE_RUN(A.nco != nullptr, LSN_FRONT_LINEAR)
+  LSN_RESAMPLE_RUN(A.nco != nullptr, LSN_FRONT_LINEAR, blockIdx.y, A.w, a, A.nant)
 }
 
 // The same launch out of a RING (lsn_stream, lsn_resample_cells_ring): raw holds ring_mask + 1 samples per antenna and sample n of the recording sits
@@ -122,7 +125,7 @@ __global__ __launch_bounds__(256) void k_resample_ring(const LsnResampleCellsArg
   extern __shared__ float2 rs_x[];
   const LsnResampleArgs& A = P.c[blockIdx.z];
   if ((uint64_t)blockIdx.x * LSN_RS_RUN >= A.n_out) return;
-  LSN_RESAMPLE_RUN(A.nco != nullptr, LSN_FRONT_RING)
+  LSN_RESAMPLE_RUN(A.nco != nullptr, LSN_FRONT_RING, blockIdx.y, A.w, a, A.nant)
 }
 
 // ---- ratios above 4: the wide-ratio run ----
@@ -144,8 +147,8 @@ struct LsnResampleWideArgs {
 };
 static_assert(sizeof(LsnResampleWideArgs) == 136, "eight of them are one kernel argument block");
 
-#define LSN_RESAMPLE_WIDE_RUN(MIXCOND, SRCSAMPLE) \
-  LSN_RESAMPLE_STAGE(W.run, MIXCOND, SRCSAMPLE)                                                                                                                         \
+#define LSN_RESAMPLE_WIDE_RUN(MIXCOND, SRCSAMPLE, SRCANT, TUNE, OUTROW, OUTROWS) \
+  LSN_RESAMPLE_STAGE(W.run, MIXCOND, SRCSAMPLE, SRCANT, TUNE)                                                                                                           \
   const uint32_t per = 256u / W.grp, gi = threadIdx.x / W.grp, gq = threadIdx.x & (W.grp - 1u);  /* outputs per round; this lane's output in it and lane in its group */ \
   for (uint32_t r = 0; r * per < W.run; r++) {                                                                                                                          \
     if (i0 + r * per >= A.n_out) break;  /* uniform over the workgroup: no output of this or a later round exists */                                                    \
@@ -184,7 +187,7 @@ static_assert(sizeof(LsnResampleWideArgs) == 136, "eight of them are one kernel 
       const uint32_t q = (uint32_t)i + A.sf_off, sf = q / A.sflen, n = q - sf * A.sflen;  /* the launcher keeps n_out + sf_off below 2^32 */                            \
       cf32 y; y.r = yr; y.i = yi;                                                                                                                                       \
       if (A.rot) y = cmul(y, A.rot[n]);                                                                                                                                 \
-      A.out[((size_t)sf * A.nant + a) * A.sflen + n] = y;                                                                                                               \
+      A.out[((size_t)sf * (OUTROWS) + (OUTROW)) * A.sflen + n] = y;                                                                                                           \
     }                                                                                                                                                                   \
   }
 
@@ -193,7 +196,7 @@ __global__ __launch_bounds__(256) void k_resample_wide(const LsnResampleWideArgs
 {
   extern __shared__ float2 rs_x[];
   const LsnResampleArgs& A = W.a;
-  LSN_RESAMPLE_WIDE_RUN(MIX, LSN_FRONT_LINEAR)
+  LSN_RESAMPLE_WIDE_RUN(MIX, LSN_FRONT_LINEAR, blockIdx.y, A.w, a, A.nant)
 }
 
 struct LsnResampleWideCellsArgs { LsnResampleWideArgs c[LSN_RS_MAX_CELLS]; };
@@ -206,7 +209,7 @@ __global__ __launch_bounds__(256) void k_resample_cells_wide(const LsnResampleWi
   const LsnResampleWideArgs& W = P.c[blockIdx.z];
   const LsnResampleArgs& A = W.a;
   if ((uint64_t)blockIdx.x * W.run >= A.n_out) return;
-  LSN_RESAMPLE_WIDE_RUN(A.nco != nullptr, LSN_FRONT_LINEAR)
+  LSN_RESAMPLE_WIDE_RUN(A.nco != nullptr, LSN_FRONT_LINEAR, blockIdx.y, A.w, a, A.nant)
 }
 
 // ... and out of a ring, as k_resample_ring
@@ -217,10 +220,91 @@ __global__ __launch_bounds__(256) void k_resample_ring_wide(const LsnResampleWid
   const LsnResampleWideArgs& W = P.c[blockIdx.z];
   const LsnResampleArgs& A = W.a;
   if ((uint64_t)blockIdx.x * W.run >= A.n_out) return;
-  LSN_RESAMPLE_WIDE_RUN(A.nco != nullptr, LSN_FRONT_RING)
+  LSN_RESAMPLE_WIDE_RUN(A.nco != nullptr, LSN_FRONT_RING, blockIdx.y, A.w, a, A.nant)
+}
+
+// ---- the antenna map ----
+//
+// The kernels above read antenna blockIdx.y of the recording, write row blockIdx.y of as many rows, and tune by the cell's one word.  With a map the three are
+// separate: a workgroup READS antenna src[blockIdx.y] of the recording's A.nant, WRITES row blockIdx.y of the cell's `rows`, and tunes by w[blockIdx.y] - a word of
+// 0 is not mixed; the test is uniform over the workgroup.  Grid: runs x the largest number of OUTPUT rows of a cell x cells; one cell is a launch of grid.z = 1.
+// The per-cell map travels in the argument block behind the cells' arguments and is read with scalar loads.  The run text, LDS, the tap loop and the 64.64
+// arithmetic are the macros above: output row a equals row src[a] of the unmapped kernel run with the word w[a], bit for bit.  A cell without a map takes part in
+// such a launch as the identity - src[a] = a, w[a] = its word, rows = the recording's antennas -, hence eight entries.
+#define LSN_RS_MAP_ROWS 8u
+struct LsnResampleMap {
+  uint32_t rows, pad;              // rows the cell writes (a workgroup with blockIdx.y >= rows returns); at most LSN_RS_MAP_ROWS
+  uint32_t src[LSN_RS_MAP_ROWS];   // < A.nant
+  uint64_t w[LSN_RS_MAP_ROWS];     // != 0 only when A.nco is set
+};
+struct LsnResampleMapCellsArgs { LsnResampleArgs c[LSN_RS_MAX_CELLS]; LsnResampleMap m[LSN_RS_MAX_CELLS]; };
+struct LsnResampleMapWideCellsArgs { LsnResampleWideArgs c[LSN_RS_MAX_CELLS]; LsnResampleMap m[LSN_RS_MAX_CELLS]; };
+static_assert(sizeof(LsnResampleMapWideCellsArgs) <= 4096, "one kernel argument block");
+
+#define LSN_RESAMPLE_MAP_ENTRY(RUNLEN)                                                                                                                                  \
+  const LsnResampleMap& M = P.m[blockIdx.z];                                                                                                                            \
+  if (blockIdx.y >= M.rows || (uint64_t)blockIdx.x * (RUNLEN) >= A.n_out) return;                                                                                       \
+  const uint32_t orow = blockIdx.y;                                                                                                                                     \
+  const uint64_t mw = M.w[orow];
+
+template <int FMT>
+__global__ __launch_bounds__(256) void k_resample_map(const LsnResampleMapCellsArgs P)
+{
+  extern __shared__ float2 rs_x[];
+  const LsnResampleArgs& A = P.c[blockIdx.z];
+  LSN_RESAMPLE_MAP_ENTRY(LSN_RS_RUN)
+  LSN_RESAMPLE_RUN(mw != 0, LSN_FRONT_LINEAR, M.src[orow], mw, orow, M.rows)
+}
+
+template <int FMT>
+__global__ __launch_bounds__(256) void k_resample_map_ring(const LsnResampleMapCellsArgs P)
+{
+  extern __shared__ float2 rs_x[];
+  const LsnResampleArgs& A = P.c[blockIdx.z];
+  LSN_RESAMPLE_MAP_ENTRY(LSN_RS_RUN)
+  LSN_RESAMPLE_RUN(mw != 0, LSN_FRONT_RING, M.src[orow], mw, orow, M.rows)
+}
+
+template <int FMT>
+__global__ __launch_bounds__(256) void k_resample_map_wide(const LsnResampleMapWideCellsArgs P)
+{
+  extern __shared__ float2 rs_x[];
+  const LsnResampleWideArgs& W = P.c[blockIdx.z];
+  const LsnResampleArgs& A = W.a;
+  LSN_RESAMPLE_MAP_ENTRY(W.run)
+  LSN_RESAMPLE_WIDE_RUN(mw != 0, LSN_FRONT_LINEAR, M.src[orow], mw, orow, M.rows)
+}
+
+template <int FMT>
+__global__ __launch_bounds__(256) void k_resample_map_ring_wide(const LsnResampleMapWideCellsArgs P)
+{
+  extern __shared__ float2 rs_x[];
+  const LsnResampleWideArgs& W = P.c[blockIdx.z];
+  const LsnResampleArgs& A = W.a;
+  LSN_RESAMPLE_MAP_ENTRY(W.run)
+  LSN_RESAMPLE_WIDE_RUN(mw != 0, LSN_FRONT_RING, M.src[orow], mw, orow, M.rows)
 }
 
 // ---- host side: one function forms a run's arguments, two launchers (lsn_resample_launch.h) ----
+
+// the map of cell k as its launch reads it, checked: a mapped cell's rows, sources (inside the recording's antennas) and words (non-zero only with NCO tables), or the
+// identity over the recording's antennas.  -> the rows it writes
+static uint32_t resample_map(const char* kernel, const LsnFrontSource& src, const LsnResampleCell& k, LsnResampleMap& M)
+{
+  memset(&M, 0, sizeof(M));
+  if (src.nant < 1 || src.nant > LSN_RS_MAP_ROWS || k.map_nout > LSN_RS_MAP_MAX_OUT) throw std::runtime_error(std::string(kernel) + ": bad antenna map");
+  if (!k.map_nout) {
+    M.rows = src.nant;
+    for (uint32_t a = 0; a < src.nant; a++) { M.src[a] = a; M.w[a] = k.nco ? k.w : 0; }
+    return M.rows;
+  }
+  M.rows = k.map_nout;
+  for (uint32_t a = 0; a < k.map_nout; a++) {
+    if (k.map_src[a] >= src.nant || (k.map_w[a] && !k.nco)) throw std::runtime_error(std::string(kernel) + ": bad antenna map");
+    M.src[a] = k.map_src[a]; M.w[a] = k.map_w[a];
+  }
+  return M.rows;
+}
 
 // the arguments of cell k's runs out of src, checked: span = samples a run needs (host: lsn_resample.cc), n_out + sf_off below 2^32 (the kernel's row arithmetic); a
 // run is LSN_RS_RUN outputs, or k.run of the wide-ratio geometry (k.grp = 8, 16 or 32 lanes per output, k.run a whole number of rounds of 256 / k.grp).
@@ -244,6 +328,7 @@ void lsn_launch_resample(const LsnFrontSource& src, const LsnResampleCell& cell,
 {
   if (!cell.n_out) return;
   if (src.ring_samples) throw std::runtime_error("k_resample: reads a linear buffer");
+  if (cell.map_nout) { lsn_launch_resample_cells(src, &cell, 1, s); return; }   // k_resample_map serves one cell too
   const size_t lds = (size_t)cell.span * sizeof(float2);
   if (cell.grp) {
     LsnResampleWideArgs W;
@@ -260,6 +345,46 @@ void lsn_launch_resample(const LsnFrontSource& src, const LsnResampleCell& cell,
   else LSN_LAUNCH_FMT(k_resample, LSN_COMMA false, src.fmt, g, dim3(256), lds, s, A);
 }
 
+// lsn_launch_resample_cells when a cell of the launch has an antenna map (the caller has checked ring and cell count): the same two launches - ratios up to 4, wide
+// ratios - through the _map kernels, grid.y = the most rows a cell of the launch writes; an unmapped cell rides as the identity
+static void launch_resample_map(const LsnFrontSource& src, const LsnResampleCell* cells, uint32_t n_cells, hipStream_t s)
+{
+  const uint64_t rn = src.ring_samples;
+  const char* kernel = rn ? "k_resample_map_ring" : "k_resample_map";
+  LsnResampleMapCellsArgs P;
+  LsnResampleMapWideCellsArgs Q;
+  memset(&P, 0, sizeof(P));
+  memset(&Q, 0, sizeof(Q));
+  uint32_t n = 0, span = 0, rows = 0, nw = 0, span_w = 0, rows_w = 0;
+  uint64_t runs = 0, runs_w = 0;
+  for (uint32_t c = 0; c < n_cells; c++) {
+    if (!cells[c].n_out) continue;
+    if (cells[c].grp) {
+      LsnResampleWideArgs& W = Q.c[nw];
+      runs_w = std::max(runs_w, resample_args(kernel, src, cells[c], W.a));
+      W.grp = cells[c].grp; W.run = cells[c].run;
+      span_w = std::max(span_w, cells[c].span);
+      rows_w = std::max(rows_w, resample_map(kernel, src, cells[c], Q.m[nw++]));
+    } else {
+      runs = std::max(runs, resample_args(kernel, src, cells[c], P.c[n]));
+      span = std::max(span, cells[c].span);
+      rows = std::max(rows, resample_map(kernel, src, cells[c], P.m[n++]));
+    }
+  }
+  if (n) {
+    const dim3 g((uint32_t)runs, rows, n);
+    const size_t lds = (size_t)span * sizeof(float2);
+    if (!rn) LSN_LAUNCH_FMT(k_resample_map, , src.fmt, g, dim3(256), lds, s, P);
+    else LSN_LAUNCH_FMT(k_resample_map_ring, , src.fmt, g, dim3(256), lds, s, P);
+  }
+  if (nw) {
+    const dim3 g((uint32_t)runs_w, rows_w, nw);
+    const size_t lds = (size_t)span_w * sizeof(float2);
+    if (!rn) LSN_LAUNCH_FMT(k_resample_map_wide, , src.fmt, g, dim3(256), lds, s, Q);
+    else LSN_LAUNCH_FMT(k_resample_map_ring_wide, , src.fmt, g, dim3(256), lds, s, Q);
+  }
+}
+
 // the cells of one launch: the source is the recording's and shared, everything else is the cell's own.  A cell with n_out = 0 takes no part; no launch when
 // none does.  Out of a ring: lsn_ring_holds(ring_samples, buf_len).  Cells of the two run geometries go to two launches on the same
 // stream - the cells of ratio up to 4 to the kernel they always went to, with the arguments they always had; the wide-ratio cells to its _wide twin
@@ -269,6 +394,9 @@ void lsn_launch_resample_cells(const LsnFrontSource& src, const LsnResampleCell*
   const char* kernel = rn ? "k_resample_ring" : "k_resample_cells";
   if (rn && !lsn_ring_holds(rn, src.buf_len)) throw std::runtime_error("k_resample_ring: bad ring");
   if (n_cells > LSN_RS_MAX_CELLS || src.buf_base < 0) throw std::runtime_error(std::string(kernel) + ": bad geometry");
+  bool mapped = false;
+  for (uint32_t c = 0; c < n_cells; c++) mapped = mapped || (cells[c].n_out && cells[c].map_nout);
+  if (mapped) { launch_resample_map(src, cells, n_cells, s); return; }   // no cell of the launch is mapped: the kernels and arguments below, as they always were
   LsnResampleCellsArgs P;
   LsnResampleWideCellsArgs Q;
   memset(&P, 0, sizeof(P));
